@@ -13,10 +13,14 @@ reference's own definition of the figure: solve_reduced_system_time / linear_sol
 For N > 1 the landmarks are sharded over the ranks (strong scaling: the problem is fixed) and
 each term carries one RCCL all-reduce of the 12*n_cams vector.
 
-Timing: the warm-up is --warmup steps topped up to --warm-seconds (0.5 s) of solves, then the block of
-EXACTLY --steps steps (barrier + synchronize on both sides, maximum over the ranks) is run --repeats (5) times back to
-back; `value` / `ms_per_step` are the MEDIAN block, `value_min` / `value_max` / `block_ms` the spread, and
-`graph_us_per_term` the device time of one replayed term loop per term (event pairs on the library's stream).
+Timing: the warm-up is --warmup steps topped up to --warm-seconds (0.5 s) of solves, then EXACTLY
+--steps timed steps, one block by default (barrier + synchronize on both sides, maximum over the ranks; --repeats R splits
+the same steps into R back-to-back blocks); `value` / `ms_per_step` are over all timed steps, `value_min` / `value_max` /
+`block_ms` the spread of the blocks.  After the timed steps, diagnostic legs run the series again: `graph_us_per_term` is
+the device time of one replayed term loop per term (event pairs on the library's stream), `kernel_ms` per kernel.
+
+--dump-outputs DIR writes what the last timed step returned (the camera increment, [num_iterations, termination]) as
+float64 .npy files under DIR; the inputs are seeded, so the same command on two builds compares their outputs.
 
 Prints ONE JSON line on rank 0 (contract in the task description) with two extra objects:
   roofline     the E0 (SpMV) kernel pair against the HBM roofline in REAL bytes: `traffic` = PMC-measured HBM bytes
@@ -238,8 +242,9 @@ def main():
     ap.add_argument("--steps", type=int, default=200,
                     help="timed steps (one step = one m-term solve; 200 x 1.3 ms: long enough for an external utilisation sampler to see)")
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="the timed --steps block is run this many times back to back; `value` is the median block")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="split the --steps timed steps into this many back-to-back blocks (the total stays --steps); "
+                         "`value` is the rate over all of them, `value_min` / `value_max` the slowest / fastest block")
     ap.add_argument("--warm-seconds", type=float, default=0.5,
                     help="the warm-up is topped up to this much device work whatever --warmup says")
     ap.add_argument("--problem", default="venice-1778", choices=sorted(synth.BAL_SHAPES))
@@ -270,7 +275,13 @@ def main():
                     help="also run the final-13682 shape (HUBER 20, 29 M observations: a term loop whose working set is ten "
                          "times the Infinity Cache) in a child process and report its rate and measured fraction under "
                          "`final_13682` (about a minute of problem generation and layout)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed blocks write what the last timed step handed its caller as DIR/<name>.npy (float64): "
+                         "increment.npy (the camera increment of the series, 12 or 11 per camera) and series_status.npy "
+                         "([num_iterations, termination]); the inputs are seeded, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(sys.argv[1:], args.gpus))  # nothing has touched the GPU yet
@@ -470,9 +481,11 @@ def main():
             if rank == 0:
                 print(f"[bench] peer-to-peer term exchange not used: {p2p_note}", file=sys.stderr)
 
+    last_status = [None]  # (num_iterations, termination) of the latest step: what power_series_pose returned to its caller
+
     def run_steps(k):
         for _ in range(k):
-            ctx.power_series_pose(m, 0.0, -1.0)
+            last_status[0] = ctx.power_series_pose(m, 0.0, -1.0)
 
     def agree_max(x):
         """the same number on every rank (the ranks run the same count of collectives)"""
@@ -499,21 +512,23 @@ def main():
         barrier()
         return max(args.warmup, 1) + extra
 
-    def timed_block():
-        """EXACTLY --steps steps between two barrier + synchronize pairs; the maximum over the ranks"""
+    def timed_block(k):
+        """k steps between two barrier + synchronize pairs; the maximum over the ranks"""
         barrier()
         t0 = time.perf_counter()
-        run_steps(args.steps)
+        run_steps(k)
         barrier()
         return agree_max(time.perf_counter() - t0)
 
     def timed():
-        """the --steps block --repeats times (>= 5 by default), back to back after one warm-up: `value` is the MEDIAN block,
-        the fastest and the slowest are reported beside it"""
+        """EXACTLY --steps timed steps after one warm-up: one block (default), or --repeats back-to-back blocks that split
+        them (sizes differ by at most one); returns the warm-up count, the steps of each block and each block's time"""
         n_warm = warm_up()
-        return n_warm, [timed_block() for _ in range(max(args.repeats, 1))]
+        r = min(max(args.repeats, 1), args.steps)
+        sizes = [args.steps // r + (1 if i < args.steps % r else 0) for i in range(r)]
+        return n_warm, sizes, [timed_block(k) for k in sizes]
 
-    warm_steps, blocks = timed()
+    warm_steps, block_steps, blocks = timed()
     if term_exchange.startswith("p2p"):
         # the solve is deterministic: the increment the timed loop ended with must still be the validated one; a
         # stale slab anywhere sends every rank back to the all-reduce and the timing is taken again
@@ -524,8 +539,17 @@ def main():
             term_exchange = f"all-reduce (peer-to-peer exchange dropped after the timed loop: increment off by {rel2:.1e})"
             if rank == 0:
                 print(f"[bench] {term_exchange}", file=sys.stderr)
-            warm_steps, blocks = timed()
-    dt = float(np.median(blocks))
+            warm_steps, block_steps, blocks = timed()
+    if args.dump_outputs:
+        # the result of the LAST timed step, read before the legs below run the series again (every rank reads: the read
+        # waits for the series; rank 0 writes)
+        dump = {"increment": ctx.get_increment(12)[: (11 if args.step == 2 else 12) * n_c],
+                "series_status": np.array(last_status[0], dtype=np.float64)}
+        if rank == 0:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in dump.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    dt = float(sum(blocks))  # the host time of all --steps timed steps
     # the same --steps block once more with an event pair on the library's stream around every solve (povar_timings, kind
     # "solve"): device time of the whole replayed term loop per term -- beside the host clock of the blocks above it says
     # whether a slow line is a slow device or a slow host
@@ -608,11 +632,13 @@ def main():
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": dt / args.steps * 1e3,
-        # `value` = the median of `repeats` blocks of exactly --steps steps (each between barrier + synchronize pairs, the
-        # maximum over the ranks), after `warmup_steps_run` untimed steps (--warmup, topped up to --warm-seconds of work)
+        # `value` = terms of exactly --steps timed steps / their time: `repeats` back-to-back blocks of `block_steps` steps that
+        # add up to --steps (each between barrier + synchronize pairs, the maximum over the ranks), after `warmup_steps_run`
+        # untimed steps (--warmup, topped up to --warm-seconds of work); `value_min` / `value_max`: the slowest / fastest block
         "repeats": len(blocks),
-        "value_min": terms / max(blocks),
-        "value_max": terms / min(blocks),
+        "block_steps": block_steps,
+        "value_min": min(k * m / b for k, b in zip(block_steps, blocks)),
+        "value_max": max(k * m / b for k, b in zip(block_steps, blocks)),
         "block_ms": [round(b * 1e3, 4) for b in blocks],
         "warmup_steps_run": warm_steps,
         "graph_us_per_term": graph_us_per_term,
