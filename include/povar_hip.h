@@ -82,7 +82,23 @@ enum {
    * [POVAR_LPL_PLACE=sync|async|none] */
   POVAR_FLAG_PLACEMENT_SHIFT = 12, POVAR_FLAG_PLACEMENT_MASK = 0x3u << 12,
   /* keep the 16-byte image points in the camera-chunk rows even where they pack (six-decimal observations).  [POVAR_CK_PACK=0] */
-  POVAR_FLAG_NO_PACKED_ROWS = 1u << 16
+  POVAR_FLAG_NO_PACKED_ROWS = 1u << 16,
+  /* step 1's power-series terms (solve_pOSE under POVAR_POWER_VARPROJ and POVAR_POWER_SCHUR_COMPLEMENT, povar_power_series_step,
+   * povar_right_mul_e0_pose) in single precision: the camera-chunk kernel e0_ck_f32 on a chunk layout povar_create always builds
+   * for such a context, rows placed inside the call (as POVAR_FLAG_PLACEMENT(1)).  Numerical contract:
+   *   fp32: the per-observation arithmetic of E0; the landmark slot values (h~, u = Jl^T Jp x, g = G u; u sums in LDS with
+   *         ds_add_f32); the camera records a chunk gathers (Z = sigma_c x_c, P3 and, for HUBER, the translation); the image
+   *         points -- packed rows as (float)k * 1e-6f, rows that do not pack stored as float2; HUBER weights recomputed per
+   *         observation in fp32 (CAUCHY's are 1); a chunk's own sum (<= 16 observations of one camera);
+   *   fp64: every sum across chunks of a camera (the segmented wavefront sum, the LDS accumulators, the partial records, the
+   *         cold view, the per-camera sums), B^-1 -- stored and applied in fp64 --, the running sum x and the z handed from one
+   *         term to the next (converted to fp32 where a chunk gathers it), the exchange of a sharded context.
+   * Everything else -- linearisation, b, back substitution, cost, step 2, the explicit-SC solvers -- is the fp64 path.  Not
+   * bit-reproducible: the LDS adds land in arrival order, as in the default mode.  povar_create fails with
+   * POVAR_FLAG_DETERMINISTIC, POVAR_FLAG_SERIES_KERNEL(1), POVAR_FLAG_E0_KERNEL(0) or an e0_mode other than
+   * POVAR_E0_IMPLICIT_LDSACC, and where the chunk layout cannot be built; povar_set_e0_kernel(ctx, 0),
+   * povar_set_series_kernel(ctx, 1) and povar_set_e0_mode to another mode fail on such a context.  [POVAR_FP32_TERMS=1|0] */
+  POVAR_FLAG_FP32_TERMS = 1u << 17
 };
 #define POVAR_FLAG_E0_KERNEL(k) ((((uint32_t)((k) + 1)) & 0xFu) << POVAR_FLAG_E0_KERNEL_SHIFT)
 #define POVAR_FLAG_SERIES_KERNEL(m) ((((uint32_t)((m) + 1)) & 0x3u) << POVAR_FLAG_SERIES_KERNEL_SHIFT)
@@ -335,6 +351,8 @@ typedef struct {
                            slots of its most observed cameras, the other cameras' chunks write records of their own) */
   int32_t ckh_accumulators;      /* accumulator slots per workgroup at most */
   int64_t ckh_capped_obs;        /* observations of cameras that have a slot in the lane-per-landmark layout but none here */
+  int32_t fp32_terms;   /* 1: the last step-1 power series (povar_power_series_pose / _step) ran its terms in fp32
+                           (POVAR_FLAG_FP32_TERMS: e0_ck_f32) */
 } povar_layout_info;
 int povar_get_layout_info(povar_ctx* ctx, povar_layout_info* out);
 /* The reference's constructor is a trivial allocation (sc/linearization_varproj.hpp:44-60); this library's builds the

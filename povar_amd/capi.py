@@ -33,6 +33,8 @@ class Options(C.Structure):
 
 # povar_options.flags (include/povar_hip.h: POVAR_FLAG_*)
 FLAG_DETERMINISTIC, FLAG_DET_GATHER_TERMS, FLAG_NO_GRAPH, FLAG_NO_PACKED_ROWS = 1 << 0, 1 << 1, 1 << 2, 1 << 16
+# step 1's power-series terms in single precision (the numerical contract: include/povar_hip.h)
+FLAG_FP32_TERMS = 1 << 17
 
 
 def flag_e0_kernel(k):
@@ -75,7 +77,8 @@ class LayoutInfo(C.Structure):
                 ("res_max_oq", C.c_int32), ("res_order", C.c_int32),
                 ("res_lds_bytes", C.c_int32), ("res_build_ms", C.c_double), ("tune_terms_us", C.c_float),
                 ("tune_res_us", C.c_float), ("res_failed", C.c_int32), ("ck_packed", C.c_int32), ("ck_cold_q", C.c_int32),
-                ("ckh_stride", C.c_int32), ("ckh_accumulators", C.c_int32), ("ckh_capped_obs", C.c_int64)]
+                ("ckh_stride", C.c_int32), ("ckh_accumulators", C.c_int32), ("ckh_capped_obs", C.c_int64),
+                ("fp32_terms", C.c_int32)]
 
 
 class TimingsInfo(C.Structure):

@@ -84,6 +84,7 @@ bool parse_bal_app_arguments(int argc, char** argv, BalAppOptions& o) {
   dbl("vee-factor", &o.solver.vee_factor);
   str("e0-mode", &o.solver.e0_mode);
   flag["deterministic"] = &o.solver.deterministic;
+  flag["fp32-terms"] = &o.solver.fp32_terms;
   integer("device", &o.solver.device);
   integer("gpus", &o.solver.gpus);
 

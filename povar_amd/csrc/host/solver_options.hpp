@@ -54,6 +54,8 @@ struct SolverOptions {
   std::string e0_mode = "ldsacc";  // "ldsacc" (fastest), "implicit" (bit-reproducible), "tiles" (stored tiles)
   // bit-reproducible results run to run (povar_options.flags: POVAR_FLAG_DETERMINISTIC; 1.26 x the default term on venice-1778)
   bool deterministic = false;
+  // step 1's power-series terms in single precision (povar_options.flags: POVAR_FLAG_FP32_TERMS; contract in include/povar_hip.h)
+  bool fp32_terms = false;
   int device = 0;
   // landmark shards = device contexts of ONE process (BASELINE configs 4 / 5: "landmarks sharded across 8 x MI355X"):
   // shard r runs on device (device + r) mod device count; one exchange step per power-series term (RCCL, or an in-process

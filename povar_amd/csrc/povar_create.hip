@@ -512,6 +512,30 @@ int povar_create(povar_ctx** out, int32_t n_cams, int32_t n_lms, int64_t n_obs,
     c->deterministic = true;
     c->det_ck = !det_gather;
   }
+  // POVAR_FLAG_FP32_TERMS (POVAR_FP32_TERMS=1|0): step 1's power-series terms in single precision (povar_kernels_ck_f32.hpp).  The
+  // kernel is a camera-chunk kernel that adds in arrival order and runs per term: the switches that promise something else are
+  // refused, not overridden.
+  {
+    bool want_f32 = (fl & POVAR_FLAG_FP32_TERMS) != 0;
+    if (const char* g = std::getenv("POVAR_FP32_TERMS")) want_f32 = g[0] == '1';
+    if (want_f32) {
+      const char* ek = std::getenv("POVAR_E0_CK");
+      const char* rs = std::getenv("POVAR_RES");
+      const bool lpl_forced = ek ? std::atoi(ek) == 0 : ((fl & POVAR_FLAG_E0_KERNEL_MASK) >> POVAR_FLAG_E0_KERNEL_SHIFT) == 1;
+      const bool res_forced = rs ? rs[0] == '1' : ((fl & POVAR_FLAG_SERIES_KERNEL_MASK) >> POVAR_FLAG_SERIES_KERNEL_SHIFT) == 2;
+      const char* why = want_det ? "POVAR_FLAG_DETERMINISTIC: its adds land in arrival order"
+                        : res_forced ? "POVAR_FLAG_SERIES_KERNEL(1): the resident series has no fp32 form"
+                        : lpl_forced ? "POVAR_FLAG_E0_KERNEL(0): the fp32 terms are a camera-chunk kernel"
+                        : options->e0_mode != POVAR_E0_IMPLICIT_LDSACC ? "an E0 mode other than POVAR_E0_IMPLICIT_LDSACC"
+                        : nullptr;
+      if (why) {
+        povar_destroy(c);
+        return fail(-1, std::string("POVAR_FLAG_FP32_TERMS cannot be combined with ") + why);
+      }
+      c->fp32_terms = true;
+      c->res_mode = 0;
+    }
+  }
   if (fl & POVAR_FLAG_NO_GRAPH) c->use_graph = false;
   if (const char* g = std::getenv("POVAR_NO_GRAPH")) c->use_graph = !(g[0] == '1');
   if (const char* g = std::getenv("POVAR_NO_ERR_MEMO")) c->no_err_memo = g[0] == '1';
@@ -524,6 +548,7 @@ int povar_create(povar_ctx** out, int32_t n_cams, int32_t n_lms, int64_t n_obs,
   if (const char* g = std::getenv("POVAR_E0_V1")) { c->use_lpl = !(g[0] == '1'); c->lpl_forced = true; }
   if (const char* g = std::getenv("POVAR_K1_NORMAL_EQ")) c->k1_qr = !(g[0] == '1');
   if (const char* g = std::getenv("POVAR_PREPARE_V1")) c->use_lpl_prepare = !(g[0] == '1');
+  if (c->fp32_terms) c->use_lpl = c->use_lpl_prepare = true;  // (the fp32 kernel runs on the chunk layout, whatever the size)
 
   lap("device, stream");
   Layout L;
@@ -602,6 +627,7 @@ int povar_create(povar_ctx** out, int32_t n_cams, int32_t n_lms, int64_t n_obs,
       c->ckh_variant = c->ck_variant > 0 ? 1 : 0;  // (step 2 has one camera-chunk instantiation)
       c->ck_auto = false;
     }
+    if (c->fp32_terms) c->ck_variant = 1;  // e0_ck_f32 runs the layout of variant 1 (16 wavefronts, one group)
   }
   const bool want_ck = c->use_lpl && std::getenv("POVAR_NO_CK") == nullptr;
   // the camera-chunk layout is cut for the instantiation that will run it (its tiles are scheduled over its wavefronts)
@@ -645,6 +671,7 @@ int povar_create(povar_ctx** out, int32_t n_cams, int32_t n_lms, int64_t n_obs,
     // fixed summation order) arrive would depend on the host's timing, and with it the bits of every later solve.  None at
     // all unless asked for: the gather-mode kernels do not read these rows, e0_ck_det does not care about their order.
     if (c->deterministic) place_mode = place_mode == 1 && place_forced ? 1 : 0;
+    if (c->fp32_terms) place_mode = 1;  // the rows placed in this call: every solve, from the first, runs the fp32 terms
     build_lpl(n_cams, n_lms, lm_offsets, cam_idx, obs, L.cam_hot, L.slot_of_obs, (size_t)c->n_slots, c->e0c_grid,
               c->n_hot_acc, V, place_mode == 1);
     lap("build_lpl (lane/landmark)");
@@ -785,11 +812,28 @@ int povar_create(povar_ctx** out, int32_t n_cams, int32_t n_lms, int64_t n_obs,
         build_ck(V, n_cams, c->e0c_grid, L.hot_cams, ck_nw, K, ck_place, ck_hmax, ck_ng, ck_shape1, ck_pack);
         c->ck.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tk).count();
         if (!ck_upload(c, c->ck, K, false, &c->bytes)) { povar_destroy(c); return fail(-1, "camera-chunk layout: upload failed"); }
+        if (c->fp32_terms && c->ck.ready && !c->ck.packed) {  // fp32 image points where the rows do not pack (8 bytes per entry)
+          std::vector<float2> u32(K.uv.size());
+          for (size_t i = 0; i < u32.size(); ++i) u32[i] = make_float2((float)K.uv[i].x, (float)K.uv[i].y);
+          if (int rc = upload(c->ck32_uv, u32, c)) { povar_destroy(c); return rc; }
+        }
         CkLayout KH;  // step 2's instance: 64 bytes of LDS per landmark slot, no image coordinates
         build_ck(V, n_cams, c->e0c_grid, L.hot_cams, 16, KH, ck_place, ck_hmax, 1, ck_shape2);
         if (!ck_upload(c, c->ckh, KH, false, &c->bytes, false)) { povar_destroy(c); return fail(-1, "camera-chunk layout (step 2): upload failed"); }
         lap("camera-chunk layouts");
       }
+    }
+    if (c->fp32_terms) {
+      // e0_ck_f32 addresses its partial records with 32-bit byte offsets (rec * 96) through a descriptor of their exact size:
+      // the layout must keep them under 2^31 bytes -- checked here, not assumed (e0_ck's descriptor spans 2^31 whatever the size)
+      const char* why = !want_ck || V.tile.empty() || !c->ck.ready ? "the camera-chunk layout could not be built for this problem"
+                        : (uint64_t)c->ck.part.n * sizeof(double) >= (1ull << 31) ? "the partial records exceed 2^31 bytes"
+                        : (uint64_t)c->ck.src.n * sizeof(float2) >= (1ull << 32) ? "the chunk rows exceed 2^32 bytes"
+                        : ck32_lds_bytes(c->ck.slots, c->ck.max_acc) > (size_t)CK_LDS_BYTES ? "the landmark batches exceed the LDS"
+                        : nullptr;
+      if (why) { povar_destroy(c); return fail(-1, std::string("POVAR_FLAG_FP32_TERMS: ") + why); }
+      HIP_TRY_C(c->ck32_lmrec.alloc((size_t)std::max(nt, 1) * 9 * WAVE, &c->bytes));
+      HIP_TRY_C(c->ck32_pimg.alloc((size_t)n_cams * 12, &c->bytes));
     }
     c->d.v2 = V2{c->v2_uv.p, c->v2_cw.p, c->v2_cpos.p, c->v2_w.p, c->v2_tile.p, c->v2_seg.p, c->v2_lmrec.p,
                  c->v2_lm_of.p, c->v2_lmx.p, c->v2_lml.p, c->v2_lsc.p, c->v2_lm_pos.p, c->v2_of_slot.p, c->v2_wg_tile_off.p, c->v2_wg_cam_off.p, c->v2_wg_cams.p,
@@ -950,6 +994,7 @@ void povar_destroy(povar_ctx* c) {
   (void)hipSetDevice(c->opt.device);
   c->pl_uv.release(); c->pl_cw.release(); c->pl_cpos.release(); c->pl_lm_pos.release(); c->pl_lm_of.release(); c->pl_of_slot.release();
   c->pl_c3_src.release(); c->c3_src.release();
+  c->ck32_uv.release(); c->ck32_lmrec.release(); c->ck32_pimg.release();
   c->ck.release(); c->pl_ck.release(); c->ckh.release(); c->pl_ckh.release(); c->ck_zero_range.release();
   c->res.release();
   if (c->stream) (void)hipStreamSynchronize(c->stream);
@@ -1085,6 +1130,7 @@ int povar_get_layout_info(povar_ctx* c, povar_layout_info* out) {
   out->ckh_stride = c->ckh.ready ? c->ckh.stride : 0;
   out->ckh_accumulators = c->ckh.ready ? c->ckh.max_acc : 0;
   out->ckh_capped_obs = c->ckh.ready ? c->ckh.n_capped_obs : 0;
+  out->fp32_terms = c->fp32_last;
   return 0;
 }
 

@@ -36,6 +36,7 @@
 #include "povar_kernels_ck.hpp"
 #include "povar_kernels_ck_det.hpp"
 #include "povar_kernels_ck_joint.hpp"
+#include "povar_kernels_ck_f32.hpp"
 #include "res_layout.hpp"
 #include "povar_kernels_res.hpp"
 
@@ -214,6 +215,13 @@ struct povar_ctx {
   bool deterministic = false;    // POVAR_DETERMINISTIC=1: the E0 mode and the kernel choices are pinned
   bool det_ck = false;           // ... and step 1's terms run e0_ck_det where the chunk layout fits (else: the gather form)
   bool det_check = false;        // a series of e0_ck_det is in flight whose failure bit (flags[0] & 8) has not been looked at
+  // POVAR_FLAG_FP32_TERMS: step 1's terms run e0_ck_f32 (povar_kernels_ck_f32.hpp) on the layout of variant 1
+  bool fp32_terms = false;
+  bool fp32_hold = false;        // set while the explicit-SC solvers apply E0 (e0_dense): they run the fp64 kernels
+  int32_t fp32_last = 0;         // 1: the last step-1 power series ran its terms in fp32 (povar_layout_info.fp32_terms)
+  DevBuf<float2> ck32_uv;        // [rows][64] fp32 image points of the chunk rows (only where the rows do not pack)
+  DevBuf<float> ck32_lmrec;      // [lpl tiles][9][64] fp32 h~ and G of the landmark lanes (ck32_records, after every prepare)
+  DevBuf<float> ck32_pimg;       // [n_cams][12] fp32 P3 and translation by rank (ck32_records)
   DevBuf<int2> ck_zero_range;    // [n_cams] empty runs: e0_ck leaves no per-observation cold view to the per-camera kernels
   int ck_variant = 0;            // 0: e0_lpl; 1..CK_VARIANTS: e0_ck instantiation (POVAR_CK_VARIANTS)
   int ckh_variant = 0;           // step 2: 0: e0_lpl_h; 1: e0_ck_h
@@ -405,6 +413,8 @@ bool ck_variant_fits(const povar_ctx* c, int variant);  // povar_series.hip
 void launch_e0_ck(povar_ctx* c, const Dp& da);  // povar_series.hip
 hipError_t ck_set_lds_all();  // povar_series.hip
 void ensure_ck_w(povar_ctx* c);  // povar_series.hip
+bool ck32_active(const povar_ctx* c);  // povar_series.hip
+void launch_ck32_records(povar_ctx* c);  // povar_series.hip
 void launch_e0_ck_h(povar_ctx* c, const Dp& da);  // povar_series.hip
 bool res_variant_exists(int nw, int h, int rr, int ls);  // povar_series.hip
 void launch_res(povar_ctx* c, const ResP& k);  // povar_series.hip

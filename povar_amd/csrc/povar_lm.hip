@@ -357,6 +357,7 @@ int povar_prepare_pose(povar_ctx* c, double lambda, int32_t solver_type) {
     da.p2p_peer = nullptr;  // b goes through the ordinary exchange below, not the per-term push
     da.p2p_epoch = nullptr;
     hipLaunchKernelGGL(cam_cold_sum<CCS_THREADS>, dim3(c->n_cams), dim3(CCS_THREADS), 0, c->stream, da, 0);
+    if (c->fp32_terms) launch_ck32_records(c);  // (POVAR_FLAG_FP32_TERMS: the fp32 operands of e0_ck_f32)
   } else {
     c->aux_prep_id = c->prep_id;  // this branch writes them
     ensure_legacy(c);

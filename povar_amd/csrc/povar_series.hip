@@ -19,7 +19,16 @@ bool ck_det_possible(const povar_ctx* c) {
 
 bool ck_det_active(const povar_ctx* c) { return ck_det_possible(c) && !c->joint; }
 
+// POVAR_FLAG_FP32_TERMS: step 1's terms run e0_ck_f32 on the chunk layout povar_create built for it (it refuses the flag where
+// that layout cannot be built; setters that would leave it refuse too)
+bool ck32_active(const povar_ctx* c) {
+  return c->fp32_terms && !c->fp32_hold && !c->deterministic && !c->joint && c->ck.ready && c->use_lpl && c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC &&
+         c->ck32_lmrec.p && c->ck32_pimg.p && (c->ck.packed || c->ck32_uv.p) &&
+         ck32_lds_bytes(c->ck.slots, c->ck.max_acc) <= (size_t)CK_LDS_BYTES;
+}
+
 bool ck_active(const povar_ctx* c) {
+  if (c->fp32_terms && !c->fp32_hold) return ck32_active(c);
   if (c->deterministic) return ck_det_active(c);
   return c->ck_variant > 0 && c->ck.ready && c->use_lpl && !c->joint && c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC &&
          ck_variant_fits(c, c->ck_variant);
@@ -70,7 +79,35 @@ bool ck_variant_fits(const povar_ctx* c, int variant) {
   return c->ck.ready && c->ck.nb % v.ng == 0 && ck_lds_bytes(c->ck.slots, c->ck.max_acc, v.ng) <= (size_t)CK_LDS_BYTES;
 }
 
+// the fp32 term kernel (povar_kernels_ck_f32.hpp): its partial records and cold-view q are e0_ck's, in fp64
+void launch_e0_ck32(povar_ctx* c, const Dp& da) {
+  const CkP k = ck_params(c);
+  Ck32 f{c->ck.packed ? nullptr : c->ck32_uv.p, c->ck32_lmrec.p, c->ck32_pimg.p,
+         (unsigned)(c->ck.src.n * sizeof(float2)), (unsigned)(c->ck.part.n * sizeof(double))};
+  const size_t lds = ck32_lds_bytes(c->ck.slots, c->ck.max_acc);
+  const bool huber = c->opt.robust_norm == POVAR_NORM_HUBER;  // (recomputed in registers; CAUCHY's weights are 1, as in e0_ck)
+  if (c->ck.packed) {
+    if (huber) hipLaunchKernelGGL((e0_ck_f32<true, true>), dim3(c->e0c_grid), dim3(CK32_NW * 64), lds, c->stream, da, k, f, c->ck.part.p);
+    else hipLaunchKernelGGL((e0_ck_f32<false, true>), dim3(c->e0c_grid), dim3(CK32_NW * 64), lds, c->stream, da, k, f, c->ck.part.p);
+  } else {
+    if (huber) hipLaunchKernelGGL((e0_ck_f32<true, false>), dim3(c->e0c_grid), dim3(CK32_NW * 64), lds, c->stream, da, k, f, c->ck.part.p);
+    else hipLaunchKernelGGL((e0_ck_f32<false, false>), dim3(c->e0c_grid), dim3(CK32_NW * 64), lds, c->stream, da, k, f, c->ck.part.p);
+  }
+}
+
+// fp32 landmark records and camera image of the system prepared last (povar_prepare_pose, after prepare_lpl / build_hot_rec)
+void launch_ck32_records(povar_ctx* c) {
+  const int64_t n_rec = (int64_t)c->d.v2.n_tiles * 9 * WAVE;
+  const int64_t n = std::max<int64_t>(n_rec, (int64_t)c->n_cams * 12);
+  hipLaunchKernelGGL(ck32_records, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, (const double*)c->v2_lmrec.p, c->ck32_lmrec.p,
+                     n_rec, (const double*)c->hot_rec.p, c->ck32_pimg.p, c->n_cams);
+}
+
 void launch_e0_ck(povar_ctx* c, const Dp& da) {
+  if (ck32_active(c)) {
+    launch_e0_ck32(c, da);
+    return;
+  }
   if (c->deterministic) {  // the bit-reproducible form (povar_kernels_ck_det.hpp)
     const CkP k = ck_params(c);
     const size_t lds = ck_lds_bytes_det(c->ck.slots, c->ck.max_acc);
@@ -102,6 +139,11 @@ hipError_t ck_set_lds_all() {
   if (e == hipSuccess) e = hipFuncSetAttribute((const void*)e0_ck_h_det<16, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, CK_LDS_BYTES);
   if (e == hipSuccess) e = hipFuncSetAttribute((const void*)e0_ck_h_det<16, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CK_LDS_BYTES);
   if (e == hipSuccess) e = hipFuncSetAttribute((const void*)e0_ck_det<16, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CK_LDS_BYTES);
+  // (e0_ck_f32 is launched from this translation unit: its attributes are set on this unit's instantiations)
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)e0_ck_f32<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, CK_LDS_BYTES);
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)e0_ck_f32<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, CK_LDS_BYTES);
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)e0_ck_f32<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CK_LDS_BYTES);
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)e0_ck_f32<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CK_LDS_BYTES);
 #define X(id, nw, sd, db, ng) if (e == hipSuccess) e = ck_set_lds_t<nw, sd, db, ng>();
   POVAR_CK_VARIANTS(X)
 #undef X
@@ -412,7 +454,7 @@ void launch_binv(povar_ctx* c, int mode, int want_norms) {
 }
 
 int ck_autotune(povar_ctx* c) {
-  if (!c->ck_auto || c->ck_tuned || !c->ck.ready || !c->use_lpl || c->joint || c->opt.e0_mode != POVAR_E0_IMPLICIT_LDSACC ||
+  if (c->fp32_terms || !c->ck_auto || c->ck_tuned || !c->ck.ready || !c->use_lpl || c->joint || c->opt.e0_mode != POVAR_E0_IMPLICIT_LDSACC ||
       !ck_variant_fits(c, 1))
     return 0;
   c->ck_tuned = true;
@@ -489,6 +531,7 @@ int ck_autotune(povar_ctx* c) {
 int tune_agree(povar_ctx* c, int step) {
   // (the condition holds on every rank or on none: options and environment are the run's, not the rank's)
   if (!sharded(c) || !c->ck_auto || c->deterministic || c->opt.e0_mode != POVAR_E0_IMPLICIT_LDSACC) return 0;
+  if (step == 0 && c->fp32_terms) return 0;  // (step 1 is pinned to e0_ck_f32; a run's flags are every rank's)
   const bool fresh = c->ck_fresh[step];
   const float* us = step ? c->ckh_tune_us : c->ck_tune_us;
   const bool ready = c->use_lpl && (step ? c->ckh.ready : c->ck.ready);
@@ -582,6 +625,7 @@ int povar_power_series_step(povar_ctx* c) {
   if (int rc = check_ctx(c)) return rc;
   if (int rc = res_verify(c)) return rc;  // (a resident series that gave up is repeated BEFORE its state is overwritten / continued)
   int mode = 1;
+  if (!c->joint) c->fp32_last = ck32_active(c) ? 1 : 0;
   if (int rc = launch_e0(c, &mode, 0)) return rc;
   launch_binv(c, mode, 0);
   HIP_TRY(hipGetLastError());
@@ -741,6 +785,7 @@ int povar_power_series_pose(povar_ctx* c, int32_t m, double q_tol, double r_tol,
   const bool norms = q_tol > 0 || r_tol > 0;
   const bool p2p_terms = c->p2p && !c->joint && c->use_lpl && c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC;
   const bool use_res = m > 0 && m <= 250 && res_active(c);  // (a granule tag carries the term in 8 bits)
+  if (!c->joint) c->fp32_last = ck32_active(c) && !use_res ? 1 : 0;
   if (int rc = run_series(c, m, q_tol, r_tol, use_res)) return rc;
   int iters = m, status = POVAR_LINEAR_SOLVER_NO_CONVERGENCE;
   if (p2p_terms) c->flag0_clean = false;  // the waits of the exchange kernels raise bit 1 of flags[0] on a time-out
@@ -828,6 +873,8 @@ int povar_set_e0_mode(povar_ctx* c, int32_t mode) {
   if (mode != POVAR_E0_IMPLICIT && mode != POVAR_E0_TILES && mode != POVAR_E0_IMPLICIT_LDSACC &&
       mode != POVAR_E0_TILES_LDSACC) return fail(-1, "bad e0 mode");
   if (c->deterministic) return 0;  // pinned (POVAR_DETERMINISTIC)
+  if (c->fp32_terms && mode != POVAR_E0_IMPLICIT_LDSACC)
+    return fail(-1, "POVAR_FLAG_FP32_TERMS: the fp32 terms run in the LDS-accumulating E0 mode only");
   c->opt.e0_mode = mode;
   if (c->linearized) return ensure_tiles(c);
   return 0;
@@ -893,6 +940,18 @@ int povar_e0_model_bytes(povar_ctx* c, int64_t* lm_kernel, int64_t* cam_kernel) 
   }
   switch (c->opt.e0_mode) {
     case POVAR_E0_IMPLICIT_LDSACC:
+      if (ck32_active(c)) {
+        // e0_ck_f32: the rows on both passes at 8 + 2 bytes (packed or fp32 image points + slot), the 36-byte fp32 landmark
+        // records once, the camera image (z 96 in fp64 + P 48 in fp32), lane metadata on both passes, fp64 partial records
+        const int64_t part = (int64_t)c->ck.n_part_rec * 96;
+        lm = 2 * c->ck.rows * WAVE * 10 + (int64_t)c->d.v2.n_tiles * WAVE * 36 + nc * (96 + 48) + 2 * (int64_t)(c->ck.lane_meta.n) * 8 + part;
+        cm = part + tail;
+        if (c->ck.cold_q) {
+          lm += 36 * c->n_cold3;
+          cm += 56 * c->n_cold3;
+        }
+        break;
+      }
       if (ck_active(c)) {
         // e0_ck: the chunk rows (uv 16 + landmark slot 2 bytes) on BOTH passes -- the kernel as built reads them twice --,
         // the 72-byte landmark records once, 8 bytes of lane metadata per chunk lane and pass, the partial records out
@@ -949,6 +1008,13 @@ int povar_set_e0_kernel(povar_ctx* c, int32_t kernel) {
   if (kernel < -1 || kernel > CK_VARIANTS) return fail(-1, "unknown E0 kernel");
   if (kernel > 0 && !c->ck_zero_range.p) return fail(-1, "the camera-chunk layout was not built for this context");
   if (c->deterministic) return 0;  // pinned (POVAR_DETERMINISTIC)
+  if (c->fp32_terms && kernel == 0) return fail(-1, "POVAR_FLAG_FP32_TERMS: step 1's terms run the camera-chunk kernel e0_ck_f32");
+  if (c->fp32_terms) {  // step 1 stays on e0_ck_f32 (the layout of variant 1); the choice is step 2's
+    c->ck_auto = kernel < 0;
+    c->ckh_tuned = false;
+    c->ckh_variant = kernel > 0 ? 1 : 0;
+    return 0;
+  }
   if (kernel < 0) {  // back to the library's own choice
     c->ck_auto = true;
     c->ck_tuned = c->ckh_tuned = false;
@@ -965,6 +1031,7 @@ int povar_set_series_kernel(povar_ctx* c, int32_t mode) {
   if (int rc = check_ctx(c)) return rc;
   if (mode < -1 || mode > 1) return fail(-1, "unknown series kernel");
   if (mode == 1 && !c->res.ready) return fail(-1, "the resident-series layout was not built for this context");
+  if (mode == 1 && c->fp32_terms) return fail(-1, "POVAR_FLAG_FP32_TERMS: the resident series has no fp32 form");
   if (int rc = res_verify(c)) return rc;
   if (c->deterministic) return 0;  // pinned (POVAR_DETERMINISTIC)
   c->res_mode = mode;
