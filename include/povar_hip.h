@@ -86,8 +86,9 @@ enum {
   /* step 1's power-series terms (solve_pOSE under POVAR_POWER_VARPROJ and POVAR_POWER_SCHUR_COMPLEMENT, povar_power_series_step,
    * povar_right_mul_e0_pose) in single precision: the camera-chunk kernel e0_ck_f32 on a chunk layout povar_create always builds
    * for such a context, rows placed inside the call (as POVAR_FLAG_PLACEMENT(1)).  Numerical contract:
-   *   fp32: the per-observation arithmetic of E0; the landmark slot values (h~, u = Jl^T Jp x, g = G u; u sums in LDS with
-   *         ds_add_f32); the camera records a chunk gathers (Z = sigma_c x_c, P3 and, for HUBER, the translation); the image
+   *   fp32: the per-observation arithmetic of E0; the landmark records (h~ and G = S Hll^-1 S, rounded from fp64 by
+   *         ck32_records) and slot values (h~, u = Jl^T Jp x, g = G u; u sums in LDS with ds_add_f32); the scalars sb^2, sa^2
+   *         and the Huber threshold; the camera records a chunk gathers (Z = sigma_c x_c, P3 and, for HUBER, the translation); the image
    *         points -- packed rows as (float)k * 1e-6f, rows that do not pack stored as float2; HUBER weights recomputed per
    *         observation in fp32 (CAUCHY's are 1); a chunk's own sum (<= 16 observations of one camera);
    *   fp64: every sum across chunks of a camera (the segmented wavefront sum, the LDS accumulators, the partial records, the
