@@ -547,4 +547,34 @@ inline void build_ck(const LplLayout& L, int n_cams, int grid, const std::vector
   });
 }
 
+// e0_ck's first requests of a launch without bt_off in their chain: for every instantiation shape (plane 0..3: one group of 16,
+// 12 or 8 wavefronts, two groups of 8), workgroup and first-round position j of a wavefront (its first tile of its group's
+// first batch b = group is tile_of(tb0, 0) = tb0 + j, its second tb0 + GW + GW - 1 - j: povar_kernels_ck.hpp), one vector load
+// away: meta [plane][grid][16][64] x = rank of the lane's camera in the first tile | rank in the second << 16 (0xffff: empty
+// lane or no such tile), y = the first tile (-1: none); hdr [plane][grid][16] = that tile's header.  Slot s = group * GW + j.
+constexpr int CK_FIRST_PLANES = 4;
+inline int ck_first_gw(int plane) { return plane == 0 ? 16 : plane == 1 ? 12 : 8; }
+inline int ck_first_ng(int plane) { return plane == 3 ? 2 : 1; }
+inline void ck_first_tables(const CkLayout& K, int grid, std::vector<int2>& meta, std::vector<int4>& hdr) {
+  meta.assign((size_t)CK_FIRST_PLANES * grid * 16 * WAVE, make_int2(0xffff | (0xffff << 16), -1));
+  hdr.assign((size_t)CK_FIRST_PLANES * grid * 16, make_int4(0, 0, 0, 0));
+  const int nb = K.nb;
+  auto rank16 = [&](int t, int lane) { const int r = K.lane_cam[(size_t)t * WAVE + lane]; return r < 0 ? 0xffff : (r & 0xffff); };
+  for (int p = 0; p < CK_FIRST_PLANES; ++p) {
+    const int gw = ck_first_gw(p), ng = ck_first_ng(p);
+    for (int w = 0; w < grid; ++w)
+      for (int s = 0; s < ng * gw; ++s) {
+        const int b = s / gw, j = s % gw;
+        if (b >= nb) continue;
+        const int tb0 = K.bt_off[(size_t)w * nb + b], tb1 = K.bt_off[(size_t)w * nb + b + 1];
+        const int t = tb0 + j, t2 = tb0 + gw + (gw - 1 - j);
+        if (t >= tb1) continue;
+        const size_t at = ((size_t)p * grid + w) * 16 + s;
+        hdr[at] = K.tile[t];
+        for (int lane = 0; lane < WAVE; ++lane)
+          meta[at * WAVE + lane] = make_int2(rank16(t, lane) | ((t2 < tb1 ? rank16(t2, lane) : 0xffff) << 16), t);
+      }
+  }
+}
+
 }  // namespace povar

@@ -241,6 +241,12 @@ bool ck_upload(povar_ctx* c, povar_ctx::CkDev& D, const CkLayout& K, bool locked
   up(D.li, K.li); up(D.src, K.src); up(D.tile, K.tile); up(D.lane_meta, meta);
   up(D.bt_off, K.bt_off); up(D.slot_rec, K.slot_rec); up(D.part_range, K.part_range);
   if (c->det_ck) { up(D.lcnt, K.lcnt_log2); up(D.tick, K.tick); }
+  if (need_uv) {  // (step 1's e0_ck)
+    std::vector<int2> fm;
+    std::vector<int4> fh;
+    ck_first_tables(K, K.nb > 0 ? (int)((K.bt_off.size() - 1) / K.nb) : 0, fm, fh);
+    up(D.first_meta, fm); up(D.first_hdr, fh);
+  }
   D.cold_q = K.cold_q;
   if (K.cold_q) up(D.cpos, K.cpos);
   if (ok) guarded([&] { ok = D.part.alloc((size_t)std::max(K.n_part_rec, 1) * 12, bytes) == hipSuccess; });

@@ -163,6 +163,8 @@ struct povar_ctx {
     DevBuf<uint32_t> li;
     DevBuf<int> src, bt_off, slot_rec;
     DevBuf<int2> lane_meta;
+    DevBuf<int2> first_meta;     // e0_ck: the first requests of a launch (ck_first_tables; step 1 only)
+    DevBuf<int4> first_hdr;
     DevBuf<int4> tile;
     DevBuf<int2> part_range;
     DevBuf<double> part, w;
@@ -177,7 +179,7 @@ struct povar_ctx {
     bool ready = false;
     void release() {
       cpos.release(); cold_q = false;
-      uv.release(); uvp.release(); li.release(); src.release(); lane_meta.release(); bt_off.release();
+      uv.release(); uvp.release(); li.release(); src.release(); lane_meta.release(); bt_off.release(); first_meta.release(); first_hdr.release();
       slot_rec.release(); tile.release(); part_range.release(); part.release(); w.release();
       packed = false;
       lcnt.release(); tick.release();

@@ -45,6 +45,8 @@ struct CkP {
   int uv_packed;           // uv holds packed image points (the PK instantiations of e0_ck)
   const int* cpos;         // [rows][64] cold-view position of the entries of chunks WITHOUT an accumulator slot (CkLayout::cpos), or nullptr:
   double4* q4c;            // ... such a lane stores q of every observation there (the per-camera kernel forms h~ (x) q), no record
+  const int2* first_meta;  // the first requests of a launch, by instantiation shape, workgroup and first-round position (ck_first_tables)
+  const int4* first_hdr;
 };
 // a packed image coordinate back to the double it was packed from: the sequence ck_pack_uv (ck_layout.hpp) verified on the host
 // for every entry -- int -> double, a multiplication, two fused multiply-adds: correctly rounded operations, the same bits
@@ -163,14 +165,19 @@ __device__ inline CkRows ck_rows(const CkP& k) {
 template <int D, bool ROBUST, bool PK = false>
 struct CkStream {
   double2 uv[D];
+  unsigned pk[D][2];  // (PK: the packed words.  They are decoded when the row is worked on, not when it is requested: a decode
+                      //  at the request makes the wavefront wait for the row there, and e0_ck requests a batch's first rows in
+                      //  front of the barrier that ends the batch before)
   uint32_t w[D];
   __device__ inline void clear() {
 #pragma unroll
     for (int i = 0; i < D; ++i) {
       uv[i] = make_double2(0, 0);
+      pk[i][0] = pk[i][1] = 0;
       w[i] = 0xffffffffu;
     }
   }
+  __device__ inline double2 get(int i) const { return PK ? make_double2(ck_unpack_uv(pk[i][0]), ck_unpack_uv(pk[i][1])) : uv[i]; }
   // buffer i <- row j of the tile (j clamped into the tile: a request past its end re-reads its last row -- a cache hit --
   // so that every step issues the same loads and the wait counters can be exact: with loads under `if (j < h)` the
   // compiler waited for all but the newest load, i.e. for the row it had requested one step earlier).
@@ -184,7 +191,8 @@ struct CkStream {
     if (PK) {  // packed image points: 8 bytes per observation
       typedef unsigned __attribute__((ext_vector_type(2))) u2;
       const u2 a = __builtin_amdgcn_raw_buffer_load_b64(R.uv, ul * 8u, ro >> 1, 0);
-      uv[i] = make_double2(ck_unpack_uv(a.x), ck_unpack_uv(a.y));
+      pk[i][0] = a.x;
+      pk[i][1] = a.y;
     } else {
       typedef unsigned __attribute__((ext_vector_type(4))) u4;
       const u4 a = __builtin_amdgcn_raw_buffer_load_b128(R.uv, ul * 16u, ro, 0);
@@ -204,7 +212,7 @@ struct CkStream {
 template <int D, bool ROBUST, bool PK>
 __device__ inline void ck_forward_step(const Dp& d, const CkRows& k, CkStream<D, ROBUST, PK>& st, int row0, int li0, int h, int lane,
                                        const double* zz, const double* P3, const double* lh, double* lu, int S, int j, int i) {
-  const double2 uv = st.uv[i];
+  const double2 uv = st.get(i);
   const uint32_t s = (st.w[i] >> (16 * (j & 1))) & 0xffffu;
   st.load(k, row0, li0, j + D, h, lane, i);
   if (s != 0xffffu) {
@@ -229,7 +237,7 @@ __device__ inline void ck_forward_rows(const Dp& d, const CkRows& k, CkStream<D,
 template <int D, bool ROBUST, bool PK>
 __device__ inline void ck_backward_step(const Dp& d, const CkRows& k, CkStream<D, ROBUST, PK>& st, int row0, int li0, int h, int lane,
                                         const double* P3, const double* lh, const double* lg, int S, double* y, int j, int i) {
-  const double2 uv = st.uv[i];
+  const double2 uv = st.get(i);
   const uint32_t s = (st.w[i] >> (16 * (j & 1))) & 0xffffu;
   st.load(k, row0, li0, j - D, h, lane, i);
   if (s != 0xffffu) {
@@ -264,7 +272,7 @@ __device__ inline void ck_backward_rows_cold(const Dp& d, const CkP& k, const Ck
     CkStream<2, ROBUST, PK> one;
     one.load(R, row0, li0, j, h, lane, 0);
     const int cp = cold_lane ? k.cpos[(size_t)(row0 + j) * WAVE + lane] : -1;
-    const double2 uv = one.uv[0];
+    const double2 uv = one.get(0);
     const uint32_t s = (one.w[0] >> (16 * (j & 1))) & 0xffffu;
     if (s != 0xffffu) {
       const double hx = lh[s], hy = lh[s + 1], hz = lh[s + 2];
@@ -464,19 +472,94 @@ __global__ __launch_bounds__(NW * 64) void e0_ck(Dp d, CkP k, double* part_out) 
   auto bt_of = [&](int i, bool first) {
     return (bt_lds && !first) ? __builtin_amdgcn_readfirstlane(lbt[i]) : bt[blockIdx.x * k.nb + i];
   };
-  int rank_next = 0;  // camera ranks of the wavefront's first tile of the next batch (requested with hn)
-  auto request_first_meta = [&](int b, int lane) {
-    rank_next = 0;
+  // EARLY: the first tile of a batch is requested ahead (below).  Not in the instantiations whose row loops leave no registers
+  // for it -- the HUBER weight's and the four-row streams spilled --: they request it at the batch's head, as before.
+  constexpr bool EARLY = !ROBUST && SD == 2;
+  // The next batch's first tile (tile_of(tb0, 0)): its tile range, the camera ranks of the wavefront's first and (EARLY) second
+  // tile and (EARLY) the first tile's header, requested with hn.  The header comes through a VECTOR load (a wave-uniform address; made scalar by
+  // readfirstlane where it is used): a scalar load would count against the lgkmcnt(0) of the barriers in front of its use.
+  int tb0_next = 0, tb1_next = 0, rank_next = 0, rank_next2 = 0;
+  ck_u4 hdr_next = {0, 0, 0, 0};
+  auto request_first_meta = [&](int b, int lane, bool ranks) {
+    tb0_next = tb1_next = 0;
     if (b < k.nb) {
-      const int tb0 = bt_of(b, b == grp), tb1 = bt_of(b + 1, b == grp);
-      if (tb0 + wave_t < tb1) rank_next = ck_rank(k.lane_meta[(size_t)(tb0 + wave_t) * WAVE + lane].x);
+      tb0_next = bt_of(b, b == grp);
+      tb1_next = bt_of(b + 1, b == grp);
+    }
+    if (!ranks) return;  // (the first batch of an EARLY instantiation: its ranks and header came from CkP::first_meta / first_hdr)
+    rank_next = rank_next2 = 0;
+    hdr_next = ck_u4{0, 0, 0, 0};
+    if (b < k.nb) {
+      const int tf = tile_of(tb0_next, 0), tf2 = tile_of(tb0_next, 1);
+      if (tf < tb1_next && !EARLY) rank_next = ck_rank(k.lane_meta[(size_t)tf * WAVE + lane].x);
+      if (tf < tb1_next && EARLY) {
+        const __amdgpu_buffer_rsrc_t TR = __builtin_amdgcn_make_buffer_rsrc(const_cast<int4*>(k.tile), 0, 0x7ffffff0, 0x00020000);
+        hdr_next = __builtin_amdgcn_raw_buffer_load_b128(TR, 0u, (unsigned)tf * 16u, 0);
+        rank_next = ck_rank(k.lane_meta[(size_t)tf * WAVE + lane].x);
+        if (tf2 < tb1_next) rank_next2 = ck_rank(k.lane_meta[(size_t)tf2 * WAVE + lane].x);
+      }
     }
   };
-  request_first_meta(grp, lane0);
-  request_h(grp, lane0);
+  // The first tile of a batch is requested when the wavefront has walked its last tile of the batch before (and in front of
+  // the first batch's LDS set-up): Z, P3 and first rows are in flight during the last tiles of the other wavefronts and the
+  // barrier that ends the batch, where they used to be requested behind it -- sixteen wavefronts' record gathers through one
+  // texture addresser, 9 k cycles per batch before any row was walked (profiles/r06_e0_ck_phase_stamps_final.txt).  Z first,
+  // the rows last: the wait for zz behind the first barrier then leaves the rows in flight.  Lives from here into the batch's
+  // way forward; zz and the rows are dead on the way back before it, P3 is dead after the last tile's rows.
+  double zz[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, P3[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // (P3[9..11]: t, HUBER only)
+  CkStream<SD, ROBUST, PK> st;
+  st.clear();
+  int row0 = 0, h = 0, fl = 0, li0 = 0;
+  auto request_first_tile = [&](int lane, bool have) {
+    const int tf = tile_of(tb0_next, 0);
+    const int rk = rank_next < 0 ? 0 : rank_next;
+    if (have && EARLY) {
+      row0 = __builtin_amdgcn_readfirstlane((int)hdr_next.x);
+      h = __builtin_amdgcn_readfirstlane((int)hdr_next.y);
+      fl = __builtin_amdgcn_readfirstlane((int)hdr_next.z);
+      li0 = __builtin_amdgcn_readfirstlane((int)hdr_next.w);
+      ck_load_z_img(d, rk, zz);
+      ck_load_p<ROBUST>(d, rk, P3);
+      st.template start<1>(R, row0, li0, h, lane);
+    } else if (have) {  // (the order of the batch head: Z last, the youngest request)
+      const int tf2 = tile_of(tb0_next, 1);
+      row0 = tiles[4 * tf]; h = tiles[4 * tf + 1]; fl = tiles[4 * tf + 2]; li0 = tiles[4 * tf + 3];
+      if (tf2 < tb1_next) rank_next2 = ck_rank(k.lane_meta[(size_t)tf2 * WAVE + lane].x);
+      ck_load_p<ROBUST>(d, rk, P3);
+      st.template start<1>(R, row0, li0, h, lane);
+      ck_load_z_img(d, rk, zz);
+    } else {  // (every value defined on this path too: see the batch loop)
+#pragma unroll
+      for (int e = 0; e < 12; ++e) zz[e] = P3[e] = 0;
+      st.clear();
+      row0 = h = fl = li0 = 0;
+    }
+  };
+  int bt_first = 0;
+  if (bt_lds && (int)threadIdx.x <= k.nb) bt_first = k.bt_off[blockIdx.x * k.nb + threadIdx.x];
+  // The first batch (EARLY): ranks, tile and header of the wavefront's first tile from the layout's table -- two vector loads
+  // indexed by the workgroup and the wavefront, where the chain was bt_off (a scalar miss) -> lane metadata -> gathers -- and
+  // its gathers and first rows in flight before the accumulators are zeroed.
+  if (EARLY) {
+    static_assert(!EARLY || (NG == 1 && (GW == 16 || GW == 12 || GW == 8)) || (NG == 2 && GW == 8), "shape without a first-request table");
+    constexpr int PLANE = NG > 1 ? 3 : GW == 16 ? 0 : GW == 12 ? 1 : 2;  // (ck_first_tables)
+    const unsigned fs = (PLANE * gridDim.x + blockIdx.x) * 16u + (unsigned)(grp * GW + wave_t);
+    const int2 fm = k.first_meta[(size_t)fs * WAVE + lane0];
+    const __amdgpu_buffer_rsrc_t HR = __builtin_amdgcn_make_buffer_rsrc(const_cast<int4*>(k.first_hdr), 0, 0x7ffffff0, 0x00020000);
+    hdr_next = __builtin_amdgcn_raw_buffer_load_b128(HR, 0u, fs * 16u, 0);
+    request_h(grp, lane0);
+    const int r1 = fm.x & 0xffff, r2 = (fm.x >> 16) & 0xffff;
+    rank_next = r1 == 0xffff ? -1 : r1;
+    rank_next2 = r2 == 0xffff ? -1 : r2;
+    request_first_tile(lane0, __builtin_amdgcn_readfirstlane(fm.y) >= 0);
+    request_first_meta(grp, lane0, false);
+  } else {
+    request_first_meta(grp, lane0, true);
+    request_h(grp, lane0);
+  }
   for (int i = threadIdx.x; i < n_acc * CK_ACC_STRIDE; i += NW * 64) acc[i] = 0;
   if (NG > 1 && threadIdx.x < NG) gbase[threadIdx.x] = 0;
-  if (bt_lds && (int)threadIdx.x <= k.nb) lbt[threadIdx.x] = k.bt_off[blockIdx.x * k.nb + threadIdx.x];
+  if (bt_lds && (int)threadIdx.x <= k.nb) lbt[threadIdx.x] = bt_first;
   if (NG > 1) ck_barrier();  // accumulators and counters are zero before any group goes on (NG = 1: the first batch barrier)
   for (int b = grp; b < k.nb; b += NG) {
     // The lane number is made opaque per batch (and again per pass): every per-lane address of the body (a dozen 64-bit
@@ -486,14 +569,10 @@ __global__ __launch_bounds__(NW * 64) void e0_ck(Dp d, CkP k, double* part_out) 
     // VGPRs held across the way back; the row loop's camera record went to scratch: 8 reloads per row).
     int lane = lane0;
     asm volatile("" : "+v"(lane));
-    const int tb0 = bt_of(b, b == grp), tb1 = bt_of(b + 1, b == grp);
+    const int tb0 = tb0_next, tb1 = tb1_next;
     int q_t = 0;  // round of the tile walk
     int t = tile_of(tb0, 0);
     int rank = rank_next;
-    double zz[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, P3[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // (P3[9..11]: t, HUBER only)
-    CkStream<SD, ROBUST, PK> st;
-    st.clear();
-    int row0 = 0, h = 0, fl = 0, li0 = 0;
     // (Order of the requests: the rows of a tile are requested after everything else of its phase.  The wait counters
     // retire in issue order; with younger loads pending behind the rows, the compiler's merge of the loop-entry and
     // back-edge states at the head of the row loop came out as s_waitcnt vmcnt(0): every row waited for the row
@@ -504,19 +583,13 @@ __global__ __launch_bounds__(NW * 64) void e0_ck(Dp d, CkP k, double* part_out) 
     // then starts without the 8-9 thousand cycles (gather + rows, one dependent round trip under load) that made the
     // four wavefronts with a second tile the tail of every pass.
     int tn = tile_of(tb0, 1);
-    int rank_n = 0, rank_nn = 0;
+    if (!EARLY) request_first_tile(lane, t < tb1);
+    int rank_n = rank_next2, rank_nn = 0;
     double zn[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, Pn[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     CkStream<SD, ROBUST, PK> stn;
     stn.clear();
     int row0n = 0, hnx = 0, fln = 0, li0n = 0;
-    // ---- the way forward starts: record and first rows of the first tile (the metadata came with the last phase)
-    if (t < tb1) {
-      row0 = tiles[4 * t]; h = tiles[4 * t + 1]; fl = tiles[4 * t + 2]; li0 = tiles[4 * t + 3];
-      if (tn < tb1) rank_n = ck_rank(k.lane_meta[(size_t)tn * WAVE + lane].x);
-      ck_load_p<ROBUST>(d, rank < 0 ? 0 : rank, P3);
-      st.template start<1>(R, row0, li0, h, lane);
-    }
-    if (t < tb1) ck_load_z_img(d, rank < 0 ? 0 : rank, zz);
+    // ---- the way forward starts: record and first rows of the first tile are in flight (request_first_tile)
     // ---- landmark coordinates of the batch into LDS (requested a phase ago), u = 0
 #pragma unroll
     for (int q = 0; q < HM; ++q) {
@@ -555,8 +628,8 @@ __global__ __launch_bounds__(NW * 64) void e0_ck(Dp d, CkP k, double* part_out) 
     };
     request_next_fwd();
     group_barrier();
-    // (Z is the youngest request of the first tile: waited for HERE, once -- left to the row loop's first use the compiler
-    // merges the loop's entry and back-edge states into a wait for every outstanding load at the head of each row)
+    // (Z is waited for HERE, once -- left to the row loop's first use the compiler merges the loop's entry and back-edge
+    // states into a wait for every outstanding load at the head of each row)
 #pragma unroll
     for (int e = 0; e < 12; ++e) asm volatile("" : "+v"(zz[e]));
     // ---- forward
@@ -616,7 +689,7 @@ __global__ __launch_bounds__(NW * 64) void e0_ck(Dp d, CkP k, double* part_out) 
       st.template start<-1>(R, row0, li0, h, lane);
     }
     group_barrier();
-    request_first_meta(b + NG, lane);  // the next batch is started from here: its coordinates and first metadata are in
+    request_first_meta(b + NG, lane, true);  // the next batch is started from here: its coordinates and first metadata are in
     request_h(b + NG, lane);           // flight during the way back (behind the barrier: see lbt)
     // ---- g = G u per landmark slot (over u)
 #pragma unroll
@@ -692,6 +765,7 @@ __global__ __launch_bounds__(NW * 64) void e0_ck(Dp d, CkP k, double* part_out) 
         st.template start<-1>(R, row0, li0, h, lane);
       }
     }
+    if (EARLY) request_first_tile(lane, tile_of(tb0_next, 0) < tb1_next);
     group_barrier();  // the next batch overwrites h~ and u; after the last one: the accumulators are complete
   }
   if (NG > 1) ck_barrier();  // every group is done: the accumulators are complete

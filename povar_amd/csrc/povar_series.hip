@@ -4,7 +4,8 @@
 CkP ck_params(const povar_ctx* c, const povar_ctx::CkDev& D) {
   return CkP{D.packed ? reinterpret_cast<const double2*>(D.uvp.p) : D.uv.p, D.li.p, D.w.p, D.tile.p, D.lane_meta.p, D.bt_off.p, D.slot_rec.p,
              D.nb, D.slots, (unsigned)(D.src.n * (D.packed ? sizeof(int2) : sizeof(double2))), (unsigned)(D.li.n * sizeof(uint32_t)),
-             D.lcnt.p, D.tick.p, D.max_acc, D.packed ? 1 : 0, D.cold_q ? D.cpos.p : nullptr, c->q4c.p};
+             D.lcnt.p, D.tick.p, D.max_acc, D.packed ? 1 : 0, D.cold_q ? D.cpos.p : nullptr, c->q4c.p,
+             D.first_meta.p, D.first_hdr.p};
 }
 
 CkP ck_params(const povar_ctx* c) { return ck_params(c, c->ck); }

@@ -40,6 +40,10 @@ nb = li.ck_batches
 names = ["start", "h in LDS", "gather issued", "barrier1", "fwd done", "barrier2", "Gu+barrier3", "bwd done"]
 t0 = s[:, :nw, 0].min(axis=1, keepdims=True)  # the workgroup's first wavefront to start
 print(f"cycles since the workgroup's start, median over {li.grid} workgroups; columns: wavefronts 0..{nw - 1}")
+entry = (s[:, :nw, 36] > 0).all()  # stamp 36: the kernel's entry (from the build that requests batch 0's first tile before "start")
+if entry:
+    v = np.median(s[:, :nw, 36] - t0, axis=0)
+    print(f"   {'kernel entry':14s}" + "".join(f"{x / 1000:7.1f}" for x in v))
 for b in range(nb):
     for i, nm in enumerate(names):
         v = np.median(s[:, :nw, 8 * b + i] - t0, axis=0)
@@ -50,6 +54,11 @@ for i, nm in ((8 * nb, "last barrier"), (8 * nb + 1, "flushed")):
 for i, nm in ((20, 'b0 fwd tile0 done'), (21, 'b0 tile1 issued'), (22, 'b0 fwd tile1 done')):
     v = np.median(s[:, :nw, i] - t0, axis=0)
     print(f"   {nm:14s}" + "".join(f"{x / 1000:7.1f}" for x in v))
+# the prologue of each batch: from the batch's start (the last barrier of the batch before; batch 0: the workgroup's first
+# start stamp, or its first kernel-entry stamp where the build has one) to the barrier in front of its way forward
+for b in range(nb):
+    st0 = (s[:, :nw, 36].min(axis=1) if entry else t0[:, 0]) if b == 0 else np.median(s[:, :nw, 8 * b], axis=1)
+    print(f"b{b} start -> barrier1: {np.median(np.median(s[:, :nw, 8 * b + 3], axis=1) - st0) / 1000:.1f} k cycles (median over workgroups)")
 # Who does a barrier wait for?  Per workgroup: the wavefront that reaches "fwd done" / "bwd done" LAST, how far behind the
 # workgroup's median wavefront it is, whether it walked a second tile (stamp 22 set), and what is left between its arrival
 # and the barrier opening (the drain of its LDS traffic + the barrier itself)
@@ -89,9 +98,9 @@ for b in range(min(nb, 4)):
         prev = cur
     print(f"   the last wavefront to finish its rows: " + ", ".join(parts))
 # the kernel ends with its slowest workgroup: duration (first wavefront's start -> flushed) over the workgroups
-dur = s[:, :nw, 8 * nb + 1].max(axis=1) - s[:, :nw, 0].min(axis=1)
+dur = s[:, :nw, 8 * nb + 1].max(axis=1) - (s[:, :nw, 36] if entry else s[:, :nw, 0]).min(axis=1)  # (from the entry where stamped)
 order = np.argsort(dur)
-print("workgroup durations (k cycles): min %.1f  10 %% %.1f  median %.1f  90 %% %.1f  max %.1f;  slowest workgroups: %s" % (
+print("workgroup durations (k cycles, first " + ("kernel entry" if entry else "start") + " -> flushed): min %.1f  10 %% %.1f  median %.1f  90 %% %.1f  max %.1f;  slowest workgroups: %s" % (
     dur.min() / 1000, np.percentile(dur, 10) / 1000, np.median(dur) / 1000, np.percentile(dur, 90) / 1000, dur.max() / 1000,
     " ".join(f"{int(w)}:{dur[w] / 1000:.1f}" for w in order[-6:][::-1])))
 ctx.close()

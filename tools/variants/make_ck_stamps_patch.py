@@ -38,7 +38,7 @@ def main():
     open(p, "w").write(s)
     p = os.path.join(b, "povar_series.hip")
     s = open(p).read()
-    s = sub(s, "D.packed ? 1 : 0, D.cold_q ? D.cpos.p : nullptr, c->q4c.p};", "D.packed ? 1 : 0, D.cold_q ? D.cpos.p : nullptr, c->q4c.p, c->ck_stamps.p};")
+    s = sub(s, "D.first_meta.p, D.first_hdr.p};", "D.first_meta.p, D.first_hdr.p, c->ck_stamps.p};")
     i = s.index("int povar_debug_ck_stamps(povar_ctx* c, uint64_t* out, int64_t n) {")
     j = s.index("\n}\n", i) + 3
     s = s[:i] + """int povar_debug_ck_stamps(povar_ctx* c, uint64_t* out, int64_t n) {
@@ -71,8 +71,8 @@ def main():
     # ---- povar_kernels_ck.hpp
     p = os.path.join(b, "povar_kernels_ck.hpp")
     s = open(p).read()
-    s = sub(s, "  double4* q4c;            // ... such a lane stores q of every observation there (the per-camera kernel forms h~ (x) q), no record\n};",
-            "  double4* q4c;            // ... such a lane stores q of every observation there (the per-camera kernel forms h~ (x) q), no record\n"
+    s = sub(s, "  const int4* first_hdr;\n};",
+            "  const int4* first_hdr;\n"
             "  unsigned long long* stamps;  // diagnostic build: [grid][16][CK_N_STAMPS] s_memtime stamps, else nullptr\n};\n"
             "constexpr int CK_N_STAMPS = 40;\n"
             "#ifndef POVAR_CK_NO_STAMPS  // (the timing-only experiment builds are compiled with -DPOVAR_CK_NO_STAMPS)\n"
@@ -114,23 +114,26 @@ def main():
             "    const int rec = k.slot_rec[cam0 + r];\n#if defined(POVAR_CK_EXP_NOPART) || defined(POVAR_CK_EXP_NOPART_FLUSH)\n"
             "    if (acc[r * CK_ACC_STRIDE + m] == 1.2345e300)\n#endif\n    ck_store_part(")
     # stamps
-    s = sub(s, "    asm volatile(\"\" : \"+v\"(lane));\n    const int tb0 = bt_of(b, b == grp), tb1 = bt_of(b + 1, b == grp);\n    int q_t = 0;",
-            "    asm volatile(\"\" : \"+v\"(lane));\n    CK_STAMP(8 * (b / NG) + 0);\n    const int tb0 = bt_of(b, b == grp), tb1 = bt_of(b + 1, b == grp);\n    int q_t = 0;")
-    s = sub(s, "    if (t < tb1) ck_load_z_img(d, rank < 0 ? 0 : rank, zz);\n", "    if (t < tb1) ck_load_z_img(d, rank < 0 ? 0 : rank, zz);\n    CK_STAMP(8 * (b / NG) + 1);\n")
+    # (stamp 36: the kernel's entry -- batch 0's first tile is requested in front of its "start" stamp)
+    s = sub(s, "  int bt_first = 0;\n", "  CK_STAMP(36);\n  int bt_first = 0;\n")
+    s = sub(s, "    asm volatile(\"\" : \"+v\"(lane));\n    const int tb0 = tb0_next, tb1 = tb1_next;\n    int q_t = 0;",
+            "    asm volatile(\"\" : \"+v\"(lane));\n    CK_STAMP(8 * (b / NG) + 0);\n    const int tb0 = tb0_next, tb1 = tb1_next;\n    int q_t = 0;")
+    s = sub(s, "    if (!EARLY) request_first_tile(lane, t < tb1);\n", "    if (!EARLY) request_first_tile(lane, t < tb1);\n    CK_STAMP(8 * (b / NG) + 1);\n")
     s = sub(s, "    request_next_fwd();\n    group_barrier();\n", "    request_next_fwd();\n    CK_STAMP(8 * (b / NG) + 2);\n    group_barrier();\n    CK_STAMP(8 * (b / NG) + 3);\n")
     s = sub(s, "      ck_forward_rows<SD, ROBUST, PK>(d, R, st, row0, li0, h, lane, zz, P3, lh, lu, S);\n",
             "      ck_forward_rows<SD, ROBUST, PK>(d, R, st, row0, li0, h, lane, zz, P3, lh, lu, S);\n      if (b < NG) CK_STAMP(20 + 2 * q_t);\n")
     s = sub(s, "    // ---- the way back starts before the barriers in front of it:", "    CK_STAMP(8 * (b / NG) + 4);\n    // ---- the way back starts before the barriers in front of it:")
-    s = sub(s, "      st.template start<-1>(R, row0, li0, h, lane);\n    }\n    group_barrier();\n    request_first_meta(b + NG, lane);",
+    s = sub(s, "      st.template start<-1>(R, row0, li0, h, lane);\n    }\n    group_barrier();\n    request_first_meta(b + NG, lane, true);",
             "      CK_STAMP(24 + 4 * (b / NG));      // G + metadata of the way back requested\n"
             "      st.template start<-1>(R, row0, li0, h, lane);\n    }\n"
             "    CK_STAMP(25 + 4 * (b / NG));        // ... and its first rows\n"
             "    asm volatile(\"s_waitcnt lgkmcnt(0)\" ::: \"memory\");\n"
             "    CK_STAMP(26 + 4 * (b / NG));        // LDS atomics + scalar loads drained (what the barrier's lgkmcnt(0) waits for)\n"
-            "    group_barrier();\n    CK_STAMP(8 * (b / NG) + 5);\n    request_first_meta(b + NG, lane);")
+            "    group_barrier();\n    CK_STAMP(8 * (b / NG) + 5);\n    request_first_meta(b + NG, lane, true);")
     s = sub(s, "    request_next_bwd();\n    group_barrier();\n", "    request_next_bwd();\n    group_barrier();\n    CK_STAMP(8 * (b / NG) + 6);\n")
-    s = sub(s, "    group_barrier();  // the next batch overwrites h~ and u; after the last one: the accumulators are complete\n",
-            "    CK_STAMP(8 * (b / NG) + 7);\n    group_barrier();  // the next batch overwrites h~ and u; after the last one: the accumulators are complete\n")
+    s = sub(s, "    if (EARLY) request_first_tile(lane, tile_of(tb0_next, 0) < tb1_next);\n    group_barrier();  // the next batch overwrites h~ and u; after the last one: the accumulators are complete\n",
+            "    CK_STAMP(8 * (b / NG) + 7);\n    if (EARLY) request_first_tile(lane, tile_of(tb0_next, 0) < tb1_next);\n"
+            "    group_barrier();  // the next batch overwrites h~ and u; after the last one: the accumulators are complete\n")
     s = sub(s, "  // ---- accumulators -> this workgroup's partial records (camera-major in part_out)\n  const __amdgpu_buffer_rsrc_t PR",
             "  CK_STAMP(8 * (k.nb / NG));\n  // ---- accumulators -> this workgroup's partial records (camera-major in part_out)\n  const __amdgpu_buffer_rsrc_t PR")
     s = sub(s, "  if (d.p2p_epoch && blockIdx.x == 0 && threadIdx.x == 0) *d.p2p_epoch += 1;  // one tick per term (as e0_lpl)",
