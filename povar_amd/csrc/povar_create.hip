@@ -578,51 +578,9 @@ int povar_create(povar_ctx** out, int32_t n_cams, int32_t n_lms, int64_t n_obs,
     c->e0c_bins_per_wg = std::max((c->n_bins + cus - 1) / cus, 1);
     c->e0c_grid = (c->n_bins + c->e0c_bins_per_wg - 1) / c->e0c_bins_per_wg;
     c->n_hot = std::min(n_cams, HOT_MAX);
-    HIP_TRY_C(hipFuncSetAttribute((const void*)e0_lm_cached<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                HOT_MAX * HOT_REC * (int)sizeof(double2)));
-    HIP_TRY_C(hipFuncSetAttribute((const void*)e0_tiles_cached, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                HOT_ACC_MAX * (HOT_REC_T * (int)sizeof(double2) + 96)));
-    HIP_TRY_C(hipFuncSetAttribute((const void*)e0_lm_cached_h, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                HOT_ACC_MAX * (HOT_REC_H * (int)sizeof(double2) + 96)));
-    HIP_TRY_C(hipFuncSetAttribute((const void*)e0_lm_cached<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                HOT_ACC_MAX * (HOT_REC * (int)sizeof(double2) + 96)));
-    HIP_TRY_C(hipFuncSetAttribute((const void*)e0_lpl<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lpl_lds_bytes(HOT_ACC_MAX)));
-    HIP_TRY_C(hipFuncSetAttribute((const void*)e0_lpl<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lpl_lds_bytes(HOT_ACC_MAX)));
-    HIP_TRY_C(hipFuncSetAttribute((const void*)e0_lpl_h<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lpl_lds_bytes_h(HOT_ACC_MAX)));
-    HIP_TRY_C(hipFuncSetAttribute((const void*)e0_lpl_h<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lpl_lds_bytes_h(HOT_ACC_MAX)));
-    HIP_TRY_C(hipFuncSetAttribute((const void*)prepare_lpl<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)prep_lds_bytes(HOT_ACC_MAX)));
-    HIP_TRY_C(hipFuncSetAttribute((const void*)prepare_lpl<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)prep_lds_bytes(HOT_ACC_MAX)));
-    HIP_TRY_C(hipFuncSetAttribute((const void*)lpl_pass_h<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)pass_lds_bytes(HOT_ACC_MAX)));
-    HIP_TRY_C(hipFuncSetAttribute((const void*)lpl_pass_h<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)pass_lds_bytes(HOT_ACC_MAX)));
-    HIP_TRY_C(hipFuncSetAttribute((const void*)backsub_lpl_h<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)back_lds_bytes_h(HOT_ACC_MAX)));
-    HIP_TRY_C(hipFuncSetAttribute((const void*)backsub_lpl_h<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)back_lds_bytes_h(HOT_ACC_MAX)));
-    HIP_TRY_C(hipFuncSetAttribute((const void*)lpl_pass<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)pass_lds_bytes(HOT_ACC_MAX)));
-    HIP_TRY_C(hipFuncSetAttribute((const void*)lpl_pass<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)pass_lds_bytes(HOT_ACC_MAX)));
-    HIP_TRY_C(hipFuncSetAttribute((const void*)backsub_lpl<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)back_lds_bytes(HOT_ACC_MAX)));
-    HIP_TRY_C(hipFuncSetAttribute((const void*)backsub_lpl<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)back_lds_bytes(HOT_ACC_MAX)));
-    HIP_TRY_C(hipFuncSetAttribute((const void*)prepare_lpl_h<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)prep_lds_bytes(HOT_ACC_MAX)));
-    HIP_TRY_C(hipFuncSetAttribute((const void*)prepare_lpl_h<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)prep_lds_bytes(HOT_ACC_MAX)));
-    HIP_TRY_C(ck_set_lds_all());
-    HIP_TRY_C(hipFuncSetAttribute((const void*)e0_ck_h<16, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, CK_LDS_BYTES));
-    HIP_TRY_C(hipFuncSetAttribute((const void*)e0_ck_h<16, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CK_LDS_BYTES));
-    HIP_TRY_C(hipFuncSetAttribute((const void*)e0_ck_h<16, 2, false, CKH_STRIDE_WIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, CK_LDS_BYTES));
-    HIP_TRY_C(hipFuncSetAttribute((const void*)e0_ck_h<16, 2, true, CKH_STRIDE_WIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, CK_LDS_BYTES));
+    // (dynamic LDS of the kernels each unit launches, set on that unit's instantiations)
+    HIP_TRY_C(term_set_lds_all());
+    HIP_TRY_C(lm_set_lds_all());
   }
   // per-term E0 kernel of step 1: e0_lpl (0) or an e0_ck instantiation (POVAR_E0_CK=<variant>, povar_set_e0_kernel)
   {
@@ -1088,8 +1046,8 @@ int povar_get_layout_info(povar_ctx* c, povar_layout_info* out) {
   out->hubs = c->d.v2.hubs;
   out->placement = c->placement;
   out->placement_ms = c->placer_state.load(std::memory_order_acquire) >= 2 ? c->placement_ms : 0.0;
-  out->e0_kernel = c->ck_variant > 0 && c->ck.ready && c->use_lpl && c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC && ck_variant_fits(c, c->ck_variant) ? c->ck_variant : 0;
-  if (c->deterministic) out->e0_kernel = ck_det_possible(c) ? CK_VARIANTS + 1 : 0;  // (the fixed-point form of e0_ck)
+  const TermPlan p1 = term_plan(c, 1, TermUse::series), p2 = term_plan(c, 2, TermUse::series);
+  out->e0_kernel = p1.e0 == E0K::ck_det ? CK_VARIANTS + 1 : p1.variant;  // (e0_ck_f32 runs the layout of variant 1)
   out->ck_ready = c->ck.ready ? 1 : 0;
   out->ck_batches = c->ck.nb;
   out->ck_slots = c->ck.slots;
@@ -1102,9 +1060,7 @@ int povar_get_layout_info(povar_ctx* c, povar_layout_info* out) {
   out->e0_auto = c->ck_auto ? (c->ck_tuned ? 2 : 1) : 0;
   out->tune_lpl_us = c->ck_tune_us[0];
   out->tune_ck_us = c->ck_tune_us[1];
-  out->e0_kernel_h = c->ckh_variant > 0 && c->ckh.ready && c->use_lpl && c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC &&
-                     c->ckh.slots <= c->ckh.stride ? 1 : 0;
-  if (c->deterministic) out->e0_kernel_h = ckh_det_possible(c) ? 2 : 0;  // (2: e0_ck_h_det)
+  out->e0_kernel_h = p2.e0 == E0K::ck_h_det ? 2 : p2.e0 == E0K::ck_h ? 1 : 0;
   out->ckh_ready = c->ckh.ready ? 1 : 0;
   out->ckh_batches = c->ckh.nb;
   out->ckh_slots = c->ckh.slots;

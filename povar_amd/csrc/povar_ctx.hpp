@@ -219,7 +219,6 @@ struct povar_ctx {
   bool det_check = false;        // a series of e0_ck_det is in flight whose failure bit (flags[0] & 8) has not been looked at
   // POVAR_FLAG_FP32_TERMS: step 1's terms run e0_ck_f32 (povar_kernels_ck_f32.hpp) on the layout of variant 1
   bool fp32_terms = false;
-  bool fp32_hold = false;        // set while the explicit-SC solvers apply E0 (e0_dense): they run the fp64 kernels
   int32_t fp32_last = 0;         // 1: the last step-1 power series ran its terms in fp32 (povar_layout_info.fp32_terms)
   DevBuf<float2> ck32_uv;        // [rows][64] fp32 image points of the chunk rows (only where the rows do not pack)
   DevBuf<float> ck32_lmrec;      // [lpl tiles][9][64] fp32 h~ and G of the landmark lanes (ck32_records, after every prepare)
@@ -359,6 +358,53 @@ void launch_reduce(povar_ctx* c, double* out) {
 
 inline bool sharded(const povar_ctx* c) { return c->comm != nullptr || c->host_fn != nullptr; }
 
+// the lane-per-landmark kernels run the context (use_lpl in the LDS-accumulating mode): e0_lpl[_h] / e0_ck* for the terms,
+// lpl_pass[_h] for linearisation and cost, and ldsacc_dp's cold view and partial records are theirs
+inline bool lpl_mode(const povar_ctx* c) { return c->use_lpl && c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC; }
+
+// ---- one application of E0 in a power-series term: which kernels run it (term_plan), and the one launcher (launch_e0)
+// who applies E0: the term loop of a series (with the norms of its check or without), povar_right_mul_e0_pose (the fp32
+// terms cover it), the explicit-SC solvers (e0_dense: always fp64), the timing of the two E0 kernels (ck_autotune)
+enum class TermUse { series, series_norms, right_mul, dense, timing };
+enum class E0K {
+  lm_cached,      // e0_lm_cached<false>: lane per observation (POVAR_E0_IMPLICIT)
+  lm_cached_acc,  // e0_lm_cached<true>: ... accumulating in LDS (POVAR_E0_IMPLICIT_LDSACC without lane per landmark)
+  lm_tiles,       // lm_regular<OpE0Tiles> (POVAR_E0_TILES)
+  tiles_cached,   // e0_tiles_cached (POVAR_E0_TILES_LDSACC)
+  lpl,            // e0_lpl: lane per landmark, cameras in LDS
+  ck,             // e0_ck<variant>: lane per camera chunk, landmarks in LDS
+  ck_det,         // e0_ck_det (POVAR_DETERMINISTIC)
+  ck_f32,         // e0_ck_f32 (POVAR_FLAG_FP32_TERMS)
+  lm_h,           // step 2: lm_regular<OpE0H> (outside the LDS-accumulating mode)
+  lm_cached_h,    // e0_lm_cached_h
+  lpl_h,          // e0_lpl_h
+  ck_h,           // e0_ck_h (stride CKH_STRIDE or CKH_STRIDE_WIDE)
+  ck_h_det,       // e0_ck_h_det
+};
+enum class CamStep {  // the per-camera kernel behind the E0 kernel
+  scatter,      // cm_scatter: item sums (cam_binv_axpy mode 1)
+  scatter_sum,  // cm_scatter + cam_sum_items: dense y (sharded)
+  sum,          // cam_cold_sum[_h]: dense y
+  fused,        // cam_cold_sum_binv[_h]: B^-1, AXPY and z too
+};
+enum class Exch { none, allreduce, p2p };  // y across the ranks: ... or the peer-to-peer push of cam_cold_sum
+struct TermPlan {
+  int step = 1;
+  TermUse use = TermUse::series;
+  E0K e0 = E0K::lm_cached;
+  int variant = 0;          // e0_ck / e0_ck_f32: the instantiation whose layout runs (POVAR_CK_VARIANTS); e0_ck_h: 1
+  bool long_after = false;  // lm_long of the E0 kernel's operator follows (the long landmarks)
+  CamStep cam = CamStep::scatter;
+  Exch exch = Exch::none;
+  bool ck() const { return e0 == E0K::ck || e0 == E0K::ck_det || e0 == E0K::ck_f32 || e0 == E0K::ck_h || e0 == E0K::ck_h_det; }
+  // what the caller must look at once the series is done: the tickets of e0_ck[_h]_det (flags[0] & 8), the waits of the
+  // peer-to-peer exchange (flags[0] & 2)
+  bool det_check() const { return e0 == E0K::ck_det || e0 == E0K::ck_h_det; }
+  bool p2p_check() const { return exch == Exch::p2p; }
+  // what cam_binv_axpy does next: 1 item sums, 2 dense y, 4 nothing (fused), 5 wait for the world's slabs
+  int binv_mode() const { return cam == CamStep::fused ? 4 : exch == Exch::p2p ? 5 : cam == CamStep::scatter ? 1 : 2; }
+};
+
 // the per-term exchange runs through the peer-to-peer kernels: no library / host call inside the term loop
 
 // povar_timings: a pair of events on the context's stream around an entry point (kinds: 0 linearize, 1 prepare,
@@ -403,39 +449,18 @@ struct EventSet {
 
 
 // ---- functions one translation unit defines and another calls
-CkP ck_params(const povar_ctx* c, const povar_ctx::CkDev& D);  // povar_series.hip
-CkP ck_params(const povar_ctx* c);  // povar_series.hip
-bool ck_det_possible(const povar_ctx* c);  // povar_series.hip
-bool ck_det_active(const povar_ctx* c);  // povar_series.hip
-bool ck_active(const povar_ctx* c);  // povar_series.hip
-bool ckh_det_possible(const povar_ctx* c);  // povar_series.hip
-bool ckh_active(const povar_ctx* c);  // povar_series.hip
-void ck_dp(const povar_ctx* c, Dp& da);  // povar_series.hip
-bool ck_variant_fits(const povar_ctx* c, int variant);  // povar_series.hip
-void launch_e0_ck(povar_ctx* c, const Dp& da);  // povar_series.hip
-hipError_t ck_set_lds_all();  // povar_series.hip
-void ensure_ck_w(povar_ctx* c);  // povar_series.hip
-bool ck32_active(const povar_ctx* c);  // povar_series.hip
+TermPlan term_plan(const povar_ctx* c, int step, TermUse use, int variant = -1);  // povar_series.hip
+int launch_e0(povar_ctx* c, const TermPlan& p);  // povar_series.hip
+hipError_t term_set_lds_all();  // povar_series.hip
 void launch_ck32_records(povar_ctx* c);  // povar_series.hip
-void launch_e0_ck_h(povar_ctx* c, const Dp& da);  // povar_series.hip
 bool res_variant_exists(int nw, int h, int rr, int ls);  // povar_series.hip
-void launch_res(povar_ctx* c, const ResP& k);  // povar_series.hip
 hipError_t res_set_lds_all();  // povar_series.hip
-bool res_possible(const povar_ctx* c);  // povar_series.hip
 bool res_active(const povar_ctx* c);  // povar_series.hip
-ResP res_params(const povar_ctx* c, int m, double q_tol, double r_tol);  // povar_series.hip
-int enqueue_series_res(povar_ctx* c, int32_t m, double q_tol, double r_tol);  // povar_series.hip
 void prof_mark(povar_ctx* c, int kind);  // povar_series.hip
 Dp ldsacc_dp(povar_ctx* c, bool long_in_kernel = false);  // povar_series.hip
-int launch_e0(povar_ctx* c, int* binv_mode, int fuse_norms = -1);  // povar_series.hip
-void launch_binv(povar_ctx* c, int mode, int want_norms);  // povar_series.hip
-int ck_autotune(povar_ctx* c);  // povar_series.hip
+int ck_autotune(povar_ctx* c, int step);  // povar_series.hip
 int tune_agree(povar_ctx* c, int step);  // povar_series.hip
-int ckh_autotune(povar_ctx* c);  // povar_series.hip
-extern "C" int enqueue_series(povar_ctx* c, int32_t m, double q_tol, double r_tol);  // povar_series.hip
-extern "C" int run_series(povar_ctx* c, int32_t m, double q_tol, double r_tol, bool use_res);  // povar_series.hip
 extern "C" int res_verify(povar_ctx* c);  // povar_series.hip
-extern "C" int res_autotune(povar_ctx* c, int32_t m, double q_tol, double r_tol);  // povar_series.hip
 int ck_max_cams();  // povar_create.hip
 bool ck_upload(povar_ctx* c, povar_ctx::CkDev& D, const CkLayout& K, bool locked, size_t* bytes, bool need_uv = true);  // povar_create.hip
 int res_upload(povar_ctx* c, const ResLayout& R);  // povar_create.hip
@@ -448,7 +473,7 @@ int read_flags(povar_ctx* c, int (&f)[4]);  // povar_create.hip
 int read_scal(povar_ctx* c, double* h, int n);  // povar_create.hip
 int write_cam_vector(povar_ctx* c, double* dst, const double* in, size_t n);  // povar_create.hip
 int read_cam_vector(povar_ctx* c, double* out, const double* src, size_t n);  // povar_create.hip
-bool lpl_only(const povar_ctx* c);  // povar_lm.hip
+hipError_t lm_set_lds_all();  // povar_lm.hip
 void build_views(povar_ctx* c);  // povar_lm.hip
 void lanes_from(povar_ctx* c, const double4* src, double4* dst);  // povar_lm.hip
 void ensure_lmx(povar_ctx* c);  // povar_lm.hip

@@ -2,8 +2,24 @@
 #include "povar_ctx.hpp"
 
 // every kernel of the LM iteration runs on the lane-per-landmark layout: nothing reads the legacy camera-major copies
-bool lpl_only(const povar_ctx* c) {
-  return c->use_lpl && c->use_lpl_prepare && c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC;
+static bool lpl_only(const povar_ctx* c) { return lpl_mode(c) && c->use_lpl_prepare; }
+
+// dynamic LDS of the lane-per-landmark kernels this unit launches (povar_create)
+hipError_t lm_set_lds_all() {
+  const auto set = [](const void* f, size_t bytes) { return hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); };
+  hipError_t e = set((const void*)prepare_lpl<false>, prep_lds_bytes(HOT_ACC_MAX));
+  if (e == hipSuccess) e = set((const void*)prepare_lpl<true>, prep_lds_bytes(HOT_ACC_MAX));
+  if (e == hipSuccess) e = set((const void*)lpl_pass_h<0>, pass_lds_bytes(HOT_ACC_MAX));
+  if (e == hipSuccess) e = set((const void*)lpl_pass_h<1>, pass_lds_bytes(HOT_ACC_MAX));
+  if (e == hipSuccess) e = set((const void*)backsub_lpl_h<false>, back_lds_bytes_h(HOT_ACC_MAX));
+  if (e == hipSuccess) e = set((const void*)backsub_lpl_h<true>, back_lds_bytes_h(HOT_ACC_MAX));
+  if (e == hipSuccess) e = set((const void*)lpl_pass<0>, pass_lds_bytes(HOT_ACC_MAX));
+  if (e == hipSuccess) e = set((const void*)lpl_pass<1>, pass_lds_bytes(HOT_ACC_MAX));
+  if (e == hipSuccess) e = set((const void*)backsub_lpl<false>, back_lds_bytes(HOT_ACC_MAX));
+  if (e == hipSuccess) e = set((const void*)backsub_lpl<true>, back_lds_bytes(HOT_ACC_MAX));
+  if (e == hipSuccess) e = set((const void*)prepare_lpl_h<false>, prep_lds_bytes(HOT_ACC_MAX));
+  if (e == hipSuccess) e = set((const void*)prepare_lpl_h<true>, prep_lds_bytes(HOT_ACC_MAX));
+  return e;
 }
 
 void build_views(povar_ctx* c) {
@@ -243,7 +259,7 @@ int povar_error_pose(povar_ctx* c, double alpha, povar_residual_info* out) {
   set_alpha(c, alpha);
   if (err_memo_hit(c, 1, alpha, out)) return 0;
   if (int rc = clear_flag0(c)) return rc;
-  if (c->use_lpl && c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC) {
+  if (lpl_mode(c)) {
     ensure_lmx(c);
     hipLaunchKernelGGL(lpl_pass<1>, dim3(c->e0c_grid), dim3(E0C_BLOCK), pass_lds_bytes(c->v2_max_slots), c->stream, c->d, c->part.p);
     hipLaunchKernelGGL((reduce_partials<3>), dim3(1), dim3(1024), 0, c->stream, c->part.p, c->e0c_grid, c->scal.p);
@@ -341,7 +357,7 @@ int povar_prepare_pose(povar_ctx* c, double lambda, int32_t solver_type) {
   c->new_linearization_point = false;
   c->d.lambda_lm = solver_type == POVAR_POWER_SCHUR_COMPLEMENT ? lambda : 0.0;  // cpp:197-200
   hipLaunchKernelGGL(build_hot_rec, dim3(grid_for((int64_t)c->n_cams * 12, 256)), dim3(256), 0, c->stream, c->d, 0);
-  if (c->use_lpl && c->use_lpl_prepare && c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC) {
+  if (lpl_only(c)) {
     // lane-per-landmark K7: Hll^-1, landmark records and the per-camera partial sums of b in one kernel, then the
     // per-camera sum of the partials and the cold observations (same kernel as the per-term one, output b)
     Dp da = ldsacc_dp(c, true);
@@ -371,7 +387,7 @@ int povar_prepare_pose(povar_ctx* c, double lambda, int32_t solver_type) {
   if (int rc = ensure_tiles(c)) return rc;
   // the one-off choice between the step-1 term kernels is part of the preparation, not of the first solve's time
   // (solve_reduced_system_time of the caller's log: bal_bundle_adjustment.cpp:355-360)
-  if (int rc = ck_autotune(c)) return rc;
+  if (int rc = ck_autotune(c, 1)) return rc;
   if (int rc = tune_agree(c, 0)) return rc;
   HIP_TRY(hipGetLastError());
   return 0;
@@ -389,7 +405,7 @@ int povar_apply_pose(povar_ctx* c, int32_t solver_type, double alpha, const doub
   if (solver_type == POVAR_POWER_VARPROJ) {
     // cpp:250-256: scale, update cameras, unscale, back-substitute at the new cameras
     hipLaunchKernelGGL(cam_apply_inc, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, c->d, 0);
-    lpl_back = c->use_lpl && c->use_lpl_prepare && c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC;
+    lpl_back = lpl_only(c);
     if (lpl_back) {
       const Dp da = ldsacc_dp(c, true);
       ensure_lmx(c);
@@ -452,7 +468,7 @@ int povar_error_homogeneous(povar_ctx* c, povar_residual_info* out) {
   TimeScope ts(c, 4);
   if (err_memo_hit(c, 2, 0.0, out)) return 0;
   if (int rc = clear_flag0(c)) return rc;
-  if (c->use_lpl && c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC) {
+  if (lpl_mode(c)) {
     ensure_lmx(c);
     hipLaunchKernelGGL(lpl_pass_h<1>, dim3(c->e0c_grid), dim3(E0C_BLOCK), pass_lds_bytes(c->v2_max_slots), c->stream, c->d, c->part.p);
     hipLaunchKernelGGL((reduce_partials<6>), dim3(1), dim3(1024), 0, c->stream, c->part.p, c->e0c_grid, c->scal.p);
@@ -539,7 +555,7 @@ int povar_prepare_joint(povar_ctx* c, double lambda) {
   c->new_linearization_point = false;
   c->d.lambda_lm = lambda;  // set_landmark_damping_joint, linearizor_power_varproj.cpp:136
   hipLaunchKernelGGL(build_hot_rec, dim3(grid_for((int64_t)c->n_cams * 12, 256)), dim3(256), 0, c->stream, c->d, 1);
-  if (c->use_lpl && c->use_lpl_prepare && c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC) {
+  if (lpl_only(c)) {
     // lane-per-landmark K7' (see povar_prepare_pose): landmark half + per-camera partials, per-camera sum of the
     // partials and the cold observations into the ambient 12-vector, then the tangent projection N_c^T
     Dp da = ldsacc_dp(c, true);
@@ -567,7 +583,7 @@ int povar_prepare_joint(povar_ctx* c, double lambda) {
   if (int rc = allreduce(c, c->d.b, 11 * (size_t)c->n_cams)) return rc;
   hipLaunchKernelGGL(cam_build_binv_h, dim3(grid_for(c->n_cams, K8_CAMS_PER_WG)), dim3(K8_THREADS), 0, c->stream, c->d,
                      lambda, (const double*)c->ncw.p);
-  if (int rc = ckh_autotune(c)) return rc;  // (as in povar_prepare_pose: the one-off kernel choice is preparation)
+  if (int rc = ck_autotune(c, 2)) return rc;  // (as in povar_prepare_pose: the one-off kernel choice is preparation)
   if (int rc = tune_agree(c, 1)) return rc;
   HIP_TRY(hipGetLastError());
   return 0;

@@ -44,13 +44,10 @@ int build_schur_jacobi(povar_ctx* c, double lambda) {
 
 // E0 * (vector last written by emit_z) into the dense ambient y
 int e0_dense(povar_ctx* c) {
-  int mode = 1;
-  const bool hold = c->fp32_hold;
-  c->fp32_hold = true;  // (POVAR_FLAG_FP32_TERMS covers the power-series terms only: the explicit-SC solvers stay in fp64)
-  const int rc = launch_e0(c, &mode);
-  c->fp32_hold = hold;
-  if (rc) return rc;
-  if (mode == 1)
+  // (POVAR_FLAG_FP32_TERMS covers the power-series terms only: the explicit-SC solvers stay in fp64)
+  const TermPlan p = term_plan(c, c->joint ? 2 : 1, TermUse::dense);
+  if (int rc = launch_e0(c, p)) return rc;
+  if (p.cam == CamStep::scatter)
     hipLaunchKernelGGL(cam_sum_items, dim3(grid_for(c->n_cams, 4)), dim3(256), 0, c->stream, c->d, c->d.y, 1);
   return 0;
 }

@@ -1,55 +1,91 @@
-// povar_series.hip -- the term loop: E0 / B^-1 launchers, kernel choice by timing, hipGraph capture, the power-series entry points.
+// povar_series.hip -- the term loop: the term's plan and its launcher, kernel choice by timing, hipGraph capture, the power-series entry points.
 #include "povar_ctx.hpp"
 
-CkP ck_params(const povar_ctx* c, const povar_ctx::CkDev& D) {
+static CkP ck_params(const povar_ctx* c, const povar_ctx::CkDev& D) {
   return CkP{D.packed ? reinterpret_cast<const double2*>(D.uvp.p) : D.uv.p, D.li.p, D.w.p, D.tile.p, D.lane_meta.p, D.bt_off.p, D.slot_rec.p,
              D.nb, D.slots, (unsigned)(D.src.n * (D.packed ? sizeof(int2) : sizeof(double2))), (unsigned)(D.li.n * sizeof(uint32_t)),
              D.lcnt.p, D.tick.p, D.max_acc, D.packed ? 1 : 0, D.cold_q ? D.cpos.p : nullptr, c->q4c.p,
              D.first_meta.p, D.first_hdr.p};
 }
 
-CkP ck_params(const povar_ctx* c) { return ck_params(c, c->ck); }
-
-
-// (POVAR_DETERMINISTIC: the context is in the gather mode -- its linearisation and preparation kernels have no atomics --
-// and step 1's terms run the fixed-point form of e0_ck on the records those kernels leave in lane order)
-bool ck_det_possible(const povar_ctx* c) {
-  return c->det_ck && c->ck.ready && c->ck.lcnt.p && c->ck.tick.p && c->use_lpl && c->opt.e0_mode == POVAR_E0_IMPLICIT &&
-         c->ck.nb >= 1 && ck_lds_bytes_det(c->ck.slots, c->ck.max_acc) <= (size_t)CK_LDS_BYTES;
+// an instantiation runs a layout whose batches fit its groups: the LDS holds ng batches at once
+static bool ck_variant_fits(const povar_ctx* c, int variant) {
+  const CkVariant v = ck_variant_info(variant);
+  return c->ck.ready && c->ck.nb % v.ng == 0 && ck_lds_bytes(c->ck.slots, c->ck.max_acc, v.ng) <= (size_t)CK_LDS_BYTES;
 }
 
-bool ck_det_active(const povar_ctx* c) { return ck_det_possible(c) && !c->joint; }
-
-// POVAR_FLAG_FP32_TERMS: step 1's terms run e0_ck_f32 on the chunk layout povar_create built for it (it refuses the flag where
-// that layout cannot be built; setters that would leave it refuse too)
-bool ck32_active(const povar_ctx* c) {
-  return c->fp32_terms && !c->fp32_hold && !c->deterministic && !c->joint && c->ck.ready && c->use_lpl && c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC &&
-         c->ck32_lmrec.p && c->ck32_pimg.p && (c->ck.packed || c->ck32_uv.p) &&
-         ck32_lds_bytes(c->ck.slots, c->ck.max_acc) <= (size_t)CK_LDS_BYTES;
-}
-
-bool ck_active(const povar_ctx* c) {
-  if (c->fp32_terms && !c->fp32_hold) return ck32_active(c);
-  if (c->deterministic) return ck_det_active(c);
-  return c->ck_variant > 0 && c->ck.ready && c->use_lpl && !c->joint && c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC &&
-         ck_variant_fits(c, c->ck_variant);
-}
-
-bool ckh_det_possible(const povar_ctx* c) {
-  return c->det_ck && c->ckh.ready && c->ckh.lcnt.p && c->ckh.tick.p && c->use_lpl && c->opt.e0_mode == POVAR_E0_IMPLICIT &&
-         c->ckh.stride == CKH_STRIDE && c->ckh.slots <= CKH_STRIDE && ckh_lds_bytes_det(c->ckh.max_acc) <= (size_t)CK_LDS_BYTES;
-}
-
-bool ckh_active(const povar_ctx* c) {
-  if (c->deterministic) return c->joint && ckh_det_possible(c);
-  return c->joint && c->ckh_variant > 0 && c->ckh.ready && c->use_lpl && c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC &&
-         (c->ckh.stride == CKH_STRIDE || c->ckh.stride == CKH_STRIDE_WIDE) && c->ckh.slots <= c->ckh.stride &&
-         ckh_lds_bytes(c->ckh.max_acc, c->ckh.stride) <= (size_t)CK_LDS_BYTES;
+// The kernels of one application of E0 for the system of `step` (1: pose, 2: joint), decided from the context's mode, layouts
+// and switches.  variant >= 0 puts that camera-chunk choice in place of the context's (0: the lane-per-landmark kernel).
+TermPlan term_plan(const povar_ctx* c, int step, TermUse use, int variant) {
+  TermPlan p;
+  p.step = step;
+  p.use = use;
+  const int mode = c->opt.e0_mode;
+  const bool lpl = lpl_mode(c);
+  const bool series = use == TermUse::series || use == TermUse::series_norms;
+  if (step == 1) {
+    if (variant < 0) variant = c->ck_variant;
+    const povar_ctx::CkDev& D = c->ck;
+    if (c->fp32_terms && use != TermUse::dense) {
+      // POVAR_FLAG_FP32_TERMS: e0_ck_f32 on the chunk layout povar_create built for it (it refuses the flag where that layout
+      // cannot be built; setters that would leave it refuse too); the explicit-SC solvers stay in fp64
+      if (!c->deterministic && D.ready && lpl && c->ck32_lmrec.p && c->ck32_pimg.p && (D.packed || c->ck32_uv.p) &&
+          ck32_lds_bytes(D.slots, D.max_acc) <= (size_t)CK_LDS_BYTES) {
+        p.e0 = E0K::ck_f32;
+        p.variant = variant;
+      }
+    } else if (c->deterministic) {
+      // POVAR_DETERMINISTIC: the context is in the gather mode -- its linearisation and preparation kernels have no atomics --
+      // and the terms run the fixed-point form of e0_ck on the records those kernels leave in lane order
+      if (c->det_ck && D.ready && D.lcnt.p && D.tick.p && c->use_lpl && mode == POVAR_E0_IMPLICIT && D.nb >= 1 &&
+          ck_lds_bytes_det(D.slots, D.max_acc) <= (size_t)CK_LDS_BYTES)
+        p.e0 = E0K::ck_det;
+    } else if (variant > 0 && D.ready && lpl && ck_variant_fits(c, variant)) {
+      p.e0 = E0K::ck;
+      p.variant = variant;
+    }
+    if (!p.ck()) {
+      // (the lane-per-observation kernels of the LDS-accumulating mode walk the long landmarks themselves where
+      // long_in_kernel; e0_lpl has no long/short distinction)
+      const bool walks_long = mode == POVAR_E0_IMPLICIT_LDSACC && c->long_in_kernel;
+      p.e0 = mode == POVAR_E0_TILES ? E0K::lm_tiles : mode == POVAR_E0_TILES_LDSACC ? E0K::tiles_cached
+             : lpl ? E0K::lpl : mode == POVAR_E0_IMPLICIT_LDSACC ? E0K::lm_cached_acc : E0K::lm_cached;
+      p.long_after = c->n_long > 0 && (mode == POVAR_E0_TILES || mode == POVAR_E0_TILES_LDSACC || !walks_long);
+    }
+  } else {
+    if (variant < 0) variant = c->ckh_variant;
+    const povar_ctx::CkDev& D = c->ckh;
+    if (c->deterministic) {
+      if (c->det_ck && D.ready && D.lcnt.p && D.tick.p && c->use_lpl && mode == POVAR_E0_IMPLICIT && D.stride == CKH_STRIDE &&
+          D.slots <= CKH_STRIDE && ckh_lds_bytes_det(D.max_acc) <= (size_t)CK_LDS_BYTES)
+        p.e0 = E0K::ck_h_det;
+    } else if (variant > 0 && D.ready && lpl && (D.stride == CKH_STRIDE || D.stride == CKH_STRIDE_WIDE) &&
+               D.slots <= D.stride && ckh_lds_bytes(D.max_acc, D.stride) <= (size_t)CK_LDS_BYTES) {
+      p.e0 = E0K::ck_h;
+      p.variant = 1;
+    }
+    if (!p.ck()) {
+      p.e0 = lpl ? E0K::lpl_h : mode == POVAR_E0_IMPLICIT_LDSACC ? E0K::lm_cached_h : E0K::lm_h;
+      p.long_after = c->n_long > 0 && (p.e0 == E0K::lm_h || (p.e0 == E0K::lm_cached_h && !c->long_in_kernel));
+    }
+  }
+  // the LDS-accumulating kernels (and the camera-chunk kernels, the fixed-point ones included) leave partial records and a
+  // cold view to cam_cold_sum; the unsharded term loop may run B^-1 + AXPY inside it.  What is timed is that fused pair.
+  const bool acc = p.ck() || mode == POVAR_E0_IMPLICIT_LDSACC || (step == 1 && mode == POVAR_E0_TILES_LDSACC);
+  if (acc)
+    p.cam = use == TermUse::timing || (series && !sharded(c) && c->fuse_binv) ? CamStep::fused : CamStep::sum;
+  else
+    p.cam = sharded(c) ? CamStep::scatter_sum : CamStep::scatter;
+  // peer-to-peer exchange: only inside the term loop of the step-1 lane-per-landmark kernels; every other caller wants the
+  // dense, all-reduced y
+  if (series && step == 1 && c->p2p && lpl && p.cam == CamStep::sum) p.exch = Exch::p2p;
+  else if (use != TermUse::timing && sharded(c)) p.exch = Exch::allreduce;
+  return p;
 }
 
 // the per-camera kernels behind e0_ck / e0_ck_h: partial records only (its own table), no per-observation cold view
-void ck_dp(const povar_ctx* c, Dp& da) {
-  const povar_ctx::CkDev& D = c->joint ? c->ckh : c->ck;
+static void ck_dp(const povar_ctx* c, int step, Dp& da) {
+  const povar_ctx::CkDev& D = step == 2 ? c->ckh : c->ck;
   da.hot_part = D.part.p;
   da.part_range = D.part_range.p;
   da.cmv.src = nullptr;
@@ -59,138 +95,6 @@ void ck_dp(const povar_ctx* c, Dp& da) {
   da.cmv.cam_range = c->ck_zero_range.p;
   da.cmv.n = 0;
 }
-
-template <int NW, int SD, bool DB, int NG>
-void launch_e0_ck_t(povar_ctx* c, const Dp& da) {
-  const CkP k = ck_params(c);
-  const size_t lds = ck_lds_bytes(c->ck.slots, c->ck.max_acc, NG);
-  const bool huber = c->opt.robust_norm == POVAR_NORM_HUBER;  // (the kernel recomputes the weights; CAUCHY's are 1: compute_error_weight)
-  if (c->ck.packed) {
-    if (huber) hipLaunchKernelGGL((e0_ck<NW, SD, DB, NG, true, true>), dim3(c->e0c_grid), dim3(NW * 64), lds, c->stream, da, k, c->ck.part.p);
-    else hipLaunchKernelGGL((e0_ck<NW, SD, DB, NG, false, true>), dim3(c->e0c_grid), dim3(NW * 64), lds, c->stream, da, k, c->ck.part.p);
-  } else {
-    if (huber) hipLaunchKernelGGL((e0_ck<NW, SD, DB, NG, true, false>), dim3(c->e0c_grid), dim3(NW * 64), lds, c->stream, da, k, c->ck.part.p);
-    else hipLaunchKernelGGL((e0_ck<NW, SD, DB, NG, false, false>), dim3(c->e0c_grid), dim3(NW * 64), lds, c->stream, da, k, c->ck.part.p);
-  }
-}
-
-// an instantiation runs a layout whose batches fit its groups: the LDS holds ng batches at once
-bool ck_variant_fits(const povar_ctx* c, int variant) {
-  const CkVariant v = ck_variant_info(variant);
-  return c->ck.ready && c->ck.nb % v.ng == 0 && ck_lds_bytes(c->ck.slots, c->ck.max_acc, v.ng) <= (size_t)CK_LDS_BYTES;
-}
-
-// the fp32 term kernel (povar_kernels_ck_f32.hpp): its partial records and cold-view q are e0_ck's, in fp64
-void launch_e0_ck32(povar_ctx* c, const Dp& da) {
-  const CkP k = ck_params(c);
-  Ck32 f{c->ck.packed ? nullptr : c->ck32_uv.p, c->ck32_lmrec.p, c->ck32_pimg.p,
-         (unsigned)(c->ck.src.n * sizeof(float2)), (unsigned)(c->ck.part.n * sizeof(double))};
-  const size_t lds = ck32_lds_bytes(c->ck.slots, c->ck.max_acc);
-  const bool huber = c->opt.robust_norm == POVAR_NORM_HUBER;  // (recomputed in registers; CAUCHY's weights are 1, as in e0_ck)
-  if (c->ck.packed) {
-    if (huber) hipLaunchKernelGGL((e0_ck_f32<true, true>), dim3(c->e0c_grid), dim3(CK32_NW * 64), lds, c->stream, da, k, f, c->ck.part.p);
-    else hipLaunchKernelGGL((e0_ck_f32<false, true>), dim3(c->e0c_grid), dim3(CK32_NW * 64), lds, c->stream, da, k, f, c->ck.part.p);
-  } else {
-    if (huber) hipLaunchKernelGGL((e0_ck_f32<true, false>), dim3(c->e0c_grid), dim3(CK32_NW * 64), lds, c->stream, da, k, f, c->ck.part.p);
-    else hipLaunchKernelGGL((e0_ck_f32<false, false>), dim3(c->e0c_grid), dim3(CK32_NW * 64), lds, c->stream, da, k, f, c->ck.part.p);
-  }
-}
-
-// fp32 landmark records and camera image of the system prepared last (povar_prepare_pose, after prepare_lpl / build_hot_rec)
-void launch_ck32_records(povar_ctx* c) {
-  const int64_t n_rec = (int64_t)c->d.v2.n_tiles * 9 * WAVE;
-  const int64_t n = std::max<int64_t>(n_rec, (int64_t)c->n_cams * 12);
-  hipLaunchKernelGGL(ck32_records, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, (const double*)c->v2_lmrec.p, c->ck32_lmrec.p,
-                     n_rec, (const double*)c->hot_rec.p, c->ck32_pimg.p, c->n_cams);
-}
-
-void launch_e0_ck(povar_ctx* c, const Dp& da) {
-  if (ck32_active(c)) {
-    launch_e0_ck32(c, da);
-    return;
-  }
-  if (c->deterministic) {  // the bit-reproducible form (povar_kernels_ck_det.hpp)
-    const CkP k = ck_params(c);
-    const size_t lds = ck_lds_bytes_det(c->ck.slots, c->ck.max_acc);
-    if (c->opt.robust_norm == POVAR_NORM_HUBER)
-      hipLaunchKernelGGL((e0_ck_det<16, 2, true>), dim3(c->e0c_grid), dim3(1024), lds, c->stream, da, k, c->ck.part.p);
-    else
-      hipLaunchKernelGGL((e0_ck_det<16, 2, false>), dim3(c->e0c_grid), dim3(1024), lds, c->stream, da, k, c->ck.part.p);
-    return;
-  }
-  switch (c->ck_variant) {
-#define X(id, nw, sd, db, ng) case id: launch_e0_ck_t<nw, sd, db, ng>(c, da); break;
-    POVAR_CK_VARIANTS(X)
-#undef X
-    default: break;
-  }
-}
-
-template <int NW, int SD, bool DB, int NG>
-hipError_t ck_set_lds_t() {
-  hipError_t e = hipFuncSetAttribute((const void*)e0_ck<NW, SD, DB, NG, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, CK_LDS_BYTES);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)e0_ck<NW, SD, DB, NG, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, CK_LDS_BYTES);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)e0_ck<NW, SD, DB, NG, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CK_LDS_BYTES);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)e0_ck<NW, SD, DB, NG, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CK_LDS_BYTES);
-  return e;
-}
-
-hipError_t ck_set_lds_all() {
-  hipError_t e = hipFuncSetAttribute((const void*)e0_ck_det<16, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, CK_LDS_BYTES);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)e0_ck_h_det<16, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, CK_LDS_BYTES);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)e0_ck_h_det<16, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CK_LDS_BYTES);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)e0_ck_det<16, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CK_LDS_BYTES);
-  // (e0_ck_f32 is launched from this translation unit: its attributes are set on this unit's instantiations)
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)e0_ck_f32<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, CK_LDS_BYTES);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)e0_ck_f32<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, CK_LDS_BYTES);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)e0_ck_f32<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CK_LDS_BYTES);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)e0_ck_f32<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CK_LDS_BYTES);
-#define X(id, nw, sd, db, ng) if (e == hipSuccess) e = ck_set_lds_t<nw, sd, db, ng>();
-  POVAR_CK_VARIANTS(X)
-#undef X
-  return e;
-}
-
-// Which of the two step-1 E0 kernels is faster depends on the graph (e0_ck: venice-like camera counts, any share of
-// observations whose camera has no LDS slot; e0_lpl: many cameras and few observations per (camera, batch), where a chunk
-// is a single observation -- final-13682).  Unless the caller has forced one, both are timed once per layout on the
-// problem itself: a warm-up and three launches each on the prepared system (they only write their partial records).
-
-
-// robust weights in chunk order (V2::w is written by the linearisation walk in lane-per-landmark order)
-void ensure_ck_w(povar_ctx* c) {
-  povar_ctx::CkDev& D = c->joint ? c->ckh : c->ck;
-  if (!c->opt.robust_norm || !D.ready || !D.w.p || !c->v2_w.p || D.w_lin_id == c->lin_id) return;
-  const int64_t n = (int64_t)D.src.n;  // every row, the padding included (weight 0)
-  hipLaunchKernelGGL(ck_gather_w, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, (const int*)D.src.p, (const double*)c->v2_w.p,
-                     D.w.p, n);
-  D.w_lin_id = c->lin_id;
-}
-
-void launch_e0_ck_h(povar_ctx* c, const Dp& da) {
-  const CkP k = ck_params(c, c->ckh);
-  if (c->deterministic) {  // the bit-reproducible form (povar_kernels_ck_det.hpp)
-    const size_t ldsd = ckh_lds_bytes_det(c->ckh.max_acc);
-    if (c->opt.robust_norm)
-      hipLaunchKernelGGL((e0_ck_h_det<16, 2, true>), dim3(c->e0c_grid), dim3(1024), ldsd, c->stream, da, k, c->ckh.part.p);
-    else
-      hipLaunchKernelGGL((e0_ck_h_det<16, 2, false>), dim3(c->e0c_grid), dim3(1024), ldsd, c->stream, da, k, c->ckh.part.p);
-    return;
-  }
-  const size_t lds = ckh_lds_bytes(c->ckh.max_acc, c->ckh.stride);
-  if (c->ckh.stride == CKH_STRIDE_WIDE) {  // two landmark batches instead of three, fewer accumulators (povar_kernels_ck_joint.hpp)
-    if (c->opt.robust_norm)
-      hipLaunchKernelGGL((e0_ck_h<16, 2, true, CKH_STRIDE_WIDE>), dim3(c->e0c_grid), dim3(1024), lds, c->stream, da, k, c->ckh.part.p);
-    else
-      hipLaunchKernelGGL((e0_ck_h<16, 2, false, CKH_STRIDE_WIDE>), dim3(c->e0c_grid), dim3(1024), lds, c->stream, da, k, c->ckh.part.p);
-    return;
-  }
-  if (c->opt.robust_norm)
-    hipLaunchKernelGGL((e0_ck_h<16, 2, true>), dim3(c->e0c_grid), dim3(1024), lds, c->stream, da, k, c->ckh.part.p);
-  else
-    hipLaunchKernelGGL((e0_ck_h<16, 2, false>), dim3(c->e0c_grid), dim3(1024), lds, c->stream, da, k, c->ckh.part.p);
-}
-
 
 // instantiations: wavefronts per workgroup, rows per chunk, chunks per lane, landmark slots per lane.  1024-thread
 // workgroups (128 VGPRs per lane): one chunk of at most two rows; 512-thread ones (256): two chunks of up to four rows
@@ -296,7 +200,7 @@ Dp ldsacc_dp(povar_ctx* c, bool long_in_kernel) {
   dt.hot_part = c->hot_part.p;
   dt.q4c = c->q4c.p;
   dt.cold_pos = c->cold_pos.p;
-  if (c->use_lpl && c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC) {
+  if (lpl_mode(c)) {
     // e0_lpl: its own cold view (observations whose camera is not resident in their workgroup) and partial records
     dt.cmv.h = c->c3_h.p;
     dt.cmv.n = c->n_cold3;
@@ -320,146 +224,244 @@ Dp ldsacc_dp(povar_ctx* c, bool long_in_kernel) {
   return dt;
 }
 
-// E0 x for the current term: implicit (LM pass, CM pass) or stored tiles.  The per-camera
-// result is consumed by cam_binv_axpy (mode 1: scatter items, mode 2: dense y).
-// fuse_norms >= 0: the caller is the term loop and takes B^-1 + AXPY next with want_norms = fuse_norms,
-// so the unsharded step-1 LDSACC path may run them inside the per-camera sum (binv_mode 4: done)
-int launch_e0(povar_ctx* c, int* binv_mode, int fuse_norms) {
-  prof_mark(c, 0);
-  if (!(c->use_lpl && c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC)) ensure_legacy(c);  // cm_scatter / legacy cold views
-  if (ck_active(c) || ckh_active(c)) ensure_ck_w(c);  // (a no-op inside the graph capture: the solve entry points have called it before)
-  if (c->joint) {
-    const bool ckh_now = ckh_active(c);
-    const bool acc = c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC || ckh_now;  // (e0_ck_h_det leaves partial records too)
-    Dp dj = ldsacc_dp(c, true);  // what the per-camera kernels below see: e0_ck_h leaves partial records only
-    if (ckh_now) ck_dp(c, dj);
-    if (ckh_now) {
-      launch_e0_ck_h(c, dj);
-    } else if (acc && c->use_lpl) {
-      Dp da = ldsacc_dp(c, true);
-      if (c->opt.robust_norm)
-        hipLaunchKernelGGL(e0_lpl_h<true>, dim3(c->e0c_grid), dim3(E0C_BLOCK), lpl_lds_bytes_h(c->v2_max_slots), c->stream, da, c->v2_part.p);
-      else
-        hipLaunchKernelGGL(e0_lpl_h<false>, dim3(c->e0c_grid), dim3(E0C_BLOCK), lpl_lds_bytes_h(c->v2_max_slots), c->stream, da, c->v2_part.p);
-    } else if (acc) {
-      // cold observations write q to their camera-major position (q4c); long landmarks are walked inside the kernel
-      const Dp da = ldsacc_dp(c, true);
-      hipLaunchKernelGGL(e0_lm_cached_h, dim3(c->e0c_grid), dim3(E0C_BLOCK),
-                         (size_t)c->n_hot_acc * (HOT_REC_H * sizeof(double2) + 96), c->stream, da,
-                         c->e0c_bins_per_wg, c->hot_part.p);
-      if (c->n_long > 0 && !c->long_in_kernel)
-        hipLaunchKernelGGL((lm_long<OpE0H>), dim3(c->n_long), dim3(LM_BLOCK), 0, c->stream, da, OpE0H{}, c->part.p);
-    } else {
-      launch_lm(c, OpE0H{});
-    }
-    if (acc && fuse_norms >= 0 && !sharded(c) && c->fuse_binv) {
-      hipLaunchKernelGGL(cam_cold_sum_binv_h<CCS_THREADS>, dim3(c->n_cams), dim3(CCS_THREADS), 0, c->stream, dj, fuse_norms,
-                         (const double*)c->ncw.p);
-      *binv_mode = 4;  // B^-1, AXPY and z already done
-    } else if (acc) {
-      hipLaunchKernelGGL(cam_cold_sum<CCS_THREADS>, dim3(c->n_cams), dim3(CCS_THREADS), 0, c->stream, dj, 1);
-      *binv_mode = 2;  // dense y (sigma applied)
-    } else {
-      hipLaunchKernelGGL(cm_scatter, dim3(grid_for(std::max(c->n_items, 1), 4)), dim3(256), 0, c->stream, c->d, 1, 1);
-      *binv_mode = 1;
-      if (sharded(c)) {
-        hipLaunchKernelGGL(cam_sum_items, dim3(grid_for(c->n_cams, 4)), dim3(256), 0, c->stream, c->d, c->d.y, 1);
-        *binv_mode = 2;
-      }
-    }
+
+// what the plan's kernels see: the context's Dp, or the cold view and partial records of the accumulating kernels
+// (e0_tiles_cached: without the long landmarks' view), the chunk layout's records behind e0_ck*, the peers' buffers
+static Dp term_dp(povar_ctx* c, const TermPlan& p) {
+  if (p.cam == CamStep::scatter || p.cam == CamStep::scatter_sum) return c->d;
+  Dp d = ldsacc_dp(c, p.e0 != E0K::tiles_cached);
+  if (p.ck()) {
+    ck_dp(c, p.step, d);
+    if (p.step == 1) d.long_in_kernel = 1;  // (e0_ck walks every landmark)
+  }
+  if (p.exch == Exch::p2p) p2p_dp(c, d);
+  return d;
+}
+
+template <int NW, int SD, bool DB, int NG>
+void launch_e0_ck_t(povar_ctx* c, const Dp& da) {
+  const CkP k = ck_params(c, c->ck);
+  const size_t lds = ck_lds_bytes(c->ck.slots, c->ck.max_acc, NG);
+  const bool huber = c->opt.robust_norm == POVAR_NORM_HUBER;  // (the kernel recomputes the weights; CAUCHY's are 1: compute_error_weight)
+  if (c->ck.packed) {
+    if (huber) hipLaunchKernelGGL((e0_ck<NW, SD, DB, NG, true, true>), dim3(c->e0c_grid), dim3(NW * 64), lds, c->stream, da, k, c->ck.part.p);
+    else hipLaunchKernelGGL((e0_ck<NW, SD, DB, NG, false, true>), dim3(c->e0c_grid), dim3(NW * 64), lds, c->stream, da, k, c->ck.part.p);
   } else {
-    const bool ck_now = ck_active(c);
-    // (the fixed-point e0_ck of the deterministic mode leaves partial records like the LDS-accumulating kernels)
-    const bool acc = c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC || c->opt.e0_mode == POVAR_E0_TILES_LDSACC || ck_now;
-    // ACC: cold observations write q to their camera-major position (q4c); the implicit form also walks the
-    // long landmarks inside e0_lm_cached (its own cold view)
-    const bool lik = (c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC && c->long_in_kernel) || ck_now;
-    Dp da = acc ? ldsacc_dp(c, lik) : c->d;
-    if (ck_now) {
-      ck_dp(c, da);
-      da.long_in_kernel = 1;  // (e0_ck walks every landmark)
+    if (huber) hipLaunchKernelGGL((e0_ck<NW, SD, DB, NG, true, false>), dim3(c->e0c_grid), dim3(NW * 64), lds, c->stream, da, k, c->ck.part.p);
+    else hipLaunchKernelGGL((e0_ck<NW, SD, DB, NG, false, false>), dim3(c->e0c_grid), dim3(NW * 64), lds, c->stream, da, k, c->ck.part.p);
+  }
+}
+
+// fp32 landmark records and camera image of the system prepared last (povar_prepare_pose, after prepare_lpl / build_hot_rec)
+void launch_ck32_records(povar_ctx* c) {
+  const int64_t n_rec = (int64_t)c->d.v2.n_tiles * 9 * WAVE;
+  const int64_t n = std::max<int64_t>(n_rec, (int64_t)c->n_cams * 12);
+  hipLaunchKernelGGL(ck32_records, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, (const double*)c->v2_lmrec.p, c->ck32_lmrec.p,
+                     n_rec, (const double*)c->hot_rec.p, c->ck32_pimg.p, c->n_cams);
+}
+
+// robust weights in chunk order (V2::w is written by the linearisation walk in lane-per-landmark order)
+static void ensure_ck_w(povar_ctx* c, int step) {
+  povar_ctx::CkDev& D = step == 2 ? c->ckh : c->ck;
+  if (!c->opt.robust_norm || !D.ready || !D.w.p || !c->v2_w.p || D.w_lin_id == c->lin_id) return;
+  const int64_t n = (int64_t)D.src.n;  // every row, the padding included (weight 0)
+  hipLaunchKernelGGL(ck_gather_w, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, (const int*)D.src.p, (const double*)c->v2_w.p,
+                     D.w.p, n);
+  D.w_lin_id = c->lin_id;
+}
+
+// E0 x for the current term, as the plan says: the E0 kernel [+ lm_long], the per-camera kernel, the exchange of y.  What
+// cam_binv_axpy does next is plan.binv_mode().
+int launch_e0(povar_ctx* c, const TermPlan& p) {
+  if (p.use != TermUse::timing) prof_mark(c, 0);
+  if (!lpl_mode(c)) ensure_legacy(c);  // cm_scatter / legacy cold views
+  if (p.ck()) ensure_ck_w(c, p.step);  // (a no-op inside the graph capture: the solve entry points have called it before)
+  const Dp da = term_dp(c, p);
+  const bool robust = c->opt.robust_norm != 0, huber = c->opt.robust_norm == POVAR_NORM_HUBER;
+  const dim3 grid(c->e0c_grid);
+  switch (p.e0) {
+    case E0K::ck_f32: {  // (povar_kernels_ck_f32.hpp: its partial records and cold-view q are e0_ck's, in fp64)
+      const CkP k = ck_params(c, c->ck);
+      const Ck32 f{c->ck.packed ? nullptr : c->ck32_uv.p, c->ck32_lmrec.p, c->ck32_pimg.p,
+                   (unsigned)(c->ck.src.n * sizeof(float2)), (unsigned)(c->ck.part.n * sizeof(double))};
+      const size_t lds = ck32_lds_bytes(c->ck.slots, c->ck.max_acc);
+      const dim3 block(CK32_NW * 64);  // (HUBER's weights are recomputed in registers; CAUCHY's are 1, as in e0_ck)
+      if (c->ck.packed) {
+        if (huber) hipLaunchKernelGGL((e0_ck_f32<true, true>), grid, block, lds, c->stream, da, k, f, c->ck.part.p);
+        else hipLaunchKernelGGL((e0_ck_f32<false, true>), grid, block, lds, c->stream, da, k, f, c->ck.part.p);
+      } else {
+        if (huber) hipLaunchKernelGGL((e0_ck_f32<true, false>), grid, block, lds, c->stream, da, k, f, c->ck.part.p);
+        else hipLaunchKernelGGL((e0_ck_f32<false, false>), grid, block, lds, c->stream, da, k, f, c->ck.part.p);
+      }
+      break;
     }
-    // peer-to-peer exchange: only inside the term loop (fuse_norms >= 0) of the lane-per-landmark kernels; every other
-    // caller (right_mul_e0, PCG) wants the dense, all-reduced y
-    const bool p2p_now = c->p2p && fuse_norms >= 0 && c->use_lpl && c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC;
-    if (p2p_now) p2p_dp(c, da);
-    if (c->opt.e0_mode == POVAR_E0_TILES) launch_lm(c, OpE0Tiles{});
-    else if (c->opt.e0_mode == POVAR_E0_TILES_LDSACC) {
-      hipLaunchKernelGGL(e0_tiles_cached, dim3(c->e0c_grid), dim3(E0T_BLOCK),
-                         (size_t)c->n_hot_acc * (HOT_REC_T * sizeof(double2) + 96), c->stream, da,
-                         c->e0c_bins_per_wg, c->hot_part.p);
-      if (c->n_long > 0)
-        hipLaunchKernelGGL((lm_long<OpE0Tiles>), dim3(c->n_long), dim3(LM_BLOCK), 0, c->stream, da, OpE0Tiles{}, c->part.p);
+    case E0K::ck_det: {  // the bit-reproducible form (povar_kernels_ck_det.hpp)
+      const size_t lds = ck_lds_bytes_det(c->ck.slots, c->ck.max_acc);
+      if (huber) hipLaunchKernelGGL((e0_ck_det<16, 2, true>), grid, dim3(1024), lds, c->stream, da, ck_params(c, c->ck), c->ck.part.p);
+      else hipLaunchKernelGGL((e0_ck_det<16, 2, false>), grid, dim3(1024), lds, c->stream, da, ck_params(c, c->ck), c->ck.part.p);
+      break;
     }
-    else if (ck_now)
-      launch_e0_ck(c, da);
-    else if (c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC && c->use_lpl && c->opt.robust_norm)
-      hipLaunchKernelGGL(e0_lpl<true>, dim3(c->e0c_grid), dim3(E0C_BLOCK),
-                         lpl_lds_bytes(c->v2_max_slots), c->stream, da, c->v2_part.p);
-    else if (c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC && c->use_lpl)
-      hipLaunchKernelGGL(e0_lpl<false>, dim3(c->e0c_grid), dim3(E0C_BLOCK),
-                         lpl_lds_bytes(c->v2_max_slots), c->stream, da, c->v2_part.p);
-    else if (c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC)
-      hipLaunchKernelGGL(e0_lm_cached<true>, dim3(c->e0c_grid), dim3(E0C_BLOCK),
-                         (size_t)c->n_hot_acc * (HOT_REC * sizeof(double2) + 96), c->stream, da,
-                         c->e0c_bins_per_wg, c->hot_part.p);
+    case E0K::ck:
+      switch (p.variant) {
+#define X(id, nw, sd, db, ng) case id: launch_e0_ck_t<nw, sd, db, ng>(c, da); break;
+        POVAR_CK_VARIANTS(X)
+#undef X
+        default: break;
+      }
+      break;
+    case E0K::lm_cached:
+      hipLaunchKernelGGL(e0_lm_cached<false>, grid, dim3(E0C_BLOCK), (size_t)c->n_hot * HOT_REC * sizeof(double2), c->stream, da,
+                         c->e0c_bins_per_wg, (double*)nullptr);
+      break;
+    case E0K::lm_cached_acc:  // cold observations write q to their camera-major position (q4c)
+      hipLaunchKernelGGL(e0_lm_cached<true>, grid, dim3(E0C_BLOCK), (size_t)c->n_hot_acc * (HOT_REC * sizeof(double2) + 96), c->stream,
+                         da, c->e0c_bins_per_wg, c->hot_part.p);
+      break;
+    case E0K::lm_tiles:
+      hipLaunchKernelGGL((lm_regular<OpE0Tiles>), dim3(c->n_reg_blocks), dim3(LM_BLOCK), 0, c->stream, da, OpE0Tiles{}, c->part.p);
+      break;
+    case E0K::tiles_cached:
+      hipLaunchKernelGGL(e0_tiles_cached, grid, dim3(E0T_BLOCK), (size_t)c->n_hot_acc * (HOT_REC_T * sizeof(double2) + 96), c->stream,
+                         da, c->e0c_bins_per_wg, c->hot_part.p);
+      break;
+    case E0K::lpl:
+      if (robust) hipLaunchKernelGGL(e0_lpl<true>, grid, dim3(E0C_BLOCK), lpl_lds_bytes(c->v2_max_slots), c->stream, da, c->v2_part.p);
+      else hipLaunchKernelGGL(e0_lpl<false>, grid, dim3(E0C_BLOCK), lpl_lds_bytes(c->v2_max_slots), c->stream, da, c->v2_part.p);
+      break;
+    case E0K::lm_h:
+      hipLaunchKernelGGL((lm_regular<OpE0H>), dim3(c->n_reg_blocks), dim3(LM_BLOCK), 0, c->stream, da, OpE0H{}, c->part.p);
+      break;
+    case E0K::lm_cached_h:
+      hipLaunchKernelGGL(e0_lm_cached_h, grid, dim3(E0C_BLOCK), (size_t)c->n_hot_acc * (HOT_REC_H * sizeof(double2) + 96), c->stream,
+                         da, c->e0c_bins_per_wg, c->hot_part.p);
+      break;
+    case E0K::lpl_h:
+      if (robust) hipLaunchKernelGGL(e0_lpl_h<true>, grid, dim3(E0C_BLOCK), lpl_lds_bytes_h(c->v2_max_slots), c->stream, da, c->v2_part.p);
+      else hipLaunchKernelGGL(e0_lpl_h<false>, grid, dim3(E0C_BLOCK), lpl_lds_bytes_h(c->v2_max_slots), c->stream, da, c->v2_part.p);
+      break;
+    case E0K::ck_h: {
+      const CkP k = ck_params(c, c->ckh);
+      const size_t lds = ckh_lds_bytes(c->ckh.max_acc, c->ckh.stride);
+      if (c->ckh.stride == CKH_STRIDE_WIDE) {  // two landmark batches instead of three, fewer accumulators (povar_kernels_ck_joint.hpp)
+        if (robust) hipLaunchKernelGGL((e0_ck_h<16, 2, true, CKH_STRIDE_WIDE>), grid, dim3(1024), lds, c->stream, da, k, c->ckh.part.p);
+        else hipLaunchKernelGGL((e0_ck_h<16, 2, false, CKH_STRIDE_WIDE>), grid, dim3(1024), lds, c->stream, da, k, c->ckh.part.p);
+      } else {
+        if (robust) hipLaunchKernelGGL((e0_ck_h<16, 2, true>), grid, dim3(1024), lds, c->stream, da, k, c->ckh.part.p);
+        else hipLaunchKernelGGL((e0_ck_h<16, 2, false>), grid, dim3(1024), lds, c->stream, da, k, c->ckh.part.p);
+      }
+      break;
+    }
+    case E0K::ck_h_det: {
+      const size_t lds = ckh_lds_bytes_det(c->ckh.max_acc);
+      if (robust) hipLaunchKernelGGL((e0_ck_h_det<16, 2, true>), grid, dim3(1024), lds, c->stream, da, ck_params(c, c->ckh), c->ckh.part.p);
+      else hipLaunchKernelGGL((e0_ck_h_det<16, 2, false>), grid, dim3(1024), lds, c->stream, da, ck_params(c, c->ckh), c->ckh.part.p);
+      break;
+    }
+  }
+  if (p.long_after) {
+    if (p.e0 == E0K::lm_tiles || p.e0 == E0K::tiles_cached)
+      hipLaunchKernelGGL((lm_long<OpE0Tiles>), dim3(c->n_long), dim3(LM_BLOCK), 0, c->stream, da, OpE0Tiles{}, c->part.p);
+    else if (p.step == 2)
+      hipLaunchKernelGGL((lm_long<OpE0H>), dim3(c->n_long), dim3(LM_BLOCK), 0, c->stream, da, OpE0H{}, c->part.p);
     else
-      hipLaunchKernelGGL(e0_lm_cached<false>, dim3(c->e0c_grid), dim3(E0C_BLOCK),
-                         (size_t)c->n_hot * HOT_REC * sizeof(double2), c->stream, c->d, c->e0c_bins_per_wg,
-                         (double*)nullptr);
-    if ((c->opt.e0_mode == POVAR_E0_IMPLICIT || c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC) && c->n_long > 0 && !lik)
       hipLaunchKernelGGL((lm_long<OpE0>), dim3(c->n_long), dim3(LM_BLOCK), 0, c->stream, da, OpE0{}, c->part.p);
-    if (acc && fuse_norms >= 0 && !sharded(c) && c->fuse_binv) {
+  }
+  const int hom = p.step == 2 ? 1 : 0;
+  const int norms = p.use == TermUse::series_norms ? 1 : 0;
+  switch (p.cam) {
+    case CamStep::fused:  // B^-1, AXPY and z too
       // 128 threads per camera: a camera's run is at most one partial record per workgroup (256) plus ~85 cold
       // observations; two wavefronts keep four loads per thread in flight and halve the cross-wavefront reduction
       // (256 threads: 71.7 us per term, 128: 69.5, 64: 69.6 on venice-1778)
-      hipLaunchKernelGGL(cam_cold_sum_binv<CCS_THREADS>, dim3(c->n_cams), dim3(CCS_THREADS), 0, c->stream, da, fuse_norms);
-      *binv_mode = 4;  // B^-1, AXPY and z already done
-    } else if (acc) {
-      hipLaunchKernelGGL(cam_cold_sum<CCS_THREADS>, dim3(c->n_cams), dim3(CCS_THREADS), 0, c->stream, da, 0);
-      *binv_mode = 2;  // dense y (sigma applied)
-    } else {
-      hipLaunchKernelGGL(cm_scatter, dim3(grid_for(std::max(c->n_items, 1), 4)), dim3(256), 0, c->stream, c->d, 1, 0);
-      *binv_mode = 1;
-      if (sharded(c)) {
+      if (hom)
+        hipLaunchKernelGGL(cam_cold_sum_binv_h<CCS_THREADS>, dim3(c->n_cams), dim3(CCS_THREADS), 0, c->stream, da, norms, (const double*)c->ncw.p);
+      else
+        hipLaunchKernelGGL(cam_cold_sum_binv<CCS_THREADS>, dim3(c->n_cams), dim3(CCS_THREADS), 0, c->stream, da, norms);
+      break;
+    case CamStep::sum:  // dense y (sigma applied); with the peer-to-peer exchange it pushes the partials to the peers
+      hipLaunchKernelGGL(cam_cold_sum<CCS_THREADS>, dim3(c->n_cams), dim3(CCS_THREADS), 0, c->stream, da, hom);
+      break;
+    case CamStep::scatter:
+    case CamStep::scatter_sum:
+      hipLaunchKernelGGL(cm_scatter, dim3(grid_for(std::max(c->n_items, 1), 4)), dim3(256), 0, c->stream, c->d, 1, hom);
+      if (p.cam == CamStep::scatter_sum)
         hipLaunchKernelGGL(cam_sum_items, dim3(grid_for(c->n_cams, 4)), dim3(256), 0, c->stream, c->d, c->d.y, 1);
-        *binv_mode = 2;
-      }
-    }
+      break;
   }
-  if (c->p2p && fuse_norms >= 0 && *binv_mode == 2 && !c->joint && c->use_lpl && c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC) {
-    *binv_mode = 5;  // cam_cold_sum pushed the partials to the peers; cam_binv_axpy waits for the world's slabs
-    return 0;
-  }
-  if (sharded(c)) {
-    int rc = allreduce(c, c->d.y, 12 * (size_t)c->n_cams);
-    if (rc) return rc;
-  }
+  if (p.exch == Exch::allreduce) return allreduce(c, c->d.y, 12 * (size_t)c->n_cams);
   return 0;
+}
+
+// dynamic LDS of the kernels this unit launches (povar_create)
+template <int NW, int SD, bool DB, int NG>
+hipError_t ck_set_lds_t() {
+  hipError_t e = hipFuncSetAttribute((const void*)e0_ck<NW, SD, DB, NG, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, CK_LDS_BYTES);
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)e0_ck<NW, SD, DB, NG, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, CK_LDS_BYTES);
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)e0_ck<NW, SD, DB, NG, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CK_LDS_BYTES);
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)e0_ck<NW, SD, DB, NG, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CK_LDS_BYTES);
+  return e;
+}
+
+hipError_t term_set_lds_all() {
+  const auto set = [](const void* f, size_t bytes) { return hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); };
+  hipError_t e = set((const void*)e0_lm_cached<false>, HOT_MAX * HOT_REC * sizeof(double2));
+  if (e == hipSuccess) e = set((const void*)e0_tiles_cached, HOT_ACC_MAX * (HOT_REC_T * sizeof(double2) + 96));
+  if (e == hipSuccess) e = set((const void*)e0_lm_cached_h, HOT_ACC_MAX * (HOT_REC_H * sizeof(double2) + 96));
+  if (e == hipSuccess) e = set((const void*)e0_lm_cached<true>, HOT_ACC_MAX * (HOT_REC * sizeof(double2) + 96));
+  if (e == hipSuccess) e = set((const void*)e0_lpl<false>, lpl_lds_bytes(HOT_ACC_MAX));
+  if (e == hipSuccess) e = set((const void*)e0_lpl<true>, lpl_lds_bytes(HOT_ACC_MAX));
+  if (e == hipSuccess) e = set((const void*)e0_lpl_h<false>, lpl_lds_bytes_h(HOT_ACC_MAX));
+  if (e == hipSuccess) e = set((const void*)e0_lpl_h<true>, lpl_lds_bytes_h(HOT_ACC_MAX));
+  if (e == hipSuccess) e = set((const void*)e0_ck_det<16, 2, false>, CK_LDS_BYTES);
+  if (e == hipSuccess) e = set((const void*)e0_ck_det<16, 2, true>, CK_LDS_BYTES);
+  if (e == hipSuccess) e = set((const void*)e0_ck_h_det<16, 2, false>, CK_LDS_BYTES);
+  if (e == hipSuccess) e = set((const void*)e0_ck_h_det<16, 2, true>, CK_LDS_BYTES);
+  if (e == hipSuccess) e = set((const void*)e0_ck_f32<false, false>, CK_LDS_BYTES);
+  if (e == hipSuccess) e = set((const void*)e0_ck_f32<true, false>, CK_LDS_BYTES);
+  if (e == hipSuccess) e = set((const void*)e0_ck_f32<false, true>, CK_LDS_BYTES);
+  if (e == hipSuccess) e = set((const void*)e0_ck_f32<true, true>, CK_LDS_BYTES);
+  if (e == hipSuccess) e = set((const void*)e0_ck_h<16, 2, false>, CK_LDS_BYTES);
+  if (e == hipSuccess) e = set((const void*)e0_ck_h<16, 2, true>, CK_LDS_BYTES);
+  if (e == hipSuccess) e = set((const void*)e0_ck_h<16, 2, false, CKH_STRIDE_WIDE>, CK_LDS_BYTES);
+  if (e == hipSuccess) e = set((const void*)e0_ck_h<16, 2, true, CKH_STRIDE_WIDE>, CK_LDS_BYTES);
+#define X(id, nw, sd, db, ng) if (e == hipSuccess) e = ck_set_lds_t<nw, sd, db, ng>();
+  POVAR_CK_VARIANTS(X)
+#undef X
+  return e;
 }
 
 void launch_binv(povar_ctx* c, int mode, int want_norms) {
   if (mode == 4) return;  // fused into cam_cold_sum_binv
   prof_mark(c, 1);
   if (c->joint) {
-    const Dp dt = mode == 3 ? ldsacc_dp(c) : c->d;
-    hipLaunchKernelGGL(cam_binv_axpy_h, dim3(c->n_cam_blocks), dim3(K9_CAMS * 64), 0, c->stream, dt, mode == 3 ? 1 : mode,
-                       want_norms, (const double*)c->ncw.p);
-  }
-  else {
-    Dp dt = mode == 3 ? ldsacc_dp(c) : c->d;  // 3: item sums over the cold view + LDS partials
+    hipLaunchKernelGGL(cam_binv_axpy_h, dim3(c->n_cam_blocks), dim3(K9_CAMS * 64), 0, c->stream, c->d, mode, want_norms,
+                       (const double*)c->ncw.p);
+  } else {
+    Dp dt = c->d;
     if (mode == 5) p2p_dp(c, dt);
-    hipLaunchKernelGGL(cam_binv_axpy, dim3(c->n_cam_blocks), dim3(K9_CAMS * 64), 0, c->stream, dt, mode == 3 ? 1 : mode,
-                       want_norms);
+    hipLaunchKernelGGL(cam_binv_axpy, dim3(c->n_cam_blocks), dim3(K9_CAMS * 64), 0, c->stream, dt, mode, want_norms);
   }
 }
 
-int ck_autotune(povar_ctx* c) {
-  if (c->fp32_terms || !c->ck_auto || c->ck_tuned || !c->ck.ready || !c->use_lpl || c->joint || c->opt.e0_mode != POVAR_E0_IMPLICIT_LDSACC ||
-      !ck_variant_fits(c, 1))
+// Which of a step's two E0 kernels is faster depends on the graph (e0_ck: venice-like camera counts, any share of
+// observations whose camera has no LDS slot; e0_lpl: many cameras and few observations per (camera, batch), where a chunk
+// is a single observation -- final-13682).  Unless the caller has forced one, both are timed once per layout on the
+// problem itself: a warm-up and three launches each on the prepared system (they only write their partial records).
+int ck_autotune(povar_ctx* c, int step) {
+  bool& tuned = step == 2 ? c->ckh_tuned : c->ck_tuned;
+  int& variant = step == 2 ? c->ckh_variant : c->ck_variant;
+  if (!c->ck_auto || tuned || c->joint != (step == 2)) return 0;
+  const TermPlan lpl = term_plan(c, step, TermUse::timing, 0), ck = term_plan(c, step, TermUse::timing, 1);
+  if (ck.e0 != (step == 2 ? E0K::ck_h : E0K::ck)) {
+    // (a step-2 chunk layout the kernel cannot run settles step 2 on e0_lpl_h; step 1 asks again)
+    if (step == 2 && lpl.e0 == E0K::lpl_h && c->ckh.ready) {
+      tuned = true;
+      variant = 0;
+    }
     return 0;
-  c->ck_tuned = true;
-  ensure_ck_w(c);
+  }
+  tuned = true;
+  ensure_ck_w(c, step);
   HIP_TRY(hipMemsetAsync(c->flags.p + 1, 0, sizeof(int) * 3, c->stream));  // (a series that ended early leaves "done" set)
   // Two rounds of (warm-up + REPS launches) of each kernel, alternating, the FASTER round of each counts: one round's mean
   // was seen 18 % off on the same box (Zipf(0.5): e0_ck 80.2 against 67.9 us in two processes -- clocks still ramping, the
@@ -467,44 +469,27 @@ int ck_autotune(povar_ctx* c) {
   constexpr int ROUNDS = 2;
   EventSet<4 * ROUNDS> ev;
   HIP_TRY(ev.create());
-  Dp da = ldsacc_dp(c, true);
-  da.p2p_peer = nullptr;
-  da.p2p_epoch = nullptr;
-  Dp dk = da;
-  ck_dp(c, dk);
-  const int keep = c->ck_variant;
-  struct Restore {  // a failure below leaves the choice as it was and the timing to be repeated
-    povar_ctx* c; int keep; bool done = false;
-    ~Restore() { if (!done) { c->ck_variant = keep; c->ck_tuned = false; } }
-  } restore{c, keep};
-  c->ck_variant = 1;
+  struct Restore {  // a failure below leaves the timing to be repeated (step 1 on its kernel, step 2 on e0_lpl_h)
+    int& variant; bool& tuned; int keep; bool done = false;
+    ~Restore() { if (!done) { variant = keep; tuned = false; } }
+  } restore{variant, tuned, step == 2 ? 0 : variant};
   // What is timed is the PAIR of a term -- the E0 kernel and the per-camera kernel behind it --: e0_lpl leaves its cold
   // observations to the per-camera kernel (Zipf(0.5): 25 us there against 7 behind e0_ck; the E0 kernels alone were a draw
   // in some processes and the slower pair was kept).  The per-camera kernel's outputs (accum, tmp, z) are what the series'
   // first kernel writes anyway.
-  auto run_lpl = [&]() {
-    if (c->opt.robust_norm)
-      hipLaunchKernelGGL(e0_lpl<true>, dim3(c->e0c_grid), dim3(E0C_BLOCK), lpl_lds_bytes(c->v2_max_slots), c->stream, da, c->v2_part.p);
-    else
-      hipLaunchKernelGGL(e0_lpl<false>, dim3(c->e0c_grid), dim3(E0C_BLOCK), lpl_lds_bytes(c->v2_max_slots), c->stream, da, c->v2_part.p);
-    hipLaunchKernelGGL(cam_cold_sum_binv<CCS_THREADS>, dim3(c->n_cams), dim3(CCS_THREADS), 0, c->stream, da, 0);
-  };
-  auto run_ck = [&]() {
-    launch_e0_ck(c, dk);
-    hipLaunchKernelGGL(cam_cold_sum_binv<CCS_THREADS>, dim3(c->n_cams), dim3(CCS_THREADS), 0, c->stream, dk, 0);
-  };
   constexpr int REPS = 3;
   for (int r = 0; r < ROUNDS; ++r) {
-    run_lpl();
+    if (int rc = launch_e0(c, lpl)) return rc;
     HIP_TRY(hipEventRecord(ev[4 * r], c->stream));
-    for (int i = 0; i < REPS; ++i) run_lpl();
+    for (int i = 0; i < REPS; ++i)
+      if (int rc = launch_e0(c, lpl)) return rc;
     HIP_TRY(hipEventRecord(ev[4 * r + 1], c->stream));
-    run_ck();
+    if (int rc = launch_e0(c, ck)) return rc;
     HIP_TRY(hipEventRecord(ev[4 * r + 2], c->stream));
-    for (int i = 0; i < REPS; ++i) run_ck();
+    for (int i = 0; i < REPS; ++i)
+      if (int rc = launch_e0(c, ck)) return rc;
     HIP_TRY(hipEventRecord(ev[4 * r + 3], c->stream));
   }
-  c->ck_variant = keep;
   HIP_TRY(hipStreamSynchronize(c->stream));
   HIP_TRY(hipGetLastError());
   float ms_lpl = 1e30f, ms_ck = 1e30f;
@@ -516,10 +501,11 @@ int ck_autotune(povar_ctx* c) {
     ms_ck = std::min(ms_ck, b);
   }
   restore.done = true;
-  c->ck_tune_us[0] = 1e3f * ms_lpl / REPS;
-  c->ck_tune_us[1] = 1e3f * ms_ck / REPS;
-  c->ck_variant = ms_ck < 0.98f * ms_lpl ? 1 : 0;
-  c->ck_fresh[0] = true;
+  float* us = step == 2 ? c->ckh_tune_us : c->ck_tune_us;
+  us[0] = 1e3f * ms_lpl / REPS;
+  us[1] = 1e3f * ms_ck / REPS;
+  variant = ms_ck < 0.98f * ms_lpl ? 1 : 0;
+  c->ck_fresh[step - 1] = true;
   return 0;
 }
 
@@ -549,67 +535,6 @@ int tune_agree(povar_ctx* c, int step) {
   return 0;
 }
 
-// the same choice for step 2: e0_lpl_h against e0_ck_h on the prepared joint system
-int ckh_autotune(povar_ctx* c) {
-  if (!c->ck_auto || c->ckh_tuned || !c->joint || !c->ckh.ready || !c->use_lpl || c->opt.e0_mode != POVAR_E0_IMPLICIT_LDSACC) return 0;
-  c->ckh_tuned = true;
-  c->ckh_variant = 1;
-  if (!ckh_active(c)) {
-    c->ckh_variant = 0;
-    return 0;
-  }
-  ensure_ck_w(c);
-  HIP_TRY(hipMemsetAsync(c->flags.p + 1, 0, sizeof(int) * 3, c->stream));
-  constexpr int ROUNDS = 2;
-  EventSet<4 * ROUNDS> ev;
-  HIP_TRY(ev.create());
-  struct Restore {
-    povar_ctx* c; bool done = false;
-    ~Restore() { if (!done) { c->ckh_variant = 0; c->ckh_tuned = false; } }
-  } restore{c};
-  Dp da = ldsacc_dp(c, true);
-  Dp dk = da;
-  ck_dp(c, dk);
-  auto run_lpl = [&]() {
-    if (c->opt.robust_norm)
-      hipLaunchKernelGGL(e0_lpl_h<true>, dim3(c->e0c_grid), dim3(E0C_BLOCK), lpl_lds_bytes_h(c->v2_max_slots), c->stream, da, c->v2_part.p);
-    else
-      hipLaunchKernelGGL(e0_lpl_h<false>, dim3(c->e0c_grid), dim3(E0C_BLOCK), lpl_lds_bytes_h(c->v2_max_slots), c->stream, da, c->v2_part.p);
-    hipLaunchKernelGGL(cam_cold_sum_binv_h<CCS_THREADS>, dim3(c->n_cams), dim3(CCS_THREADS), 0, c->stream, da, 0, (const double*)c->ncw.p);
-  };
-  auto run_ck = [&]() {
-    launch_e0_ck_h(c, dk);
-    hipLaunchKernelGGL(cam_cold_sum_binv_h<CCS_THREADS>, dim3(c->n_cams), dim3(CCS_THREADS), 0, c->stream, dk, 0, (const double*)c->ncw.p);
-  };
-  constexpr int REPS = 3;
-  for (int r = 0; r < ROUNDS; ++r) {  // (two alternating rounds of the term's pair, the faster one of each counts: see ck_autotune)
-    run_lpl();
-    HIP_TRY(hipEventRecord(ev[4 * r], c->stream));
-    for (int i = 0; i < REPS; ++i) run_lpl();
-    HIP_TRY(hipEventRecord(ev[4 * r + 1], c->stream));
-    run_ck();
-    HIP_TRY(hipEventRecord(ev[4 * r + 2], c->stream));
-    for (int i = 0; i < REPS; ++i) run_ck();
-    HIP_TRY(hipEventRecord(ev[4 * r + 3], c->stream));
-  }
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  HIP_TRY(hipGetLastError());
-  float ms_lpl = 1e30f, ms_ck = 1e30f;
-  for (int r = 0; r < ROUNDS; ++r) {
-    float ta = 0, tb = 0;
-    HIP_TRY(hipEventElapsedTime(&ta, ev[4 * r], ev[4 * r + 1]));
-    HIP_TRY(hipEventElapsedTime(&tb, ev[4 * r + 2], ev[4 * r + 3]));
-    ms_lpl = std::min(ms_lpl, ta);
-    ms_ck = std::min(ms_ck, tb);
-  }
-  restore.done = true;
-  c->ckh_tune_us[0] = 1e3f * ms_lpl / REPS;
-  c->ckh_tune_us[1] = 1e3f * ms_ck / REPS;
-  c->ckh_variant = ms_ck < 0.98f * ms_lpl ? 1 : 0;
-  c->ck_fresh[1] = true;
-  return 0;
-}
-
 extern "C" {
 
 
@@ -625,27 +550,27 @@ int povar_power_series_begin(povar_ctx* c) {
 int povar_power_series_step(povar_ctx* c) {
   if (int rc = check_ctx(c)) return rc;
   if (int rc = res_verify(c)) return rc;  // (a resident series that gave up is repeated BEFORE its state is overwritten / continued)
-  int mode = 1;
-  if (!c->joint) c->fp32_last = ck32_active(c) ? 1 : 0;
-  if (int rc = launch_e0(c, &mode, 0)) return rc;
-  launch_binv(c, mode, 0);
+  const TermPlan p = term_plan(c, c->joint ? 2 : 1, TermUse::series);
+  if (p.step == 1) c->fp32_last = p.e0 == E0K::ck_f32 ? 1 : 0;
+  if (int rc = launch_e0(c, p)) return rc;
+  launch_binv(c, p.binv_mode(), 0);
   HIP_TRY(hipGetLastError());
   return 0;
 }
 
 int enqueue_series(povar_ctx* c, int32_t m, double q_tol, double r_tol) {
   const bool norms = q_tol > 0 || r_tol > 0;
+  const TermPlan p = term_plan(c, c->joint ? 2 : 1, norms ? TermUse::series_norms : TermUse::series);
   HIP_TRY(hipMemsetAsync(c->flags.p + 1, 0, sizeof(int) * 3, c->stream));
   launch_binv(c, 0, (m > 0 && r_tol > 0) ? 1 : 0);
   if (m > 0 && r_tol > 0)
     hipLaunchKernelGGL(series_check, dim3(1), dim3(64), 0, c->stream, c->d, c->n_cam_blocks, 0, q_tol, r_tol);
   for (int i = 1; i <= m; ++i) {
-    int mode = 1;
-    if (int rc = launch_e0(c, &mode, norms ? 1 : 0)) return rc;
-    launch_binv(c, mode, norms ? 1 : 0);
+    if (int rc = launch_e0(c, p)) return rc;
+    launch_binv(c, p.binv_mode(), norms ? 1 : 0);
     if (norms)  // the fused kernel leaves one norm partial per camera, cam_binv_axpy one per workgroup
-      hipLaunchKernelGGL(series_check, dim3(1), dim3(64), 0, c->stream, c->d, mode == 4 ? c->n_cams : c->n_cam_blocks, i,
-                         q_tol, r_tol);
+      hipLaunchKernelGGL(series_check, dim3(1), dim3(64), 0, c->stream, c->d, p.cam == CamStep::fused ? c->n_cams : c->n_cam_blocks,
+                         i, q_tol, r_tol);
   }
   prof_mark(c, -1);
   return 0;
@@ -655,14 +580,15 @@ int enqueue_series(povar_ctx* c, int32_t m, double q_tol, double r_tol) {
 // hipGraph where the context allows a capture.
 int run_series(povar_ctx* c, int32_t m, double q_tol, double r_tol, bool use_res) {
   const bool norms = q_tol > 0 || r_tol > 0;
+  const TermPlan p = term_plan(c, c->joint ? 2 : 1, norms ? TermUse::series_norms : TermUse::series);
   // with a communicator the loop is launched kernel by kernel (the per-term all-reduce dominates and
   // RCCL-in-capture is not something a 1-GPU box can validate); POVAR_GRAPH_COMM=1 opts in
-  const bool p2p_terms = c->p2p && !c->joint && c->use_lpl && c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC;
-  if (c->use_graph && !c->profile && m > 0 && (use_res || p2p_terms || (!c->host_fn && (!c->comm || c->graph_with_comm)))) {
+  if (c->use_graph && !c->profile && m > 0 && (use_res || p.p2p_check() || (!c->host_fn && (!c->comm || c->graph_with_comm)))) {
     // the whole loop (memset, B^-1, m x {E0 kernels, [all-reduce], B^-1 + AXPY, [check]}) is one graph
     // launch; it is re-captured only when a kernel argument changes
     const int key[6] = {m, (c->joint ? 1 : 0) | (use_res ? 2 : 0) | (use_res ? (res_params(c, m, q_tol, r_tol).w_mode << 2) : 0),
-                        c->opt.e0_mode + 16 * (c->joint ? (ckh_active(c) ? 1 : 0) : ck_active(c) ? c->ck_variant : 0), (sharded(c) ? 1 : 0) | (p2p_terms ? 2 : 0), norms ? 1 : 0, r_tol > 0 ? 1 : 0};
+                        c->opt.e0_mode + 16 * ((int)p.e0 + 16 * p.variant), (p.exch != Exch::none ? 1 : 0) | (p.p2p_check() ? 2 : 0),
+                        norms ? 1 : 0, r_tol > 0 ? 1 : 0};
     // (the landmark damping is an argument of the prepare / back-substitution kernels only: no kernel of the loop reads
     // it, and step 2 changes it with every LM iteration -- a capture + instantiation of 0.25 ms each time)
     Dp key_d = c->d;
@@ -778,23 +704,22 @@ int povar_power_series_pose(povar_ctx* c, int32_t m, double q_tol, double r_tol,
   if (int rc = check_ctx(c)) return rc;
   if (m < 0) return fail(-1, "power_sc_iterations < 0");
   TimeScope ts(c, 2);
-  if (!(c->use_lpl && c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC)) ensure_legacy(c);  // not inside the graph capture
-  if (int rc = ck_autotune(c)) return rc;
-  if (int rc = ckh_autotune(c)) return rc;
-  if (ck_active(c) || ckh_active(c)) ensure_ck_w(c);
-  if (int rc = res_autotune(c, m, q_tol, r_tol)) return rc;
+  if (!lpl_mode(c)) ensure_legacy(c);  // not inside the graph capture
+  if (int rc = ck_autotune(c, c->joint ? 2 : 1)) return rc;
   const bool norms = q_tol > 0 || r_tol > 0;
-  const bool p2p_terms = c->p2p && !c->joint && c->use_lpl && c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC;
+  const TermPlan p = term_plan(c, c->joint ? 2 : 1, norms ? TermUse::series_norms : TermUse::series);
+  if (p.ck()) ensure_ck_w(c, p.step);
+  if (int rc = res_autotune(c, m, q_tol, r_tol)) return rc;
   const bool use_res = m > 0 && m <= 250 && res_active(c);  // (a granule tag carries the term in 8 bits)
-  if (!c->joint) c->fp32_last = ck32_active(c) && !use_res ? 1 : 0;
+  if (p.step == 1) c->fp32_last = p.e0 == E0K::ck_f32 && !use_res ? 1 : 0;
   if (int rc = run_series(c, m, q_tol, r_tol, use_res)) return rc;
   int iters = m, status = POVAR_LINEAR_SOLVER_NO_CONVERGENCE;
-  if (p2p_terms) c->flag0_clean = false;  // the waits of the exchange kernels raise bit 1 of flags[0] on a time-out
-  if (c->deterministic && (ck_active(c) || ckh_active(c))) {  // e0_ck[_h]_det: a ticket that never came up raises bit 3 (bounded spins):
+  if (p.p2p_check()) c->flag0_clean = false;  // the waits of the exchange kernels raise bit 1 of flags[0] on a time-out
+  if (p.det_check()) {  // e0_ck[_h]_det: a ticket that never came up raises bit 3 (bounded spins):
     c->flag0_clean = false;                // looked at where the caller next waits for the series (res_verify)
     c->det_check = true;
   }
-  if (p2p_terms) {
+  if (p.p2p_check()) {
     int f[4];
     if (int rc = read_flags(c, f)) return rc;
     if (f[0] & 2) {
@@ -846,12 +771,10 @@ int povar_right_mul_e0_pose(povar_ctx* c, const double* x, double* y) {
   // z = sigma * x
   HIP_TRY(hipMemcpyAsync(c->inc.p, c->tmp.p, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
   hipLaunchKernelGGL(cam_apply_inc, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, c->d, 1);
-  int mode = 1;
-  if (int rc = launch_e0(c, &mode)) return rc;
-  if (mode == 1 || mode == 3) {
-    const Dp dt = mode == 3 ? ldsacc_dp(c) : c->d;
-    hipLaunchKernelGGL(cam_sum_items, dim3(grid_for(c->n_cams, 4)), dim3(256), 0, c->stream, dt, c->d.y, 1);
-  }
+  const TermPlan p = term_plan(c, c->joint ? 2 : 1, TermUse::right_mul);
+  if (int rc = launch_e0(c, p)) return rc;
+  if (p.cam == CamStep::scatter)
+    hipLaunchKernelGGL(cam_sum_items, dim3(grid_for(c->n_cams, 4)), dim3(256), 0, c->stream, c->d, c->d.y, 1);
   HIP_TRY(hipMemcpyAsync(y, c->y.p, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemsetAsync(c->y.p, 0, sizeof(double) * n, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -916,88 +839,86 @@ int povar_e0_model_bytes(povar_ctx* c, int64_t* lm_kernel, int64_t* cam_kernel) 
   const int64_t ns = c->n_slots, nl = c->n_lms, nc = c->n_cams, no = c->n_obs;
   const int64_t robust = c->opt.robust_norm ? 8 : 0;
   const int64_t cam_static = nc * (96 + 96);            // z (12 doubles) + P (12 doubles) per camera
-  const bool acc = c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC || c->opt.e0_mode == POVAR_E0_TILES_LDSACC;
-  const bool lik = c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC && c->long_in_kernel;
-  const bool lpl = c->use_lpl && c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC;
+  const TermPlan p = term_plan(c, c->joint ? 2 : 1, TermUse::series);
+  E0K k = p.e0;
+  if (k == E0K::lm_h)  // (step 2 outside the LDS-accumulating mode is priced as step 1's kernel of the mode)
+    k = c->opt.e0_mode == POVAR_E0_TILES ? E0K::lm_tiles : c->opt.e0_mode == POVAR_E0_TILES_LDSACC ? E0K::tiles_cached : E0K::lm_cached;
+  const bool lpl = k == E0K::lpl || k == E0K::lpl_h;
+  const bool lik = (k == E0K::lm_cached_acc || k == E0K::lm_cached_h) && c->long_in_kernel;
+  const bool acc = k == E0K::lm_cached_acc || k == E0K::lm_cached_h || k == E0K::tiles_cached;
   const int64_t n_cold = lpl ? c->n_cold3 : lik ? c->n_cold2 : c->n_cold;
   const int64_t hot_flush = lpl ? (int64_t)c->v2_part.n * 8 : acc ? (int64_t)c->e0c_grid * c->n_hot_acc * 96 : 0;
   const int64_t tail = nc * (1152 + 96 /*sigma*/ + 3 * 96 /*accum rw, tmp*/ + 96 /*z*/);
+  const int64_t part = (int64_t)(p.step == 2 ? c->ckh : c->ck).n_part_rec * 96;
   int64_t lm = 0, cm = 0;
-  if (c->deterministic && ck_active(c)) {
-    // e0_ck_det: as e0_ck below with the rows THREE times (two walks forward, one back), the landmark records twice (h~, G),
-    // and 1 + 2 bytes of counts / tickets per landmark lane / chunk lane
-    const int64_t part = (int64_t)c->ck.n_part_rec * 96;
-    *lm_kernel = 3 * c->ck.rows * WAVE * 18 + (int64_t)c->d.v2.n_tiles * WAVE * (72 + 1) + cam_static +
-                 4 * (int64_t)(c->ck.lane_meta.n) * 8 + (int64_t)c->ck.lane_meta.n * 2 + part;
-    *cam_kernel = part + tail;
-    return 0;
-  }
-  if (c->deterministic && ckh_active(c)) {  // e0_ck_h_det: the 2-byte rows (+ 8 with a robust norm) three times, X / records twice
-    const int64_t part = (int64_t)c->ckh.n_part_rec * 96;
-    *lm_kernel = 3 * c->ckh.rows * WAVE * (2 + robust) + (int64_t)c->d.v2.n_tiles * WAVE * (112 + 1) + cam_static +
-                 4 * (int64_t)(c->ckh.lane_meta.n) * 8 + (int64_t)c->ckh.lane_meta.n * 2 + part;
-    *cam_kernel = part + tail;
-    return 0;
-  }
-  switch (c->opt.e0_mode) {
-    case POVAR_E0_IMPLICIT_LDSACC:
-      if (ck32_active(c)) {
-        // e0_ck_f32: the rows on both passes at 8 + 2 bytes (packed or fp32 image points + slot), the 36-byte fp32 landmark
-        // records once, the camera image (z 96 in fp64 + P 48 in fp32), lane metadata on both passes, fp64 partial records
-        const int64_t part = (int64_t)c->ck.n_part_rec * 96;
-        lm = 2 * c->ck.rows * WAVE * 10 + (int64_t)c->d.v2.n_tiles * WAVE * 36 + nc * (96 + 48) + 2 * (int64_t)(c->ck.lane_meta.n) * 8 + part;
-        cm = part + tail;
-        if (c->ck.cold_q) {
-          lm += 36 * c->n_cold3;
-          cm += 56 * c->n_cold3;
-        }
-        break;
+  switch (k) {
+    case E0K::ck_det:
+      // e0_ck_det: as e0_ck below with the rows THREE times (two walks forward, one back), the landmark records twice (h~, G),
+      // and 1 + 2 bytes of counts / tickets per landmark lane / chunk lane
+      lm = 3 * c->ck.rows * WAVE * 18 + (int64_t)c->d.v2.n_tiles * WAVE * (72 + 1) + cam_static +
+           4 * (int64_t)(c->ck.lane_meta.n) * 8 + (int64_t)c->ck.lane_meta.n * 2 + part;
+      cm = part + tail;
+      break;
+    case E0K::ck_h_det:  // e0_ck_h_det: the 2-byte rows (+ 8 with a robust norm) three times, X / records twice
+      lm = 3 * c->ckh.rows * WAVE * (2 + robust) + (int64_t)c->d.v2.n_tiles * WAVE * (112 + 1) + cam_static +
+           4 * (int64_t)(c->ckh.lane_meta.n) * 8 + (int64_t)c->ckh.lane_meta.n * 2 + part;
+      cm = part + tail;
+      break;
+    case E0K::ck_f32:
+      // e0_ck_f32: the rows on both passes at 8 + 2 bytes (packed or fp32 image points + slot), the 36-byte fp32 landmark
+      // records once, the camera image (z 96 in fp64 + P 48 in fp32), lane metadata on both passes, fp64 partial records
+      lm = 2 * c->ck.rows * WAVE * 10 + (int64_t)c->d.v2.n_tiles * WAVE * 36 + nc * (96 + 48) + 2 * (int64_t)(c->ck.lane_meta.n) * 8 + part;
+      cm = part + tail;
+      if (c->ck.cold_q) {
+        lm += 36 * c->n_cold3;
+        cm += 56 * c->n_cold3;
       }
-      if (ck_active(c)) {
-        // e0_ck: the chunk rows (uv 16 + landmark slot 2 bytes) on BOTH passes -- the kernel as built reads them twice --,
-        // the 72-byte landmark records once, 8 bytes of lane metadata per chunk lane and pass, the partial records out
-        // (one per workgroup slot + one per chunk of a camera without a slot); the per-camera kernel reads those back
-        const int64_t part = (int64_t)c->ck.n_part_rec * 96;
-        lm = 2 * c->ck.rows * WAVE * (c->ck.packed ? 10 : 18) /* image point 16 bytes (8 packed) + slot 2; no weight array: recomputed (ck_huber_w) */ + (int64_t)c->d.v2.n_tiles * WAVE * 72 + cam_static +
-             2 * (int64_t)(c->ck.lane_meta.n) * 8 + part;
-        cm = part + tail;
-        if (c->ck.cold_q) {  // cold observations: position 4 + q 32 bytes out of e0_ck, q 32 + landmark copy 24 into the per-camera kernel
-          lm += 36 * c->n_cold3;
-          cm += 56 * c->n_cold3;
-        }
-        break;
+      break;
+    case E0K::ck:
+      // e0_ck: the chunk rows (uv 16 + landmark slot 2 bytes) on BOTH passes -- the kernel as built reads them twice --,
+      // the 72-byte landmark records once, 8 bytes of lane metadata per chunk lane and pass, the partial records out
+      // (one per workgroup slot + one per chunk of a camera without a slot); the per-camera kernel reads those back
+      lm = 2 * c->ck.rows * WAVE * (c->ck.packed ? 10 : 18) /* image point 16 bytes (8 packed) + slot 2; no weight array: recomputed (ck_huber_w) */ + (int64_t)c->d.v2.n_tiles * WAVE * 72 + cam_static +
+           2 * (int64_t)(c->ck.lane_meta.n) * 8 + part;
+      cm = part + tail;
+      if (c->ck.cold_q) {  // cold observations: position 4 + q 32 bytes out of e0_ck, q 32 + landmark copy 24 into the per-camera kernel
+        lm += 36 * c->n_cold3;
+        cm += 56 * c->n_cold3;
       }
-      if (ckh_active(c)) {
-        // e0_ck_h: landmark slot (2 bytes) [+ weight] per observation on both passes -- the step-2 operator does not read
-        // the image coordinates --, the 112-byte landmark records once, lane metadata, partial records out and back
-        const int64_t part = (int64_t)c->ckh.n_part_rec * 96;
-        lm = 2 * c->ckh.rows * WAVE * (2 + robust) + (int64_t)c->d.v2.n_tiles * WAVE * 112 + cam_static +
-             2 * (int64_t)(c->ckh.lane_meta.n) * 8 + part;
-        cm = part + tail;
-        break;
-      }
-      if (c->use_lpl)  // e0_lpl: uv + camera slot per row slot, 72-byte landmark records; e0_lpl_h: the camera slot only (its
-                       // operator does not depend on uv: the loads are dead code), 112-byte records; cold: position + q out
-        lm = c->v2_rows * WAVE * ((c->joint ? 4 : 20) + robust) + (int64_t)c->d.v2.n_tiles * WAVE * (c->joint ? 112 : 72) + cam_static +
+      break;
+    case E0K::ck_h:
+      // e0_ck_h: landmark slot (2 bytes) [+ weight] per observation on both passes -- the step-2 operator does not read
+      // the image coordinates --, the 112-byte landmark records once, lane metadata, partial records out and back
+      lm = 2 * c->ckh.rows * WAVE * (2 + robust) + (int64_t)c->d.v2.n_tiles * WAVE * 112 + cam_static +
+           2 * (int64_t)(c->ckh.lane_meta.n) * 8 + part;
+      cm = part + tail;
+      break;
+    case E0K::lpl:
+    case E0K::lpl_h:
+    case E0K::lm_cached_acc:
+    case E0K::lm_cached_h:
+      if (lpl)  // e0_lpl: uv + camera slot per row slot, 72-byte landmark records; e0_lpl_h: the camera slot only (its
+                // operator does not depend on uv: the loads are dead code), 112-byte records; cold: position + q out
+        lm = c->v2_rows * WAVE * ((k == E0K::lpl_h ? 4 : 20) + robust) + (int64_t)c->d.v2.n_tiles * WAVE * (k == E0K::lpl_h ? 112 : 72) + cam_static +
              n_cold * (c->q_rows ? 32 : 36) + hot_flush;  // q_rows: no position load, the per-camera kernel reads the index
       else
-          lm = ns * (E0_SLOT_BYTES + robust) + nl * E0_LMREC_BYTES + cam_static + n_cold * 32 + hot_flush;
+        lm = ns * (E0_SLOT_BYTES + robust) + nl * E0_LMREC_BYTES + cam_static + n_cold * 32 + hot_flush;
       cm = hot_flush + n_cold * (32 + 24 + (lpl && c->q_rows ? 4 : 0)) + tail;
       break;
-    case POVAR_E0_IMPLICIT:
+    case E0K::lm_cached:
       lm = ns * (28 + robust) + nl * 96 + cam_static + no * 32;   // uv, cam, lm, meta; q4 out
       cm = no * (4 + 32 + 24) + tail;                                // cm_slot, q4 gather, cm_h
       break;
-    case POVAR_E0_TILES:
+    case E0K::lm_tiles:
       lm = ns * (12 + 480 + robust) + nl * 72 + nc * 96 + no * 32;
       cm = no * (4 + 32 + 24) + tail;
       break;
-    case POVAR_E0_TILES_LDSACC:
+    case E0K::tiles_cached:
       lm = ns * (12 + 480 + robust) + nl * 72 + nc * 96 + n_cold * 32 + hot_flush;
       cm = hot_flush + n_cold * (4 + 32 + 24) + tail;
       break;
-    default:
-      return fail(-1, "bad e0 mode");
+    case E0K::lm_h:
+      break;
   }
   *lm_kernel = lm;
   *cam_kernel = cm;
