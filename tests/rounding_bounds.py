@@ -1,6 +1,8 @@
-"""Componentwise rounding-error bounds for the step-1 E0 kernels: a long-double reference of each kernel's own factorisation
-and, from the same chain run on absolute values, a bound on |y_dev - y_ref| for EVERY output entry (helper module of
-tests/test_rounding_bounds.py and tests/test_gpu_e0_bounds.py; not a test module).
+"""Componentwise rounding-error bounds for the E0 kernels of both steps: a long-double reference of each kernel's own
+factorisation and, from the same chain run on absolute values, a bound on |y_dev - y_ref| for EVERY output entry (helper
+module of tests/test_rounding_bounds.py, tests/test_gpu_e0_bounds.py and tests/test_gpu_e0h_bounds.py; not a test module).
+Step 1 (pOSE: Step1, evaluate, emulate, edge_problem) comes first, step 2 (RIPOBA: Step2, evaluate_joint, emulate_joint,
+edge_problem_joint) after it.
 
 Why componentwise.  A relative 2-norm over 12 n_cams outputs is dominated by the hub cameras: a tail camera's block can be
 dropped, doubled or stale without moving it past 1e-12; and for the fp32 terms no normwise tolerance fits, because an
@@ -81,6 +83,87 @@ Jp = sb sw sigma Jp0 and Jl = sb sw s Jl0; there the magnitudes are |Jl0|^T D^2 
 |Jp0|^T D^2 |Jl0| |G| |Jl0|^T D^2 |Jp0| |z| (as exact_rational._rows builds the rows), with KF = 24 (Jp entries: three
 products, 3; Jp x: a 12-term dot, 12; Jl entries: P0 - u P2 and three scalings, 5; Jl^T t: 4), KG = 3 (Hi tot) and KB = 13
 (Jl v: 3; Jl entries: 5; pose_q: 4; then gamma_1 for h~ q).
+
+Step 2 (RIPOBA: homogeneous landmarks X in R^4, tangent bases).  One application takes the previous term x11 (11 per
+camera) to the next one; with N = (I - beta w w^T)[:, 1:] the Householder bases of cameras (BUF_NC_HOUSEHOLDER) and
+landmarks (house4 of X), pc = P X = (x, y, z), D = [[1/z, 0, -x/z^2], [0, 1/z, -y/z^2]], sw = sqrt of the robust weight:
+
+    input     z = sigma (N_c x11)
+    forward   t = sw D (Z X) (2-vector, Z = z_c as 3x4),   U4_l += P^T D^T (sw t)
+    middle    u3 = N_l^T (s o U4),   g3 = Hi u3,   G4 = s o (N_l g3)        (s: BUF_JL_COL_SCALE_H, Hi: BUF_HLL_INV, 3x3)
+    backward  q = sw D^T (sw D (P G4)),   Y_c += X (x) q  (entry 4 m + j = X_j q_m)
+    tail      y11 = N_c^T (sigma o Y),   t_next = B^-1_c y11               (BUF_B_INV_JOINT, 11x11)
+
+This ambient form (e0_ck_h) and the per-observation form Jl3 = sw D P diag(s) N_l of the other kernels are the same
+reference: u3 = sum Jl3^T t = N_l^T (s o U4), Jl3 g3 = sw D P G4 (the header of povar_kernels_ck_joint.hpp).  The operands
+-- the cameras and landmarks of the linearisation point, sigma, s, Hi, the camera reflectors (w, beta), B^-1 -- are the
+doubles of the context under test taken as exact numbers; that THEY are right is the business of the normwise tests against
+the oracle (test_gpu_step2.py, test_gpu_fuzz.py, ...), not of this module.  N_l is not readable: the reference recomputes
+house4 in long double from X, and the model carries the device's fp64 w0, beta as an operand perturbation dN.  Hi is used
+as the landmark records keep it (its upper triangle); OpE0H reads all nine entries, so |Hi - Hi^T| u3m is added (zero for
+a symmetric inverse).  Weights: compute_error_weight's (HUBER: min(1, t / |r|), r = (x/z - u, y/z - v); CAUCHY and NONE: 1,
+so CAUCHY has no branch and nothing to round) in long double; the device stores the fp64 weight at linearisation and every
+kernel applies its sqrt twice per pass.
+
+The step-2 bound.  Magnitudes use |N| = |I| + beta |w| |w|^T and |D| = A = (|1/z|, |x|/z^2, |y|/z^2); x, y, z are computed
+4-term dots, err(x) <= gamma_4 (|P0| . |X|) =: gamma_4 xm, so with ez = gamma_4 zm / |z|
+
+    E00 = A00 (ez + u),   E02 = A02 (2 ez + kD u) + gamma_4 xm / z^2     (E12 alike)
+
+-- a small |z| inflates the bound through err(z) / |z|, not through a constant.  With dm = |X| . |Z| and the input error
+Ez = gamma_15 sigma (|[0; x]| + beta |w| (|w[1:]| . |x|)) (an 11-term dot, beta w_i wt, the difference, sigma:
+cam_cold_sum_binv_h, povar_kernels_joint.hpp:1525-1538; cam_binv_axpy_h :663-669):
+
+    Ed   = |X| . Ez + gamma_4 dm
+    tm_k = sw (A00 dm_k + A_k2 dm_2),    Et_k = sw (A00 Ed_k + A_k2 Ed_2 + E00 dm_k + E_k2 dm_2) + (gamma_3 + rho) tm_k
+    em   = sw |D|^T tm,                  Ee   = sw (|D|^T Et + E^T tm) + (gamma_2 | gamma_3 + rho) em
+    vm   = |P|^T em,                     Ev   = |P|^T Ee + (gamma_kv + rho) vm
+    UM_l = sum vm,                       EU   = sum Ev  (+ the fixed-point grid of e0_ck_h_det, below)
+    u3m  = |N_l|^T (s o UM),             Eu3  = |N_l|^T (s o EU) + (gamma_klm + gamma_{n_l} + dN) u3m
+    g3m  = |Hi| u3m,                     Eg3  = |Hi| Eu3 + gamma_3 g3m + |Hi - Hi^T| u3m
+    G4m  = s o (|N_l| g3m),              EG4  = s o (|N_l| Eg3) + (gamma_7 + dN) G4m
+    pm   = |P| G4m,                      Ep   = |P| EG4 + gamma_4 pm
+    sm, qm, Es, Eq as tm, em, Et, Ee;    Ym_c = sum |X| (x) qm,   EY = sum (|X| (x) Eq + gamma_1 |X| (x) qm) + gamma_{n_c} Ym
+    y12m = sigma Ym,                     Ey12 = sigma EY + u y12m
+    y11m = |N_c|^T y12m,                 Ey11 = |N_c|^T Ey12 + gamma_15 y11m
+    bound = |B^-1| Ey11 + gamma_11 |B^-1| y11m
+
+The per-observation and the ambient form have the SAME magnitudes: jl4m^T tm = |P|^T (sw |D|^T tm) = vm entry by entry, and
+|N_l|^T distributes over the landmark's sum.  Only the counts differ, one ModelH per family:
+
+  kD       D02 beyond 2 ez.  hom_project (povar_kernels_joint.hpp:25-35): z z and the division, 2.  ckh_project
+           (povar_kernels_ck_joint.hpp:91-101): D00 D00 carries D00's own rounding twice and rounds, x iz2 rounds, 4.
+  t, s     hom_jp_x (:65-69): a product, an FMA, the scale: gamma_3; d: a 4-term dot (gamma_4).  ckh_obs_backward
+           (ck_joint:125-127): dot4 (gamma_4 on pm), then the same three.
+  e, q     sw D00 t: two products (gamma_2); sw (D02 t0 + D12 t1): gamma_3 (ckh_obs_forward, ck_joint:112; hom_q, :70-72).
+  kv       ambient: P0j e0 + P1j e1 + P2j e2 (ck_joint:113-116), gamma_3, on top of e's gamma_3: 6.  Jl3 form: the entry
+           sw (D00 P + D02 P2) s of hom_jl4 (:37-46): product, FMA, two scalings, 4 (it replaces e's count, not adds to it;
+           6 and 4 are both upper counts of the same sum Ev).
+  klm      ambient, ckh_landmark_step (ck_joint:176-194): s o U4 (1), aw a 4-term dot (4), hbeta aw hw and the difference
+           (3): 8.  Jl3 form, jl3_of_jl4 (:56-63): the same 7, then jl3 t0 + jl3' t1 (:216, :351, :846): 9.
+  n_l      the landmark's sum in any order (LDS atomics in arrival order, a segmented scan, wave_sum of lm_long): gamma_{n_l}.
+  back     G4: hbeta times a 3-term dot (4), gw hw, the difference, s (3): gamma_7 (ck_joint:189-193).  Jl3 form: jl3_of_jl4's
+           7 on the row, hom_jl4's 4 where the ambient form has dot4's 4, a 3-term dot where it has hom_jp_x's 3: the same 14.
+  n_c      X_j q_m rounds once (or is an FMA into the sum); the camera's sum in any tree (chunk registers, LDS accumulators of
+           either stride, partial records of capped accumulators, the cold view, block_sum_dpp; adding zeros is exact):
+           gamma_{n_c}.
+  tail     sigma (1); nt_apply (:589-595): a 12-term dot, beta w wy (2), the difference: gamma_15; the B^-1 row: an 11-term
+           dot (cam_cold_sum_binv_h :1508-1513; cam_binv_axpy_h :641-654 after cam_cold_sum: the same counts).
+  dN       house4 (:48-55): nv = sqrt of a 4-term sum of squares (gamma_4 at most), w0 = X.x +- nv with equal signs (one
+           more: gamma_5), beta = 2 / (sum of four squares, w0^2 among them: 2 gamma_5 + 1, the sum 4, the division 1:
+           gamma_15 at most); an entry beta w_i w_j of N moves by gamma_15 + 2 gamma_5 <= gamma_25 of itself <= of |N|.
+  rho_i    HUBER only, the relative error of the stored weight's sqrt (it enters four times: twice per pass):
+             err(x/z) <= gamma_4 xm / |z| + |x/z| (ez + u),   err(r0) <= err(x/z) + u (|x/z| + |u|)
+             rel = (2 (|r0| err(r0) + |r1| err(r1))) / r2 + gamma_3,   rho = rel / 4 + gamma_4
+           (w = t / sqrt(r2) halves rel, its sqrt halves it again; t t, two square roots, the division).  rho is charged
+           wherever r2 (1 + rel) reaches t^2 -- also where the device may take the other branch of r2 < t^2: then one side
+           has sw = 1 and the other (t^2 / r2)^(1/4) within rel / 4 of it --, no entry is left out.
+  det      e0_ck_h_det sums U4 on the grid 2^(E + L - 61), 2^E > the largest |component| of the landmark's contributions
+           (first walk), L = ceil(log2 n_l) (povar_kernels_ck_det.hpp:250-287, :355-377): each contribution rounds by at most
+           2^(L - 61) max vm; the integer sum is exact and its conversion back rounds once.
+
+First order, every gamma rounded up, as for step 1; no underflow floor (the cameras have unit norm and the terms of the
+first five steps stay far above 2^-1022; the camera without observations has bound 0 and must be exactly 0).
 
 Slack.  On the problems of test_rounding_bounds.py, NumPy emulations that follow the kernels' operation order and operand
 roundings reach at most the err/bound ratios recorded in that module's docstring; a ratio near 1 would mean a count is
@@ -476,3 +559,406 @@ def edge_problem(seed=0):
     obs[rng.random(len(lm)) < 0.05] += rng.normal(scale=3.0, size=(1, 2))  # outliers for the robust norms
     obs = np.rint(obs * 1e6) / 1e6
     return n_c, lm_off, cam_idx, obs, cams, X
+
+
+# ======== step 2 (RIPOBA: homogeneous landmarks, tangent bases) -- the module docstring's second half
+class ModelH:
+    """The rounding model of one step-2 kernel family (module docstring: step 2)."""
+
+    def __init__(self, name, u, kd, kv, klm, det=False, dn=None):
+        self.name, self.u, self.kd, self.kv, self.klm, self.det = name, u, kd, kv, klm, det
+        self.dn = float(gam(25, u)) if dn is None else dn
+
+
+MODELS_H = {
+    # e0_ck_h (either stride): ckh_project, the ambient U4 / G4 through LDS, N_l, s, Hll^-1 once per slot
+    "ckh": ModelH("ckh", U64, kd=4, kv=6, klm=8),
+    # e0_ck_h_det: the same with U4 summed on the fixed-point grid
+    "ckh_det": ModelH("ckh_det", U64, kd=4, kv=6, klm=8, det=True),
+    # e0_lpl_h, e0_lm_cached_h, lm_regular / lm_long<OpE0H>: hom_project, hom_jl4, jl3_of_jl4 per observation
+    "jl3": ModelH("jl3", U64, kd=2, kv=4, klm=9),
+    # the long-double reference itself (checked against exact rationals with the reflectors given: dn = 0 there)
+    "longdouble": ModelH("longdouble", ULD, kd=4, kv=6, klm=8),
+}
+
+
+class Step2:
+    """The operands of one prepared joint system, as exact numbers.  lw: optional [n_lms, 5] landmark reflectors (w, beta)
+    taken as given instead of recomputed from X (test_rounding_bounds.py's exact-rational case)."""
+
+    def __init__(self, n_cams, lm_off, cam_idx, obs, cams, lms_h, sigma, s, hi, ncw, binv, robust="NONE", huber=1.0, lw=None):
+        f = np.float64
+        self.n_cams = int(n_cams)
+        self.lm_off = np.asarray(lm_off, dtype=np.int64)
+        self.cam_idx = np.asarray(cam_idx, dtype=np.int64)
+        self.obs = np.asarray(obs, dtype=f).reshape(-1, 2)
+        self.cams = np.asarray(cams, dtype=f).reshape(-1, 12)
+        self.lms = np.asarray(lms_h, dtype=f).reshape(-1, 4)
+        self.sigma = np.asarray(sigma, dtype=f).reshape(-1, 12)
+        self.s = np.asarray(s, dtype=f).reshape(-1, 4)
+        self.hi = np.asarray(hi, dtype=f).reshape(-1, 3, 3)
+        self.ncw = np.asarray(ncw, dtype=f).reshape(-1, 13)
+        self.binv = np.asarray(binv, dtype=f).reshape(-1, 11, 11)
+        self.robust, self.huber = robust, float(huber)
+        self.lw = None if lw is None else np.asarray(lw, dtype=f).reshape(-1, 5)
+        self.n_l = np.diff(self.lm_off)
+        self.n_c = np.bincount(self.cam_idx, minlength=self.n_cams)
+        self.lm = np.repeat(np.arange(len(self.n_l)), self.n_l)
+
+    @classmethod
+    def from_context(cls, ctx, obs, robust="NONE", huber=1.0):
+        """After linearize_homogeneous and prepare_joint (the cameras and landmarks are the linearisation point)."""
+        from povar_amd import capi
+        return cls(ctx.n_cams, ctx.lm_off, ctx.cam_idx, obs, ctx.get_cameras(), ctx.get_landmarks_homogeneous(),
+                   ctx.get_buffer(capi.BUF_POSE_SCALING), ctx.get_buffer(capi.BUF_JL_COL_SCALE_H), ctx.get_buffer(capi.BUF_HLL_INV),
+                   ctx.get_buffer(capi.BUF_NC_HOUSEHOLDER), ctx.get_buffer(capi.BUF_B_INV_JOINT), robust, huber)
+
+
+def house4(X, sign=None):
+    """(w [n, 4], beta [n]) of house4 (povar_kernels_joint.hpp:48) in X's dtype; sign: +-1 per row instead of X.x >= 0."""
+    nv = np.sqrt(X[:, 0] * X[:, 0] + X[:, 1] * X[:, 1] + X[:, 2] * X[:, 2] + X[:, 3] * X[:, 3])
+    sg = np.where(X[:, 0] >= 0, 1, -1) if sign is None else sign
+    w = X.copy()
+    w[:, 0] = X[:, 0] + sg * nv
+    return w, 2 / (w[:, 0] * w[:, 0] + w[:, 1] * w[:, 1] + w[:, 2] * w[:, 2] + w[:, 3] * w[:, 3])
+
+
+def _nt(w, b, a, sign=-1):
+    """N^T a = a[1:] - beta (w . a) w[1:] per row (sign = +1 with |w|: the map |N|^T = |I| + beta |w| |w|^T)."""
+    return a[:, 1:] + sign * (b * (w * a).sum(1))[:, None] * w[:, 1:]
+
+
+def _n(w, b, g, sign=-1):
+    """N g = [0; g] - beta (w[1:] . g) w per row."""
+    out = sign * (b * (w[:, 1:] * g).sum(1))[:, None] * w
+    out[:, 1:] += g
+    return out
+
+
+def ambient(prob, t):
+    """N_c t per camera in long double: the basis-independent image of a tangent 11-vector per camera, [12 n_cams]."""
+    return _n(prob.ncw[:, :12].astype(LD), prob.ncw[:, 12].astype(LD), np.asarray(t, dtype=np.float64).reshape(-1, 11).astype(LD)).reshape(-1)
+
+
+def weights_joint(prob, px, py, pz, xm, ym, zm, u):
+    """(sw, rho): sqrt of compute_error_weight's weight in long double from r = (x / z - u, y / z - v), and the relative error
+    of the stored fp64 one against it (module docstring: rho_i of step 2)."""
+    n = len(px)
+    if prob.robust != "HUBER":  # CAUCHY: w = 1 in compute_error_weight (oracle/povar_oracle.c): nothing to round
+        return np.ones(n, dtype=LD), np.zeros(n)
+    f = np.float64
+    uv = prob.obs.astype(LD)
+    qx, qy = px / pz, py / pz
+    r0, r1 = qx - uv[:, 0], qy - uv[:, 1]
+    r2 = r0 * r0 + r1 * r1
+    g4 = float(gam(4, u))
+    az = np.abs(pz.astype(f))
+    e0 = g4 * xm / az + np.abs(qx.astype(f)) * (g4 * zm / az + 2 * u) + u * np.abs(prob.obs[:, 0])
+    e1 = g4 * ym / az + np.abs(qy.astype(f)) * (g4 * zm / az + 2 * u) + u * np.abs(prob.obs[:, 1])
+    r2f = np.maximum(r2.astype(f), 1e-300)
+    rel = (2 * (np.abs(r0.astype(f)) * e0 + np.abs(r1.astype(f)) * e1)) / r2f + float(gam(3, u))
+    t2 = LD(prob.huber) ** 2
+    w = np.where(r2 < t2, LD(1), LD(prob.huber) / np.sqrt(np.maximum(r2, LD(1e-300))))
+    near = r2f * (1 + rel) >= float(t2)
+    return np.sqrt(w), np.where(near, rel / 4 + g4, 0.0)
+
+
+def evaluate_joint(prob, x, model=MODELS_H["ckh"], mutate=None, want_parts=False):
+    """(t_ref, bound), both [11 n_cams]: the long-double next term B^-1 N_c^T sigma E0 sigma N_c x of the joint system and the
+    componentwise bound of `model` on |t_dev - t_ref| for a device that starts from the same x (its own previous term).
+    mutate: test hook (a dict) that perturbs the reference's chain -- test_rounding_bounds.py's mutations."""
+    f, u = np.float64, model.u
+    mutate = mutate or {}
+    g1, g2, g3, g4 = (float(gam(k, u)) for k in (1, 2, 3, 4))
+    nC = prob.n_cams
+    x = np.asarray(x, dtype=f).reshape(nC, 11)
+    wc, bc = prob.ncw[:, :12], prob.ncw[:, 12]
+    wcL, bcL, wca = wc.astype(LD), bc.astype(LD), np.abs(wc)
+    sig, sigL = prob.sigma, prob.sigma.astype(LD)
+    # ---- z = sigma (N_c x): an 11-term dot, beta w_i wt (2), the difference, sigma
+    z = sigL * _n(wcL, bcL, x.astype(LD))
+    if "z" in mutate:
+        z = mutate["z"](z)
+    Ez = float(gam(15, u)) * sig * _n(wca, bc, np.abs(x), +1)
+    c, lm = prob.cam_idx, prob.lm
+    P, X = prob.cams[c].astype(LD), prob.lms[lm].astype(LD)
+    Pa, Xa = np.abs(prob.cams[c]), np.abs(prob.lms[lm])
+    Pr, Par = [P[:, 4 * r:4 * r + 4] for r in range(3)], [Pa[:, 4 * r:4 * r + 4] for r in range(3)]
+    px, py, pz = ((Pr[r] * X).sum(1) for r in range(3))
+    xm, ym, zm = ((Par[r] * Xa).sum(1) for r in range(3))
+    # ---- D and its error: x, y, z are computed dots (gamma_4 of |P_r| . |X|), so a small |z| inflates through err(z) / |z|
+    iz = 1 / pz
+    D = [iz, -px * iz * iz, -py * iz * iz]
+    az = np.abs(pz.astype(f))
+    ezr = g4 * zm / az
+    A = [1 / az, np.abs(px.astype(f)) / az ** 2, np.abs(py.astype(f)) / az ** 2]
+    E = [A[0] * (ezr + u), A[1] * (2 * ezr + model.kd * u) + g4 * xm / az ** 2, A[2] * (2 * ezr + model.kd * u) + g4 * ym / az ** 2]
+    sw, rho = weights_joint(prob, px, py, pz, xm, ym, zm, u)
+    if "sw" in mutate:
+        sw = mutate["sw"](sw)
+    sw2 = mutate["sw2"](sw) if "sw2" in mutate else sw  # (the second of the two factors sw of either pass)
+    swa = np.abs(sw.astype(f))
+
+    def two_rows(a, Ea, am):
+        """(rows, magnitudes, errors) of sw D applied to a 3-vector given with its magnitude and error: 2 values."""
+        v = [sw * (D[0] * a[0] + D[1] * a[2]), sw * (D[0] * a[1] + D[2] * a[2])]
+        vm = [swa * (A[0] * am[0] + A[1] * am[2]), swa * (A[0] * am[1] + A[2] * am[2])]
+        Ev = [swa * (A[0] * Ea[k] + A[k + 1] * Ea[2] + E[0] * am[k] + E[k + 1] * am[2]) + (g3 + rho) * vm[k] for k in range(2)]
+        return v, vm, Ev
+
+    def three_cols(t, Et, tm):
+        """sw D^T applied to a 2-vector: 3 values (hom_q without its fourth entry)."""
+        v = [sw2 * D[0] * t[0], sw2 * D[0] * t[1], sw2 * (D[1] * t[0] + D[2] * t[1])]
+        vm = [swa * A[0] * tm[0], swa * A[0] * tm[1], swa * (A[1] * tm[0] + A[2] * tm[1])]
+        Ev = [swa * (A[0] * Et[0] + E[0] * tm[0]) + (g2 + rho) * vm[0], swa * (A[0] * Et[1] + E[0] * tm[1]) + (g2 + rho) * vm[1],
+              swa * (A[1] * Et[0] + A[2] * Et[1] + E[1] * tm[0] + E[2] * tm[1]) + (g3 + rho) * vm[2]]
+        return v, vm, Ev
+
+    # ---- forward: t = sw D (Z X), v = P^T D^T (sw t)
+    Z, Za, EZ = z[c], np.abs(z[c].astype(f)), Ez[c]
+    d = [(X * Z[:, 4 * r:4 * r + 4]).sum(1) for r in range(3)]
+    dm = [(Xa * Za[:, 4 * r:4 * r + 4]).sum(1) for r in range(3)]
+    Ed = [(Xa * EZ[:, 4 * r:4 * r + 4]).sum(1) + g4 * dm[r] for r in range(3)]
+    t, tm, Et = two_rows(d, Ed, dm)
+    e, em, Ee = three_cols(t, Et, tm)
+    v = sum(Pr[r] * e[r][:, None] for r in range(3))
+    vm = sum(Par[r] * em[r][:, None] for r in range(3))
+    Ev = sum(Par[r] * Ee[r][:, None] for r in range(3)) + (float(gam(model.kv, u)) + rho)[:, None] * vm
+    # ---- per landmark
+    nl = prob.n_l
+    keep = nl > 0
+    starts = prob.lm_off[:-1][keep]
+    n_lms = len(nl)
+
+    def lsum(a, dtype):
+        out = np.zeros((n_lms, a.shape[1]), dtype=dtype)
+        out[keep] = np.add.reduceat(a, starts, axis=0)
+        return out
+    U, UM, EU = lsum(v, LD), lsum(vm, f), lsum(Ev, f)
+    if model.det:
+        vmax = np.zeros(n_lms)
+        vmax[keep] = np.maximum.reduceat(vm.max(1), starts)
+        L = np.ceil(np.log2(np.maximum(nl, 1)))
+        EU += (nl * 2.0 ** (L - 61) * vmax)[:, None] * (1 + 8 * U64) + U64 * UM
+    sL, sa = prob.s.astype(LD), np.abs(prob.s)
+    if prob.lw is None:
+        lw, lb = house4(prob.lms.astype(LD), mutate["sign"](np.where(prob.lms[:, 0] >= 0, 1, -1)) if "sign" in mutate else None)
+        dn = model.dn
+    else:
+        lw, lb, dn = prob.lw[:, :4].astype(LD), prob.lw[:, 4].astype(LD), 0.0
+    lwa, lba = np.abs(lw.astype(f)), lb.astype(f)
+    a, am, Ea = sL * U, sa * UM, sa * EU
+    u3, u3m = _nt(lw, lb, a), _nt(lwa, lba, am, +1)
+    Eu3 = _nt(lwa, lba, Ea, +1) + (float(gam(model.klm, u)) + gam(nl, u) + dn)[:, None] * u3m
+    hi = prob.hi
+    if "hi" in mutate:
+        hi = mutate["hi"](hi)
+    up = np.triu(hi)
+    hs = up + np.transpose(np.triu(hi, 1), (0, 2, 1))  # (the upper triangle, as the landmark records keep it)
+    asym = np.abs(hi - np.transpose(hi, (0, 2, 1)))    # (OpE0H reads all nine entries)
+    ha = np.abs(hs)
+    g, gm = np.einsum("lab,lb->la", hs.astype(LD), u3), np.einsum("lab,lb->la", ha, u3m)
+    Eg = np.einsum("lab,lb->la", ha, Eu3) + g3 * gm + np.einsum("lab,lb->la", asym, u3m)
+    G4, G4m = sL * _n(lw, lb, g), sa * _n(lwa, lba, gm, +1)
+    EG4 = sa * _n(lwa, lba, Eg, +1) + (float(gam(7, u)) + dn) * G4m
+    # ---- backward: q = hom_q(sw D (P G4)), Y_c += X (x) q
+    G, Gm, EG = G4[lm], G4m[lm], EG4[lm]
+    p = [(Pr[r] * G).sum(1) for r in range(3)]
+    pm = [(Par[r] * Gm).sum(1) for r in range(3)]
+    Ep = [(Par[r] * EG).sum(1) + g4 * pm[r] for r in range(3)]
+    s2, s2m, Es2 = two_rows(p, Ep, pm)
+    q, qm, Eq = three_cols(s2, Es2, s2m)
+    y = np.stack([X[:, j] * q[m] for m in range(3) for j in range(4)], 1)
+    ym_ = np.stack([Xa[:, j] * qm[m] for m in range(3) for j in range(4)], 1)
+    ey = np.stack([Xa[:, j] * Eq[m] for m in range(3) for j in range(4)], 1) + g1 * ym_
+    order = np.argsort(c, kind="stable")
+    cs = c[order]
+    cst = np.flatnonzero(np.r_[True, cs[1:] != cs[:-1]])
+    here = cs[cst]
+    Y, Ym, EY = np.zeros((nC, 12), dtype=LD), np.zeros((nC, 12)), np.zeros((nC, 12))
+    if len(c):
+        Y[here], Ym[here], EY[here] = (np.add.reduceat(w_[order], cst, axis=0) for w_ in (y, ym_, ey))
+    EY += gam(prob.n_c, u)[:, None] * Ym
+    # ---- the camera tail: sigma, N_c^T (nt_apply: a 12-term dot, beta w_j wy (2), the difference), the B^-1 row
+    y12, y12m, Ey12 = sigL * Y, sig * Ym, sig * EY + u * sig * Ym
+    if "y12" in mutate:
+        y12 = mutate["y12"](y12)
+    y11, y11m = _nt(wcL, bcL, y12), _nt(wca, bc, y12m, +1)
+    Ey11 = _nt(wca, bc, Ey12, +1) + float(gam(15, u)) * y11m
+    ba = np.abs(prob.binv)
+    t_ref = np.einsum("cij,cj->ci", prob.binv.astype(LD), y11).reshape(-1)
+    tm_ = np.einsum("cij,cj->ci", ba, y11m)
+    bound = ((np.einsum("cij,cj->ci", ba, Ey11) + float(gam(11, u)) * tm_) * (1 + 1e-6)).reshape(-1)
+    if want_parts:
+        return t_ref, bound, dict(z=z, tm=tm_.reshape(-1), pz=pz, sw=sw, rho=rho)
+    return t_ref, bound
+
+
+def _dot(a, b):
+    out = a[:, 0] * b[:, 0]
+    for k in range(1, a.shape[1]):
+        out = out + a[:, k] * b[:, k]
+    return out
+
+
+def emulate_joint(prob, x, form):
+    """The next term in fp64 in the kernels' operation order.  form "ambient": e0_ck_h (ckh_project's one division, U4 summed
+    in row order, N_l, s, Hll^-1 once per landmark); "jl3": e0_lpl_h / e0_lm_cached_h / OpE0H (hom_project's three divisions,
+    hom_jl4, jl3_of_jl4 per observation).  Both: the stored weight's sqrt twice per pass, the camera sums in row order, then
+    cam_cold_sum_binv_h's tail.  (NumPy does not contract to FMAs: every product rounds.)"""
+    f = np.float64
+    nC = prob.n_cams
+    x = np.asarray(x, dtype=f).reshape(nC, 11)
+    wc, bc, sg = prob.ncw[:, :12], prob.ncw[:, 12], prob.sigma
+    wt = _dot(wc[:, 1:], x)
+    z = (np.concatenate([np.zeros((nC, 1)), x], 1) - (bc * wt)[:, None] * wc) * sg
+    c, lm = prob.cam_idx, prob.lm
+    P, X, Z = prob.cams[c], prob.lms[lm], z[c]
+    Pr = [P[:, 4 * r:4 * r + 4] for r in range(3)]
+    px, py, pz = (_dot(Pr[r], X) for r in range(3))
+    if prob.robust == "HUBER":  # (lpl_pass_h<0> / OpLinearizeH: hom_project's residual, error_weight; the weight is stored)
+        r0, r1 = px / pz - prob.obs[:, 0], py / pz - prob.obs[:, 1]
+        r2 = r0 * r0 + r1 * r1
+        sw = np.sqrt(np.where(r2 < prob.huber * prob.huber, 1.0, prob.huber / np.sqrt(np.maximum(r2, 1e-300))))
+    else:
+        sw = np.ones(len(c))
+    if form == "ambient":
+        D00 = 1 / pz
+        iz2 = D00 * D00
+        D02, D12 = -px * iz2, -py * iz2
+    else:
+        D00, D02, D12 = 1 / pz, -px / (pz * pz), -py / (pz * pz)
+    d = [_dot(X, Z[:, 4 * r:4 * r + 4]) for r in range(3)]
+    t0, t1 = sw * (D00 * d[0] + D02 * d[2]), sw * (D00 * d[1] + D12 * d[2])
+    n_lms = len(prob.n_l)
+    lw, lb = house4(prob.lms)
+    s, hi = prob.s, prob.hi
+    H = [hi[:, 0, 0], hi[:, 0, 1], hi[:, 0, 2], hi[:, 1, 1], hi[:, 1, 2], hi[:, 2, 2]]
+
+    def hmul(r):
+        return np.stack([H[0] * r[:, 0] + H[1] * r[:, 1] + H[2] * r[:, 2], H[1] * r[:, 0] + H[3] * r[:, 1] + H[4] * r[:, 2],
+                         H[2] * r[:, 0] + H[4] * r[:, 1] + H[5] * r[:, 2]], 1)
+    if form == "ambient":
+        e0, e1, e2 = sw * D00 * t0, sw * D00 * t1, sw * (D02 * t0 + D12 * t1)
+        v = Pr[0] * e0[:, None] + Pr[1] * e1[:, None] + Pr[2] * e2[:, None]
+        U = np.zeros((n_lms, 4))
+        np.add.at(U, lm, v)  # (row order, one rounding per add)
+        a = s * U
+        aw = _dot(a, lw)
+        u3 = a[:, 1:] - (lb * aw)[:, None] * lw[:, 1:]
+        g3 = hmul(u3)
+        gw = lb * _dot(lw[:, 1:], g3)
+        G4 = s * (np.concatenate([np.zeros((n_lms, 1)), g3], 1) - gw[:, None] * lw)
+        G = G4[lm]
+        p = [_dot(Pr[r], G) for r in range(3)]
+        s0, s1 = sw * (D00 * p[0] + D02 * p[2]), sw * (D00 * p[1] + D12 * p[2])
+    else:
+        sl, wl, bl = s[lm], lw[lm], lb[lm]
+        jl4 = [np.stack([sw * (D00 * Pr[r][:, j] + (D02, D12)[r] * Pr[2][:, j]) * sl[:, j] for j in range(4)], 1) for r in range(2)]
+        jl3 = [jl4[r][:, 1:] - (bl * _dot(jl4[r], wl))[:, None] * wl[:, 1:] for r in range(2)]
+        red = np.zeros((n_lms, 3))
+        np.add.at(red, lm, jl3[0] * t0[:, None] + jl3[1] * t1[:, None])
+        g = hmul(red)[lm]
+        s0, s1 = _dot(jl3[0], g), _dot(jl3[1], g)
+    q = [sw * D00 * s0, sw * D00 * s1, sw * (D02 * s0 + D12 * s1)]
+    y = np.stack([X[:, j] * q[m] for m in range(3) for j in range(4)], 1)
+    Y = np.zeros((nC, 12))
+    np.add.at(Y, c, y)
+    y12 = Y * sg
+    wy = _dot(wc, y12)
+    y11 = y12[:, 1:] - (bc[:, None] * wc[:, 1:]) * wy[:, None]
+    out = np.zeros((nC, 11))
+    for j in range(11):
+        out += prob.binv[:, :, j] * y11[:, j:j + 1]
+    return out.reshape(-1)
+
+
+def system_joint(n_cams, lm_off, cam_idx, obs, cams, lms_h, lam, robust="NONE", huber=1.0, eps=1e-5):
+    """A prepared joint system in fp64 (the roles of BUF_POSE_SCALING, BUF_JL_COL_SCALE_H, BUF_HLL_INV, BUF_NC_HOUSEHOLDER and
+    BUF_B_INV_JOINT, taken as exact numbers like a context's): povar_kernels_joint.hpp's header comment in NumPy."""
+    lm_off, cam_idx = np.asarray(lm_off, dtype=np.int64), np.asarray(cam_idx, dtype=np.int64)
+    cams, X4 = np.asarray(cams, dtype=np.float64).reshape(-1, 12), np.asarray(lms_h, dtype=np.float64).reshape(-1, 4)
+    n_l = len(lm_off) - 1
+    lm = np.repeat(np.arange(n_l), np.diff(lm_off))
+    P, X = cams[cam_idx].reshape(-1, 3, 4), X4[lm]
+    pc = np.einsum("nij,nj->ni", P, X)
+    px, py, pz = pc[:, 0], pc[:, 1], pc[:, 2]
+    r2 = (px / pz - obs[:, 0]) ** 2 + (py / pz - obs[:, 1]) ** 2
+    w = np.where(r2 < huber * huber, 1.0, huber / np.sqrt(np.maximum(r2, 1e-300))) if robust == "HUBER" else np.ones(len(lm))
+    sw = np.sqrt(w)
+    D = np.zeros((len(lm), 2, 3))
+    D[:, 0, 0] = D[:, 1, 1] = 1 / pz
+    D[:, 0, 2], D[:, 1, 2] = -px / pz ** 2, -py / pz ** 2
+    J4 = sw[:, None, None] * np.einsum("nra,naj->nrj", D, P)
+    col = np.zeros((n_l, 4))
+    np.add.at(col, lm, (J4 ** 2).sum(1))
+    s = 1.0 / (eps + np.sqrt(col))
+    lw, lb = house4(X4)
+    N = (np.eye(4)[None] - lb[:, None, None] * lw[:, :, None] * lw[:, None, :])[:, :, 1:]
+    Jl3 = np.einsum("nrj,njk->nrk", J4 * s[lm][:, None, :], N[lm])
+    H = np.zeros((n_l, 3, 3))
+    np.add.at(H, lm, np.einsum("nra,nrb->nab", Jl3, Jl3))
+    hi = np.linalg.inv(H + lam * np.eye(3)[None])
+    hi = 0.5 * (hi + np.transpose(hi, (0, 2, 1)))
+    Jp = np.einsum("nra,nj->nraj", sw[:, None, None] * D, X).reshape(-1, 2, 12)
+    A = np.zeros((n_cams, 12, 12))
+    np.add.at(A, cam_idx, np.einsum("nra,nrb->nab", Jp, Jp))
+    sigma = 1.0 / (eps + np.sqrt(np.einsum("caa->ca", A)))
+    nv = np.linalg.norm(cams, axis=1)
+    wc = cams.copy()
+    wc[:, 0] += np.where(cams[:, 0] >= 0, nv, -nv)
+    bc = 2.0 / (wc * wc).sum(1)
+    Nc = (np.eye(12)[None] - bc[:, None, None] * wc[:, :, None] * wc[:, None, :])[:, :, 1:]
+    B = np.einsum("cai,cab,cbj->cij", Nc, sigma[:, :, None] * A * sigma[:, None, :], Nc) + lam * np.eye(11)[None]
+    prob = Step2(n_cams, lm_off, cam_idx, obs, cams, X4, sigma, s, hi, np.concatenate([wc, bc[:, None]], 1), np.linalg.inv(B),
+                 robust, huber)
+    # the series' first term -B^-1 b, b = N_c^T sigma Jp12^T (r - Jl3 Hll^-1 Jl3^T r): where the real term sequence starts
+    r = sw[:, None] * np.stack([px / pz - obs[:, 0], py / pz - obs[:, 1]], 1)
+    jr = np.zeros((n_l, 3))
+    np.add.at(jr, lm, np.einsum("nra,nr->na", Jl3, r))
+    e = r - np.einsum("nra,na->nr", Jl3, np.einsum("lab,lb->la", hi, jr)[lm])
+    b12 = np.zeros((n_cams, 12))
+    np.add.at(b12, cam_idx, np.einsum("nra,nr->na", Jp, e))
+    prob.t0 = -np.einsum("cij,cj->ci", prob.binv, np.einsum("cai,ca->ci", Nc, sigma * b12)).reshape(-1)
+    return prob
+
+
+EDGE_HUBER_H = 0.03
+EDGE_LAM_H = 1e-4
+
+
+def edge_problem_joint(seed=0):
+    """edge_problem's graph plus one camera without observations, with step-2 state that takes the paths the step-2 kernels
+    can get wrong:
+      * landmarks with X.x < 0, X.x > 0 and exactly X.x = 0, each at least a tenth (house4's sign branch);
+      * X_w != 1 on more than a fifth of the landmarks (un-normalised, as between apply_joint and normalize_joint);
+      * cameras of unit Frobenius norm with vec(P)[0] of either sign (the N_c reflector), near twins kept near;
+      * 36 landmarks of at most four observations moved (through X_w) to a depth of 1e-2 of the typical one in their first
+        camera -- every observation stays valid (|z| >= 1e-5);
+      * image points = projections + N(0, 0.02) noise, 5 % outliers, on the six-decimal grid: EDGE_HUBER_H splits the residuals.
+    Returns (n_cams, lm_off, cam_idx, obs, cams, lms_h)."""
+    n_c, lm_off, cam_idx, _, _, _ = edge_problem(seed)
+    rng = np.random.default_rng(seed + 1000)
+    n_twin = 30
+    n_l = len(lm_off) - 1
+    cams = rng.normal(size=(n_c + 1, 12))
+    cams[:, 8:11] *= 0.1
+    cams[:, 11] = 5 + rng.random(n_c + 1)
+    cams[n_c - n_twin:n_c] = cams[4:4 + n_twin] + 1e-5 * rng.normal(size=(n_twin, 12))
+    cams /= np.linalg.norm(cams, axis=1, keepdims=True)
+    X = np.concatenate([rng.normal(size=(n_l, 3)), np.ones((n_l, 1))], 1)
+    X[rng.random(n_l) < 0.12, 0] = 0.0
+    scaled = rng.random(n_l) < 0.3
+    X[scaled] *= rng.uniform(0.5, 2.0, size=(int(scaled.sum()), 1))
+    lm = np.repeat(np.arange(n_l), np.diff(lm_off))
+    depth = lambda: np.einsum("nj,nj->n", cams[cam_idx][:, 8:12], X[lm])
+    typical = float(np.median(np.abs(depth())))
+    short = np.flatnonzero((np.diff(lm_off) <= 4) & ~scaled)
+    for l in rng.choice(short, 36, replace=False):
+        P2 = cams[cam_idx[lm_off[l]], 8:12]
+        X[l, 3] = (1e-2 * typical - P2[:3] @ X[l, :3]) / P2[3]
+    pc = np.einsum("nij,nj->ni", cams[cam_idx].reshape(-1, 3, 4), X[lm])
+    obs = pc[:, :2] / pc[:, 2:3] + rng.normal(scale=0.02, size=(len(lm), 2))
+    obs[rng.random(len(lm)) < 0.05] += rng.normal(scale=1.0, size=(1, 2))
+    obs = np.rint(obs * 1e6) / 1e6
+    return n_c + 1, lm_off, cam_idx, obs, cams, X
