@@ -41,7 +41,7 @@ def _inv3(H):
 
 
 class ExactStep1:
-    """E0 x, b and d = diag(Jp^T Jp) of the UNSCALED system in exact arithmetic."""
+    """E0 x, b, d = diag(Jp^T Jp), Hpp, the squared Jl column norms and Hll^-1 of the UNSCALED system in exact arithmetic."""
 
     def __init__(self, alpha, n_cams, lm_off, cam_idx, obs, cams, lms):
         self.n_cams = int(n_cams)
@@ -65,6 +65,24 @@ class ExactStep1:
                 for j in range(12):
                     d[12 * c + j] += sum(self.D2[r] * Jp0[r][j] ** 2 for r in range(4))
         return d
+
+    def hpp(self):
+        """Hpp_c = sum_i Jp_i^T D^2 Jp_i per camera, [n_cams][12][12] (landmark_block.hpp:530-536), unscaled."""
+        out = [[[F(0)] * 12 for _ in range(12)] for _ in range(self.n_cams)]
+        for ob, _ in self.lm:
+            for c, Jp0, _, _ in ob:
+                for i in range(12):
+                    for j in range(12):
+                        out[c][i][j] += sum(self.D2[r] * Jp0[r][i] * Jp0[r][j] for r in range(4))
+        return out
+
+    def jl_col_sq(self):
+        """Squared column norms of the unscaled Jl per landmark, [n_lms][3] (scale_Jl_cols_pOSE, landmark_block.hpp:284-295)."""
+        return [[sum(self.D2[r] * Jl0[r][a] ** 2 for _, _, Jl0, _ in ob for r in range(4)) for a in range(3)] for ob, _ in self.lm]
+
+    def hll_inv(self):
+        """Hll^-1 of the UNSCALED Jl per landmark, [n_lms][3][3]; with the column scale s: (S Hll S)^-1 = S^-1 Hll^-1 S^-1."""
+        return [Hi for _, Hi in self.lm]
 
     def e0(self, x):
         """E0 x for a vector of doubles or Fractions (linearization_power_varproj.hpp:377-396)."""
@@ -101,6 +119,13 @@ def sigma_60_digits(d, eps):
     getcontext().prec = 60
     e = Decimal(float(eps))
     return [float(1 / (e + (Decimal(t.numerator) / Decimal(t.denominator)).sqrt())) for t in d]
+
+
+def scale_decimal(d, eps):
+    """1 / (eps + sqrt(d)) to 60 digits as Decimals (for references that carry more than a double)."""
+    getcontext().prec = 60
+    e = Decimal(float(eps))
+    return [1 / (e + (Decimal(t.numerator) / Decimal(t.denominator)).sqrt()) for t in d]
 
 
 def rel_err(approx, exact):

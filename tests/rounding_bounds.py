@@ -25,7 +25,8 @@ This is the reference's Jp^T D^2 Jl Hll^-1 Jl^T D^2 Jp with the sb / sa rows mer
 P3^T C d exactly (tests/exact_rational.py builds the explicit rows; test_rounding_bounds.py checks the restatement against
 them).  Its intermediates are NOT bounded by |Jp|, |Jl| of the explicit tiles, so the magnitudes follow this algebra.  The
 inputs -- G (from Hi and S), sigma, the cameras, the landmarks -- are the doubles of the context under test, taken as exact
-numbers (the device's Hll^-1 differs from the oracle's by 1e-10 at venice size, far above any fp64 rounding bound).  The
+numbers (the device's Hll^-1 differs from the oracle's by 1e-10 at venice size, far above any fp64 rounding bound of E0;
+tests/operand_bounds.py holds these operands themselves to bounds that scale with each landmark's cancellation).  The
 weights are compute_error_weight's (oracle/povar_oracle.c; HUBER: min(1, t / |r|) of the pOSE residual at the linearisation
 point; CAUCHY and NONE: 1 in these kernels).
 
@@ -97,8 +98,9 @@ landmarks (house4 of X), pc = P X = (x, y, z), D = [[1/z, 0, -x/z^2], [0, 1/z, -
 This ambient form (e0_ck_h) and the per-observation form Jl3 = sw D P diag(s) N_l of the other kernels are the same
 reference: u3 = sum Jl3^T t = N_l^T (s o U4), Jl3 g3 = sw D P G4 (the header of povar_kernels_ck_joint.hpp).  The operands
 -- the cameras and landmarks of the linearisation point, sigma, s, Hi, the camera reflectors (w, beta), B^-1 -- are the
-doubles of the context under test taken as exact numbers; that THEY are right is the business of the normwise tests against
-the oracle (test_gpu_step2.py, test_gpu_fuzz.py, ...), not of this module.  N_l is not readable: the reference recomputes
+doubles of the context under test taken as exact numbers; that THEY are right, entry by entry, is the business of
+tests/operand_bounds.py (test_operand_bounds.py, test_gpu_operand_bounds.py: a long-double reference and a bound for every
+operand of both steps, built from what the caller set), not of this module.  N_l is not readable: the reference recomputes
 house4 in long double from X, and the model carries the device's fp64 w0, beta as an operand perturbation dN.  Hi is used
 as the landmark records keep it (its upper triangle); OpE0H reads all nine entries, so |Hi - Hi^T| u3m is added (zero for
 a symmetric inverse).  Weights: compute_error_weight's (HUBER: min(1, t / |r|), r = (x/z - u, y/z - v); CAUCHY and NONE: 1,
