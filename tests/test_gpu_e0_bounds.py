@@ -145,7 +145,10 @@ EDGE_RUNS = [(f, "NONE", {}, 0) for f in C_FORM + PER_OBS] + [(f, "HUBER", {}, 0
     [(f, "NONE", {"POVAR_HOT_ACC": "8"}, 0) for f in CHUNK] + \
     [(f, "NONE", {"POVAR_CK_NB": "3", "POVAR_CK_HMAX": "5"}, 0) for f in CHUNK] + \
     [(f, "HUBER", {"POVAR_CK_NB": "3", "POVAR_CK_HMAX": "5"}, 0) for f in CHUNK] + \
-    [(f, "NONE", {}, "FLAG_NO_PACKED_ROWS") for f in ("e0_ck", "e0_ck_f32")]
+    [(f, "NONE", {}, "FLAG_NO_PACKED_ROWS") for f in ("e0_ck", "e0_ck_f32")] + \
+    [("e0_ck_det", r, {"POVAR_E0_WGS": "1", "POVAR_CK_HMAX": "3"}, 0) for r in ("NONE", "HUBER")]
+# (the last two: one workgroup and chunks of at most 3 rows -- a batch of more than 16 tiles, so that a wavefront walks a
+# SECOND tile and reloads its camera record between the passes and on the way back; every other edge run has 16 per batch)
 
 
 @pytest.mark.parametrize("fam,robust,env,flag", EDGE_RUNS,
@@ -160,6 +163,8 @@ def test_edge_graph_within_bound(monkeypatch, fam, robust, env, flag):
     if fam in ("e0_ck", "e0_ck_f32") and not env and not flag:
         li = ctx.layout_info()
         assert li.ck_packed == 1
+    if "POVAR_E0_WGS" in env:
+        assert ctx.layout_info().ck_tiles_max > 16, "no wavefront has a second tile in a batch"
     xs = _xs(n_c) + _xs(n_c, ctx)[2:]
     _run(ctx, fam, obs, robust, RB.EDGE_HUBER, xs, f"edge/{robust}/{env or flag or 'default'}")
     # exact zeros: the camera without observations

@@ -107,7 +107,10 @@ def _edge():
 
 EDGE_RUNS = [(f, "NONE", {}) for f in ALL] + [(f, r, {}) for r in ("HUBER", "CAUCHY") for f in ALL] + \
     [(f, "NONE", e) for e in ({"POVAR_HOT_ACC": "8"}, {"POVAR_CK_NB": "3"}) for f in CHUNK] + \
-    [(f, "NONE", {"POVAR_NO_FUSE": "1"}) for f in ("e0_ck_h", "e0_lpl_h")]
+    [(f, "NONE", {"POVAR_NO_FUSE": "1"}) for f in ("e0_ck_h", "e0_lpl_h")] + \
+    [("e0_ck_h_det", r, {"POVAR_E0_WGS": "1", "POVAR_CK_HMAX": "3"}) for r in ("NONE", "HUBER")]
+# (the last two: one workgroup and chunks of at most 3 rows -- more than 16 tiles in a batch, so that a wavefront walks a
+# SECOND tile and reloads its camera record between the passes and on the way back; every other edge run has 16 per batch)
 
 
 @pytest.mark.parametrize("fam,robust,env", EDGE_RUNS,
@@ -115,6 +118,9 @@ EDGE_RUNS = [(f, "NONE", {}) for f in ALL] + [(f, r, {}) for r in ("HUBER", "CAU
 def test_edge_graph_terms_within_bound(monkeypatch, fam, robust, env):
     n_c, lm_off, cam_idx, obs, cams, lms_h = _edge()
     ctx = _context(monkeypatch, fam, n_c, lm_off, cam_idx, obs, cams, lms_h, robust, RB.EDGE_HUBER_H, env)
+    if "POVAR_E0_WGS" in env:
+        li = ctx.layout_info()
+        assert li.ckh_chunks > 64 * 16 * li.ckh_batches * li.grid, "no wavefront has a second tile in a batch"
     _terms_within_bound(ctx, fam, obs, robust, RB.EDGE_HUBER_H, f"edge/{robust}/{'+'.join(f'{k}={v}' for k, v in env.items()) or 'default'}", unobserved=[n_c - 1])
     ctx.close()
 
