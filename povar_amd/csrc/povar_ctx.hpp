@@ -94,11 +94,6 @@ struct povar_ctx {
   povar_options opt{};
   hipStream_t stream = nullptr;
   size_t bytes = 0;
-  // camera-major landmark copies of the legacy kernels (cm_h and the cold views cc/c2) are built lazily in the
-  // lane-per-landmark mode, which does not read them: lin_id counts linearisations, views_lin_id is the one they hold
-  int64_t lin_id = 0, views_lin_id = -1, aux_lin_id = -1;  // aux: the per-slot sqrt(w) / weighted residual arrays
-  // prepare_lpl[_h] writes only the lane-per-landmark records; hll_inv / lmrec of the legacy kernels follow lazily
-  int64_t prep_id = 0, aux_prep_id = 0, prep_lin_id = -1;
   char* pin = nullptr;  // pinned host block of the small read-backs (read_scal_flags)
   size_t pin_bytes = 0;
 
@@ -278,16 +273,21 @@ struct povar_ctx {
 
   // hipGraph of the m-term series loop (launch-bound on small problems and at 8 GPUs)
   double create_ms = 0;  // host wall time of povar_create (layout construction + uploads)
-  // lane-ordered mirrors of lms4 / lms_lin4 / jl_scale4 (V2::lmx, lml, lsc): lms_ver counts the writes to lms4, the
-  // *_ver / *_lin_id fields say what each mirror currently reflects
-  DevBuf<double4> v2_lmx, v2_lml, v2_lsc;
-  uint64_t lms_ver = 1, lmx_ver = 0;
-  int64_t lml_lin_id = -1, lsc_lin_id = -1;
-  int64_t jls_lin_id = -1;  // linearisation whose Jl column scale the landmark-order master jl_scale4 holds
-  int64_t lmslin_lin_id = -1;  // ... and whose landmarks the landmark-order master lms_lin4 holds (lazily, from lml)
-  // compute_error_* of an unchanged state (the LM loop asks again at the top of every iteration,
-  // bal_bundle_adjustment.cpp:302-310 / 600-605): cams_ver counts the writes to cams4 as lms_ver does for lms4
-  uint64_t cams_ver = 1;
+  DevBuf<double4> v2_lmx, v2_lml, v2_lsc;  // lane-ordered mirrors of lms4 / lms_lin4 / jl_scale4 (V2::lmx, lml, lsc)
+  // Who is current.  Three clocks, and beside each the copies that are rebuilt lazily with the tick they hold:
+  // the state: lms_ver / cams_ver count the writes to lms4 / cams4 (the cost memo below answers for an unchanged pair);
+  //   lmx_ver: the landmarks the lane-ordered mirror v2_lmx holds
+  uint64_t lms_ver = 1, cams_ver = 1, lmx_ver = 0;
+  // the linearisation: lin_id counts them.  The lane-per-landmark kernels leave the mirrors v2_lml / v2_lsc (lml_lin_id,
+  //   lsc_lin_id), the lane-per-observation ones the landmark-order masters lms_lin4 / jl_scale4 (lmslin_lin_id,
+  //   jls_lin_id), the per-slot sqrt(w) / weighted residual arrays (aux_lin_id) and the camera-major landmark copies
+  //   cm_h, cc_h, c2_h (views_lin_id); whichever family did not run gets its copies when it asks (povar_lm.hip)
+  int64_t lin_id = 0, lml_lin_id = -1, lsc_lin_id = -1, lmslin_lin_id = -1, jls_lin_id = -1, aux_lin_id = -1, views_lin_id = -1;
+  // the preparation: prep_id counts them, prep_lin_id is the linearisation the last one was taken on.  prepare_lpl[_h]
+  //   writes only the lane-per-landmark records; hll_inv / lmrec of the legacy kernels (aux_prep_id) follow lazily
+  int64_t prep_id = 0, aux_prep_id = 0, prep_lin_id = -1;
+  // compute_error_* of an unchanged state: the LM loop asks again at the top of every iteration
+  // (bal_bundle_adjustment.cpp:302-310 / 600-605)
   struct ErrMemo {
     bool valid = false;
     uint64_t lms_ver = 0, cams_ver = 0;
@@ -343,12 +343,12 @@ inline int grid_for(int64_t n, int block) { return (int)((n + block - 1) / block
 // launch helpers
 // ------------------------------------------------------------------------------------------
 template <class Op>
-void launch_lm(povar_ctx* c, const Op& op) {
-  hipLaunchKernelGGL((lm_regular<Op>), dim3(c->n_reg_blocks), dim3(LM_BLOCK), 0, c->stream, c->d, op,
-                     c->part.p);
-  if (c->n_long > 0)
-    hipLaunchKernelGGL((lm_long<Op>), dim3(c->n_long), dim3(LM_BLOCK), 0, c->stream, c->d, op, c->part.p);
+void launch_lm(povar_ctx* c, const Op& op, const Dp& d) {
+  hipLaunchKernelGGL((lm_regular<Op>), dim3(c->n_reg_blocks), dim3(LM_BLOCK), 0, c->stream, d, op, c->part.p);
+  if (c->n_long > 0) hipLaunchKernelGGL((lm_long<Op>), dim3(c->n_long), dim3(LM_BLOCK), 0, c->stream, d, op, c->part.p);
 }
+template <class Op>
+void launch_lm(povar_ctx* c, const Op& op) { launch_lm(c, op, c->d); }
 
 template <int N>
 void launch_reduce(povar_ctx* c, double* out) {
@@ -478,8 +478,6 @@ void build_views(povar_ctx* c);  // povar_lm.hip
 void lanes_from(povar_ctx* c, const double4* src, double4* dst);  // povar_lm.hip
 void ensure_lmx(povar_ctx* c);  // povar_lm.hip
 void ensure_lin_mirrors(povar_ctx* c);  // povar_lm.hip
-void ensure_jl_scale4(povar_ctx* c);  // povar_lm.hip
-void ensure_lms_lin(povar_ctx* c);  // povar_lm.hip
 void ensure_legacy(povar_ctx* c);  // povar_lm.hip
 int clear_flag0(povar_ctx* c);  // povar_lm.hip
 bool err_memo_hit(const povar_ctx* c, int kind, double alpha, povar_residual_info* out);  // povar_lm.hip

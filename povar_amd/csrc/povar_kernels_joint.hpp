@@ -1264,7 +1264,7 @@ __global__ __launch_bounds__(E0C_BLOCK) void lpl_pass_h(Dp d, double* part) {
     if (MODE == 0) {
       const int sg = v.seg[(size_t)c_t * WAVE + lane];
       if (c_fl & 1) seg_reduce_steps<4>(red, lane, sg & 255, (sg >> 8) & 255, 4);
-      // lane-ordered; the landmark-order copy (Dp::jl_scale4) is filled on demand (povar_lm.hip: ensure_jl_scale4)
+      // lane-ordered; the landmark-order copy (Dp::jl_scale4) is filled on demand (povar_lm.hip: ensure_legacy)
       v.lsc[(size_t)c_t * WAVE + lane] = make_double4(1.0 / (d.eps + sqrt(red[0])), 1.0 / (d.eps + sqrt(red[1])),
                                                       1.0 / (d.eps + sqrt(red[2])), 1.0 / (d.eps + sqrt(red[3])));
     }

@@ -20,7 +20,7 @@ weight w_i carries 2 rho_i and its square root rho_i.  Step 2: weights_joint's r
 residual, povar_kernels_joint.hpp:25-35); w = sw sw carries 2 rho.
 
 Step 1 (pOSE).  Per observation i of camera c and landmark l: h = [X_l; 1], (u, v), sb^2 = 1 - alpha, sa^2 = alpha.
-  dsb      sb = sqrt(1 - alpha), sa = sqrt(alpha) in fp64 (set_alpha, povar_lm.hip:235-238): the difference and the root,
+  dsb      sb = sqrt(1 - alpha), sa = sqrt(alpha) in fp64 (set_alpha, povar_lm.hip:200-203): the difference and the root,
            gamma_2 each; sb sb: gamma_4 + 1 (cam_finish_linearize :2534, cam_build_binv :2597).
   DIAG2    cm_gram (:2448-2492) sums m_k hh_j, m = w (1, u, v, u^2 + v^2), hh = h_i h_j, into four moments of ten entries;
            cam_finish_linearize (:2505-2538) sums the items in sixteen streams and a fixed-order final sum, and takes

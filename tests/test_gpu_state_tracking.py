@@ -426,3 +426,59 @@ def test_behaviour_switches_through_the_abi_flags_word(monkeypatch):
     assert run(capi.flag_placement(3))[1].placement == 0 and run(capi.flag_placement(1))[1].placement == 1
     monkeypatch.setenv("POVAR_DETERMINISTIC", "0")  # the variable wins over the flag
     assert run(capi.FLAG_DETERMINISTIC)[1].e0_kernel != 7
+
+
+@pytest.mark.parametrize("e0_mode", [0, 2])
+@pytest.mark.parametrize("v1", ["1", "0"])
+def test_a_stage_before_its_linearisation_is_refused_and_changes_nothing(v1, e0_mode, small_problem, monkeypatch):
+    """prepare_* / apply_* need the linearisation of their own step: before any, and after the other step's, they raise and
+    name the missing call.  A refused call leaves no trace: from the same state, one LM step of the context that saw the
+    refusals equals that of a context that never did -- bit for bit in e0_mode 0 (bit-reproducible from context to
+    context), to 1e-11 where atomics order the sums (the LDS-accumulating mode, lane per landmark or per observation)."""
+    from povar_amd import capi
+    monkeypatch.setenv("POVAR_E0_V1", v1)
+    p = small_problem
+    ctx, ref = _ctx(p, True, e0_mode=e0_mode), _ctx(p, True, e0_mode=e0_mode)
+    assert ctx.layout_info().lane_per_landmark == (1 if v1 == "0" else 0)
+    zero12, zero11 = np.zeros(12 * p.n_cams), np.zeros(11 * p.n_cams)
+
+    def refused(missing, *calls):
+        for call in calls:
+            with pytest.raises(capi.PovarError, match=f"before {missing}$"):
+                call()
+
+    step1_calls = (lambda: ctx.prepare_pose(LAM), lambda: ctx.apply_pose(capi.POWER_VARPROJ, ALPHA, zero12))
+    step2_calls = (lambda: ctx.prepare_joint(LAM), lambda: ctx.apply_joint(zero11))
+    ctx.set_cameras(p.cams)
+    ctx.init_landmarks_pose(ALPHA)
+    lms = ctx.get_landmarks()
+    X = np.concatenate([lms, np.ones((p.n_lms, 1))], axis=1)
+    refused("povar_linearize_pose", *step1_calls)
+    refused("povar_linearize_homogeneous", *step2_calls)
+
+    def lm_step(c, step, refuse):
+        """one LM step from the same state in either context; refuse: the other step's calls, right after the linearisation"""
+        c.set_cameras(p.cams)
+        if step == 1:
+            c.set_landmarks(lms)
+            assert c.linearize_pose(ALPHA)
+        else:
+            c.set_landmarks_homogeneous(X)
+            c.normalize_joint()
+            assert c.linearize_homogeneous()
+        refuse()
+        inc, _, _, rc = c.solve_pose(LAM, capi.POWER_VARPROJ, M) if step == 1 else c.solve_joint(LAM, M)
+        assert rc == 0
+        ld = c.apply_pose(capi.POWER_VARPROJ, ALPHA, inc) if step == 1 else c.apply_joint(inc)
+        return inc, np.array([ld]), c.get_cameras(), c.get_landmarks() if step == 1 else c.get_landmarks_homogeneous()
+
+    # step 1 (step 2 was never linearised), step 2 (drops step 1's linearisation), step 1 again (drops step 2's)
+    for step in (1, 2, 1):
+        got = lm_step(ctx, step, lambda: refused("povar_linearize_homogeneous", *step2_calls) if step == 1
+                      else refused("povar_linearize_pose", *step1_calls))
+        want = lm_step(ref, step, lambda: None)
+        for name, g, w in zip(("increment", "l_diff", "cameras", "landmarks"), got, want):
+            print(f"step {step} {name}: rel {rel(g, w):.3e}")
+            assert np.array_equal(g, w) if e0_mode == 0 else rel(g, w) <= 1e-11, (step, name)
+    ctx.close()
+    ref.close()
