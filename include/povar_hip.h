@@ -75,7 +75,8 @@ enum {
    * kernels once per layout and keeps the faster), 0 = e0_lpl / e0_lpl_h, 1..6 = a camera-chunk instantiation.  [POVAR_E0_CK=k] */
   POVAR_FLAG_E0_KERNEL_SHIFT = 4, POVAR_FLAG_E0_KERNEL_MASK = 0xFu << 4,
   /* bits 8..9: the m-term loop, as povar_set_series_kernel: POVAR_FLAG_SERIES_KERNEL(m), m = -1 (field 0: timed), 0 = per-term
-   * kernels, 1 = the resident launch wherever the context allows it.  [POVAR_RES=m] */
+   * kernels, 1 = the resident launch wherever the context allows it; one switch for the series of both steps (solve_pOSE and
+   * solve_joint).  [POVAR_RES=m] */
   POVAR_FLAG_SERIES_KERNEL_SHIFT = 8, POVAR_FLAG_SERIES_KERNEL_MASK = 0x3u << 8,
   /* bits 12..13: LDS bank placement of the lane-per-landmark rows: POVAR_FLAG_PLACEMENT(p), p = 0 (by size: inside povar_create
    * under 2^20 observations, on a host thread from there on), 1 = inside povar_create, 2 = on a host thread, 3 = none.
@@ -352,6 +353,17 @@ typedef struct {
                            slots of its most observed cameras, the other cameras' chunks write records of their own) */
   int32_t ckh_accumulators;      /* accumulator slots per workgroup at most */
   int64_t ckh_capped_obs;        /* observations of cameras that have a slot in the lane-per-landmark layout but none here */
+  /* resident power series of step 2 (series_res_h, povar_kernels_res_joint.hpp): the loop of solve_joint (:240-287) in one
+   * launch.  The res_* fields above stay step 1's.  (fp32_terms stays the struct's last
+   * field; these stand in front of it.) */
+  int32_t res_ready_h;  /* 1: step 2 has an instance (its own, or step 1's: res_shared_h) and an instantiation for its shape */
+  int32_t res_active_h; /* 1: the next povar_solve_joint of this context runs its series as the resident kernel */
+  int32_t res_auto_h;   /* as res_auto, for step 2: 0 forced, 1 to be timed at the next step-2 series, 2 timed */
+  int32_t res_shared_h; /* 1: step 1's cut fits the LDS under the step-2 formula: the two instances share every array but uv */
+  int32_t res_wgs_h, res_waves_h, res_rows_h, res_rounds_h;
+  int32_t res_lds_bytes_h;
+  double res_build_h_ms;  /* host time of the step-2 instance (the check of step 1's cut, or the second build and upload) */
+  float tune_terms_h_us, tune_res_h_us;  /* step 2, microseconds per term: per-term kernels, resident series */
   int32_t fp32_terms;   /* 1: the last step-1 power series (povar_power_series_pose / _step) ran its terms in fp32
                            (POVAR_FLAG_FP32_TERMS: e0_ck_f32) */
 } povar_layout_info;
@@ -372,12 +384,14 @@ int povar_layout_finalize(povar_ctx* ctx, int32_t wait);
  * default when nothing is forced): the library times both kernels of a step once per layout on the prepared problem and
  * keeps the faster one (povar_layout_info.e0_auto[_h], tune_*_us). */
 int povar_set_e0_kernel(povar_ctx* ctx, int32_t kernel);
-/* The m-term loop of solve_pOSE (sc/linearization_power_varproj.hpp:191-237) as per-term kernels inside a hipGraph
+/* The m-term loop of solve_pOSE (sc/linearization_power_varproj.hpp:191-237) and of solve_joint (:240-287; povar_solve_joint
+ * runs series_res_h, with a layout instance, a timing and a choice of its own) as per-term kernels inside a hipGraph
  * (mode 0) or as ONE resident launch that keeps the term-invariant operands on the chip (mode 1; contexts of up to 400 000
  * observations -- POVAR_RES_MAX_OBS -- in the LDS-accumulating E0 mode, without peers: a context with a communicator of more
  * than one rank or with the peer-to-peer exchange runs the per-term kernels);
- * -1 (default): the library times both once per context on the caller's prepared system and keeps the faster one
- * (povar_layout_info.res_auto, tune_terms_us, tune_res_us).  Environment: POVAR_RES=0|1. */
+ * -1 (default): the library times both once per context and step on the caller's prepared system and keeps the faster one
+ * (povar_layout_info.res_auto[_h], tune_terms[_h]_us, tune_res[_h]_us).  The switch covers both steps; a series of either
+ * step that gives up (res_failed) leaves both on the per-term kernels.  Environment: POVAR_RES=0|1. */
 int povar_set_series_kernel(povar_ctx* ctx, int32_t mode);
 /* Diagnostic builds only (tools/variants/build_variant.sh ck_stamps -- a patched copy of the sources --, tools/ck_stamps.py):
  * in-kernel s_memtime stamps of e0_ck's phases, [workgroups][16 wavefronts][40]; the first call arms the collection.  The

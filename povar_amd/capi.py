@@ -78,6 +78,10 @@ class LayoutInfo(C.Structure):
                 ("res_lds_bytes", C.c_int32), ("res_build_ms", C.c_double), ("tune_terms_us", C.c_float),
                 ("tune_res_us", C.c_float), ("res_failed", C.c_int32), ("ck_packed", C.c_int32), ("ck_cold_q", C.c_int32),
                 ("ckh_stride", C.c_int32), ("ckh_accumulators", C.c_int32), ("ckh_capped_obs", C.c_int64),
+                ("res_ready_h", C.c_int32), ("res_active_h", C.c_int32), ("res_auto_h", C.c_int32), ("res_shared_h", C.c_int32),
+                ("res_wgs_h", C.c_int32), ("res_waves_h", C.c_int32), ("res_rows_h", C.c_int32), ("res_rounds_h", C.c_int32),
+                ("res_lds_bytes_h", C.c_int32), ("res_build_h_ms", C.c_double), ("tune_terms_h_us", C.c_float),
+                ("tune_res_h_us", C.c_float),
                 ("fp32_terms", C.c_int32)]
 
 

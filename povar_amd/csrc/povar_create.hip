@@ -264,11 +264,10 @@ bool ck_upload(povar_ctx* c, povar_ctx::CkDev& D, const CkLayout& K, bool locked
 // ------------------------------------------------------------------------------------------
 // resident power series (series_res): upload, kernel parameters, launch
 // ------------------------------------------------------------------------------------------
-int res_upload(povar_ctx* c, const ResLayout& R) {
-  povar_ctx::ResDev& D = c->res;
+int res_upload(povar_ctx* c, povar_ctx::ResDev& D, const ResLayout& R) {
   int rc = 0;
   if ((rc = upload(D.lane_cam, R.lane_cam, c)) || (rc = upload(D.lane_seg, R.lane_seg, c)) ||
-      (rc = upload(D.uv, R.uv, c)) || (rc = upload(D.lslot, R.lslot, c)) || (rc = upload(D.oslot, R.oslot, c)) ||
+      (!R.uv.empty() && (rc = upload(D.uv, R.uv, c))) /* (step 2's rows carry none) */ || (rc = upload(D.lslot, R.lslot, c)) || (rc = upload(D.oslot, R.oslot, c)) ||
       (rc = upload(D.wave_h, R.wave_h, c)) || (rc = upload(D.lm_off, R.lm_off, c)) || (rc = upload(D.lm_id, R.lm_id, c)) ||
       (rc = upload(D.cam_off, R.cam_off, c)) || (rc = upload(D.cam_id, R.cam_id, c)) || (rc = upload(D.cam_zi, R.cam_zi, c)) ||
       (rc = upload(D.own_off, R.own_off, c)) || (rc = upload(D.own_cam, R.own_cam, c)) || (rc = upload(D.own_zi, R.own_zi, c)) ||
@@ -294,10 +293,15 @@ int res_upload(povar_ctx* c, const ResLayout& R) {
 
 // the layout for a context: the lightest instantiation that holds it (fewest rows in registers first)
 void res_build_for(int n_cams, int n_lms, const int32_t* lm_off, const int32_t* cam_idx, const double* obs,
-                   const std::vector<int>& rank1, const std::vector<int>& slot_of_obs, int wgs, ResLayout& R) {
-  build_res(n_cams, n_lms, lm_off, cam_idx, obs, rank1, slot_of_obs, wgs, 16, 1, 1, 2, 1, R);
-  if (R.fits) return;
-  build_res(n_cams, n_lms, lm_off, cam_idx, obs, rank1, slot_of_obs, wgs, 8, 2, 1, 4, 2, R);
+                   const std::vector<int>& rank1, const std::vector<int>& slot_of_obs, int wgs, ResLayout& R, const ResShape& sh) {
+  if (sh.has_uv) {  // (step 1; series_res_h has no 1024-thread instantiation: POVAR_RES_H_VARIANTS)
+    build_res(n_cams, n_lms, lm_off, cam_idx, obs, rank1, slot_of_obs, wgs, 16, 1, 1, 2, 1, R, -1, sh);
+    if (R.fits) return;
+  }
+  build_res(n_cams, n_lms, lm_off, cam_idx, obs, rank1, slot_of_obs, wgs, 8, 2, 1, 4, 2, R, -1, sh);
+  // (fixed landmark arrays are charged at the slot capacity: with many cameras per workgroup the 512 slots of one per lane fit
+  // where the 1024 of two do not)
+  if (!R.fits && sh.lm_fixed) build_res(n_cams, n_lms, lm_off, cam_idx, obs, rank1, slot_of_obs, wgs, 8, 2, 1, 4, 1, R, -1, sh);
 }
 
 // The placed rows (povar_ctx::placer) replace the natural order.  Only between linearisations: everything lane-ordered
@@ -828,10 +832,26 @@ int povar_create(povar_ctx** out, int32_t n_cams, int32_t n_lms, int64_t n_obs,
       ResLayout R;
       res_build_for(n_cams, n_lms, lm_offsets, cam_idx, obs, L.cam_hot, L.slot_of_obs, wgs, R);
       if (R.fits && res_variant_exists(R.NW, R.H, R.R, R.LS)) {
-        if (int rc = res_upload(c, R)) { povar_destroy(c); return rc; }
+        if (int rc = res_upload(c, c->res, R)) { povar_destroy(c); return rc; }
         c->res.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr).count();
       }
       lap("resident-series layout");
+      // step 2 (series_res_h): step 1's instance where its cut fits the step-2 LDS formula and series_res_h has the shape;
+      // else a cut of its own (64 bytes per landmark slot at the instantiation's slot capacity, no image points)
+      const auto th = std::chrono::steady_clock::now();
+      if (c->res.ready && res_shared_fits(R) && res_variant_exists(R.NW, R.H, R.R, R.LS, true)) {
+        c->res_h_shared = true;
+        c->res_h_lds = res_lds_bytes_of(R, res_shape_step2());
+      } else {
+        ResLayout RH;
+        res_build_for(n_cams, n_lms, lm_offsets, cam_idx, obs, L.cam_hot, L.slot_of_obs, wgs, RH, res_shape_step2());
+        if (RH.fits && res_variant_exists(RH.NW, RH.H, RH.R, RH.LS, true)) {
+          if (int rc = res_upload(c, c->res_h, RH)) { povar_destroy(c); return rc; }
+          c->res_h_lds = RH.lds_bytes;
+        }
+      }
+      c->res_h_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - th).count();
+      lap("resident-series layout (step 2)");
     }
   }
   part_b.join();
@@ -961,6 +981,7 @@ void povar_destroy(povar_ctx* c) {
   c->ck32_uv.release(); c->ck32_lmrec.release(); c->ck32_pimg.release();
   c->ck.release(); c->pl_ck.release(); c->ckh.release(); c->pl_ckh.release(); c->ck_zero_range.release();
   c->res.release();
+  c->res_h.release();
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->series_graph) (void)hipGraphExecDestroy(c->series_graph);
   if (c->pin) (void)hipHostFree(c->pin);
@@ -1070,7 +1091,7 @@ int povar_get_layout_info(povar_ctx* c, povar_layout_info* out) {
   out->tune_lpl_h_us = c->ckh_tune_us[0];
   out->tune_ck_h_us = c->ckh_tune_us[1];
   out->res_ready = c->res.ready ? 1 : 0;
-  out->res_active = res_active(c) ? 1 : 0;
+  out->res_active = !c->joint && res_active(c, false) ? 1 : 0;  // (the step-1 answer: 0 while the joint system is the prepared one)
   out->res_auto = c->res_mode < 0 ? (c->res_tuned ? 2 : 1) : 0;
   out->res_wgs = c->res.W;
   out->res_waves = c->res.NW;
@@ -1093,6 +1114,22 @@ int povar_get_layout_info(povar_ctx* c, povar_layout_info* out) {
   out->ckh_accumulators = c->ckh.ready ? c->ckh.max_acc : 0;
   out->ckh_capped_obs = c->ckh.ready ? c->ckh.n_capped_obs : 0;
   out->fp32_terms = c->fp32_last;
+  {
+    const bool ready = res_ready(c, true);
+    const povar_ctx::ResDev& D = res_dev(c, true);
+    out->res_ready_h = ready ? 1 : 0;
+    out->res_active_h = res_active(c, true) ? 1 : 0;
+    out->res_auto_h = c->res_mode < 0 ? (c->res_tuned_h ? 2 : 1) : 0;
+    out->res_shared_h = ready && c->res_h_shared ? 1 : 0;
+    out->res_wgs_h = ready ? D.W : 0;
+    out->res_waves_h = ready ? D.NW : 0;
+    out->res_rows_h = ready ? D.H : 0;
+    out->res_rounds_h = ready ? D.R : 0;
+    out->res_lds_bytes_h = ready ? (int32_t)c->res_h_lds : 0;
+    out->res_build_h_ms = c->res_h_build_ms;
+    out->tune_terms_h_us = c->res_tune_h_us[0];
+    out->tune_res_h_us = c->res_tune_h_us[1];
+  }
   return 0;
 }
 

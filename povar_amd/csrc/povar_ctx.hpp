@@ -39,6 +39,7 @@
 #include "povar_kernels_ck_f32.hpp"
 #include "res_layout.hpp"
 #include "povar_kernels_res.hpp"
+#include "povar_kernels_res_joint.hpp"
 
 using namespace povar;
 
@@ -200,11 +201,19 @@ struct povar_ctx {
       uv.release(); own_q.release(); part.release(); zbuf.release(); nrm.release(); launch.release();
       ready = false;
     }
-  } res;
+  } res,
+    res_h;                       // step 2 (series_res_h): an instance of its own (no uv) where step 1's cut does not serve it
+  // step 2 runs step 1's instance where that cut fits the LDS under the step-2 formula (res_layout.hpp: res_shared_fits) and
+  // series_res_h has an instantiation for its shape: every array is shared, uv is simply not read
+  bool res_h_shared = false;
+  size_t res_h_lds = 0;          // dynamic LDS of series_res_h on the instance it runs
+  double res_h_build_ms = 0;
   int res_mode = -1;             // -1: the library times the resident series against the per-term kernels once per context
                                  // (res_autotune); 0: per-term kernels; 1: resident series whenever the context allows
   bool res_tuned = false, res_choice = false, res_failed = false;
   float res_tune_us[2] = {0, 0}; // per term: per-term kernels (hipGraph), resident series
+  bool res_tuned_h = false, res_choice_h = false;  // the same for step 2, timed on the prepared joint system
+  float res_tune_h_us[2] = {0, 0};
   bool res_check = false;        // a resident series is in flight whose give-up bit (flags[0] & 4) has not been looked at
   int res_last_m = 0;
   double res_last_tol[2] = {0, 0};
@@ -358,6 +367,10 @@ void launch_reduce(povar_ctx* c, double* out) {
 
 inline bool sharded(const povar_ctx* c) { return c->comm != nullptr || c->host_fn != nullptr; }
 
+// the resident-series instance a step's series runs on
+inline const povar_ctx::ResDev& res_dev(const povar_ctx* c, bool joint) { return joint && !c->res_h_shared ? c->res_h : c->res; }
+inline bool res_ready(const povar_ctx* c, bool joint) { return joint ? (c->res_h_shared ? c->res.ready : c->res_h.ready) : c->res.ready; }
+
 // the lane-per-landmark kernels run the context (use_lpl in the LDS-accumulating mode): e0_lpl[_h] / e0_ck* for the terms,
 // lpl_pass[_h] for linearisation and cost, and ldsacc_dp's cold view and partial records are theirs
 inline bool lpl_mode(const povar_ctx* c) { return c->use_lpl && c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC; }
@@ -453,9 +466,9 @@ TermPlan term_plan(const povar_ctx* c, int step, TermUse use, int variant = -1);
 int launch_e0(povar_ctx* c, const TermPlan& p);  // povar_series.hip
 hipError_t term_set_lds_all();  // povar_series.hip
 void launch_ck32_records(povar_ctx* c);  // povar_series.hip
-bool res_variant_exists(int nw, int h, int rr, int ls);  // povar_series.hip
+bool res_variant_exists(int nw, int h, int rr, int ls, bool joint = false);  // povar_series.hip
 hipError_t res_set_lds_all();  // povar_series.hip
-bool res_active(const povar_ctx* c);  // povar_series.hip
+bool res_active(const povar_ctx* c, bool joint);  // povar_series.hip
 void prof_mark(povar_ctx* c, int kind);  // povar_series.hip
 Dp ldsacc_dp(povar_ctx* c, bool long_in_kernel = false);  // povar_series.hip
 int ck_autotune(povar_ctx* c, int step);  // povar_series.hip
@@ -463,8 +476,8 @@ int tune_agree(povar_ctx* c, int step);  // povar_series.hip
 extern "C" int res_verify(povar_ctx* c);  // povar_series.hip
 int ck_max_cams();  // povar_create.hip
 bool ck_upload(povar_ctx* c, povar_ctx::CkDev& D, const CkLayout& K, bool locked, size_t* bytes, bool need_uv = true);  // povar_create.hip
-int res_upload(povar_ctx* c, const ResLayout& R);  // povar_create.hip
-void res_build_for(int n_cams, int n_lms, const int32_t* lm_off, const int32_t* cam_idx, const double* obs, const std::vector<int>& rank1, const std::vector<int>& slot_of_obs, int wgs, ResLayout& R);  // povar_create.hip
+int res_upload(povar_ctx* c, povar_ctx::ResDev& D, const ResLayout& R);  // povar_create.hip
+void res_build_for(int n_cams, int n_lms, const int32_t* lm_off, const int32_t* cam_idx, const double* obs, const std::vector<int>& rank1, const std::vector<int>& slot_of_obs, int wgs, ResLayout& R, const ResShape& sh = ResShape());  // povar_create.hip
 int swap_in_placed_rows(povar_ctx* c, bool wait);  // povar_create.hip
 int check_ctx(povar_ctx* c);  // povar_create.hip
 int ensure_pin(povar_ctx* c);  // povar_create.hip

@@ -31,13 +31,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "layout_host.hpp"  // WAVE
+
 // Kernels that are not templates have internal linkage: the headers are included by every translation unit of the library
 // (povar_create.hip, povar_lm.hip, povar_series.hip, ...), each of which compiles the kernels it launches.
 #define POVAR_KERNEL static __attribute__((unused)) __global__
 
 namespace povar {
 
-constexpr int WAVE = 64;
 constexpr int LM_BLOCK = 256;   // 4 wave bins per workgroup
 constexpr int CM_ITEM_MAX = 512; // observations of one camera per CM work item
 constexpr int CM_COLD_ITEM_MAX = 128;  // same for the small "cold" view of the LDSACC mode (more, shorter waves)

@@ -594,6 +594,18 @@ __device__ inline void nt_apply(const double* w, double beta, const double (&y)[
   for (int j = 0; j < 11; ++j) o[j] = y[j + 1] - beta * w[j + 1] * wy;
 }
 
+// One row of x = B_c^-1 y (11 x 11, row stride 11 in the camera's block of Dp::binv; right_mul_b_inv_joint :342-360): the
+// ONE body of the series start x_0 = B^-1 (-b) -- cam_binv_axpy_h and the prologue of series_res_h
+// (povar_kernels_res_joint.hpp) leave the same bits --, one fused multiply-add per entry in index order, spelled out so
+// that no call site is contracted differently.  y: anything indexable (registers, LDS).
+template <class Y>
+__device__ inline double binv_row11(const double* Bi, const Y& y) {
+  double s = 0;
+#pragma unroll
+  for (int j = 0; j < 11; ++j) s = fma(Bi[j], y[j], s);
+  return s;
+}
+
 // b11_c = N_c^T (sigma * sum_items); one wavefront per camera
 POVAR_KERNEL __launch_bounds__(256) void cam_sum_items_h(Dp d, double* out11, const double* ncw) {
   const int lane = threadIdx.x & 63;
@@ -649,9 +661,7 @@ POVAR_KERNEL __launch_bounds__(K9_CAMS * 64) void cam_binv_axpy_h(Dp d, int mode
   double nrm[2] = {0, 0};
   double s = 0;
   if (in && lane < 11) {
-    const double* Bi = d.binv + 144 * (size_t)c + 11 * lane;
-#pragma unroll
-    for (int j = 0; j < 11; ++j) s += Bi[j] * y11[j];
+    s = binv_row11(d.binv + 144 * (size_t)c + 11 * lane, y11);
     const size_t idx = 11 * (size_t)c + lane;
     const double acc = mode == 0 ? s : d.accum[idx] + s;
     d.tmp[idx] = s;

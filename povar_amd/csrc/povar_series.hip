@@ -99,6 +99,11 @@ static void ck_dp(const povar_ctx* c, int step, Dp& da) {
 // instantiations: wavefronts per workgroup, rows per chunk, chunks per lane, landmark slots per lane.  1024-thread
 // workgroups (128 VGPRs per lane): one chunk of at most two rows; 512-thread ones (256): two chunks of up to four rows
 #define POVAR_RES_VARIANTS(X) X(16, 1, 1, 1) X(16, 2, 1, 1) X(8, 1, 2, 1) X(8, 1, 2, 2) X(8, 2, 2, 1) X(8, 2, 2, 2) X(8, 4, 2, 1) X(8, 4, 2, 2)
+// series_res_h: a table of its own -- the shapes whose code objects use no scratch (profiles/res_joint_isa.txt).  The two
+// 1024-thread shapes are not in it: P_c (24 registers per chunk instead of P3's 18), s and Hll^-1 (20 per landmark slot
+// instead of G's 12) and house4 between the passes do not fit 128 registers (7 to 21 spilt), so step 2 cuts its instance
+// for 512-thread workgroups (res_build_for)
+#define POVAR_RES_H_VARIANTS(X) X(8, 1, 2, 1) X(8, 1, 2, 2) X(8, 2, 2, 1) X(8, 2, 2, 2) X(8, 4, 2, 1) X(8, 4, 2, 2)
 template <int NW, int H, int RR, int LS>
 void launch_res_t(povar_ctx* c, const ResP& k) {
   if (c->opt.robust_norm)
@@ -106,22 +111,45 @@ void launch_res_t(povar_ctx* c, const ResP& k) {
   else
     hipLaunchKernelGGL((series_res<NW, H, RR, LS, false>), dim3(c->res.W), dim3(NW * 64), c->res.lds_bytes, c->stream, c->d, k);
 }
+template <int NW, int H, int RR, int LS>
+void launch_res_h_t(povar_ctx* c, const ResP& k) {
+  const double* ncw = c->ncw.p;
+  if (c->opt.robust_norm)
+    hipLaunchKernelGGL((series_res_h<NW, H, RR, LS, true>), dim3(k.W), dim3(NW * 64), c->res_h_lds, c->stream, c->d, k, ncw);
+  else
+    hipLaunchKernelGGL((series_res_h<NW, H, RR, LS, false>), dim3(k.W), dim3(NW * 64), c->res_h_lds, c->stream, c->d, k, ncw);
+}
 
-bool res_variant_exists(int nw, int h, int rr, int ls) {
+bool res_variant_exists(int nw, int h, int rr, int ls, bool joint) {
 #define X(NW_, H_, R_, LS_) if (nw == NW_ && h == H_ && rr == R_ && ls == LS_) return true;
-  POVAR_RES_VARIANTS(X)
+  if (joint) {
+    POVAR_RES_H_VARIANTS(X)
+  } else {
+    POVAR_RES_VARIANTS(X)
+  }
 #undef X
   return false;
 }
 
 void launch_res(povar_ctx* c, const ResP& k) {
-#define X(NW_, H_, R_, LS_)                                                              \
-  if (c->res.NW == NW_ && c->res.H == H_ && c->res.R == R_ && c->res.LS == LS_) {        \
-    launch_res_t<NW_, H_, R_, LS_>(c, k);                                                \
-    return;                                                                              \
+  const povar_ctx::ResDev& D = res_dev(c, c->joint);
+#define X(NW_, H_, R_, LS_)                                                  \
+  if (D.NW == NW_ && D.H == H_ && D.R == R_ && D.LS == LS_) {                \
+    launch_res_t<NW_, H_, R_, LS_>(c, k);                                    \
+    return;                                                                  \
   }
-  POVAR_RES_VARIANTS(X)
+#define XH(NW_, H_, R_, LS_)                                                 \
+  if (D.NW == NW_ && D.H == H_ && D.R == R_ && D.LS == LS_) {                \
+    launch_res_h_t<NW_, H_, R_, LS_>(c, k);                                  \
+    return;                                                                  \
+  }
+  if (c->joint) {
+    POVAR_RES_H_VARIANTS(XH)
+  } else {
+    POVAR_RES_VARIANTS(X)
+  }
 #undef X
+#undef XH
 }
 
 template <int NW, int H, int RR, int LS>
@@ -130,29 +158,41 @@ hipError_t res_set_lds_t() {
   if (e != hipSuccess) return e;
   return hipFuncSetAttribute((const void*)series_res<NW, H, RR, LS, true>, hipFuncAttributeMaxDynamicSharedMemorySize, RES_LDS_BYTES);
 }
+template <int NW, int H, int RR, int LS>
+hipError_t res_h_set_lds_t() {
+  hipError_t e = hipFuncSetAttribute((const void*)series_res_h<NW, H, RR, LS, false>, hipFuncAttributeMaxDynamicSharedMemorySize, RES_LDS_BYTES);
+  if (e != hipSuccess) return e;
+  return hipFuncSetAttribute((const void*)series_res_h<NW, H, RR, LS, true>, hipFuncAttributeMaxDynamicSharedMemorySize, RES_LDS_BYTES);
+}
 
 hipError_t res_set_lds_all() {
   hipError_t e = hipSuccess;
 #define X(NW_, H_, R_, LS_) if (e == hipSuccess) e = res_set_lds_t<NW_, H_, R_, LS_>();
   POVAR_RES_VARIANTS(X)
 #undef X
+#define X(NW_, H_, R_, LS_) if (e == hipSuccess) e = res_h_set_lds_t<NW_, H_, R_, LS_>();
+  POVAR_RES_H_VARIANTS(X)
+#undef X
   return e;
 }
 
-// the context can run the resident series now (whether it SHOULD is res_mode / the timing of res_autotune)
-bool res_possible(const povar_ctx* c) {
+// the context can run the resident series of a step now (whether it SHOULD is res_mode / the timing of res_autotune).  A
+// give-up in either step (res_failed) keeps both on the per-term kernels: the workgroups were not on the device together,
+// which is the device's load and not the step's
+bool res_possible(const povar_ctx* c, bool joint) {
   // (a communicator of ONE rank exchanges nothing: such a context -- the one-GPU proxy of a shard, tools/shard_sweep.sh --
   // is as good as unsharded; with peers the resident kernel would need their sums inside the launch: not built)
-  return c->res.ready && !c->res_failed && !c->joint && c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC && !c->profile &&
+  return res_ready(c, joint) && !c->res_failed && c->opt.e0_mode == POVAR_E0_IMPLICIT_LDSACC && !c->profile &&
          (!sharded(c) || (c->world == 1 && !c->p2p));
 }
 
-bool res_active(const povar_ctx* c) {
-  return res_possible(c) && (c->res_mode == 1 || (c->res_mode < 0 && c->res_tuned && c->res_choice));  // (and m <= 250: run_series' caller)
+bool res_active(const povar_ctx* c, bool joint) {
+  const bool tuned = joint ? c->res_tuned_h : c->res_tuned, choice = joint ? c->res_choice_h : c->res_choice;
+  return res_possible(c, joint) && (c->res_mode == 1 || (c->res_mode < 0 && tuned && choice));  // (and m <= 250: run_series' caller)
 }
 
 ResP res_params(const povar_ctx* c, int m, double q_tol, double r_tol) {
-  const povar_ctx::ResDev& D = c->res;
+  const povar_ctx::ResDev& D = res_dev(c, c->joint);
   ResP k{};
   k.lane_cam = D.lane_cam.p; k.lane_seg = D.lane_seg.p;
   k.uv = D.uv.p; k.lslot = D.lslot.p; k.oslot = D.oslot.p; k.wave_h = D.wave_h.p;
@@ -171,11 +211,12 @@ ResP res_params(const povar_ctx* c, int m, double q_tol, double r_tol) {
   return k;
 }
 
-// the whole series as one launch (+ the node that numbers the next one)
+// the whole series as one launch (+ the node that numbers the next one): series_res, or series_res_h for a joint system
 int enqueue_series_res(povar_ctx* c, int32_t m, double q_tol, double r_tol) {
   HIP_TRY(hipMemsetAsync(c->flags.p + 1, 0, sizeof(int) * 3, c->stream));
-  launch_res(c, res_params(c, m, q_tol, r_tol));
-  hipLaunchKernelGGL(res_bump_launch, dim3(1), dim3(1), 0, c->stream, c->res.launch.p);
+  const ResP k = res_params(c, m, q_tol, r_tol);
+  launch_res(c, k);
+  hipLaunchKernelGGL(res_bump_launch, dim3(1), dim3(1), 0, c->stream, k.launch);
   return 0;
 }
 
@@ -658,12 +699,16 @@ int res_verify(povar_ctx* c) {
 // workgroup): unless one is forced (POVAR_RES, povar_set_series_kernel) both are run once on the caller's prepared system
 // -- a warm-up and REPS timed solves each, the same m and tolerances -- and the faster one is kept.
 int res_autotune(povar_ctx* c, int32_t m, double q_tol, double r_tol) {
-  if (c->res_mode >= 0 || c->res_tuned || !res_possible(c) || m < 4 || m > 250) return 0;
-  c->res_tuned = true;
+  // (once per step, on the system prepared last: the two kernels and their per-term counterparts differ)
+  bool& tuned = c->joint ? c->res_tuned_h : c->res_tuned;
+  bool& choice = c->joint ? c->res_choice_h : c->res_choice;
+  float* tune_us = c->joint ? c->res_tune_h_us : c->res_tune_us;
+  if (c->res_mode >= 0 || tuned || !res_possible(c, c->joint) || m < 4 || m > 250) return 0;
+  tuned = true;
   struct Restore {  // a failure below leaves the choice open and the timing to be repeated (as ck_autotune)
-    povar_ctx* c; bool done = false;
-    ~Restore() { if (!done) { c->res_tuned = false; c->res_choice = false; } }
-  } restore{c};
+    bool& tuned; bool& choice; bool done = false;
+    ~Restore() { if (!done) { tuned = false; choice = false; } }
+  } restore{tuned, choice};
   // Two alternating rounds of (warm-up + REPS series) of each form, the FASTER round of each counts -- one round's mean was
   // seen 18 % off in some processes (ck_autotune) --, and both forms run all m terms: the tolerances are off while timing (an
   // early exit would time a few terms of one form against a few of the other; the caller's series follows with its own)
@@ -681,7 +726,7 @@ int res_autotune(povar_ctx* c, int32_t m, double q_tol, double r_tol) {
       if (which == 1) {
         HIP_TRY(hipStreamSynchronize(c->stream));
         if (int rc = res_verify(c)) return rc;
-        if (c->res_failed) { restore.done = true; c->res_choice = false; return 0; }
+        if (c->res_failed) { restore.done = true; choice = false; return 0; }
       }
     }
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -693,9 +738,9 @@ int res_autotune(povar_ctx* c, int32_t m, double q_tol, double r_tol) {
       ms[which] = std::min(ms[which], t);
     }
   restore.done = true;
-  c->res_tune_us[0] = 1e3f * ms[0] / (REPS * m);
-  c->res_tune_us[1] = 1e3f * ms[1] / (REPS * m);
-  c->res_choice = ms[1] < 0.98f * ms[0];
+  tune_us[0] = 1e3f * ms[0] / (REPS * m);
+  tune_us[1] = 1e3f * ms[1] / (REPS * m);
+  choice = ms[1] < 0.98f * ms[0];
   return 0;
 }
 
@@ -710,7 +755,7 @@ int povar_power_series_pose(povar_ctx* c, int32_t m, double q_tol, double r_tol,
   const TermPlan p = term_plan(c, c->joint ? 2 : 1, norms ? TermUse::series_norms : TermUse::series);
   if (p.ck()) ensure_ck_w(c, p.step);
   if (int rc = res_autotune(c, m, q_tol, r_tol)) return rc;
-  const bool use_res = m > 0 && m <= 250 && res_active(c);  // (a granule tag carries the term in 8 bits)
+  const bool use_res = m > 0 && m <= 250 && res_active(c, c->joint);  // (a granule tag carries the term in 8 bits)
   if (p.step == 1) c->fp32_last = p.e0 == E0K::ck_f32 && !use_res ? 1 : 0;
   if (int rc = run_series(c, m, q_tol, r_tol, use_res)) return rc;
   int iters = m, status = POVAR_LINEAR_SOLVER_NO_CONVERGENCE;
@@ -952,12 +997,12 @@ int povar_set_e0_kernel(povar_ctx* c, int32_t kernel) {
 int povar_set_series_kernel(povar_ctx* c, int32_t mode) {
   if (int rc = check_ctx(c)) return rc;
   if (mode < -1 || mode > 1) return fail(-1, "unknown series kernel");
-  if (mode == 1 && !c->res.ready) return fail(-1, "the resident-series layout was not built for this context");
+  if (mode == 1 && !c->res.ready && !res_ready(c, true)) return fail(-1, "the resident-series layout was not built for this context");
   if (mode == 1 && c->fp32_terms) return fail(-1, "POVAR_FLAG_FP32_TERMS: the resident series has no fp32 form");
   if (int rc = res_verify(c)) return rc;
   if (c->deterministic) return 0;  // pinned (POVAR_DETERMINISTIC)
   c->res_mode = mode;
-  if (mode < 0) c->res_tuned = false;
+  if (mode < 0) c->res_tuned = c->res_tuned_h = false;  // (both steps are timed again)
   return 0;
 }
 

@@ -29,7 +29,7 @@
 #include <numeric>
 #include <vector>
 
-#include "lpl_layout.hpp"
+#include "layout_host.hpp"
 
 namespace povar {
 
@@ -46,7 +46,7 @@ struct ResLayout {
   std::vector<int> lane_seg;         // first | last << 8 lane (of the wavefront) of the run of lanes that share the camera
                                      // | 1 << 16: the camera's only run in the workgroup (plain store instead of an LDS add)
   // per row [W][R][H][T]
-  std::vector<double2> uv;
+  std::vector<double2> uv;           // (empty for a shape without image points: ResShape::has_uv)
   std::vector<int> lslot;            // 3 x landmark slot of the workgroup (-1: no observation)
   std::vector<int> oslot;            // wave-bin slot of the observation (robust weight: Dp::sw / V2::w through V2::of_slot)
   std::vector<int> wave_h;           // [W][R][NW] rows of the wavefront's chunks | needs a segmented sum << 8 | scan steps << 12
@@ -75,20 +75,45 @@ struct ResLayout {
 // camera B^-1, sigma, sum, term, E0 row, norms and five partial sums
 constexpr int RES_LM_BYTES = 48;
 constexpr int RES_OWN_DOUBLES = 144 + 12 + 12 + 12 + 12 + 2 + 5 * 12;
+// step 2 (series_res_h, povar_kernels_res_joint.hpp): X and U4 / G4 per landmark slot (s and Hll^-1 in the registers of the
+// slot's lane), and per owned camera B^-1 11 x 11, sigma, the reflector (w, beta) of N_c, sum (11), term (11), E0 row, norms
+// and the five partial sums
+constexpr int RES_LM_BYTES_H = 64;
+constexpr int RES_OWN_DOUBLES_H = 121 + 12 + 13 + 11 + 11 + 12 + 2 + 5 * 12;
 __host__ __device__ inline size_t res_region_doubles(int n_cam, int n_oq) {
   const size_t a = (size_t)n_cam * RES_ACC_STRIDE, b = (size_t)n_oq * 12;
   return a > b ? a : b;
 }
-inline size_t res_lds_bytes(int n_lm, int n_cam, int n_own, int n_oq) {
-  return 64 + (size_t)n_lm * RES_LM_BYTES + res_region_doubles(n_cam, n_oq) * 8 + (size_t)n_own * (RES_OWN_DOUBLES * 8 + 16) +
-         (size_t)(n_cam + n_oq) * 4 + 8;
+// What the kernel of a step keeps per landmark slot, per owned camera and per row (as CkShape in ck_layout.hpp); the
+// default is step 1's series_res
+struct ResShape {
+  int lm_bytes = RES_LM_BYTES;        // LDS bytes per landmark slot
+  bool lm_fixed = false;              // the landmark arrays are component-major with a compile-time stride: they take the
+                                      // bytes of the instantiation's slot capacity (LS T) whatever the workgroup holds
+  int own_doubles = RES_OWN_DOUBLES;  // doubles per owned camera
+  bool has_uv = true;                 // rows carry image points (step 2's operator does not read them)
+};
+inline ResShape res_shape_step2() { return ResShape{RES_LM_BYTES_H, true, RES_OWN_DOUBLES_H, false}; }
+// lm_cap: the slot capacity of a shape with fixed landmark arrays
+inline size_t res_lds_bytes(int n_lm, int n_cam, int n_own, int n_oq, const ResShape& sh = ResShape(), int lm_cap = 0) {
+  return 64 + (size_t)(sh.lm_fixed ? lm_cap : n_lm) * sh.lm_bytes + res_region_doubles(n_cam, n_oq) * 8 +
+         (size_t)n_own * (sh.own_doubles * 8 + 16) + (size_t)(n_cam + n_oq) * 4 + 8;
+}
+
+// LDS of the fullest workgroup of a layout under a shape's formula
+inline size_t res_lds_bytes_of(const ResLayout& R, const ResShape& sh) {
+  size_t b = 0;
+  for (int g = 0; g < R.W; ++g)
+    b = std::max(b, res_lds_bytes(R.lm_off[g + 1] - R.lm_off[g], R.cam_off[g + 1] - R.cam_off[g], R.own_off[g + 1] - R.own_off[g],
+                                  R.oq_off[g + 1] - R.oq_off[g], sh, R.LS * R.NW * WAVE));
+  return b;
 }
 
 // W workgroups of NW wavefronts whose lanes hold R chunks of at most H rows each; the smallest H <= hmax (a power of
 // two, >= hmin) that fits is taken.  rank1[c] = 1 + popularity rank of camera c.
 inline void build_res(int n_cams, int n_lms, const int32_t* lm_off, const int32_t* cam_idx, const double* obs,
                       const std::vector<int>& rank1, const std::vector<int>& slot_of_obs, int W, int NW, int R_, int hmin, int hmax,
-                      int ls_max, ResLayout& R, int force_order = -1) {
+                      int ls_max, ResLayout& R, int force_order = -1, const ResShape& sh = ResShape()) {
   const int T = NW * WAVE;
   R = ResLayout();
   R.NW = NW;
@@ -138,7 +163,7 @@ inline void build_res(int n_cams, int n_lms, const int32_t* lm_off, const int32_
         else if (cnt[c] % H == 0) ++add_chunks;
       }
       const bool over = lms > 0 && (chunks + add_chunks > cap || lms + 1 > ls_max * T ||
-                                    res_lds_bytes(lms + 1, cams + add_cams, own_guess, oq_guess) > (size_t)RES_LDS_BYTES);
+                                    res_lds_bytes(lms + 1, cams + add_cams, own_guess, oq_guess, sh, ls_max * T) > (size_t)RES_LDS_BYTES);
       if (over) {
         pairs += cams;
         ++groups;
@@ -292,7 +317,7 @@ inline void build_res(int n_cams, int n_lms, const int32_t* lm_off, const int32_
   const size_t n_pos = (size_t)W * R.R * T;
   R.lane_cam.assign(n_pos, -1);
   R.lane_seg.assign(n_pos, 0);
-  R.uv.assign(n_pos * H, make_double2(0, 0));
+  if (sh.has_uv) R.uv.assign(n_pos * H, make_double2(0, 0));
   R.lslot.assign(n_pos * H, -1);
   R.oslot.assign(n_pos * H, -1);
   R.wave_h.assign((size_t)W * R.R * NW, 0);
@@ -316,7 +341,7 @@ inline void build_res(int n_cams, int n_lms, const int32_t* lm_off, const int32_
       for (int j = 0; j < ch[q].len; ++j) {
         const Ob& o = ob[ch[q].at + j];
         const size_t row = (((size_t)g * R.R + rt.first) * H + j) * T + rt.second;
-        R.uv[row] = make_double2(obs[2 * (size_t)o.i], obs[2 * (size_t)o.i + 1]);
+        if (sh.has_uv) R.uv[row] = make_double2(obs[2 * (size_t)o.i], obs[2 * (size_t)o.i + 1]);
         R.lslot[row] = o.slot3;
         R.oslot[row] = slot_of_obs[o.i];
       }
@@ -351,12 +376,15 @@ inline void build_res(int n_cams, int n_lms, const int32_t* lm_off, const int32_
     for (size_t pos = 0; pos < (size_t)R.R * T; ++pos)
       if (ci_of_pos[pos] >= 0 && runs[ci_of_pos[pos]] == 1) R.lane_seg[(size_t)g * R.R * T + pos] |= 1 << 16;
   });
-  R.lds_bytes = 0;
-  for (int g = 0; g < W; ++g)
-    R.lds_bytes = std::max(R.lds_bytes, res_lds_bytes(R.lm_off[g + 1] - R.lm_off[g], R.cam_off[g + 1] - R.cam_off[g],
-                                                      R.own_off[g + 1] - R.own_off[g], R.oq_off[g + 1] - R.oq_off[g]));
+  R.lds_bytes = res_lds_bytes_of(R, sh);
   if (R.lds_bytes > (size_t)RES_LDS_BYTES) { R.why = "landmarks + accumulators + owned cameras exceed the LDS"; return; }
   R.fits = true;
+}
+
+// step 1's cut serves step 2 as well where its fullest workgroup fits the LDS under the step-2 formula: the two instances
+// then share every array except uv
+inline bool res_shared_fits(const ResLayout& R) {
+  return R.fits && res_lds_bytes_of(R, res_shape_step2()) <= (size_t)RES_LDS_BYTES;
 }
 
 }  // namespace povar
