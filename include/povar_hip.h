@@ -216,7 +216,7 @@ int povar_normalize_joint(povar_ctx* ctx);
 
 /* ---- explicit-Schur-complement solvers: LinearizorSC (solver/linearizor_sc.cpp), selected by
  * --solver-type-step-1 PCG | CHOLESKY and --solver-type-step-2 RIPCG (solver/linearizor.cpp:51-53,
- * 67-72).  The reduced camera system S x = b, S = (Hpp + lambda I) - E0, is solved without landmark
+ * 67-72), and --solver-type-step-2 RICHOLESKY (not in the reference).  The reduced camera system S x = b, S = (Hpp + lambda I) - E0, is solved without landmark
  * damping in step 1 (linearizor_sc.cpp:85-160) and with it in step 2 (:224-303); linearisation,
  * error evaluation and apply are the calls above (povar_apply_pose with POVAR_POWER_VARPROJ ==
  * LinearizorSC::apply, linearizor_sc.cpp:65-83). ---- */
@@ -240,6 +240,21 @@ int povar_solve_pose_sc(povar_ctx* ctx, double lambda, int32_t method, int32_t m
  * 11 n_cams tangent system */
 int povar_solve_joint_sc(povar_ctx* ctx, double lambda, int32_t min_iterations, int32_t max_iterations,
                          double eta, double* inc, int32_t* num_iterations, int32_t* termination);
+/* The same with the solver named, as povar_solve_pose_sc (povar_solve_joint_sc forwards with POVAR_SC_PCG).
+ * POVAR_SC_CHOLESKY: direct solve of the joint system -- the dense S = (N_c^T sigma Hpp sigma N_c + lambda I) -
+ * N_c^T sigma E0 sigma N_c of the 11 n_cams tangent coordinates is assembled on the device (landmark damping
+ * included, as povar_prepare_joint leaves it) and factored by the kernels of CHOLESKY (needs 8 * (11 n_cams)^2 bytes
+ * of HBM; num_iterations = 0; min / max_iterations and eta are not read).  The reference has no direct step-2
+ * solver: this is `bal --solver-type-step-2 RICHOLESKY`, the limit RIPOBA and RIPCG approach.  The assembly adds
+ * with fp64 atomics, so it is not bit-reproducible (as step 1's).  A system that is not positive definite gives a
+ * non-finite increment and POVAR_NUMERIC_FAILURE; an unknown method is an argument error. */
+int povar_solve_joint_sc_method(povar_ctx* ctx, double lambda, int32_t method, int32_t min_iterations,
+                                int32_t max_iterations, double eta, double* inc /*11 n_cams*/,
+                                int32_t* num_iterations, int32_t* termination);
+/* right_mul_e0_joint (sc/linearization_power_varproj.hpp:408-453) in tangent coordinates:
+ * y = N_c^T sigma E0 sigma N_c x on the joint system prepared last (povar_prepare_joint, or any step-2 solve), with the
+ * per-term E0 kernels the series and RIPCG use; x, y: 11 n_cams.  An error when the system prepared last is step 1's. */
+int povar_right_mul_e0_joint(povar_ctx* ctx, const double* x, double* y);
 
 /* ---- inspection of internal state in the reference's layouts (parity tests) ---- */
 enum {

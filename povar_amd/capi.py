@@ -280,13 +280,21 @@ class Context:
                        allow_numeric=True)
         return inc, it.value, st.value, rc
 
-    def solve_joint_sc(self, lam, min_iterations=0, max_iterations=500, eta=1e-2):
+    def solve_joint_sc(self, lam, min_iterations=0, max_iterations=500, eta=1e-2, method=SC_PCG):
         inc = np.zeros(11 * self.n_cams)
         it, st = C.c_int32(), C.c_int32()
-        rc = self._chk(self.L.povar_solve_joint_sc(self.h, C.c_double(lam), C.c_int32(min_iterations),
-                                                   C.c_int32(max_iterations), C.c_double(eta), _p(inc),
-                                                   C.byref(it), C.byref(st)), allow_numeric=True)
+        rc = self._chk(self.L.povar_solve_joint_sc_method(self.h, C.c_double(lam), C.c_int32(method),
+                                                          C.c_int32(min_iterations), C.c_int32(max_iterations),
+                                                          C.c_double(eta), _p(inc), C.byref(it), C.byref(st)),
+                       allow_numeric=True)
         return inc, it.value, st.value, rc
+
+    def right_mul_e0_joint(self, x):
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        assert x.size == 11 * self.n_cams
+        y = np.zeros(11 * self.n_cams)
+        self._chk(self.L.povar_right_mul_e0_joint(self.h, _p(x), _p(y)))
+        return y
 
     def apply_joint(self, inc):
         inc = np.ascontiguousarray(inc, dtype=np.float64)

@@ -22,7 +22,11 @@ const char* to_string(SolverOptions::SolverType t) {
   }
 }
 const char* to_string(SolverOptions::SolverTypeRiemannian t) {
-  return t == SolverOptions::SolverTypeRiemannian::RIPOBA ? "RIPOBA" : "RIPCG";
+  switch (t) {
+    case SolverOptions::SolverTypeRiemannian::RIPOBA: return "RIPOBA";
+    case SolverOptions::SolverTypeRiemannian::RIPCG: return "RIPCG";
+    default: return "RICHOLESKY";
+  }
 }
 
 namespace {
@@ -50,7 +54,8 @@ bool parse_bal_app_arguments(int argc, char** argv, BalAppOptions& o) {
     return parse_enum<S::SolverType>(v, {{"PCG", S::SolverType::PCG}, {"POWER_SCHUR_COMPLEMENT", S::SolverType::POWER_SCHUR_COMPLEMENT},
                                          {"POWER_VARPROJ", S::SolverType::POWER_VARPROJ}, {"CHOLESKY", S::SolverType::CHOLESKY}}, o.solver.solver_type_step_1); };
   val["solver-type-step-2"] = [&](const std::string& v) {
-    return parse_enum<S::SolverTypeRiemannian>(v, {{"RIPOBA", S::SolverTypeRiemannian::RIPOBA}, {"RIPCG", S::SolverTypeRiemannian::RIPCG}}, o.solver.solver_type_step_2); };
+    return parse_enum<S::SolverTypeRiemannian>(v, {{"RIPOBA", S::SolverTypeRiemannian::RIPOBA}, {"RIPCG", S::SolverTypeRiemannian::RIPCG},
+                                                   {"RICHOLESKY", S::SolverTypeRiemannian::RICHOLESKY}}, o.solver.solver_type_step_2); };
   val["optimized-cost"] = [&](const std::string& v) {
     return parse_enum<S::OptimizedCost>(v, {{"ERROR", S::OptimizedCost::ERROR}, {"ERROR_VALID", S::OptimizedCost::ERROR_VALID},
                                             {"ERROR_VALID_AVG", S::OptimizedCost::ERROR_VALID_AVG}}, o.solver.optimized_cost); };
@@ -95,7 +100,10 @@ bool parse_bal_app_arguments(int argc, char** argv, BalAppOptions& o) {
       for (auto& kv : val) std::printf(" --%s", kv.first.c_str());
       std::printf("\n  boolean options (--x / --no-x):");
       for (auto& kv : flag) std::printf(" --%s", kv.first.c_str());
-      std::printf("\n");
+      std::printf("\n  --solver-type-step-1 PCG | POWER_SCHUR_COMPLEMENT | POWER_VARPROJ | CHOLESKY\n"
+                  "  --solver-type-step-2 RIPOBA | RIPCG | RICHOLESKY\n"
+                  "      RICHOLESKY is not a value of the reference: the direct solve of the joint system (dense Cholesky on the\n"
+                  "      device), the limit RIPOBA and RIPCG approach\n");
       return false;
     }
     if (a.rfind("--", 0) != 0) {

@@ -101,7 +101,8 @@ class LinearizorPowerVarprojHip : public Linearizor, public StateMirror {
     }
     using ST = SolverOptions::SolverType;
     sc_step1_ = !homogeneous && (options.solver_type_step_1 == ST::PCG || options.solver_type_step_1 == ST::CHOLESKY);
-    sc_step2_ = homogeneous && options.solver_type_step_2 == SolverOptions::SolverTypeRiemannian::RIPCG;
+    using ST2 = SolverOptions::SolverTypeRiemannian;
+    sc_step2_ = homogeneous && (options.solver_type_step_2 == ST2::RIPCG || options.solver_type_step_2 == ST2::RICHOLESKY);
     // LinearizorSC::linearize_pOSE does not scale the landmark Jacobian columns (linearizor_sc.cpp:163-191)
     check(povar_set_jl_col_scaling(ctx_, sc_step1_ ? 0 : 1), "povar_set_jl_col_scaling");
     // IterationSummary timings come from the device (hipEvents on the library's stream, povar_timings), not from
@@ -199,12 +200,14 @@ class LinearizorPowerVarprojHip : public Linearizor, public StateMirror {
     VecX inc(11 * (size_t)bal_problem_.num_cameras());
     Timer t;
     int32_t iters = 0, term = 0;
-    if (sc_step2_) {  // LinearizorSC::solve_joint, linearizor_sc.cpp:224-303
-      require_schur_jacobi();
-      check(povar_solve_joint_sc(ctx_, lambda, options_.min_linear_solver_iterations, options_.max_linear_solver_iterations,
-                                 options_.eta, inc.data(), &iters, &term), "povar_solve_joint_sc");
+    if (sc_step2_) {  // LinearizorSC::solve_joint, linearizor_sc.cpp:224-303; RICHOLESKY: the direct solve (not in the reference)
+      const bool chol = options_.solver_type_step_2 == SolverOptions::SolverTypeRiemannian::RICHOLESKY;
+      if (!chol) require_schur_jacobi();
+      check(povar_solve_joint_sc_method(ctx_, lambda, chol ? POVAR_SC_CHOLESKY : POVAR_SC_PCG, options_.min_linear_solver_iterations,
+                                        options_.max_linear_solver_iterations, options_.eta, inc.data(), &iters, &term),
+            "povar_solve_joint_sc_method");
       IF_SET(it_summary_)->prepare_time_in_seconds = device_seconds(1);
-      fill_sc_summary(device_seconds(2), iters, term, false);
+      fill_sc_summary(device_seconds(2), iters, term, chol);
       return inc;
     }
     check(povar_solve_joint(ctx_, lambda, options_.power_sc_iterations, options_.eta, options_.r_tolerance,
@@ -429,7 +432,8 @@ class LinearizorPowerVarprojHipMulti : public Linearizor, public StateMirror {
       : options_(options), bal_problem_(bal_problem), summary_(summary), homogeneous_(homogeneous), team_(options.gpus) {
     using ST = SolverOptions::SolverType;
     if (options.solver_type_step_1 == ST::PCG || options.solver_type_step_1 == ST::CHOLESKY ||
-        options.solver_type_step_2 == SolverOptions::SolverTypeRiemannian::RIPCG) {
+        options.solver_type_step_2 == SolverOptions::SolverTypeRiemannian::RIPCG ||
+        options.solver_type_step_2 == SolverOptions::SolverTypeRiemannian::RICHOLESKY) {
       std::fprintf(stderr, "FATAL: --gpus > 1 serves the power-series solvers (POWER_VARPROJ, POWER_SCHUR_COMPLEMENT, RIPOBA)\n");
       std::abort();
     }

@@ -20,7 +20,8 @@ struct BaLogOptions {
 
 struct SolverOptions {
   enum class SolverType { PCG, POWER_SCHUR_COMPLEMENT, POWER_VARPROJ, CHOLESKY };
-  enum class SolverTypeRiemannian { RIPOBA, RIPCG };
+  // RICHOLESKY: dense Cholesky of the joint reduced system on the device (povar_solve_joint_sc_method); not a reference value
+  enum class SolverTypeRiemannian { RIPOBA, RIPCG, RICHOLESKY };
   enum class OptimizedCost { ERROR, ERROR_VALID, ERROR_VALID_AVG };
   enum class PreconditionerType { JACOBI, SCHUR_JACOBI };
 

@@ -5,7 +5,7 @@
 //   povar_lm.hip       the stages of an LM iteration: state, cost, linearise, prepare, apply (both steps), exports
 //   povar_series.hip   the term loop: E0 / B^-1 launchers, kernel choice by timing, hipGraph, the series entry points
 //   povar_comm.hip     exchange steps: RCCL / host-hook all-reduce, the peer-to-peer term exchange
-//   povar_sc.hip       explicit-Schur-complement solvers (PCG / CHOLESKY / RIPCG)
+//   povar_sc.hip       explicit-Schur-complement solvers (PCG / CHOLESKY / RIPCG / RICHOLESKY)
 // Device code: povar_kernels*.hpp (kernels that are not templates have internal linkage: every unit compiles what it launches).
 #pragma once
 #include "../../include/povar_hip.h"
@@ -255,7 +255,8 @@ struct povar_ctx {
   // explicit-SC solvers (PCG / CHOLESKY / RIPCG), allocated on first use
   DevBuf<double> sc_dm_part, sc_dm, sc_bmat, sc_minv, sc_x, sc_r, sc_p, sc_q, sc_zv, sc_part, sc_s;
   ScP sc{};
-  DevBuf<double> sc_dense, sc_xpad;      // CHOLESKY: augmented S (povar_kernels_chol.hpp) and the padded solution
+  DevBuf<double> sc_dense, sc_xpad;      // CHOLESKY / RICHOLESKY: augmented S (povar_kernels_chol.hpp) and the padded solution,
+                                         // grown to the larger of the two systems a context solves (run_cholesky)
   DevBuf<int> sc_lm_slot0, sc_lm_cnt, sc_info;
 
   Dp d{};
@@ -502,4 +503,4 @@ int allreduce(povar_ctx* c, double* buf, size_t n);  // povar_comm.hip
 void p2p_dp(povar_ctx* c, Dp& dt);  // povar_comm.hip
 int ensure_sc(povar_ctx* c);  // povar_sc.hip
 int e0_dense(povar_ctx* c);  // povar_sc.hip
-int run_cholesky(povar_ctx* c, int32_t* num_iterations, int32_t* termination);  // povar_sc.hip
+int run_cholesky(povar_ctx* c, int dim, int32_t* num_iterations, int32_t* termination);  // povar_sc.hip (dim: 12 step 1, 11 step 2)

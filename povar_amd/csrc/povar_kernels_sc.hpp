@@ -586,15 +586,145 @@ POVAR_KERNEL __launch_bounds__(256) void sc_dense_offdiag(Dp d, const int* lm_sl
   }
 }
 
-// S_cc += B_c = Hpp_c + lambda I (landmark_block.hpp:381-384 + linearization_sc.hpp:477-481) and the
-// right-hand side -b into column N of the augmented matrix (povar_kernels_chol.hpp)
-POVAR_KERNEL __launch_bounds__(256) void sc_dense_diag(Dp d, const double* bmat, double* S, int64_t ld, int N) {
+// S_cc += B_c = Hpp_c + lambda I (landmark_block.hpp:381-384 + linearization_sc.hpp:477-481; step 2: its tangent
+// projection, cam_build_sc<true>'s out_mat) and the right-hand side -b into column N of the augmented matrix
+// (povar_kernels_chol.hpp).  DIM = 12 (step 1) or 11 (step 2): B_c is DIM x DIM row-major at stride 144.
+template <int DIM>
+__global__ __launch_bounds__(256) void sc_dense_diag(Dp d, const double* bmat, double* S, int64_t ld, int N) {
   const int c = blockIdx.x, e = threadIdx.x;
-  if (e < 144) {
-    const int r = e / 12, cc = e - 12 * r;
-    atomicAdd(S + (12 * (int64_t)c + r) * ld + 12 * (int64_t)c + cc, bmat[144 * (size_t)c + e]);
+  if (e < DIM * DIM) {
+    const int r = e / DIM, cc = e - DIM * r;
+    atomicAdd(S + (DIM * (int64_t)c + r) * ld + DIM * (int64_t)c + cc, bmat[144 * (size_t)c + e]);
   }
-  if (e < 12) S[(12 * (int64_t)c + e) * ld + N] = -d.b[12 * (size_t)c + e];
+  if (e < DIM) S[(DIM * (int64_t)c + e) * ld + N] = -d.b[DIM * (size_t)c + e];
+}
+
+// ------------------------------------------------------------------------------------------
+// RICHOLESKY (step 2; the reference has no direct solve of the joint system): the dense S of the 11 n_cams tangent
+// system in the same augmented layout, S = (N_c^T sigma Hpp sigma N_c + lambda I) - N_c^T sigma E0 sigma N_c.
+// Off-diagonal and E0-diagonal part of add_Hb_joint (landmark_block.hpp:452-463) in closed form: with
+//     F_i = sw_i Dm_i^T Jl3_i  (3 x 3; Dm = [[D00,0,D02],[0,D00,D12]], Jl3 = sw (D P) diag(s) N_l as cm_gram_sc<true>)
+// the ambient 12 x 12 block of a pair of observations of one landmark is  -(F_i Hll^-1 F_j^T) (x) X X^T  between
+// sigma_ci and sigma_cj, i.e.  -sum_ab T_ab u_a v_b^T  with T = F_i Hll^-1 F_j^T, u_a = sigma_ci o (e_a (x) X),
+// v_b = sigma_cj o (e_b (x) X).  The tangent projection acts on the vectors, N_ci^T u_a and N_cj^T v_b, so each
+// observation's three projected 11-vectors are formed once while it is staged and a pair costs 121 entries of a 3 x 3
+// bilinear form; the reflector stays out of the pair loop.  The i == j terms are the E0 part of the diagonal block
+// (what cm_gram_sc<true> + cam_build_sc<true> subtract for the preconditioner); B_c comes from sc_dense_diag<11>.
+// Workgroup per landmark, chunks of 32 staged observations (two arrays: 26 KB of LDS), a 16-lane group per camera
+// pair, camera_i <= camera_j only, fp64 atomics as in step 1 (so the assembly is not bit-reproducible either).
+// ------------------------------------------------------------------------------------------
+constexpr int SCDH_CHUNK = 32;
+struct ScdObsH {
+  double U[33];       // N_c^T (sigma_c o (e_a (x) X)), a = 0..2: 11 entries each
+  double F[9], G[9];  // F_i and F_i Hll^-1
+  int cam;
+};
+static_assert(2 * SCDH_CHUNK * sizeof(ScdObsH) < 64 * 1024, "sc_dense_offdiag_h: static LDS");
+
+__device__ inline void scdh_stage(const Dp& d, const double* ncw, int slot, const double4& X, const double4& s,
+                                  const double* Hi, const double (&hw)[4], double hbeta, ScdObsH& o) {
+  const int cam = d.cam[slot];
+  const Cam P = load_cam(d.cams_lin4, cam);
+  const double2 uv = d.uv[slot];
+  const double sw = d.robust ? d.sw[slot] : 1.0;
+  const Hom h = hom_project(P, X, uv.x, uv.y);
+  double jl4[8], jl3[6];
+  hom_jl4(P, h, sw, s, jl4);
+  jl3_of_jl4(jl4, hw, hbeta, jl3);
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    o.F[j] = sw * h.D00 * jl3[j];
+    o.F[3 + j] = sw * h.D00 * jl3[3 + j];
+    o.F[6 + j] = sw * (h.D02 * jl3[j] + h.D12 * jl3[3 + j]);
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) o.G[3 * i + j] = o.F[3 * i] * Hi[j] + o.F[3 * i + 1] * Hi[3 + j] + o.F[3 * i + 2] * Hi[6 + j];
+  const double* w = ncw + 13 * (size_t)cam;
+  const double beta = w[12];
+  const double* sg = d.sigma + 12 * (size_t)cam;
+  const double xs[4] = {X.x, X.y, X.z, X.w};
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    double v[4], wv = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      v[k] = sg[4 * a + k] * xs[k];
+      wv += w[4 * a + k] * v[k];
+    }
+#pragma unroll
+    for (int j = 0; j < 11; ++j) {  // (N^T v)_j = v_{j+1} - beta w_{j+1} (w . v)
+      const int i = j + 1;
+      const double e = (i >= 4 * a && i < 4 * a + 4) ? v[i - 4 * a] : 0.0;
+      o.U[11 * a + j] = e - beta * w[i] * wv;
+    }
+  }
+  o.cam = cam;
+}
+
+POVAR_KERNEL __launch_bounds__(256) void sc_dense_offdiag_h(Dp d, const double* ncw, const int* lm_slot0, const int* lm_cnt,
+                                                            double* S, int64_t ld) {
+  __shared__ ScdObsH oi[SCDH_CHUNK], oj[SCDH_CHUNK];
+  const int lm = blockIdx.x;
+  const int s0 = lm_slot0[lm], k = lm_cnt[lm];
+  // (the landmark record povar_prepare_joint(lambda) leaves: X, s, damped tangent Hll^-1 -- as cm_gram_sc<true> reads it)
+  const double4* rec = reinterpret_cast<const double4*>(d.lmrec) + 4 * (size_t)lm;
+  const double4 X = rec[0], s = rec[1], r2 = rec[2], r3 = rec[3];
+  const double Hi[9] = {r2.x, r2.y, r2.z, r2.y, r2.w, r3.x, r2.z, r3.x, r3.y};
+  double hw[4], hbeta;
+  house4(X, hw, hbeta);
+  const int grp = threadIdx.x >> 4, gl = threadIdx.x & 15;
+  for (int ic = 0; ic < k; ic += SCDH_CHUNK) {
+    const int ni = min(SCDH_CHUNK, k - ic);
+    __syncthreads();
+    if ((int)threadIdx.x < ni) scdh_stage(d, ncw, s0 + ic + threadIdx.x, X, s, Hi, hw, hbeta, oi[threadIdx.x]);
+    for (int jc = ic; jc < k; jc += SCDH_CHUNK) {
+      const int nj = min(SCDH_CHUNK, k - jc);
+      __syncthreads();
+      if ((int)threadIdx.x < nj) scdh_stage(d, ncw, s0 + jc + threadIdx.x, X, s, Hi, hw, hbeta, oj[threadIdx.x]);
+      __syncthreads();
+      for (int pp = grp; pp < ni * nj; pp += 16) {
+        const int i = pp / nj, j = pp - i * nj;
+        if (ic == jc && i > j) continue;  // cameras ascend inside a landmark: keep camera_i <= camera_j
+        const ScdObsH& a = oi[i];
+        const ScdObsH& b = oj[j];
+        double T[9];  // F_i Hll^-1 F_j^T
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+#pragma unroll
+          for (int q = 0; q < 3; ++q) T[3 * p + q] = a.G[3 * p] * b.F[3 * q] + a.G[3 * p + 1] * b.F[3 * q + 1] + a.G[3 * p + 2] * b.F[3 * q + 2];
+        double* blk = S + 11 * (int64_t)a.cam * ld + 11 * (int64_t)b.cam;
+        for (int e = gl; e < 121; e += 16) {
+          const int r = e / 11, c = e - 11 * r;
+          const double v0 = b.U[c], v1 = b.U[11 + c], v2 = b.U[22 + c];
+          const double t = a.U[r] * (T[0] * v0 + T[1] * v1 + T[2] * v2) + a.U[11 + r] * (T[3] * v0 + T[4] * v1 + T[5] * v2) +
+                           a.U[22 + r] * (T[6] * v0 + T[7] * v1 + T[8] * v2);
+          atomicAdd(blk + r * ld + c, -t);
+        }
+      }
+    }
+  }
+}
+
+// povar_right_mul_e0_joint: z = sigma (N_c x) of a caller's tangent vector (one wavefront per camera, as pcg_dir) ...
+POVAR_KERNEL __launch_bounds__(K9_CAMS * 64) void sc_emit_z_h(Dp d, const double* ncw, const double* x) {
+  const int lane = threadIdx.x & 63;
+  const int c = blockIdx.x * K9_CAMS + (threadIdx.x >> 6);
+  const bool in = c < d.n_cams;
+  const double v = (in && lane < 11) ? x[11 * (size_t)c + lane] : 0.0;
+  emit_z<true>(d, ncw, c, lane, in, v);
+}
+// ... and out11 = N_c^T y of the dense ambient y (sigma applied) that E0 left
+POVAR_KERNEL __launch_bounds__(256) void sc_project_y_h(Dp d, const double* ncw, double* out11) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= d.n_cams) return;
+  double y[12], o[11];
+#pragma unroll
+  for (int j = 0; j < 12; ++j) y[j] = d.y[12 * (size_t)c + j];
+  nt_apply(ncw + 13 * (size_t)c, ncw[13 * (size_t)c + 12], y, o);
+#pragma unroll
+  for (int j = 0; j < 11; ++j) out11[11 * (size_t)c + j] = o[j];
 }
 
 }  // namespace povar

@@ -53,19 +53,28 @@ int e0_dense(povar_ctx* c) {
 }
 
 // solve_direct_pOSE (linearization_sc.hpp:236-245): accum = LLT(S).solve(-b) with the dense S,
-// factored by the kernels of povar_kernels_chol.hpp
-int run_cholesky(povar_ctx* c, int32_t* num_iterations, int32_t* termination) {
-  const int n = 12 * c->n_cams;
+// factored by the kernels of povar_kernels_chol.hpp.  dim = 12: step 1's system; dim = 11: the joint tangent system of
+// step 2 (RICHOLESKY; not in the reference).  A context that solves both keeps one dense buffer, sized for the larger.
+int run_cholesky(povar_ctx* c, int dim, int32_t* num_iterations, int32_t* termination) {
+  const int n = dim * c->n_cams;
   const int N = (n + CH_NB - 1) / CH_NB * CH_NB;
   const int64_t ld = (int64_t)N + CH_T;
   const size_t count = (size_t)(N + CH_NB) * (size_t)ld;  // slack rows / columns for the 128 x 128 update tiles
-  if (!c->sc_dense.p) {
+  if (c->sc_dense.n < count) {
+    if (c->sc_dense.p) {
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      c->bytes -= c->sc_dense.n * sizeof(double);
+      c->sc_dense.release();
+      c->sc_dense.n = 0;
+    }
     size_t free_b = 0, total_b = 0;
     HIP_TRY(hipMemGetInfo(&free_b, &total_b));
     if (count * sizeof(double) + (1u << 30) > free_b)
-      return fail(-1, "CHOLESKY: not enough device memory for the dense reduced camera matrix (" +
-                          std::to_string(count * sizeof(double) >> 20) + " MiB)");
+      return fail(-1, std::string(dim == 11 ? "RICHOLESKY" : "CHOLESKY") + ": not enough device memory for the dense reduced camera matrix of " +
+                          std::to_string(n) + " rows (" + std::to_string(count * sizeof(double) >> 20) + " MiB)");
     HIP_TRY(c->sc_dense.alloc(count, &c->bytes));
+  }
+  if (!c->sc_info.p) {
     HIP_TRY(c->sc_info.alloc(1, &c->bytes));
     std::vector<int> s0(c->n_lms), cnt(c->n_lms);
     for (int l = 0; l < c->n_lms; ++l) {
@@ -80,12 +89,20 @@ int run_cholesky(povar_ctx* c, int32_t* num_iterations, int32_t* termination) {
   HIP_TRY(hipMemsetAsync(c->sc_info.p, 0, sizeof(int), c->stream));
   // replicated parts (B_c, -b, padding identity) once over the ranks; the landmark part is sharded
   if (c->rank == 0) {
-    hipLaunchKernelGGL(sc_dense_diag, dim3(c->n_cams), dim3(256), 0, c->stream, c->d, (const double*)c->sc.bmat, M, ld, N);
+    if (dim == 11)
+      hipLaunchKernelGGL(sc_dense_diag<11>, dim3(c->n_cams), dim3(256), 0, c->stream, c->d, (const double*)c->sc.bmat, M, ld, N);
+    else
+      hipLaunchKernelGGL(sc_dense_diag<12>, dim3(c->n_cams), dim3(256), 0, c->stream, c->d, (const double*)c->sc.bmat, M, ld, N);
     if (N > n) hipLaunchKernelGGL(chol_pad, dim3(1), dim3(64), 0, c->stream, M, ld, n, N);
   }
-  if (c->n_lms > 0)
-    hipLaunchKernelGGL(sc_dense_offdiag, dim3(c->n_lms), dim3(256), 0, c->stream, c->d, (const int*)c->sc_lm_slot0.p,
-                       (const int*)c->sc_lm_cnt.p, M, ld);
+  if (c->n_lms > 0) {
+    if (dim == 11)
+      hipLaunchKernelGGL(sc_dense_offdiag_h, dim3(c->n_lms), dim3(256), 0, c->stream, c->d, c->sc.ncw, (const int*)c->sc_lm_slot0.p,
+                         (const int*)c->sc_lm_cnt.p, M, ld);
+    else
+      hipLaunchKernelGGL(sc_dense_offdiag, dim3(c->n_lms), dim3(256), 0, c->stream, c->d, (const int*)c->sc_lm_slot0.p,
+                         (const int*)c->sc_lm_cnt.p, M, ld);
+  }
   HIP_TRY(hipGetLastError());
   if (int rc = allreduce(c, M, count)) return rc;
   for (int K0 = 0; K0 < N; K0 += CH_OB) {
@@ -102,7 +119,14 @@ int run_cholesky(povar_ctx* c, int32_t* num_iterations, int32_t* termination) {
       hipLaunchKernelGGL(chol_syrk_outer, dim3((unsigned)((N - R0) / CH_T + 1), (unsigned)((N - R0 + CH_T - 1) / CH_T)),
                          dim3(256), 0, c->stream, M, ld, K0, kdepth);
   }
-  if (!c->sc_xpad.p) HIP_TRY(c->sc_xpad.alloc((size_t)N, &c->bytes));
+  if (c->sc_xpad.n < (size_t)N) {
+    if (c->sc_xpad.p) {
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      c->bytes -= c->sc_xpad.n * sizeof(double);
+      c->sc_xpad.release();
+    }
+    HIP_TRY(c->sc_xpad.alloc((size_t)N, &c->bytes));
+  }
   double* x = c->sc_xpad.p;  // N entries, the first n are the solution
   hipLaunchKernelGGL(chol_copy_rhs, dim3(grid_for(N, 256)), dim3(256), 0, c->stream, (const double*)M, ld, N, x);
   for (int k0 = N - CH_NB; k0 >= 0; k0 -= CH_NB) {
@@ -186,7 +210,7 @@ int povar_solve_pose_sc(povar_ctx* c, double lambda, int32_t method, int32_t min
   {
     TimeScope ts(c, 2);
     if (method == POVAR_SC_CHOLESKY) {
-      if (int rc = run_cholesky(c, num_iterations, termination)) return rc;
+      if (int rc = run_cholesky(c, 12, num_iterations, termination)) return rc;
     } else {
       if (int rc = run_pcg<12, false>(c, min_iterations, max_iterations, eta, num_iterations, termination)) return rc;
     }
@@ -197,9 +221,10 @@ int povar_solve_pose_sc(povar_ctx* c, double lambda, int32_t method, int32_t min
   return 0;
 }
 
-int povar_solve_joint_sc(povar_ctx* c, double lambda, int32_t min_iterations, int32_t max_iterations, double eta,
-                         double* inc, int32_t* num_iterations, int32_t* termination) {
-  // LinearizorSC::solve_joint (linearizor_sc.cpp:224-303)
+int povar_solve_joint_sc_method(povar_ctx* c, double lambda, int32_t method, int32_t min_iterations, int32_t max_iterations,
+                                double eta, double* inc, int32_t* num_iterations, int32_t* termination) {
+  if (method != POVAR_SC_PCG && method != POVAR_SC_CHOLESKY) return fail(-1, "povar_solve_joint_sc_method: unknown method");
+  // LinearizorSC::solve_joint (linearizor_sc.cpp:224-303); landmark damping is part of the prepared system
   if (int rc = povar_prepare_joint(c, lambda)) return rc;
   // cm_gram_sc reads the per-slot sqrt(w) and the landmark-order records: after a lane-per-landmark linearisation /
   // prepare they are rebuilt here (missing until round 3: RIPCG with a robust norm took stale weights on every problem
@@ -210,12 +235,42 @@ int povar_solve_joint_sc(povar_ctx* c, double lambda, int32_t min_iterations, in
   if (int rc = build_schur_jacobi<true>(c, lambda)) return rc;
   {
     TimeScope ts(c, 2);
-    if (int rc = run_pcg<11, true>(c, min_iterations, max_iterations, eta, num_iterations, termination)) return rc;
+    if (method == POVAR_SC_CHOLESKY) {
+      if (int rc = run_cholesky(c, 11, num_iterations, termination)) return rc;
+    } else {
+      if (int rc = run_pcg<11, true>(c, min_iterations, max_iterations, eta, num_iterations, termination)) return rc;
+    }
   }
   if (int rc = povar_get_increment(c, inc)) return rc;
   for (size_t i = 0; i < 11 * (size_t)c->n_cams; ++i)
     if (!std::isfinite(inc[i])) return POVAR_NUMERIC_FAILURE;
   return 0;
+}
+
+int povar_solve_joint_sc(povar_ctx* c, double lambda, int32_t min_iterations, int32_t max_iterations, double eta,
+                         double* inc, int32_t* num_iterations, int32_t* termination) {
+  return povar_solve_joint_sc_method(c, lambda, POVAR_SC_PCG, min_iterations, max_iterations, eta, inc, num_iterations, termination);
+}
+
+int povar_right_mul_e0_joint(povar_ctx* c, const double* x, double* y) {
+  if (int rc = check_ctx(c)) return rc;
+  if (!x || !y) return fail(-1, "null argument");
+  if (!c->joint || c->prep_id == 0) return fail(-1, "povar_right_mul_e0_joint: the system prepared last is not the joint one (povar_prepare_joint)");
+  if (int rc = res_verify(c)) return rc;
+  const size_t n = 11 * (size_t)c->n_cams;
+  // tmp11 = x, z = sigma (N_c x), dense y = sigma E0 z, out = N_c^T y: the operator RIPCG applies (schur_times) without B
+  if (int rc = write_cam_vector(c, c->tmp.p, x, n)) return rc;
+  HIP_TRY(hipMemsetAsync(c->flags.p + 1, 0, sizeof(int) * 3, c->stream));
+  hipLaunchKernelGGL(sc_emit_z_h, dim3(c->n_cam_blocks), dim3(K9_CAMS * 64), 0, c->stream, c->d, (const double*)c->ncw.p,
+                     (const double*)c->tmp.p);
+  const TermPlan p = term_plan(c, 2, TermUse::right_mul);
+  if (int rc = launch_e0(c, p)) return rc;
+  if (p.cam == CamStep::scatter)
+    hipLaunchKernelGGL(cam_sum_items, dim3(grid_for(c->n_cams, 4)), dim3(256), 0, c->stream, c->d, c->d.y, 1);
+  hipLaunchKernelGGL(sc_project_y_h, dim3(grid_for(c->n_cams, 256)), dim3(256), 0, c->stream, c->d, (const double*)c->ncw.p, c->tmp.p);
+  HIP_TRY(hipMemsetAsync(c->y.p, 0, sizeof(double) * 12 * (size_t)c->n_cams, c->stream));
+  HIP_TRY(hipGetLastError());
+  return read_cam_vector(c, y, c->tmp.p, n);
 }
 
 }  // extern "C"
