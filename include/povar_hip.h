@@ -343,7 +343,7 @@ typedef struct {
   int64_t ckh_chunks, ckh_cold_chunks;
   int32_t e0_auto_h;    /* as e0_auto: 0 forced, 1 to be timed at the next step-2 power series, 2 timed */
   float tune_lpl_h_us, tune_ck_h_us;
-  /* resident power series (series_res, povar_kernels_res.hpp): the whole loop of solve_pOSE
+  /* resident power series (series_res, povar_kernels_res.hpp: res_series with ResPose): the whole loop of solve_pOSE
    * (sc/linearization_power_varproj.hpp:191-237) in one launch, observation rows in registers, landmarks and B^-1 in LDS */
   int32_t res_ready;    /* 1: the layout exists (the context's observations fit the lanes of one workgroup per CU) */
   int32_t res_active;   /* 1: the next step-1 power series of this context runs as the resident kernel */
@@ -368,8 +368,8 @@ typedef struct {
                            slots of its most observed cameras, the other cameras' chunks write records of their own) */
   int32_t ckh_accumulators;      /* accumulator slots per workgroup at most */
   int64_t ckh_capped_obs;        /* observations of cameras that have a slot in the lane-per-landmark layout but none here */
-  /* resident power series of step 2 (series_res_h, povar_kernels_res_joint.hpp): the loop of solve_joint (:240-287) in one
-   * launch.  The res_* fields above stay step 1's.  (fp32_terms stays the struct's last
+  /* resident power series of step 2 (series_res_h, povar_kernels_res.hpp: one body with series_res): the loop of
+   * solve_joint (:240-287) in one launch.  The res_* fields above stay step 1's.  (fp32_terms stays the struct's last
    * field; these stand in front of it.) */
   int32_t res_ready_h;  /* 1: step 2 has an instance (its own, or step 1's: res_shared_h) and an instantiation for its shape */
   int32_t res_active_h; /* 1: the next povar_solve_joint of this context runs its series as the resident kernel */

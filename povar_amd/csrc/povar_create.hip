@@ -1092,7 +1092,7 @@ int povar_get_layout_info(povar_ctx* c, povar_layout_info* out) {
   out->tune_ck_h_us = c->ckh_tune_us[1];
   out->res_ready = c->res.ready ? 1 : 0;
   out->res_active = !c->joint && res_active(c, false) ? 1 : 0;  // (the step-1 answer: 0 while the joint system is the prepared one)
-  out->res_auto = c->res_mode < 0 ? (c->res_tuned ? 2 : 1) : 0;
+  out->res_auto = c->res_mode < 0 ? (c->res_tune[0].tuned ? 2 : 1) : 0;
   out->res_wgs = c->res.W;
   out->res_waves = c->res.NW;
   out->res_rows = c->res.H;
@@ -1105,8 +1105,8 @@ int povar_get_layout_info(povar_ctx* c, povar_layout_info* out) {
   out->res_order = c->res.order;
   out->res_lds_bytes = (int32_t)c->res.lds_bytes;
   out->res_build_ms = c->res.build_ms;
-  out->tune_terms_us = c->res_tune_us[0];
-  out->tune_res_us = c->res_tune_us[1];
+  out->tune_terms_us = c->res_tune[0].us[0];
+  out->tune_res_us = c->res_tune[0].us[1];
   out->res_failed = c->res_failed ? 1 : 0;
   out->ck_packed = c->ck.ready && c->ck.packed ? 1 : 0;
   out->ck_cold_q = c->ck.ready && c->ck.cold_q ? 1 : 0;
@@ -1119,7 +1119,7 @@ int povar_get_layout_info(povar_ctx* c, povar_layout_info* out) {
     const povar_ctx::ResDev& D = res_dev(c, true);
     out->res_ready_h = ready ? 1 : 0;
     out->res_active_h = res_active(c, true) ? 1 : 0;
-    out->res_auto_h = c->res_mode < 0 ? (c->res_tuned_h ? 2 : 1) : 0;
+    out->res_auto_h = c->res_mode < 0 ? (c->res_tune[1].tuned ? 2 : 1) : 0;
     out->res_shared_h = ready && c->res_h_shared ? 1 : 0;
     out->res_wgs_h = ready ? D.W : 0;
     out->res_waves_h = ready ? D.NW : 0;
@@ -1127,8 +1127,8 @@ int povar_get_layout_info(povar_ctx* c, povar_layout_info* out) {
     out->res_rounds_h = ready ? D.R : 0;
     out->res_lds_bytes_h = ready ? (int32_t)c->res_h_lds : 0;
     out->res_build_h_ms = c->res_h_build_ms;
-    out->tune_terms_h_us = c->res_tune_h_us[0];
-    out->tune_res_h_us = c->res_tune_h_us[1];
+    out->tune_terms_h_us = c->res_tune[1].us[0];
+    out->tune_res_h_us = c->res_tune[1].us[1];
   }
   return 0;
 }

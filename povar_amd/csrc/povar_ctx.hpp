@@ -39,7 +39,6 @@
 #include "povar_kernels_ck_f32.hpp"
 #include "res_layout.hpp"
 #include "povar_kernels_res.hpp"
-#include "povar_kernels_res_joint.hpp"
 
 using namespace povar;
 
@@ -210,10 +209,11 @@ struct povar_ctx {
   double res_h_build_ms = 0;
   int res_mode = -1;             // -1: the library times the resident series against the per-term kernels once per context
                                  // (res_autotune); 0: per-term kernels; 1: resident series whenever the context allows
-  bool res_tuned = false, res_choice = false, res_failed = false;
-  float res_tune_us[2] = {0, 0}; // per term: per-term kernels (hipGraph), resident series
-  bool res_tuned_h = false, res_choice_h = false;  // the same for step 2, timed on the prepared joint system
-  float res_tune_h_us[2] = {0, 0};
+  struct ResTune {               // res_autotune's answer for one step, timed on the system prepared for it
+    bool tuned = false, choice = false;
+    float us[2] = {0, 0};        // per term: per-term kernels (hipGraph), resident series
+  } res_tune[2];                 // [0] step 1, [1] step 2 (the joint system)
+  bool res_failed = false;
   bool res_check = false;        // a resident series is in flight whose give-up bit (flags[0] & 4) has not been looked at
   int res_last_m = 0;
   double res_last_tol[2] = {0, 0};

@@ -596,7 +596,7 @@ __device__ inline void nt_apply(const double* w, double beta, const double (&y)[
 
 // One row of x = B_c^-1 y (11 x 11, row stride 11 in the camera's block of Dp::binv; right_mul_b_inv_joint :342-360): the
 // ONE body of the series start x_0 = B^-1 (-b) -- cam_binv_axpy_h and the prologue of series_res_h
-// (povar_kernels_res_joint.hpp) leave the same bits --, one fused multiply-add per entry in index order, spelled out so
+// (povar_kernels_res.hpp) leave the same bits --, one fused multiply-add per entry in index order, spelled out so
 // that no call site is contracted differently.  y: anything indexable (registers, LDS).
 template <class Y>
 __device__ inline double binv_row11(const double* Bi, const Y& y) {

@@ -1,6 +1,11 @@
 // povar_kernels_res.hpp -- gfx950 device code of the RESIDENT power series: the whole loop of solve_pOSE
 // (linearization_power_varproj.hpp:191-237: x_0 = B^-1 (-b); x_i = B^-1 E0 x_{i-1}; sum, early exit) in ONE launch, for
-// contexts whose term-invariant operands fit on the chip (res_layout.hpp).
+// contexts whose term-invariant operands fit on the chip (res_layout.hpp): series_res; and series_res_h, the same for the
+// loop of solve_joint (:240-287: x_i = B^-1 N_c^T sigma E0 sigma N_c x_{i-1}; step 2, RIPOBA).  ONE body, two steps:
+// res_series holds the structure -- phase order, barriers B1-B7, hand-overs, bounded spins, give-up bit, norm sweep, the reuse
+// of the region --, and ResPose / ResJoint say what a landmark slot, a lane and an owned camera hold and compute; the two
+// kernels are wrappers.  What follows describes the body in step 1's terms; ResJoint's comment says what step 2 puts in
+// their place.
 //
 // The per-term kernels re-read per term what does not change between the terms of a solve: rows, landmark records, tile
 // metadata, B^-1 -- and pay a launch ramp, a flush and two kernel boundaries each time (29 us per term on a venice-1778
@@ -44,6 +49,7 @@
 #pragma once
 
 #include "povar_kernels_ck.hpp"
+#include "povar_kernels_ck_joint.hpp"
 #include "res_layout.hpp"
 
 namespace povar {
@@ -147,48 +153,255 @@ __device__ inline bool res_gather(__amdgpu_buffer_rsrc_t r, int n, RowOf row_of,
   return fine;
 }
 
-// the per-lane state of one chunk
-template <int H>
+// ---- the two steps.  ONE body (res_series) holds the protocol; a step (ResPose, ResJoint) says what a landmark slot, a lane's
+// chunk and an owned camera hold, and how an observation, a landmark and an owner's term are computed.  The body and the
+// steps' members are __forceinline__ and the body takes Dp and ResP by value, as a kernel does: the compiler then sees what
+// it saw when each kernel was written out (left to its own inlining order, series_res<8, 4, 2, 2, true> spills one more register
+// and the early-exit test is compared twice; profiles/res_unify_isa.txt).  For the same reason the owner's step is ONE member,
+// Step::solve, with x, the sum and the z entry in the one exec region each step had: with step 1's z entry in a region of
+// its own behind the stores, its load of sigma was one more LDS round trip per term (profiles/res_unify_term_times.txt).
+
+// the owner's arrays in LDS ([nO] records each), carved from a step's sizes: BINV doubles of B^-1, 12 of sigma, NCW of the
+// reflector, NX each of the running sum and the last term, 12 of the E0 row of the term (sigma * sum of the camera's records),
+// 2 squared norms (last term / sum) and the partial sums of the camera's records (five groups of twelve lanes)
+template <class Step>
+struct ResOwn {
+  static constexpr int DOUBLES = Step::BINV + 12 + Step::NCW + 2 * Step::NX + 12 + 2 + 60;
+  double *binv, *sig, *ncw, *acc, *tmp, *y, *nrm, *ps, *end;
+  __device__ __forceinline__ ResOwn(double* p, int nO)
+      : binv(p), sig(binv + Step::BINV * nO), ncw(sig + 12 * nO), acc(ncw + Step::NCW * nO), tmp(acc + Step::NX * nO),
+        y(tmp + Step::NX * nO), nrm(y + 12 * nO), ps(nrm + 2 * nO), end(ps + 60 * nO) {}
+};
+
+// the per-lane state of one chunk: what the step keeps of the camera and the rows (Step::Lane), landmark slot word and
+// robust weight of each row, camera slot, run of lanes, rows / segmented sum / scan steps of the wavefront
+template <class Step, int H>
 struct ResChunk {
-  double2 uv[H];
+  typename Step::template Lane<H> s;
   int ls[H];
   double rw[H];
-  double P3[9];
   int ci, seg, hrows, dup, steps;
 };
 
+// step 1 (solve_pOSE).  Landmarks: h~ and u / g [nL][3], slot word = 3 x slot, G = diag(s) Hll^-1 diag(s) in the registers
+// of the slot's lane.  Lane: image points and P3 = P_c[:, :3].  Owner: B^-1 12 x 12, x = B^-1 y, z = sigma x
+struct ResPose {
+  static constexpr int NX = 12;                                    // unknowns of a camera
+  static constexpr int LM_BYTES = 48, NCO = 3, LMREC = 9, NREG = 6;  // LDS per slot; coordinates, rows of V2::lmrec, registers of a slot
+  static constexpr int BINV = 144, NCW = 0;
+  typedef ResOwn<ResPose> Own;
+  template <int H> struct Lane { double2 uv[H]; double P3[9]; };
+  struct Z { double v[12]; };
+  __device__ static __forceinline__ int lm_count(int n, int) { return n; }
+  __device__ static __forceinline__ int lm_cap(int nL, int) { return nL; }
+  template <int STRIDE> __device__ static __forceinline__ int at(int slot, int e) { return 3 * slot + e; }
+  __device__ static __forceinline__ int slot_word(int l3, int) { return l3; }
+  template <int H> __device__ static __forceinline__ void load_row(const ResP& k, Lane<H>& L, int j, size_t row) { L.uv[j] = k.uv[row]; }
+  template <int H> __device__ static __forceinline__ void load_p(const Dp& d, Lane<H>& L, int& ci, int, const int* cam_id) {
+#pragma unroll
+    for (int e = 0; e < 9; ++e) L.P3[e] = 0;
+    if (ci >= 0) {
+      const Cam P = load_cam(d.cams_lin4, cam_id[ci]);
+      L.P3[0] = P.r0.x; L.P3[1] = P.r0.y; L.P3[2] = P.r0.z;
+      L.P3[3] = P.r1.x; L.P3[4] = P.r1.y; L.P3[5] = P.r1.z;
+      L.P3[6] = P.r2.x; L.P3[7] = P.r2.y; L.P3[8] = P.r2.z;
+    }
+  }
+  __device__ static __forceinline__ void load_z(const double* zp, Z& zz) {
+#pragma unroll
+    for (int e = 0; e < 12; ++e) zz.v[e] = zp[e];
+  }
+  // u_l += P3^T (w C (Z h~_l))
+  template <bool ROBUST, int STRIDE, int H>
+  __device__ static __forceinline__ void obs_forward(const Dp& d, const Lane<H>& L, int j, double rw, int s, const Z& zz, const double* lh, double* lu) {
+    ck_obs_forward(d, L.uv[j], rw, zz.v, L.P3, lh[s], lh[s + 1], lh[s + 2], lu, 0, (uint32_t)s);
+  }
+  // g = G u
+  template <int STRIDE> __device__ static __forceinline__ void landmark_step(double*, double* lu, int s, const double (&G)[NREG]) {
+    const double u0 = lu[3 * s], u1 = lu[3 * s + 1], u2 = lu[3 * s + 2];
+    lu[3 * s] = G[0] * u0 + G[1] * u1 + G[2] * u2;
+    lu[3 * s + 1] = G[1] * u0 + G[3] * u1 + G[4] * u2;
+    lu[3 * s + 2] = G[2] * u0 + G[4] * u1 + G[5] * u2;
+  }
+  // y_c += h~_l (x) (w C (P3 g_l))
+  template <bool ROBUST, int STRIDE, int H>
+  __device__ static __forceinline__ void obs_backward(const Dp& d, const Lane<H>& L, int j, double rw, int s, const double* lh, const double* lu, double (&y)[12]) {
+    const double gg[3] = {lu[s], lu[s + 1], lu[s + 2]};
+    ck_obs_backward(d, L.uv[j], rw, L.P3, lh[s], lh[s + 1], lh[s + 2], gg, y);
+  }
+  // B^-1, sigma and (where the term will be) -b of camera c, by one wavefront
+  __device__ static __forceinline__ void load_owner(const Dp& d, const double*, const Own& A, int o, int c, int lane) {
+    for (int e = lane; e < 144; e += 64) A.binv[144 * o + e] = d.binv[144 * (size_t)c + e];
+    if (lane < 12) A.sig[12 * o + lane] = d.sigma[12 * (size_t)c + lane];
+    if (lane >= 32 && lane < 44) A.tmp[12 * o + lane - 32] = -d.b[12 * (size_t)c + lane - 32];
+  }
+  __device__ static __forceinline__ double binv_row(const Own& A, int o, int lane, const double* v) {
+    const double* Bi = A.binv + 144 * o + 12 * lane;
+    double s = 0;
+#pragma unroll
+    for (int j = 0; j < 12; ++j) s += Bi[j] * v[j];
+    return s;
+  }
+  // The owner's step, called by every lane of the wavefront.  s = entry `lane` (< NX; 0 in the other lanes) of x_0 = B^-1 (-b)
+  // (FIRST: -b is where the term will be, and stays there) or of x_i = B^-1 y, a = that entry of the sum with it; term and
+  // sum stored; entry `lane` (< 12) of z = sigma x handed to put
+  template <bool FIRST, class Put>
+  __device__ static __forceinline__ void solve(const Own& A, int o, int lane, double& s, double& a, Put put) {
+    s = 0; a = 0;
+    if (lane < 12) {
+      s = binv_row(A, o, lane, (FIRST ? A.tmp : A.y) + 12 * o);
+      a = FIRST ? s : A.acc[12 * o + lane] + s;
+      if (!FIRST) A.tmp[12 * o + lane] = s;
+      A.acc[12 * o + lane] = a;
+      put(s * A.sig[12 * o + lane]);
+    }
+  }
+  // sum, last term and its z = sigma x, where the per-term kernels leave them (povar_power_series_step goes on from there)
+  template <int NW> __device__ static __forceinline__ void store(const Dp& d, const Own& A, const int* own_cam, int nO, int t, int, int) {
+    for (int e = t; e < nO * 12; e += NW * 64) {
+      const int c = own_cam[e / 12];
+      d.accum[12 * (size_t)c + e % 12] = A.acc[e];
+      d.tmp[12 * (size_t)c + e % 12] = A.tmp[e];
+      store_z(d, c, e % 12, A.tmp[e] * A.sig[e]);
+    }
+  }
+};
+
+// Entry `lane` (< 12) of z = sigma (.) (N_c x) with x's entry `lane` in s (lanes 0..10; 0 in the others): p = [0; x] -
+// beta w (w[1:] . x), the products summed over lanes 0..15 as in cam_binv_axpy_h.  Every lane of the wavefront calls it.
+__device__ inline double resh_z_entry(int lane, double s, const double* w13, const double* sig) {
+  double wt = lane < 11 ? w13[lane + 1] * s : 0.0;
+#pragma unroll
+  for (int m = 8; m >= 1; m >>= 1) wt += shfl_xor_d(wt, m);
+  const double prev = shfl_up_d(s, 1);
+  const int l = lane < 12 ? lane : 0;
+  const double p = (lane == 0 ? 0.0 : prev) - w13[12] * w13[l] * wt;
+  return p * sig[l];
+}
+
+// step 2 (solve_joint), with the operator of e0_ck_h (povar_kernels_ck_joint.hpp) and the owner step of cam_cold_sum_binv_h
+// (povar_kernels_joint.hpp).  Landmarks: X and U4 / G4 [4][STRIDE], component-major with the compile-time stride STRIDE = LS T
+// (the instantiation's slot capacity), so that ckh_obs_forward, ckh_obs_backward and ckh_landmark_step run unchanged and the
+// "ckh" error model of tests/rounding_bounds.py is this kernel's too; the slot's lane keeps s (4) and the upper triangle of
+// Hll^-1 (6): entries 4..13 of the 14-double record of V2::lmrec, which both preparation paths write at every prepare.  Lane: the
+// camera's whole P_c (3 x 4, from cams_lin4) and no image points: the step-2 operator does not read them.  Owner: z_c is the
+// AMBIENT 12-vector sigma (N_c x_c); B^-1 11 x 11 (row stride 11), the reflector (w[12], beta) of N_c, sum and term of 11;
+// y11 = N_c^T y (nt_apply), x = B^-1 y11 (binv_row11: the bits of cam_binv_axpy_h), z = sigma (N_c x).  The clamps (landmark
+// count, slot word, camera slot) are this step's: it may run on an instance cut for step 1 (res_shared_fits)
+struct ResJoint {
+  static constexpr int NX = 11;
+  static constexpr int LM_BYTES = 64, NCO = 4, LMREC = CKH_REC, NREG = 10;
+  static constexpr int BINV = 121, NCW = 13;
+  typedef ResOwn<ResJoint> Own;
+  template <int H> struct Lane { Cam P; };
+  struct Z { double4 v[3]; };
+  __device__ static __forceinline__ int lm_count(int n, int cap) { return min(n, cap); }
+  __device__ static __forceinline__ int lm_cap(int, int cap) { return cap; }
+  template <int STRIDE> __device__ static __forceinline__ int at(int slot, int e) { return e * STRIDE + slot; }
+  // (the layout's rows carry 3 x slot: they are step 1's where the two steps share them)
+  __device__ static __forceinline__ int slot_word(int l3, int nL) { return l3 < 0 || l3 >= 3 * nL ? -1 : l3 / 3; }
+  template <int H> __device__ static __forceinline__ void load_row(const ResP&, Lane<H>&, int, size_t) {}
+  template <int H> __device__ static __forceinline__ void load_p(const Dp& d, Lane<H>& L, int& ci, int nC, const int* cam_id) {
+    L.P.r0 = L.P.r1 = L.P.r2 = make_double4(0, 0, 0, 0);
+    if (ci >= nC) ci = -1;
+    if (ci >= 0) L.P = load_cam(d.cams_lin4, cam_id[ci]);
+  }
+  __device__ static __forceinline__ void load_z(const double* zp, Z& zz) {
+    zz.v[0] = make_double4(zp[0], zp[1], zp[2], zp[3]);
+    zz.v[1] = make_double4(zp[4], zp[5], zp[6], zp[7]);
+    zz.v[2] = make_double4(zp[8], zp[9], zp[10], zp[11]);
+  }
+  // U4_l += J4^T t, t = sw D (Z X) (four LDS adds per observation)
+  template <bool ROBUST, int STRIDE, int H>
+  __device__ static __forceinline__ void obs_forward(const Dp&, const Lane<H>& L, int, double rw, int s, const Z& zz, const double* lx, double* lu) {
+    ckh_obs_forward<ROBUST, STRIDE>(L.P, zz.v, rw, lx, lu, (uint32_t)s);
+  }
+  // U4 -> G4
+  template <int STRIDE> __device__ static __forceinline__ void landmark_step(double* lx, double* lu, int s, const double (&rec)[NREG]) {
+    ckh_landmark_step<STRIDE>(lx, lu, s, rec);
+  }
+  // y_c += X_l (x) q
+  template <bool ROBUST, int STRIDE, int H>
+  __device__ static __forceinline__ void obs_backward(const Dp&, const Lane<H>& L, int, double rw, int s, const double* lx, const double* lu, double (&y)[12]) {
+    ckh_obs_backward<ROBUST, STRIDE>(L.P, rw, lx, lu, (uint32_t)s, y);
+  }
+  __device__ static __forceinline__ void load_owner(const Dp& d, const double* ncw, const Own& A, int o, int c, int lane) {
+    for (int e = lane; e < 121; e += 64) A.binv[121 * o + e] = d.binv[144 * (size_t)c + e];
+    if (lane < 12) A.sig[12 * o + lane] = d.sigma[12 * (size_t)c + lane];
+    if (lane >= 16 && lane < 29) A.ncw[13 * o + lane - 16] = ncw[13 * (size_t)c + lane - 16];
+    if (lane >= 32 && lane < 43) A.tmp[11 * o + lane - 32] = -d.b[11 * (size_t)c + lane - 32];
+  }
+  // x_0 = B^-1 (-b) (the bits of cam_binv_axpy_h, mode 0) or x_i = B^-1 N_c^T y; z = sigma (N_c x)
+  template <bool FIRST, class Put>
+  __device__ static __forceinline__ void solve(const Own& A, int o, int lane, double& s, double& a, Put put) {
+    s = 0; a = 0;
+    if (lane < 11) {
+      if (FIRST) {
+        s = binv_row11(A.binv + 121 * o + 11 * lane, A.tmp + 11 * o);
+      } else {
+        double y[12], y11[11];
+#pragma unroll
+        for (int j = 0; j < 12; ++j) y[j] = A.y[12 * o + j];
+        nt_apply(A.ncw + 13 * o, A.ncw[13 * o + 12], y, y11);
+        s = binv_row11(A.binv + 121 * o + 11 * lane, y11);
+      }
+      a = FIRST ? s : A.acc[11 * o + lane] + s;
+      if (!FIRST) A.tmp[11 * o + lane] = s;
+      A.acc[11 * o + lane] = a;
+    }
+    const double zv = resh_z_entry(lane, s, A.ncw + 13 * o, A.sig + 12 * o);
+    if (lane < 12) put(zv);
+  }
+  // sum, last term and its z = sigma N_c x (povar_power_series_step, povar_get_term and povar_apply_joint go on from there)
+  template <int NW> __device__ static __forceinline__ void store(const Dp& d, const Own& A, const int* own_cam, int nO, int, int wave, int lane) {
+    for (int o = wave; o < nO; o += NW) {
+      const int c = own_cam[o];
+      const double s = lane < 11 ? A.tmp[11 * o + lane] : 0.0;
+      const double zv = resh_z_entry(lane, s, A.ncw + 13 * o, A.sig + 12 * o);
+      if (lane < 11) {
+        d.accum[11 * (size_t)c + lane] = A.acc[11 * o + lane];
+        d.tmp[11 * (size_t)c + lane] = s;
+      }
+      if (lane < 12) store_z(d, c, lane, zv);
+    }
+  }
+};
+
+// the steps' sizes ARE the layout's: the host decides with these whether a workgroup fits the LDS (res_lds_bytes)
+static_assert(ResPose::LM_BYTES == RES_LM_BYTES && ResPose::LM_BYTES == 2 * 8 * ResPose::NCO, "step 1: landmark bytes");
+static_assert(ResJoint::LM_BYTES == RES_LM_BYTES_H && ResJoint::LM_BYTES == 2 * 8 * ResJoint::NCO, "step 2: landmark bytes");
+static_assert(ResOwn<ResPose>::DOUBLES == RES_OWN_DOUBLES, "step 1: doubles per owned camera");
+static_assert(ResOwn<ResJoint>::DOUBLES == RES_OWN_DOUBLES_H, "step 2: doubles per owned camera");
+
 // NW wavefronts per workgroup, chunks of H rows, RR chunks per lane, LS landmark slots per lane
-template <int NW, int H, int RR, int LS, bool ROBUST>
-__global__ __launch_bounds__(NW * 64) void series_res(Dp d, ResP k) {
+template <class Step, int NW, int H, int RR, int LS, bool ROBUST>
+__device__ __forceinline__ void res_series(Dp d, ResP k, const double* ncw) {
   constexpr int T = NW * 64;
+  constexpr int STRIDE = LS * T;
   constexpr int GB = NW >= 16 ? 4 : 8;
+  constexpr int NX = Step::NX, NCO = Step::NCO;
   extern __shared__ double res_lds[];
   const int g = blockIdx.x, t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const ResBufs B = res_bufs(k);
   const unsigned tag0 = (*k.launch) << 8;  // (the counter is bumped by a kernel behind this one: stream order)
-  const int L0 = k.lm_off[g], nL = k.lm_off[g + 1] - L0;
+  const int L0 = k.lm_off[g], nL = Step::lm_count(k.lm_off[g + 1] - L0, STRIDE);
   const int C0 = k.cam_off[g], nC = k.cam_off[g + 1] - C0;
   const int O0 = k.own_off[g], nO = k.own_off[g + 1] - O0;
   const int Q0 = k.oq_off[g], nQ = k.oq_off[g + 1] - Q0;
+  // LDS (res_lds_bytes): control words, the landmarks, the region, the owner's arrays, three index tables
   int* ctl = reinterpret_cast<int*>(res_lds);  // [0] a wait gave up, [1] series converged, [2] iterations, [4..5] |x_0|
-  double* lh = res_lds + 8;             // [nL][3] landmark coordinates
-  double* lu = lh + 3 * nL;             // [nL][3] u = Jl^T Jp x, then g = G u
-  double* reg = lu + 3 * nL;            // the region: z of the cameras [nC][13] -> accumulators [nC][13] -> owner's records [nQ][12]
-  double* obinv = reg + res_region_doubles(nC, nQ);  // [nO][144] B^-1 of the owned cameras
-  double* osig = obinv + 144 * nO;      // [nO][12] sigma
-  double* oacc = osig + 12 * nO;        // [nO][12] running sum
-  double* otmp = oacc + 12 * nO;        // [nO][12] last term
-  double* oy = otmp + 12 * nO;          // [nO][12] E0 row of the term: sigma * sum of the camera's records
-  double* onrm = oy + 12 * nO;          // [nO][2] squared norms of the last term / the sum
-  double* ops = onrm + 2 * nO;          // [nO][5][12] partial sums of the camera's records (five groups of twelve lanes)
-  int* lzi = reinterpret_cast<int*>(ops + 60 * nO);  // [nC] z-table row of each camera slot
+  double* lx = res_lds + 8;                                 // landmark coordinates (Step::at)
+  double* lu = lx + NCO * Step::lm_cap(nL, STRIDE);         // the landmarks' sums, then what the way back reads
+  double* reg = lu + NCO * Step::lm_cap(nL, STRIDE);        // the region: z of the cameras [nC][13] -> accumulators [nC][13] -> owner's records [nQ][12]
+  const typename Step::Own A(reg + res_region_doubles(nC, nQ), nO);
+  int* lzi = reinterpret_cast<int*>(A.end);  // [nC] z-table row of each camera slot
   int* loq = lzi + nC;                  // [nQ] the records read as an owner
   int* lown = loq + nQ;                 // [nO][4] z-table row, first / end position of the records
 
   // ---------------- prologue: everything that does not change between the terms
-  // owned cameras first (their registers are free again before the lane's own state is loaded): B^-1, sigma;
-  // x_0 = B^-1 (-b) (the series start, :196); z_0 published
+  // owned cameras first (their registers are free again before the lane's own state is loaded): B^-1, sigma, the reflector;
+  // x_0 = B^-1 (-b) (the series start); z_0 published
   if (t < 4) ctl[t] = 0;
   for (int e = t; e < nC; e += T) lzi[e] = k.cam_zi[C0 + e];
   for (int e = t; e < nQ; e += T) loq[e] = k.oq_rec[Q0 + e];
@@ -196,44 +409,33 @@ __global__ __launch_bounds__(NW * 64) void series_res(Dp d, ResP k) {
     const int2 qr = k.own_q[O0 + e];
     lown[4 * e] = k.own_zi[O0 + e]; lown[4 * e + 1] = qr.x; lown[4 * e + 2] = qr.y;
   }
-  for (int o = wave; o < nO; o += NW) {
-    const int c = k.own_cam[O0 + o];
-    for (int e = lane; e < 144; e += 64) obinv[144 * o + e] = d.binv[144 * (size_t)c + e];
-    if (lane < 12) osig[12 * o + lane] = d.sigma[12 * (size_t)c + lane];
-    if (lane >= 32 && lane < 44) otmp[12 * o + lane - 32] = -d.b[12 * (size_t)c + lane - 32];
-  }
+  for (int o = wave; o < nO; o += NW) Step::load_owner(d, ncw, A, o, k.own_cam[O0 + o], lane);
   __syncthreads();
   for (int o = wave; o < nO; o += NW) {
     const int zi = lown[4 * o];
-    double s = 0;
-    if (lane < 12) {
-      const double* Bi = obinv + 144 * o + 12 * lane;
-#pragma unroll
-      for (int j = 0; j < 12; ++j) s += Bi[j] * otmp[12 * o + j];
-      oacc[12 * o + lane] = s;
-      res_put(B.z, (unsigned)(12 * zi + lane) * 16u, s * osig[12 * o + lane], tag0 | 1u);
-    }
+    double s, a;
+    Step::template solve<true>(A, o, lane, s, a, [&](double zv) { res_put(B.z, (unsigned)(12 * zi + lane) * 16u, zv, tag0 | 1u); });
     if (k.want_norm0) {
       double n2[1] = {s * s};
       wave_sum<1>(n2);
-      if (lane == 0) { onrm[2 * o] = n2[0]; onrm[2 * o + 1] = n2[0]; }
+      if (lane == 0) { A.nrm[2 * o] = n2[0]; A.nrm[2 * o + 1] = n2[0]; }
     }
-    // (otmp = x_0 once every lane of the wavefront has read -b from it)
+    // (the term's place = x_0 once every lane of the wavefront has read -b from it)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
-    if (lane < 12) otmp[12 * o + lane] = s;
+    if (lane < NX) A.tmp[NX * o + lane] = s;
   }
   if (k.want_norm0) {
     __syncthreads();
     if (t == 0) {
       double a = 0;
-      for (int o = 0; o < nO; ++o) a += onrm[2 * o];
+      for (int o = 0; o < nO; ++o) a += A.nrm[2 * o];
       res_put(B.nrm, res_nrm_off(tag0 | 1u, g, 0), a, tag0 | 1u);
       res_put(B.nrm, res_nrm_off(tag0 | 1u, g, 1), a, tag0 | 1u);
     }
   }
-  // the lane's chunks: rows, camera slot, P3
-  ResChunk<H> ch[RR];
+  // the lane's chunks: rows (slot word, weight, what the step keeps of them), camera slot, the camera
+  ResChunk<Step, H> ch[RR];
 #pragma unroll
   for (int r = 0; r < RR; ++r) {
     const size_t li = ((size_t)g * RR + r) * T + t;
@@ -246,8 +448,8 @@ __global__ __launch_bounds__(NW * 64) void series_res(Dp d, ResP k) {
 #pragma unroll
     for (int j = 0; j < H; ++j) {
       const size_t row = (((size_t)g * RR + r) * H + j) * T + t;
-      ch[r].uv[j] = k.uv[row];
-      ch[r].ls[j] = k.lslot[row];
+      Step::load_row(k, ch[r].s, j, row);
+      ch[r].ls[j] = Step::slot_word(k.lslot[row], nL);
       ch[r].rw[j] = 1.0;
       if (ROBUST) {
         const int os = k.oslot[row];
@@ -257,32 +459,25 @@ __global__ __launch_bounds__(NW * 64) void series_res(Dp d, ResP k) {
         }
       }
     }
-#pragma unroll
-    for (int e = 0; e < 9; ++e) ch[r].P3[e] = 0;
-    if (ch[r].ci >= 0) {
-      const Cam P = load_cam(d.cams_lin4, k.cam_id[C0 + ch[r].ci]);
-      ch[r].P3[0] = P.r0.x; ch[r].P3[1] = P.r0.y; ch[r].P3[2] = P.r0.z;
-      ch[r].P3[3] = P.r1.x; ch[r].P3[4] = P.r1.y; ch[r].P3[5] = P.r1.z;
-      ch[r].P3[6] = P.r2.x; ch[r].P3[7] = P.r2.y; ch[r].P3[8] = P.r2.z;
-    }
+    Step::load_p(d, ch[r].s, ch[r].ci, nC, k.cam_id + C0);
   }
-  // the landmark slots of the lane: h~ into LDS, u = 0, G = diag(s) Hll^-1 diag(s) in registers
-  double G[LS][6];
+  // the landmark slots of the lane: coordinates into LDS, sums = 0, the rest of the landmark's record in registers
+  double rec[LS][Step::NREG];
 #pragma unroll
   for (int q = 0; q < LS; ++q) {
 #pragma unroll
-    for (int e = 0; e < 6; ++e) G[q][e] = 0;
+    for (int e = 0; e < Step::NREG; ++e) rec[q][e] = 0;
     const int s = t + q * T;
     if (s < nL) {
       const int lm = k.lm_id[L0 + s];
       const int pos = d.v2.lm_pos[lm] & ((1 << 26) - 1);
-      const double* rp = d.v2.lmrec + ((size_t)(pos >> 6) * 9) * WAVE + (pos & 63);
-      lh[3 * s] = rp[0];
-      lh[3 * s + 1] = rp[WAVE];
-      lh[3 * s + 2] = rp[2 * WAVE];
-      lu[3 * s] = 0; lu[3 * s + 1] = 0; lu[3 * s + 2] = 0;
+      const double* rp = d.v2.lmrec + ((size_t)(pos >> 6) * Step::LMREC) * WAVE + (pos & 63);
 #pragma unroll
-      for (int e = 0; e < 6; ++e) G[q][e] = rp[(3 + e) * WAVE];
+      for (int e = 0; e < NCO; ++e) lx[Step::template at<STRIDE>(s, e)] = rp[e * WAVE];
+#pragma unroll
+      for (int e = 0; e < NCO; ++e) lu[Step::template at<STRIDE>(s, e)] = 0;
+#pragma unroll
+      for (int e = 0; e < Step::NREG; ++e) rec[q][e] = rp[(NCO + e) * WAVE];
     }
   }
   int iters = k.m;
@@ -293,7 +488,8 @@ __global__ __launch_bounds__(NW * 64) void series_res(Dp d, ResP k) {
   for (int i = 1; i <= k.m + 1; ++i) {
     const unsigned tag = tag0 | (unsigned)i;
     if (i == k.m + 1 && !k.want_norms) break;  // (with the tests on: the last term's norms are looked at too)
-    // ---- the norms of term i - 1 (every owner's: the one step of a term that waits for ALL workgroups)
+    // ---- the norms of term i - 1 (every owner's: the one step of a term that waits for ALL workgroups); the tests are
+    // the reference's (:206-214 and :216-229; series_check's :259-283)
     if (k.want_norms && (i > 1 || k.want_norm0)) {
       if (wave == 0) {
         double v[2] = {0, 0};
@@ -314,8 +510,8 @@ __global__ __launch_bounds__(NW * 64) void series_res(Dp d, ResP k) {
         } else {
           const double n0 = reinterpret_cast<double*>(ctl)[2];
           bool conv = false;
-          if (k.q_tol > 0 && (i - 1) * iter_norm / acc_norm < k.q_tol) conv = true;    // :206-214
-          if (!conv && k.r_tol > 0 && iter_norm / n0 < k.r_tol) conv = true;             // :216-229
+          if (k.q_tol > 0 && (i - 1) * iter_norm / acc_norm < k.q_tol) conv = true;
+          if (!conv && k.r_tol > 0 && iter_norm / n0 < k.r_tol) conv = true;
           if (ok && conv && lane == 0) { ctl[1] = 1; ctl[2] = i - 1; }
           if (g == 0 && lane == 0) { d.norms[1] = iter_norm; d.norms[2] = acc_norm; }
         }
@@ -330,50 +526,36 @@ __global__ __launch_bounds__(NW * 64) void series_res(Dp d, ResP k) {
     if (!res_gather<T, GB>(B.z, nC * 12, z_row, tag, reg, RES_ACC_STRIDE, t, k.spin_limit) && lane == 0) ctl[0] = 1;
     __syncthreads();  // B1
     if (ctl[0]) break;
-    // ---- forward: u_l += P3^T (w C (Z h~_l))
+    // ---- forward: the landmarks' sums (Step::obs_forward: LDS adds on the landmark)
 #pragma unroll
     for (int r = 0; r < RR; ++r) {
       if (ch[r].hrows == 0) continue;  // (wave-uniform)
-      double zz[12];
-      const double* zp = reg + (ch[r].ci < 0 ? 0 : ch[r].ci) * RES_ACC_STRIDE;
+      typename Step::Z zz;
+      Step::load_z(reg + (ch[r].ci < 0 ? 0 : ch[r].ci) * RES_ACC_STRIDE, zz);
 #pragma unroll
-      for (int e = 0; e < 12; ++e) zz[e] = zp[e];
-#pragma unroll
-      for (int j = 0; j < H; ++j) {
-        if (j < ch[r].hrows && ch[r].ls[j] >= 0) {
-          const int s = ch[r].ls[j];
-          ck_obs_forward(d, ch[r].uv[j], ch[r].rw[j], zz, ch[r].P3, lh[s], lh[s + 1], lh[s + 2], lu, 0, (uint32_t)s);
-        }
-      }
+      for (int j = 0; j < H; ++j)
+        if (j < ch[r].hrows && ch[r].ls[j] >= 0)
+          Step::template obs_forward<ROBUST, STRIDE>(d, ch[r].s, j, ch[r].rw[j], ch[r].ls[j], zz, lx, lu);
     }
     __syncthreads();  // B2
-    // ---- g = G u per landmark slot; the region becomes the accumulators
+    // ---- the landmark step per slot (over the sums); the region becomes the accumulators
 #pragma unroll
     for (int q = 0; q < LS; ++q) {
       const int s = t + q * T;
-      if (s < nL) {
-        const double u0 = lu[3 * s], u1 = lu[3 * s + 1], u2 = lu[3 * s + 2];
-        lu[3 * s] = G[q][0] * u0 + G[q][1] * u1 + G[q][2] * u2;
-        lu[3 * s + 1] = G[q][1] * u0 + G[q][3] * u1 + G[q][4] * u2;
-        lu[3 * s + 2] = G[q][2] * u0 + G[q][4] * u1 + G[q][5] * u2;
-      }
+      if (s < nL) Step::template landmark_step<STRIDE>(lx, lu, s, rec[q]);
     }
     for (int e = t; e < nC * RES_ACC_STRIDE; e += T) reg[e] = 0;
     __syncthreads();  // B3
-    // ---- backward: y_c += h~_l (x) (w C (P3 g_l)); lanes of one camera are summed, the run's last lane adds to the
+    // ---- backward (Step::obs_backward, registers); lanes of one camera are summed, the run's last lane adds to the
     // camera's accumulator
 #pragma unroll
     for (int r = 0; r < RR; ++r) {
       if (ch[r].hrows == 0) continue;
       double y[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-      for (int j = 0; j < H; ++j) {
-        if (j < ch[r].hrows && ch[r].ls[j] >= 0) {
-          const int s = ch[r].ls[j];
-          const double gg[3] = {lu[s], lu[s + 1], lu[s + 2]};
-          ck_obs_backward(d, ch[r].uv[j], ch[r].rw[j], ch[r].P3, lh[s], lh[s + 1], lh[s + 2], gg, y);
-        }
-      }
+      for (int j = 0; j < H; ++j)
+        if (j < ch[r].hrows && ch[r].ls[j] >= 0)
+          Step::template obs_backward<ROBUST, STRIDE>(d, ch[r].s, j, ch[r].rw[j], ch[r].ls[j], lx, lu, y);
       // (the run's LAST lane holds its sum after the scan: no broadcast)
       if (ch[r].dup) seg_scan_steps<12>(y, lane, ch[r].seg & 255, ch[r].steps);
       if (ch[r].ci >= 0 && lane == ((ch[r].seg >> 8) & 255)) {
@@ -389,21 +571,25 @@ __global__ __launch_bounds__(NW * 64) void series_res(Dp d, ResP k) {
     }
     __syncthreads();  // B4
     // ---- the workgroup's partial records: one contiguous run of granule pairs (hand-over 1, the producer's side);
-    // u back to zero for the next term (its last readers were the backward pass)
+    // the landmarks' sums back to zero for the next term (their last readers were the backward pass)
     for (int e = t; e < nC * 12; e += T)
       res_put(B.part, (unsigned)(C0 * 12 + e) * 16u, reg[(e / 12) * RES_ACC_STRIDE + e % 12], tag);
 #pragma unroll
     for (int q = 0; q < LS; ++q) {
       const int s = t + q * T;
-      if (s < nL) { lu[3 * s] = 0; lu[3 * s + 1] = 0; lu[3 * s + 2] = 0; }
+      if (s < nL) {
+#pragma unroll
+        for (int e = 0; e < NCO; ++e) lu[Step::template at<STRIDE>(s, e)] = 0;
+      }
     }
     __syncthreads();  // B5 (the accumulators have been read: the region becomes the owner's records)
     // ---- owners (hand-over 1): the records of the cameras the workgroup owns into the region
     if (!res_gather<T, GB>(B.part, nQ * 12, q_row, tag, reg, 12, t, k.spin_limit) && lane == 0) ctl[0] = 1;
     __syncthreads();  // B6
     if (ctl[0]) break;
-    // ---- x_i = B^-1 (sigma * sum of the records), sum += x_i, z published (:200-204, :322-340).  A camera's records are
-    // summed by five groups of twelve lanes (record q of the camera by group q % 5), then the five partial sums in order
+    // ---- x_i = Step::solve of sigma * sum of the records, sum += x_i, z published (:200-204, :322-340; :246-257, :342-360).
+    // A camera's records are summed by five groups of twelve lanes (record q of the camera by group q % 5), then the five
+    // partial sums in order
     for (int o = wave; o < nO; o += NW) {
       const int zi = lown[4 * o];
       const int2 qr = make_int2(lown[4 * o + 1], lown[4 * o + 2]);
@@ -411,36 +597,29 @@ __global__ __launch_bounds__(NW * 64) void series_res(Dp d, ResP k) {
         const int e = lane % 12, grp = lane / 12;
         double a = 0;
         for (int q = qr.x + grp; q < qr.y; q += 5) a += reg[12 * q + e];
-        ops[60 * o + lane] = a;
+        A.ps[60 * o + lane] = a;
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_wave_barrier();
       if (lane < 12) {
-        const double yl = (((ops[60 * o + lane] + ops[60 * o + 12 + lane]) + ops[60 * o + 24 + lane]) + ops[60 * o + 36 + lane]) + ops[60 * o + 48 + lane];
-        oy[12 * o + lane] = yl * osig[12 * o + lane];
+        const double* ps = A.ps + 60 * o + lane;
+        const double yl = (((ps[0] + ps[12]) + ps[24]) + ps[36]) + ps[48];
+        A.y[12 * o + lane] = yl * A.sig[12 * o + lane];
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_wave_barrier();
-      double s = 0, a = 0;
-      if (lane < 12) {
-        const double* Bi = obinv + 144 * o + 12 * lane;
-#pragma unroll
-        for (int j = 0; j < 12; ++j) s += Bi[j] * oy[12 * o + j];
-        a = oacc[12 * o + lane] + s;
-        otmp[12 * o + lane] = s;
-        oacc[12 * o + lane] = a;
-        res_put(B.z, (unsigned)(12 * zi + lane) * 16u, s * osig[12 * o + lane], tag + 1u);
-      }
+      double s, a;
+      Step::template solve<false>(A, o, lane, s, a, [&](double zv) { res_put(B.z, (unsigned)(12 * zi + lane) * 16u, zv, tag + 1u); });
       if (k.want_norms) {
         double n2[2] = {s * s, a * a};
         wave_sum<2>(n2);
-        if (lane == 0) { onrm[2 * o] = n2[0]; onrm[2 * o + 1] = n2[1]; }
+        if (lane == 0) { A.nrm[2 * o] = n2[0]; A.nrm[2 * o + 1] = n2[1]; }
       }
     }
     __syncthreads();  // B7 (the owner sums have read the region: the next term's z may land in it)
     if (k.want_norms && t == 0) {
       double a = 0, b = 0;
-      for (int o = 0; o < nO; ++o) { a += onrm[2 * o]; b += onrm[2 * o + 1]; }
+      for (int o = 0; o < nO; ++o) { a += A.nrm[2 * o]; b += A.nrm[2 * o + 1]; }
       res_put(B.nrm, res_nrm_off(tag + 1u, g, 0), a, tag + 1u);
       res_put(B.nrm, res_nrm_off(tag + 1u, g, 1), b, tag + 1u);
     }
@@ -448,12 +627,7 @@ __global__ __launch_bounds__(NW * 64) void series_res(Dp d, ResP k) {
   // ---------------- epilogue: sum and last term of the owned cameras, status
   __syncthreads();
   if (ctl[1]) iters = ctl[2];
-  for (int e = t; e < nO * 12; e += T) {
-    const int c = k.own_cam[O0 + e / 12];
-    d.accum[12 * (size_t)c + e % 12] = oacc[e];
-    d.tmp[12 * (size_t)c + e % 12] = otmp[e];
-    store_z(d, c, e % 12, otmp[e] * osig[e]);  // z = sigma x of the last term, where the per-term kernels leave it (povar_power_series_step goes on from it)
-  }
+  Step::template store<NW>(d, A, k.own_cam + O0, nO, t, wave, lane);
   if (t == 0) {
     if (ctl[0]) atomicOr(&d.flags[0], 4);
     if (g == 0 && ctl[1]) {
@@ -462,6 +636,15 @@ __global__ __launch_bounds__(NW * 64) void series_res(Dp d, ResP k) {
       d.flags[3] = 1;
     }
   }
+}
+
+template <int NW, int H, int RR, int LS, bool ROBUST>
+__global__ __launch_bounds__(NW * 64) void series_res(Dp d, ResP k) {
+  res_series<ResPose, NW, H, RR, LS, ROBUST>(d, k, nullptr);
+}
+template <int NW, int H, int RR, int LS, bool ROBUST>
+__global__ __launch_bounds__(NW * 64) void series_res_h(Dp d, ResP k, const double* ncw) {
+  res_series<ResJoint, NW, H, RR, LS, ROBUST>(d, k, ncw);
 }
 
 // the launch counter (the high bits of the granule tags of the NEXT launch): a one-thread kernel behind series_res in the

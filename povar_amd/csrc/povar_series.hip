@@ -104,20 +104,18 @@ static void ck_dp(const povar_ctx* c, int step, Dp& da) {
 // instead of G's 12) and house4 between the passes do not fit 128 registers (7 to 21 spilt), so step 2 cuts its instance
 // for 512-thread workgroups (res_build_for)
 #define POVAR_RES_H_VARIANTS(X) X(8, 1, 2, 1) X(8, 1, 2, 2) X(8, 2, 2, 1) X(8, 2, 2, 2) X(8, 4, 2, 1) X(8, 4, 2, 2)
-template <int NW, int H, int RR, int LS>
-void launch_res_t(povar_ctx* c, const ResP& k) {
-  if (c->opt.robust_norm)
-    hipLaunchKernelGGL((series_res<NW, H, RR, LS, true>), dim3(c->res.W), dim3(NW * 64), c->res.lds_bytes, c->stream, c->d, k);
-  else
-    hipLaunchKernelGGL((series_res<NW, H, RR, LS, false>), dim3(c->res.W), dim3(NW * 64), c->res.lds_bytes, c->stream, c->d, k);
+// the kernel of a step and shape
+template <bool JOINT, int NW, int H, int RR, int LS, bool ROBUST>
+const void* res_kernel() {
+  if constexpr (JOINT) return (const void*)series_res_h<NW, H, RR, LS, ROBUST>;
+  else return (const void*)series_res<NW, H, RR, LS, ROBUST>;
 }
-template <int NW, int H, int RR, int LS>
-void launch_res_h_t(povar_ctx* c, const ResP& k) {
+template <bool JOINT, int NW, int H, int RR, int LS>
+void launch_res_t(povar_ctx* c, const ResP& k) {
   const double* ncw = c->ncw.p;
-  if (c->opt.robust_norm)
-    hipLaunchKernelGGL((series_res_h<NW, H, RR, LS, true>), dim3(k.W), dim3(NW * 64), c->res_h_lds, c->stream, c->d, k, ncw);
-  else
-    hipLaunchKernelGGL((series_res_h<NW, H, RR, LS, false>), dim3(k.W), dim3(NW * 64), c->res_h_lds, c->stream, c->d, k, ncw);
+  void* args[] = {(void*)&c->d, (void*)&k, (void*)&ncw};  // (series_res has the first two parameters, series_res_h all three)
+  const void* f = c->opt.robust_norm ? res_kernel<JOINT, NW, H, RR, LS, true>() : res_kernel<JOINT, NW, H, RR, LS, false>();
+  (void)hipLaunchKernel(f, dim3(k.W), dim3(NW * 64), args, JOINT ? c->res_h_lds : c->res.lds_bytes, c->stream);
 }
 
 bool res_variant_exists(int nw, int h, int rr, int ls, bool joint) {
@@ -135,43 +133,31 @@ void launch_res(povar_ctx* c, const ResP& k) {
   const povar_ctx::ResDev& D = res_dev(c, c->joint);
 #define X(NW_, H_, R_, LS_)                                                  \
   if (D.NW == NW_ && D.H == H_ && D.R == R_ && D.LS == LS_) {                \
-    launch_res_t<NW_, H_, R_, LS_>(c, k);                                    \
-    return;                                                                  \
-  }
-#define XH(NW_, H_, R_, LS_)                                                 \
-  if (D.NW == NW_ && D.H == H_ && D.R == R_ && D.LS == LS_) {                \
-    launch_res_h_t<NW_, H_, R_, LS_>(c, k);                                  \
+    launch_res_t<JOINT, NW_, H_, R_, LS_>(c, k);                             \
     return;                                                                  \
   }
   if (c->joint) {
-    POVAR_RES_H_VARIANTS(XH)
+    constexpr bool JOINT = true;
+    POVAR_RES_H_VARIANTS(X)
   } else {
+    constexpr bool JOINT = false;
     POVAR_RES_VARIANTS(X)
   }
 #undef X
-#undef XH
 }
 
-template <int NW, int H, int RR, int LS>
+template <bool JOINT, int NW, int H, int RR, int LS>
 hipError_t res_set_lds_t() {
-  hipError_t e = hipFuncSetAttribute((const void*)series_res<NW, H, RR, LS, false>, hipFuncAttributeMaxDynamicSharedMemorySize, RES_LDS_BYTES);
+  hipError_t e = hipFuncSetAttribute(res_kernel<JOINT, NW, H, RR, LS, false>(), hipFuncAttributeMaxDynamicSharedMemorySize, RES_LDS_BYTES);
   if (e != hipSuccess) return e;
-  return hipFuncSetAttribute((const void*)series_res<NW, H, RR, LS, true>, hipFuncAttributeMaxDynamicSharedMemorySize, RES_LDS_BYTES);
-}
-template <int NW, int H, int RR, int LS>
-hipError_t res_h_set_lds_t() {
-  hipError_t e = hipFuncSetAttribute((const void*)series_res_h<NW, H, RR, LS, false>, hipFuncAttributeMaxDynamicSharedMemorySize, RES_LDS_BYTES);
-  if (e != hipSuccess) return e;
-  return hipFuncSetAttribute((const void*)series_res_h<NW, H, RR, LS, true>, hipFuncAttributeMaxDynamicSharedMemorySize, RES_LDS_BYTES);
+  return hipFuncSetAttribute(res_kernel<JOINT, NW, H, RR, LS, true>(), hipFuncAttributeMaxDynamicSharedMemorySize, RES_LDS_BYTES);
 }
 
 hipError_t res_set_lds_all() {
   hipError_t e = hipSuccess;
-#define X(NW_, H_, R_, LS_) if (e == hipSuccess) e = res_set_lds_t<NW_, H_, R_, LS_>();
-  POVAR_RES_VARIANTS(X)
-#undef X
-#define X(NW_, H_, R_, LS_) if (e == hipSuccess) e = res_h_set_lds_t<NW_, H_, R_, LS_>();
-  POVAR_RES_H_VARIANTS(X)
+#define X(NW_, H_, R_, LS_) if (e == hipSuccess) e = res_set_lds_t<JOINT, NW_, H_, R_, LS_>();
+  { constexpr bool JOINT = false; POVAR_RES_VARIANTS(X) }
+  { constexpr bool JOINT = true; POVAR_RES_H_VARIANTS(X) }
 #undef X
   return e;
 }
@@ -187,8 +173,8 @@ bool res_possible(const povar_ctx* c, bool joint) {
 }
 
 bool res_active(const povar_ctx* c, bool joint) {
-  const bool tuned = joint ? c->res_tuned_h : c->res_tuned, choice = joint ? c->res_choice_h : c->res_choice;
-  return res_possible(c, joint) && (c->res_mode == 1 || (c->res_mode < 0 && tuned && choice));  // (and m <= 250: run_series' caller)
+  const povar_ctx::ResTune& tn = c->res_tune[joint];
+  return res_possible(c, joint) && (c->res_mode == 1 || (c->res_mode < 0 && tn.tuned && tn.choice));  // (and m <= 250: run_series' caller)
 }
 
 ResP res_params(const povar_ctx* c, int m, double q_tol, double r_tol) {
@@ -700,9 +686,9 @@ int res_verify(povar_ctx* c) {
 // -- a warm-up and REPS timed solves each, the same m and tolerances -- and the faster one is kept.
 int res_autotune(povar_ctx* c, int32_t m, double q_tol, double r_tol) {
   // (once per step, on the system prepared last: the two kernels and their per-term counterparts differ)
-  bool& tuned = c->joint ? c->res_tuned_h : c->res_tuned;
-  bool& choice = c->joint ? c->res_choice_h : c->res_choice;
-  float* tune_us = c->joint ? c->res_tune_h_us : c->res_tune_us;
+  bool& tuned = c->res_tune[c->joint].tuned;
+  bool& choice = c->res_tune[c->joint].choice;
+  float* tune_us = c->res_tune[c->joint].us;
   if (c->res_mode >= 0 || tuned || !res_possible(c, c->joint) || m < 4 || m > 250) return 0;
   tuned = true;
   struct Restore {  // a failure below leaves the choice open and the timing to be repeated (as ck_autotune)
@@ -1002,7 +988,7 @@ int povar_set_series_kernel(povar_ctx* c, int32_t mode) {
   if (int rc = res_verify(c)) return rc;
   if (c->deterministic) return 0;  // pinned (POVAR_DETERMINISTIC)
   c->res_mode = mode;
-  if (mode < 0) c->res_tuned = c->res_tuned_h = false;  // (both steps are timed again)
+  if (mode < 0) c->res_tune[0].tuned = c->res_tune[1].tuned = false;  // (both steps are timed again)
   return 0;
 }
 

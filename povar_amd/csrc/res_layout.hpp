@@ -73,10 +73,10 @@ struct ResLayout {
 // LDS of a workgroup: control words, h~ and u per landmark (G stays in the registers of the slot's lane), ONE region that
 // is in turn the z of the workgroup's cameras, their accumulators, and the records it reads as an owner, and per owned
 // camera B^-1, sigma, sum, term, E0 row, norms and five partial sums
+// (povar_kernels_res.hpp asserts that the steps of its kernel body, ResPose and ResJoint, carve exactly these)
 constexpr int RES_LM_BYTES = 48;
 constexpr int RES_OWN_DOUBLES = 144 + 12 + 12 + 12 + 12 + 2 + 5 * 12;
-// step 2 (series_res_h, povar_kernels_res_joint.hpp): X and U4 / G4 per landmark slot (s and Hll^-1 in the registers of the
-// slot's lane), and per owned camera B^-1 11 x 11, sigma, the reflector (w, beta) of N_c, sum (11), term (11), E0 row, norms
+// step 2 (series_res_h): X and U4 / G4 per landmark slot (s and Hll^-1 in the registers of the slot's lane), and per owned camera B^-1 11 x 11, sigma, the reflector (w, beta) of N_c, sum (11), term (11), E0 row, norms
 // and the five partial sums
 constexpr int RES_LM_BYTES_H = 64;
 constexpr int RES_OWN_DOUBLES_H = 121 + 12 + 13 + 11 + 11 + 12 + 2 + 5 * 12;

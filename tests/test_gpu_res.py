@@ -1,6 +1,6 @@
 """series_res -- the RESIDENT power series: the whole loop of solve_pOSE (sc/linearization_power_varproj.hpp:191-237:
 x_0 = B^-1 (-b), x_i = B^-1 E0 x_{i-1}, early exit :206-229) as ONE launch that keeps rows, landmarks and B^-1 on the chip
-(povar_kernels_res.hpp, res_layout.hpp) -- against the CPU oracle at the sizes it is built for (ladybug-49, trafalgar-257,
+(povar_kernels_res.hpp: res_series with ResPose; res_layout.hpp) -- against the CPU oracle at the sizes it is built for (ladybug-49, trafalgar-257,
 one rank's landmark shard of venice-1778 at world = 8), against the per-term kernels with robust norms, early exit and
 m = 0, and the library's own choice between the two forms.
 

@@ -1,6 +1,6 @@
 """series_res_h -- the RESIDENT power series of step 2: the whole loop of solve_joint (sc/linearization_power_varproj.hpp:
-240-287: x_0 = B^-1 (-b), x_i = B^-1 N_c^T sigma E0 sigma N_c x_{i-1}, early exit) as ONE launch (povar_kernels_res_joint.hpp;
-layout: res_layout.hpp, res_shape_step2()) -- against the CPU oracle at size, against the per-term kernels (e0_lpl_h /
+240-287: x_0 = B^-1 (-b), x_i = B^-1 N_c^T sigma E0 sigma N_c x_{i-1}, early exit) as ONE launch (povar_kernels_res.hpp:
+res_series with ResJoint; layout: res_layout.hpp, res_shape_step2()) -- against the CPU oracle at size, against the per-term kernels (e0_lpl_h /
 e0_ck_h + cam_cold_sum_binv_h) with robust norms, early exit, m = 0 and m = 1, its first term componentwise against the
 "ckh" rounding-error model, across linearisations, the library's own choice between the two forms, the give-up path, and a
 term-by-term continuation.

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Diagnostic build of the library with in-kernel phase stamps of series_res (never shipped: the shipping sources carry no
-stamp code).  Copies povar_amd/csrc to build/variants/res_stamps/povar_amd/csrc/, inserts s_memtime stamps behind the phase comments of
-povar_kernels_res.hpp (wavefront 0 and the last wavefront of every workgroup, at term POVAR_RES_STAMP_TERM, default 5) and a
-dump of the stamp buffer into povar_synchronize, and builds build/libpovar_hip_res_stamps.so.
+"""Diagnostic build of the library with in-kernel phase stamps of series_res and series_res_h (never shipped: the shipping
+sources carry no stamp code).  Copies povar_amd/csrc to build/variants/res_stamps/povar_amd/csrc/, inserts s_memtime stamps
+behind the phase comments of the one body of the two kernels (res_series, povar_kernels_res.hpp; wavefront 0 and the last
+wavefront of every workgroup, at term POVAR_RES_STAMP_TERM, default 5) and a dump of the stamp buffer into povar_synchronize,
+and builds build/libpovar_hip_res_stamps.so.
 Use: POVAR_LIB=build/libpovar_hip_res_stamps.so POVAR_RES_STAMPS_OUT=file python3 tools/res_stamps_report.py shape [world]"""
 import os
 import shutil
@@ -19,7 +20,7 @@ MARKS = [
     ("    // ---- the norms of term i - 1", 1),
     ("    // ---- hand-over 2: z of the workgroup's cameras into the region", 2),
     ("    __syncthreads();  // B1", 3),      # z gathered
-    ("    // ---- forward: u_l += P3^T", 4),  # behind B1
+    ("    // ---- forward: the landmarks' sums", 4),  # behind B1
     ("    __syncthreads();  // B2", 5),      # forward done
     ("    __syncthreads();  // B3", 6),      # g = G u done (behind B2)
     ("    __syncthreads();  // B4", 7),      # backward done (behind B3)
