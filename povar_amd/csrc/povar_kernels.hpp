@@ -2641,297 +2641,8 @@ POVAR_KERNEL __launch_bounds__(256) void build_hot_rec(Dp d, int hom) {
   d.hot_rec[(size_t)r * HOT_REC_STRIDE + 12 + e] = v;
 }
 
-// fixed-order sum of a camera's scatter items (+ the LDS-accumulated workgroup partials of a cached
-// camera): lanes stride over the parts, then a butterfly; every lane ends with the 12 sums
-__device__ inline void camera_item_sum(const Dp& d, int c, int lane, double (&y)[12]) {
-#pragma unroll
-  for (int j = 0; j < 12; ++j) y[j] = 0;
-  for (int it = d.cmv.cam_item_off[c] + lane; it < d.cmv.cam_item_off[c + 1]; it += WAVE) {
-    const double* ip = d.cmv.part + 12 * (size_t)it;
-#pragma unroll
-    for (int j = 0; j < 12; ++j) y[j] += ip[j];
-  }
-  if (d.hot_part && d.part_range) {
-    const int2 rr = d.part_range[c];
-    for (int w = rr.x + lane; w < rr.y; w += WAVE) {
-      const double* ip = d.hot_part + (size_t)w * 12;
-#pragma unroll
-      for (int j = 0; j < 12; ++j) y[j] += ip[j];
-    }
-  } else if (d.hot_part) {
-    const int r = d.cam_hot[c];
-    if (r > 0 && r <= d.n_hot_acc) {
-      for (int w = lane; w < d.n_hot_wg; w += WAVE) {
-        const double* ip = d.hot_part + ((size_t)(r - 1) * d.n_hot_wg + w) * 12;
-#pragma unroll
-        for (int j = 0; j < 12; ++j) y[j] += ip[j];
-      }
-    }
-  }
-  wave_sum<12>(y);
-}
-
-// LDSACC modes: y_c = sigma * ( sum over the camera's COLD observations of (h q0; h q1; h q2)
-//                                + sum of the workgroups' LDS-accumulated partials of a cached camera ).
-constexpr int CCS_THREADS = 128;  // threads per camera of the per-camera kernels of the term loop (cam_cold_sum[_binv][_h])
-// One CCS_THREADS-thread workgroup per camera, fixed summation order; replaces cm_scatter + the item sums
-// (a single wavefront walking a few hundred items per camera was a serial chain of dependent loads).
-template <int NT>
-__global__ __launch_bounds__(NT) void cam_cold_sum(Dp d, int hom) {
-  const int done = d.flags[1];  // tested after the first batch of loads is in flight
-  __shared__ double sh[4 * 12];
-  const int c = blockIdx.x, t = threadIdx.x;
-  double acc[12];
-#pragma unroll
-  for (int k = 0; k < 12; ++k) acc[k] = 0;
-  const int2 pr = d.cmv.cam_range[c];
-  const int p0 = pr.x, p1 = pr.y;
-  const int r = d.hot_part ? d.cam_hot[c] : 0;
-  const double sg_t = t < 12 ? d.sigma[12 * (size_t)c + t] : 0.0;  // requested early, used last
-  if (done) return;
-  // 4 observations per thread in flight: index loads, then the dependent gathers, then the FMAs
-  constexpr int U = 4;
-  for (int pb = p0 + t; pb < p1; pb += U * NT) {
-    double hx[U], hy[U], hz[U], hw[U];
-    double4 q[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int p = pb + u * NT;
-      const bool in = p < p1;
-      const int pc = in ? p : p0;
-      hx[u] = d.cmv.h[pc];
-      hy[u] = d.cmv.h[d.cmv.n + pc];
-      hz[u] = d.cmv.h[2 * d.cmv.n + pc];
-      hw[u] = hom ? d.cmv.h[3 * d.cmv.n + pc] : 1.0;
-      q[u] = in ? d.q4c[d.cmv.src ? d.cmv.src[pc] : pc] : make_double4(0, 0, 0, 0);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      acc[0] += hx[u] * q[u].x; acc[1] += hy[u] * q[u].x; acc[2] += hz[u] * q[u].x; acc[3] += hw[u] * q[u].x;
-      acc[4] += hx[u] * q[u].y; acc[5] += hy[u] * q[u].y; acc[6] += hz[u] * q[u].y; acc[7] += hw[u] * q[u].y;
-      acc[8] += hx[u] * q[u].z; acc[9] += hy[u] * q[u].z; acc[10] += hz[u] * q[u].z; acc[11] += hw[u] * q[u].z;
-    }
-  }
-  if (d.part_range) {  // e0_lpl: the camera's partial records are one contiguous run
-    const int2 rr = d.part_range[c];
-    for (int w = rr.x + t; w < rr.y; w += NT) {
-      const double* ip = d.hot_part + (size_t)w * 12;
-#pragma unroll
-      for (int k = 0; k < 12; ++k) acc[k] += ip[k];
-    }
-  } else if (r > 0 && r <= d.n_hot_acc) {
-    for (int w = t; w < d.n_hot_wg; w += NT) {
-      const double* ip = d.hot_part + ((size_t)(r - 1) * d.n_hot_wg + w) * 12;
-#pragma unroll
-      for (int k = 0; k < 12; ++k) acc[k] += ip[k];
-    }
-  }
-  block_sum_dpp<12, NT>(acc, sh);
-  if (t < 12) {
-    double v = 0;
-#pragma unroll
-    for (int k = 0; k < 12; ++k) v = (t == k) ? acc[k] : v;
-    v *= sg_t;
-    if (d.p2p_peer) {
-      // push this rank's partial of camera c into the slab [parity][rank] of EVERY rank's exchange buffer, then
-      // publish it with the epoch tag in the record's 13th entry.  Every store and every load of these bytes is a
-      // system-scope (sc0 sc1, write-through / cache-bypassing) access and the storing wavefront drains its stores
-      // (s_waitcnt vmcnt(0)) before the tag: no release fence -- a system-scope fence writes the whole L2 back,
-      // 44 us per term with one per camera (MI355X_MICROARCH.md, "Valid forms").  Lanes 0..11 are one wavefront.
-      const unsigned long long ep = *d.p2p_epoch;
-      const size_t off = ((((size_t)(ep & 1) * d.p2p_world + d.p2p_rank) * d.n_cams) + c) * 16;
-      for (int p = 0; p < d.p2p_world; ++p)
-        __hip_atomic_store(d.p2p_peer[p] + off + t, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (t == 0)
-        for (int p = 0; p < d.p2p_world; ++p)
-          __hip_atomic_store(reinterpret_cast<unsigned long long*>(d.p2p_peer[p] + off + 12), ep, __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_SYSTEM);
-    } else {
-      d.y[12 * (size_t)c + t] = v;
-    }
-  }
-}
-
-// cam_cold_sum fused with cam_binv_axpy (mode 2) for the unsharded LDSACC term loop: the workgroup that
-// has just summed camera c's E0 row applies B_c^-1, the AXPY and the sigma scaling itself, so the term
-// needs one kernel less (the dense y is never materialised).  Norm partials are per camera
-// (series_check then sums n_cams entries).
-template <int NT>
-__global__ __launch_bounds__(NT) void cam_cold_sum_binv(Dp d, int want_norms) {
-  const int done = d.flags[1];  // tested after the first batch of loads is in flight
-  __shared__ double sh[4 * 12];
-  const int c = blockIdx.x, t = threadIdx.x;
-  double acc[12];
-#pragma unroll
-  for (int k = 0; k < 12; ++k) acc[k] = 0;
-  const int2 pr = d.cmv.cam_range[c];  // one load instead of the two-level item index
-  const int2 rr = d.part_range ? d.part_range[c] : make_int2(0, 0);  // requested with it: the partial loop does not wait a round trip of its own
-  const int p0 = pr.x, p1 = pr.y;
-  const int r = d.hot_part ? d.cam_hot[c] : 0;
-  // everything the tail needs that depends on c only is requested now, off the critical path
-  const size_t base = 12 * (size_t)c;
-  double bi[12], sg[12], acc_old = 0;
-  if (t < 12) {
-    const double* Bi = d.binv + 144 * (size_t)c + 12 * t;
-#pragma unroll
-    for (int j = 0; j < 12; ++j) {
-      bi[j] = Bi[j];
-      sg[j] = d.sigma[base + j];
-    }
-    acc_old = d.accum[base + t];
-  }
-  if (done) return;
-  constexpr int U = 4;  // (8 with the gather through CmView::src: 1499 -> 1470 terms/s on final-13682)
-  for (int pb = p0 + t; pb < p1; pb += U * NT) {
-    double hx[U], hy[U], hz[U];
-    double4 q[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int p = pb + u * NT;
-      const bool in = p < p1;
-      const int pc = in ? p : p0;
-      hx[u] = d.cmv.h[pc];
-      hy[u] = d.cmv.h[d.cmv.n + pc];
-      hz[u] = d.cmv.h[2 * d.cmv.n + pc];
-      q[u] = in ? d.q4c[d.cmv.src ? d.cmv.src[pc] : pc] : make_double4(0, 0, 0, 0);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      acc[0] += hx[u] * q[u].x; acc[1] += hy[u] * q[u].x; acc[2] += hz[u] * q[u].x; acc[3] += q[u].x;
-      acc[4] += hx[u] * q[u].y; acc[5] += hy[u] * q[u].y; acc[6] += hz[u] * q[u].y; acc[7] += q[u].y;
-      acc[8] += hx[u] * q[u].z; acc[9] += hy[u] * q[u].z; acc[10] += hz[u] * q[u].z; acc[11] += q[u].z;
-    }
-  }
-  if (d.part_range) {  // e0_lpl: the camera's partial records are one contiguous run
-    for (int w = rr.x + t; w < rr.y; w += NT) {
-      const double* ip = d.hot_part + (size_t)w * 12;
-#pragma unroll
-      for (int k = 0; k < 12; ++k) acc[k] += ip[k];
-    }
-  } else if (r > 0 && r <= d.n_hot_acc) {
-    for (int w = t; w < d.n_hot_wg; w += NT) {
-      const double* ip = d.hot_part + ((size_t)(r - 1) * d.n_hot_wg + w) * 12;
-#pragma unroll
-      for (int k = 0; k < 12; ++k) acc[k] += ip[k];
-    }
-  }
-  block_sum_dpp<12, NT>(acc, sh);  // every thread now holds the 12 sums
-  if (t >= 64) return;
-  double nrm[2] = {0, 0};
-  if (t < 12) {
-    const size_t idx = base + t;
-    double s = 0, sgt = 0;
-#pragma unroll
-    for (int j = 0; j < 12; ++j) {
-      s += bi[j] * (acc[j] * sg[j]);
-      sgt = (t == j) ? sg[j] : sgt;
-    }
-    const double a = acc_old + s;
-    d.tmp[idx] = s;
-    d.accum[idx] = a;
-    store_z(d, c, t, s * sgt);
-    nrm[0] = s * s;
-    nrm[1] = a * a;
-  }
-  if (want_norms) {
-    wave_sum<2>(nrm);
-    if (t == 0) {
-      d.norm_part[2 * (size_t)c] = nrm[0];
-      d.norm_part[2 * (size_t)c + 1] = nrm[1];
-    }
-  }
-}
-
-// b_c = sigma * sum_items (scatter parts)   (landmark_block.hpp:529-534); one wavefront per camera
-POVAR_KERNEL __launch_bounds__(256) void cam_sum_items(Dp d, double* out, int apply_sigma) {
-  const int lane = threadIdx.x & 63;
-  const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (c >= d.n_cams) return;
-  double y[12];
-  camera_item_sum(d, c, lane, y);
-  if (lane < 12) {
-    double v = 0;
-#pragma unroll
-    for (int j = 0; j < 12; ++j) v = (lane == j) ? y[j] : v;
-    out[12 * (size_t)c + lane] = apply_sigma ? v * d.sigma[12 * (size_t)c + lane] : v;
-  }
-}
-
-// K9 + K11: tmp = B^-1 y, accum (+)= tmp, z = sigma * tmp, optional squared-norm partials
-// (right_mul_b_inv_pOSE + the loop body of solve_pOSE, linearization_power_varproj.hpp:196-207,
-// 322-340).  mode 0: y = -b (series start); 1: y = sigma * sum of scatter items (implicit E0);
-// 2: y = dense buffer d.y (the per-camera sums of the LDSACC modes, or the all-reduced vector).
-constexpr int K9_CAMS = 4;  // one wavefront per camera, 4 cameras per workgroup
-POVAR_KERNEL __launch_bounds__(K9_CAMS * 64) void cam_binv_axpy(Dp d, int mode, int want_norms) {
-  const int done = mode != 0 ? d.flags[1] : 0;  // tested before the first store: its round trip overlaps the loads
-  __shared__ double sh[K9_CAMS * 2];
-  const int lane = threadIdx.x & 63;
-  const int c = blockIdx.x * K9_CAMS + (threadIdx.x >> 6);
-  const bool in = c < d.n_cams;
-  double y[12];
-#pragma unroll
-  for (int j = 0; j < 12; ++j) y[j] = 0;
-  if (in) {
-    const size_t base = 12 * (size_t)c;
-    if (mode == 0) {
-#pragma unroll
-      for (int j = 0; j < 12; ++j) y[j] = -d.b[base + j];
-    } else if (mode == 1) {
-      camera_item_sum(d, c, lane, y);
-#pragma unroll
-      for (int j = 0; j < 12; ++j) y[j] *= d.sigma[base + j];
-    } else if (mode == 5) {
-      // peer-to-peer exchange: wait for every rank's slab of this camera (tag == epoch), sum in rank order
-      const unsigned long long ep = *d.p2p_epoch;
-      const double* mine = d.p2p_peer[d.p2p_rank];
-      const bool gave_up = (d.flags[0] & 2) != 0;  // an earlier wait of this solve timed out: do not wait again
-      for (int p = 0; p < d.p2p_world; ++p) {
-        const double* rec = mine + ((((size_t)(ep & 1) * d.p2p_world + p) * d.n_cams) + c) * 16;
-        int spins = 0;
-        while (!gave_up && __hip_atomic_load(reinterpret_cast<const unsigned long long*>(rec + 12), __ATOMIC_RELAXED,
-                                             __HIP_MEMORY_SCOPE_SYSTEM) != ep) {  // relaxed poll; the data loads below bypass the caches too
-          __builtin_amdgcn_s_sleep(8);
-          if (++spins > (1 << 22)) {  // a peer never arrived: flag it and go on (the host reports the failure)
-            if (lane == 0) atomicOr(&d.flags[0], 2);
-            break;
-          }
-        }
-#pragma unroll
-        for (int j = 0; j < 12; ++j) y[j] += __hip_atomic_load(rec + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 12; ++j) y[j] = d.y[base + j];
-    }
-  }
-  double nrm[2] = {0, 0};
-  double s = 0, acc = 0, sg = 0;
-  if (in && lane < 12) {
-    const size_t idx = 12 * (size_t)c + lane;
-    const double* Bi = d.binv + 144 * (size_t)c + 12 * lane;
-#pragma unroll
-    for (int j = 0; j < 12; ++j) s += Bi[j] * y[j];
-    acc = mode == 0 ? s : d.accum[idx] + s;
-    sg = d.sigma[idx];
-  }
-  if (done) return;
-  if (in && lane < 12) {
-    const size_t idx = 12 * (size_t)c + lane;
-    d.tmp[idx] = s;
-    d.accum[idx] = acc;
-    store_z(d, c, lane, s * sg);
-    nrm[0] = s * s;
-    nrm[1] = acc * acc;
-  }
-  if (want_norms) {
-    block_sum<2, K9_CAMS * 64>(nrm, sh);
-    if (threadIdx.x == 0) {
-      d.norm_part[2 * (size_t)blockIdx.x] = nrm[0];
-      d.norm_part[2 * (size_t)blockIdx.x + 1] = nrm[1];
-    }
-  }
-}
+// cameras per workgroup of cam_binv_axpy[_h] (povar_kernels_cam.hpp) and of the kernels shaped like it: one wavefront per camera
+constexpr int K9_CAMS = 4;
 
 // convergence tests of solve_pOSE (linearization_power_varproj.hpp:198, 206-229), on the device
 // so the m-term loop needs no host round trip; later kernels of the loop see flags[1] and exit.

@@ -20,7 +20,7 @@
 //     order they finish in), the accumulator slot carries a counter in LDS, and a run's last lane adds (read, fp64 add,
 //     write -- no atomic) when the counter shows its ticket.  A wavefront waits only for tiles that are ahead of its own in
 //     every wavefront's program order: no cycle.
-// Everything else of the term (cam_cold_sum_binv: strided sums + a butterfly) has a fixed order anyway.
+// Everything else of the term (cam_cold_sum_binv, povar_kernels_cam.hpp: strided sums + a butterfly) has a fixed order anyway.
 #pragma once
 
 #include "povar_kernels_ck.hpp"

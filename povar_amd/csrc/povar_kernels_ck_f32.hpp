@@ -6,7 +6,7 @@
 // is widened to fp64 before the segmented wavefront sum, the workgroup accumulators in LDS add doubles (ds_add_f64), the
 // partial records and q of the cold view are the doubles the per-camera kernel behind e0_ck reads -- and with them B^-1, the
 // running sum x and the z the per-camera kernel hands over (Dp::zimg, converted to fp32 where a chunk gathers it).  So the
-// per-camera kernels of the term loop (cam_cold_sum_binv, cam_cold_sum + the exchange of a sharded context + cam_binv_axpy)
+// per-camera kernels of the term loop (povar_kernels_cam.hpp: cam_cold_sum_binv, cam_cold_sum + the exchange of a sharded context + cam_binv_axpy)
 // run unchanged behind this kernel.
 //
 // What halves: the landmark slots in LDS (h~ and u / g: 12 + 12 bytes instead of 24 + 24; u accumulates with ds_add_f32),

@@ -606,86 +606,22 @@ __device__ inline double binv_row11(const double* Bi, const Y& y) {
   return s;
 }
 
-// b11_c = N_c^T (sigma * sum_items); one wavefront per camera
-POVAR_KERNEL __launch_bounds__(256) void cam_sum_items_h(Dp d, double* out11, const double* ncw) {
-  const int lane = threadIdx.x & 63;
-  const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (c >= d.n_cams) return;
-  double y[12];
-  camera_item_sum(d, c, lane, y);
+// Entry `lane` (< 12) of z = sigma (.) (N_c x) with x's entry `lane` in s (lanes 0..10; 0 in the others): p = [0; x] -
+// beta w (w[1:] . x), the products summed over lanes 0..15.  Every lane of the wavefront calls it: the ONE body of the z of
+// step 2 -- cam_binv_axpy_h, cam_cold_sum_binv_h (povar_kernels_cam.hpp) and series_res_h (povar_kernels_res.hpp).  The lane's
+// operands as values (w_next = w[lane + 1], w_l = w[lane], sig_l = sigma[lane]: a kernel may have requested them long before) ...
+__device__ inline double nc_z_entry(int lane, double s, double w_next, double w_l, double beta, double sig_l) {
+  double wt = lane < 11 ? w_next * s : 0.0;
 #pragma unroll
-  for (int j = 0; j < 12; ++j) y[j] *= d.sigma[12 * (size_t)c + j];
-  double o[11];
-  nt_apply(ncw + 13 * (size_t)c, ncw[13 * (size_t)c + 12], y, o);
-  if (lane < 11) {
-    double v = 0;
-#pragma unroll
-    for (int j = 0; j < 11; ++j) v = (lane == j) ? o[j] : v;
-    out11[11 * (size_t)c + lane] = v;
-  }
-}
-
-// K9' + K11': tmp11 = B^-1 y11, accum11 (+)= tmp11, z = sigma * (N_c tmp11)
-// (right_mul_b_inv_joint + loop body of solve_joint, linearization_power_varproj.hpp:246-257, 342-360).
-// mode 0: y11 = -b11; 1: y12 = sigma * sum of scatter items, y11 = N^T y12; 2: y12 = dense d.y (all-reduced)
-POVAR_KERNEL __launch_bounds__(K9_CAMS * 64) void cam_binv_axpy_h(Dp d, int mode, int want_norms, const double* ncw) {
-  if (mode != 0 && d.flags[1]) return;
-  __shared__ double sh[K9_CAMS * 2];
-  const int lane = threadIdx.x & 63;
-  const int c = blockIdx.x * K9_CAMS + (threadIdx.x >> 6);
-  const bool in = c < d.n_cams;
-  double y11[11];
-#pragma unroll
-  for (int j = 0; j < 11; ++j) y11[j] = 0;
-  const double* w = ncw + 13 * (size_t)(in ? c : 0);
-  const double beta = w[12];
-  if (in) {
-    if (mode == 0) {
-#pragma unroll
-      for (int j = 0; j < 11; ++j) y11[j] = -d.b[11 * (size_t)c + j];
-    } else {
-      double y[12];
-#pragma unroll
-      for (int j = 0; j < 12; ++j) y[j] = 0;
-      if (mode == 1) {
-        camera_item_sum(d, c, lane, y);
-#pragma unroll
-        for (int j = 0; j < 12; ++j) y[j] *= d.sigma[12 * (size_t)c + j];
-      } else {
-#pragma unroll
-        for (int j = 0; j < 12; ++j) y[j] = d.y[12 * (size_t)c + j];
-      }
-      nt_apply(w, beta, y, y11);
-    }
-  }
-  double nrm[2] = {0, 0};
-  double s = 0;
-  if (in && lane < 11) {
-    s = binv_row11(d.binv + 144 * (size_t)c + 11 * lane, y11);
-    const size_t idx = 11 * (size_t)c + lane;
-    const double acc = mode == 0 ? s : d.accum[idx] + s;
-    d.tmp[idx] = s;
-    d.accum[idx] = acc;
-    nrm[0] = s * s;
-    nrm[1] = acc * acc;
-  }
-  // p12 = N_c tmp11: p_i = [0; tmp]_i - beta w_i (w[1:] . tmp); lane i < 12 needs tmp_{i-1} and the dot
-  double wt = (in && lane < 11) ? w[lane + 1] * s : 0.0;
-#pragma unroll
-  for (int m = 8; m >= 1; m >>= 1) wt += shfl_xor_d(wt, m);  // lanes 0..15 hold the 11 products
+  for (int m = 8; m >= 1; m >>= 1) wt += shfl_xor_d(wt, m);
   const double prev = shfl_up_d(s, 1);
-  if (in && lane < 12) {
-    const double p = (lane == 0 ? 0.0 : prev) - beta * w[lane] * wt;
-    store_z(d, c, lane, p * d.sigma[12 * (size_t)c + lane]);
-    if (mode == 2) d.y[12 * (size_t)c + lane] = 0;
-  }
-  if (want_norms) {
-    block_sum<2, K9_CAMS * 64>(nrm, sh);
-    if (threadIdx.x == 0) {
-      d.norm_part[2 * (size_t)blockIdx.x] = nrm[0];
-      d.norm_part[2 * (size_t)blockIdx.x + 1] = nrm[1];
-    }
-  }
+  const double p = (lane == 0 ? 0.0 : prev) - beta * w_l * wt;
+  return p * sig_l;
+}
+// ... or read here from the camera's 13 reflector entries (w, beta) and its 12 of sigma
+__device__ inline double nc_z_entry(int lane, double s, const double* w13, const double* sig) {
+  const int l = lane < 12 ? lane : 0;
+  return nc_z_entry(lane, s, lane < 11 ? w13[lane + 1] : 0.0, w13[l], w13[12], sig[l]);
 }
 
 // K10' on the lane-per-landmark layout (right_mul_e0_joint, linearization_power_varproj.hpp:408-453): e0_lpl's
@@ -1444,116 +1380,6 @@ __global__ __launch_bounds__(E0C_BLOCK) void backsub_lpl_h(Dp d, double* part) {
   double sv[1] = {sc};
   block_sum<1, E0C_BLOCK>(sv, sh);
   if (threadIdx.x == 0) part[blockIdx.x] = sv[0];
-}
-
-// cam_cold_sum fused with cam_binv_axpy_h (mode 2) for the unsharded LDSACC term loop of step 2
-// (the step-2 twin of cam_cold_sum_binv): per-camera sum of the E0 row, tangent projection, B^-1 (11x11),
-// AXPY and z = sigma * (N_c tmp) in one kernel.
-template <int NT>
-__global__ __launch_bounds__(NT) void cam_cold_sum_binv_h(Dp d, int want_norms, const double* ncw) {
-  const int done = d.flags[1];
-  __shared__ double sh[4 * 12];
-  const int c = blockIdx.x, t = threadIdx.x;
-  double acc[12];
-#pragma unroll
-  for (int k = 0; k < 12; ++k) acc[k] = 0;
-  const int2 pr = d.cmv.cam_range[c];
-  const int p0 = pr.x, p1 = pr.y;
-  const int r = d.hot_part ? d.cam_hot[c] : 0;
-  const size_t base = 12 * (size_t)c;
-  double bi[11], sg[12], w[12], acc_old = 0;
-  const double beta = ncw[13 * (size_t)c + 12];
-#pragma unroll
-  for (int j = 0; j < 12; ++j) {
-    sg[j] = d.sigma[base + j];
-    w[j] = ncw[13 * (size_t)c + j];
-  }
-  if (t < 11) {
-    const double* Bi = d.binv + 144 * (size_t)c + 11 * t;
-#pragma unroll
-    for (int j = 0; j < 11; ++j) bi[j] = Bi[j];
-    acc_old = d.accum[11 * (size_t)c + t];
-  }
-  if (done) return;
-  constexpr int U = 4;
-  for (int pb = p0 + t; pb < p1; pb += U * NT) {
-    double hx[U], hy[U], hz[U], hw[U];
-    double4 q[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int p = pb + u * NT;
-      const bool in = p < p1;
-      const int pc = in ? p : p0;
-      hx[u] = d.cmv.h[pc];
-      hy[u] = d.cmv.h[d.cmv.n + pc];
-      hz[u] = d.cmv.h[2 * d.cmv.n + pc];
-      hw[u] = d.cmv.h[3 * d.cmv.n + pc];
-      q[u] = in ? d.q4c[d.cmv.src ? d.cmv.src[pc] : pc] : make_double4(0, 0, 0, 0);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      acc[0] += hx[u] * q[u].x; acc[1] += hy[u] * q[u].x; acc[2] += hz[u] * q[u].x; acc[3] += hw[u] * q[u].x;
-      acc[4] += hx[u] * q[u].y; acc[5] += hy[u] * q[u].y; acc[6] += hz[u] * q[u].y; acc[7] += hw[u] * q[u].y;
-      acc[8] += hx[u] * q[u].z; acc[9] += hy[u] * q[u].z; acc[10] += hz[u] * q[u].z; acc[11] += hw[u] * q[u].z;
-    }
-  }
-  if (d.part_range) {  // e0_lpl_h: the camera's partial records are one contiguous run
-    const int2 rr = d.part_range[c];
-    for (int wg = rr.x + t; wg < rr.y; wg += NT) {
-      const double* ip = d.hot_part + (size_t)wg * 12;
-#pragma unroll
-      for (int k = 0; k < 12; ++k) acc[k] += ip[k];
-    }
-  } else if (r > 0 && r <= d.n_hot_acc) {
-    for (int wg = t; wg < d.n_hot_wg; wg += NT) {
-      const double* ip = d.hot_part + ((size_t)(r - 1) * d.n_hot_wg + wg) * 12;
-#pragma unroll
-      for (int k = 0; k < 12; ++k) acc[k] += ip[k];
-    }
-  }
-  block_sum_dpp<12, NT>(acc, sh);  // every thread now holds the 12 ambient sums
-  if (t >= 64) return;
-  double y[12], y11[11];
-#pragma unroll
-  for (int j = 0; j < 12; ++j) y[j] = acc[j] * sg[j];
-  nt_apply(w, beta, y, y11);
-  double s = 0;
-  if (t < 11) {
-#pragma unroll
-    for (int j = 0; j < 11; ++j) s += bi[j] * y11[j];
-  }
-  double nrm[2] = {0, 0};
-  if (t < 11) {
-    const size_t idx = 11 * (size_t)c + t;
-    const double a = acc_old + s;
-    d.tmp[idx] = s;
-    d.accum[idx] = a;
-    nrm[0] = s * s;
-    nrm[1] = a * a;
-  }
-  // p12 = N_c tmp11: p_i = [0; tmp]_i - beta w_i (w[1:] . tmp)
-  double wsel = 0, wsel1 = 0, sgt = 0;
-#pragma unroll
-  for (int j = 0; j < 12; ++j) {
-    wsel = (t == j) ? w[j] : wsel;
-    sgt = (t == j) ? sg[j] : sgt;
-    if (j > 0) wsel1 = (t == j - 1) ? w[j] : wsel1;
-  }
-  double wt = t < 11 ? wsel1 * s : 0.0;
-#pragma unroll
-  for (int m = 8; m >= 1; m >>= 1) wt += shfl_xor_d(wt, m);  // lanes 0..15 hold the 11 products
-  const double prev = shfl_up_d(s, 1);
-  if (t < 12) {
-    const double pa = (t == 0 ? 0.0 : prev) - beta * wsel * wt;
-    store_z(d, c, t, pa * sgt);
-  }
-  if (want_norms) {
-    wave_sum<2>(nrm);
-    if (t == 0) {
-      d.norm_part[2 * (size_t)c] = nrm[0];
-      d.norm_part[2 * (size_t)c + 1] = nrm[1];
-    }
-  }
 }
 
 // K13' (linearizor_power_varproj.cpp:283-305) and the z = sigma * (N_c inc_c) needed by K12'.

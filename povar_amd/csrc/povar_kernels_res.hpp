@@ -267,26 +267,14 @@ struct ResPose {
   }
 };
 
-// Entry `lane` (< 12) of z = sigma (.) (N_c x) with x's entry `lane` in s (lanes 0..10; 0 in the others): p = [0; x] -
-// beta w (w[1:] . x), the products summed over lanes 0..15 as in cam_binv_axpy_h.  Every lane of the wavefront calls it.
-__device__ inline double resh_z_entry(int lane, double s, const double* w13, const double* sig) {
-  double wt = lane < 11 ? w13[lane + 1] * s : 0.0;
-#pragma unroll
-  for (int m = 8; m >= 1; m >>= 1) wt += shfl_xor_d(wt, m);
-  const double prev = shfl_up_d(s, 1);
-  const int l = lane < 12 ? lane : 0;
-  const double p = (lane == 0 ? 0.0 : prev) - w13[12] * w13[l] * wt;
-  return p * sig[l];
-}
-
 // step 2 (solve_joint), with the operator of e0_ck_h (povar_kernels_ck_joint.hpp) and the owner step of cam_cold_sum_binv_h
-// (povar_kernels_joint.hpp).  Landmarks: X and U4 / G4 [4][STRIDE], component-major with the compile-time stride STRIDE = LS T
+// (povar_kernels_cam.hpp).  Landmarks: X and U4 / G4 [4][STRIDE], component-major with the compile-time stride STRIDE = LS T
 // (the instantiation's slot capacity), so that ckh_obs_forward, ckh_obs_backward and ckh_landmark_step run unchanged and the
 // "ckh" error model of tests/rounding_bounds.py is this kernel's too; the slot's lane keeps s (4) and the upper triangle of
 // Hll^-1 (6): entries 4..13 of the 14-double record of V2::lmrec, which both preparation paths write at every prepare.  Lane: the
 // camera's whole P_c (3 x 4, from cams_lin4) and no image points: the step-2 operator does not read them.  Owner: z_c is the
 // AMBIENT 12-vector sigma (N_c x_c); B^-1 11 x 11 (row stride 11), the reflector (w[12], beta) of N_c, sum and term of 11;
-// y11 = N_c^T y (nt_apply), x = B^-1 y11 (binv_row11: the bits of cam_binv_axpy_h), z = sigma (N_c x).  The clamps (landmark
+// y11 = N_c^T y (nt_apply), x = B^-1 y11 (binv_row11: the bits of cam_binv_axpy_h), z = sigma (N_c x) (nc_z_entry).  The clamps (landmark
 // count, slot word, camera slot) are this step's: it may run on an instance cut for step 1 (res_shared_fits)
 struct ResJoint {
   static constexpr int NX = 11;
@@ -349,7 +337,7 @@ struct ResJoint {
       if (!FIRST) A.tmp[11 * o + lane] = s;
       A.acc[11 * o + lane] = a;
     }
-    const double zv = resh_z_entry(lane, s, A.ncw + 13 * o, A.sig + 12 * o);
+    const double zv = nc_z_entry(lane, s, A.ncw + 13 * o, A.sig + 12 * o);
     if (lane < 12) put(zv);
   }
   // sum, last term and its z = sigma N_c x (povar_power_series_step, povar_get_term and povar_apply_joint go on from there)
@@ -357,7 +345,7 @@ struct ResJoint {
     for (int o = wave; o < nO; o += NW) {
       const int c = own_cam[o];
       const double s = lane < 11 ? A.tmp[11 * o + lane] : 0.0;
-      const double zv = resh_z_entry(lane, s, A.ncw + 13 * o, A.sig + 12 * o);
+      const double zv = nc_z_entry(lane, s, A.ncw + 13 * o, A.sig + 12 * o);
       if (lane < 11) {
         d.accum[11 * (size_t)c + lane] = A.acc[11 * o + lane];
         d.tmp[11 * (size_t)c + lane] = s;

@@ -114,7 +114,7 @@ The step-2 bound.  Magnitudes use |N| = |I| + beta |w| |w|^T and |D| = A = (|1/z
 
 -- a small |z| inflates the bound through err(z) / |z|, not through a constant.  With dm = |X| . |Z| and the input error
 Ez = gamma_15 sigma (|[0; x]| + beta |w| (|w[1:]| . |x|)) (an 11-term dot, beta w_i wt, the difference, sigma:
-cam_cold_sum_binv_h, povar_kernels_joint.hpp:1525-1538; cam_binv_axpy_h :663-669):
+nc_z_entry, povar_kernels_joint.hpp:613-620: the one body of cam_cold_sum_binv_h and cam_binv_axpy_h, povar_kernels_cam.hpp):
 
     Ed   = |X| . Ez + gamma_4 dm
     tm_k = sw (A00 dm_k + A_k2 dm_2),    Et_k = sw (A00 Ed_k + A_k2 Ed_2 + E00 dm_k + E_k2 dm_2) + (gamma_3 + rho) tm_k
@@ -142,7 +142,7 @@ The per-observation and the ambient form have the SAME magnitudes: jl4m^T tm = |
            sw (D00 P + D02 P2) s of hom_jl4 (:37-46): product, FMA, two scalings, 4 (it replaces e's count, not adds to it;
            6 and 4 are both upper counts of the same sum Ev).
   klm      ambient, ckh_landmark_step (ck_joint:176-194): s o U4 (1), aw a 4-term dot (4), hbeta aw hw and the difference
-           (3): 8.  Jl3 form, jl3_of_jl4 (:56-63): the same 7, then jl3 t0 + jl3' t1 (:216, :351, :846): 9.
+           (3): 8.  Jl3 form, jl3_of_jl4 (:56-63): the same 7, then jl3 t0 + jl3' t1 (:216, :351, :782): 9.
   n_l      the landmark's sum in any order (LDS atomics in arrival order, a segmented scan, wave_sum of lm_long): gamma_{n_l}.
   back     G4: hbeta times a 3-term dot (4), gw hw, the difference, s (3): gamma_7 (ck_joint:189-193).  Jl3 form: jl3_of_jl4's
            7 on the row, hom_jl4's 4 where the ambient form has dot4's 4, a 3-term dot where it has hom_jp_x's 3: the same 14.
@@ -150,7 +150,7 @@ The per-observation and the ambient form have the SAME magnitudes: jl4m^T tm = |
            either stride, partial records of capped accumulators, the cold view, block_sum_dpp; adding zeros is exact):
            gamma_{n_c}.
   tail     sigma (1); nt_apply (:589-595): a 12-term dot, beta w wy (2), the difference: gamma_15; the B^-1 row: an 11-term
-           dot (cam_cold_sum_binv_h :1508-1513; cam_binv_axpy_h :641-654 after cam_cold_sum: the same counts).
+           dot (binv_row11 :602-607; CamJoint::solve, povar_kernels_cam.hpp:189-200; cam_binv_axpy_h :364-401 after cam_cold_sum: the same counts).
   dN       house4 (:48-55): nv = sqrt of a 4-term sum of squares (gamma_4 at most), w0 = X.x +- nv with equal signs (one
            more: gamma_5), beta = 2 / (sum of four squares, w0^2 among them: 2 gamma_5 + 1, the sum 4, the division 1:
            gamma_15 at most); an entry beta w_i w_j of N moves by gamma_15 + 2 gamma_5 <= gamma_25 of itself <= of |N|.
@@ -807,7 +807,7 @@ def emulate_joint(prob, x, form):
     """The next term in fp64 in the kernels' operation order.  form "ambient": e0_ck_h (ckh_project's one division, U4 summed
     in row order, N_l, s, Hll^-1 once per landmark); "jl3": e0_lpl_h / e0_lm_cached_h / OpE0H (hom_project's three divisions,
     hom_jl4, jl3_of_jl4 per observation).  Both: the stored weight's sqrt twice per pass, the camera sums in row order, then
-    cam_cold_sum_binv_h's tail.  (NumPy does not contract to FMAs: every product rounds.)"""
+    cam_cold_sum_binv_h's tail (CamJoint::solve, povar_kernels_cam.hpp).  (NumPy does not contract to FMAs: every product rounds.)"""
     f = np.float64
     nC = prob.n_cams
     x = np.asarray(x, dtype=f).reshape(nC, 11)

@@ -57,15 +57,12 @@ def main():
 """ + s[j:]
     open(p, "w").write(s)
 
-    # ---- povar_kernels.hpp: the per-camera kernel without its partial-record loads
-    p = os.path.join(b, "povar_kernels.hpp")
+    # ---- povar_kernels_cam.hpp: the per-camera gather (cam_row_sum: cam_cold_sum_binv and its kin) without its partial-record loads
+    p = os.path.join(b, "povar_kernels_cam.hpp")
     s = open(p).read()
-    i = s.index("__global__ __launch_bounds__(NT) void cam_cold_sum_binv(Dp d, int want_norms) {")
-    old = "  if (d.part_range) {  // e0_lpl: the camera's partial records are one contiguous run\n    for (int w = rr.x + t; w < rr.y; w += NT) {"
-    k = s.index(old, i)
-    e = s.index("  block_sum_dpp<12, NT>(acc, sh);  // every thread now holds the 12 sums", k)
-    s = s[:k] + "#if !defined(POVAR_CK_EXP_NOPART) && !defined(POVAR_CK_EXP_NOPART_LOADS)\n" + s[k:e] + \
-        "#else\n  acc[0] = (double)(rr.y - rr.x + r);\n#endif\n" + s[e:]
+    s = sub(s, "  part_add(d, part_run(d, rq.part), t, NT, acc);\n",
+            "#if !defined(POVAR_CK_EXP_NOPART) && !defined(POVAR_CK_EXP_NOPART_LOADS)\n  part_add(d, part_run(d, rq.part), t, NT, acc);\n"
+            "#else\n  acc[0] = (double)(rq.part.y - rq.part.x + rq.part.z);\n#endif\n")
     open(p, "w").write(s)
 
     # ---- povar_kernels_ck.hpp
