@@ -1221,13 +1221,6 @@ __device__ inline void lpl_read_p3(const double2* h, double* P3) {
   P3[8] = h[10].x;
 }
 
-// The row stream of one wavefront is a static address sequence: tile t forward rows, tile t backward rows (the same
-// rows again, now L2 hits), tile t + 16 ...  A scalar prefetch cursor runs LPL_DEPTH rows ahead of the consumer
-// along that sequence, across the pass and tile boundaries, so the wavefront never waits for a load it has just
-// issued (s_waitcnt vmcnt retires in issue order: the e0_lm_cached loop exposed two HBM latencies per bin that way).
-// The next tile's landmark record is requested when the backward pass starts: G is dead by then (g = G u is
-// formed), so only the three coordinates need a second set of registers.
-constexpr int LPL_DEPTH = 3;
 // Accumulator slots.  ds_add_f64 collisions inside a 32-lane half serialise, and the most observed cameras collect
 // several observations per row (Zipf hub: 9 % of all observations): the LPL_HUBS hottest cameras therefore get four
 // accumulator replicas each, chosen per observation by the layout (lpl_layout.hpp), summed at the flush.
@@ -1248,15 +1241,13 @@ __host__ __device__ inline size_t lpl_lds_bytes(int n_hot) {
 // where a cold observation of row j, lane `lane` leaves its q in Dp::q4c (fl, nh: tile.w, tile.z; lpl_layout.hpp)
 __device__ inline int lpl_cold_q(int fl, int nh, int j, int lane) { return ((fl >> 4) + (j - nh)) * WAVE + lane; }
 
-struct LplRow {
-  double2 uv;
-  int cw;
-  double w;
-};
-struct LplCursor {  // wave-uniform (SGPRs)
-  int t, pass, j, row0, k;
-};
+}  // namespace povar
+#include "povar_kernels_lpl.hpp"  // tile source, row streams, accumulator flush and record readers of the kernels below
+namespace povar {
 
+// The rows come from an LplStream2 (three rows ahead, across the pass and tile boundaries).  The next tile's landmark record
+// is requested when the backward pass starts: G is dead by then (g = G u is formed), so only the three coordinates need a
+// second set of registers.
 template <bool ROBUST>
 __global__ __launch_bounds__(E0C_BLOCK) void e0_lpl(Dp d, double* hot_out) {
   const int done = d.flags[1];  // requested first, tested after the LDS staging (no global side effects before)
@@ -1292,75 +1283,13 @@ __global__ __launch_bounds__(E0C_BLOCK) void e0_lpl(Dp d, double* hot_out) {
     frec[u] = i < n_hot * 6 ? v.wg_slot_rec[cam0 + i / 6] : 0;
   }
   const int lane = threadIdx.x & 63;
-  // The workgroup's tiles are sorted longest first; its wavefronts take them on demand (one LDS counter), so a
-  // wavefront's last tile is a short one.  The workgroups carry equal observation totals (lpl_layout.hpp).
-  const int t_begin = __builtin_amdgcn_readfirstlane(v.wg_tile_off[blockIdx.x]);
-  const int t_end = __builtin_amdgcn_readfirstlane(v.wg_tile_off[blockIdx.x + 1]);
-  auto grab = [&]() -> int {
-    int n = 0;
-    if (lane == 0) n = __hip_atomic_fetch_add(grab_ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    n = __builtin_amdgcn_readfirstlane(n);
-    const long long t = (long long)t_begin + n;
-    return t < t_end ? (int)t : t_end;
-  };
-
-  // tile table through the scalar cache (constant address space + wave-uniform index => s_load_dwordx4): a vector
-  // load here would put a vmcnt(0) drain inside the row pipeline
-  typedef const int __attribute__((address_space(4))) * cint_p;
-  const cint_p tiles = (cint_p)(uintptr_t)v.tile;
-  auto tile_info = [&](int t, int& row0, int& k, int& nh, int& fl) {
-    row0 = tiles[4 * t];
-    k = tiles[4 * t + 1];
-    nh = tiles[4 * t + 2];
-    fl = tiles[4 * t + 3];
-  };
-  LplCursor pc;
-  {
-    const long long t0 = (long long)t_begin + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    pc.t = t0 < t_end ? (int)t0 : t_end;
-  }
-  pc.pass = 0;
-  pc.j = 0;
-  pc.row0 = 0;
-  pc.k = 1;
-  int c_t = pc.t, c_row0 = 0, c_k = 0, c_nh = 0, c_fl = 0;
-  // the tile after the one being consumed, taken when the consumer enters a tile (the first one after the staging
-  // barrier below: the counter lives in LDS): the prefetch cursor runs at most LPL_DEPTH = 3 rows ahead and a tile has
-  // at least 4 row steps, so it never needs more than this one -- and not before the consumer has started
-  int nx_t = t_end;
-  if (c_t < t_end) {
-    tile_info(c_t, c_row0, c_k, c_nh, c_fl);
-    pc.row0 = c_row0;
-    pc.k = c_k;
-  }
-  // request the row under the prefetch cursor and advance it
-  auto issue = [&](LplRow& r) {
-    if (pc.t < t_end) {
-      // the backward pass walks the rows in reverse: the rows read last are the ones most likely still in L2
-      const size_t i = ((size_t)pc.row0 + (pc.pass ? pc.k - 1 - pc.j : pc.j)) * WAVE + lane;
-      r.uv = v.uv[i];
-      r.cw = v.cw[i];
-      if (ROBUST) r.w = v.w[i];
-      if (++pc.j == pc.k) {
-        pc.j = 0;
-        if (++pc.pass == 2) {
-          pc.pass = 0;
-          pc.t = nx_t;
-          if (pc.t < t_end) {
-            int nh_, fl_;
-            tile_info(pc.t, pc.row0, pc.k, nh_, fl_);
-          }
-        }
-      }
-    }
-  };
-  LplRow n1, n2, n3;
-  n1.cw = n2.cw = n3.cw = -1;
-  n1.w = n2.w = n3.w = 1.0;
-  n1.uv = n2.uv = n3.uv = make_double2(0, 0);
-  issue(n1);
-  issue(n2);
-  issue(n3);
+  const LplTiles T(v, grab_ctr, lane);
+  const int t_end = T.t_end;
+  int c_t = T.nth(__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))), c_row0 = 0, c_k = 0, c_nh = 0, c_fl = 0;
+  if (c_t < t_end) T.info(c_t, c_row0, c_k, c_nh, c_fl);
+  // the first rows go out now; the tile after this one is taken behind the staging barrier below (the counter lives in LDS)
+  LplStream2<ROBUST> rows;
+  rows.start(T, v, c_t, c_row0, c_k, t_end);
   double hx = 0, hy = 0, hz = 0, G00 = 0, G01 = 0, G02 = 0, G11 = 0, G12 = 0, G22 = 0;
   if (c_t < t_end) {
     const double* rp = v.lmrec + ((size_t)c_t * 9) * WAVE + lane;
@@ -1383,14 +1312,11 @@ __global__ __launch_bounds__(E0C_BLOCK) void e0_lpl(Dp d, double* hot_out) {
   }
   __syncthreads();
   if (done) return;
-  if (c_t < t_end) nx_t = grab();
+  if (c_t < t_end) rows.ahead(T.grab());
   while (c_t < t_end) {
     double red[3] = {0, 0, 0};
     for (int j = 0; j < c_k; ++j) {
-      const LplRow cur = n1;
-      n1 = n2;
-      n2 = n3;
-      issue(n3);
+      const LplRow cur = rows.next(T, v);
       double zz[12], P3[9];
       LplObs o;
       o.set(d, cur.uv, ROBUST ? cur.w : 1.0);
@@ -1419,7 +1345,7 @@ __global__ __launch_bounds__(E0C_BLOCK) void e0_lpl(Dp d, double* hot_out) {
     const double g[3] = {G00 * red[0] + G01 * red[1] + G02 * red[2], G01 * red[0] + G11 * red[1] + G12 * red[2],
                          G02 * red[0] + G12 * red[1] + G22 * red[2]};
     // the next tile's record: G into its own (now dead) registers, the coordinates into a second set
-    const int n_t = nx_t;
+    const int n_t = rows.nx_t;
     double nhx = 0, nhy = 0, nhz = 0;
     if (n_t < t_end) {
       const double* rp = v.lmrec + ((size_t)n_t * 9) * WAVE + lane;
@@ -1428,10 +1354,7 @@ __global__ __launch_bounds__(E0C_BLOCK) void e0_lpl(Dp d, double* hot_out) {
     }
     for (int jj = 0; jj < c_k; ++jj) {
       const int j = c_k - 1 - jj;
-      const LplRow cur = n1;
-      n1 = n2;
-      n2 = n3;
-      issue(n3);
+      const LplRow cur = rows.next(T, v);
       double P3[9], q[3];
       LplObs o;
       o.set(d, cur.uv, ROBUST ? cur.w : 1.0);
@@ -1455,8 +1378,8 @@ __global__ __launch_bounds__(E0C_BLOCK) void e0_lpl(Dp d, double* hot_out) {
     }
     c_t = n_t;
     if (c_t < t_end) {
-      tile_info(c_t, c_row0, c_k, c_nh, c_fl);
-      nx_t = grab();
+      T.info(c_t, c_row0, c_k, c_nh, c_fl);
+      rows.ahead(T.grab());
     }
     hx = nhx; hy = nhy; hz = nhz;
   }
@@ -1467,20 +1390,8 @@ __global__ __launch_bounds__(E0C_BLOCK) void e0_lpl(Dp d, double* hot_out) {
 #pragma unroll
     for (int u = 0; u < FPASSES; ++u) {
       const int i = threadIdx.x + u * E0C_BLOCK;
-      if (i < n_hot * 6) {
-        const int r = i / 6, m = 2 * (i % 6);
-        const double* a0 = acc + m * n_slots;
-        const double* a1 = a0 + n_slots;
-        double2 s;
-        if (r < hubs) {
-          s.x = (a0[4 * r] + a0[4 * r + 1]) + (a0[4 * r + 2] + a0[4 * r + 3]);
-          s.y = (a1[4 * r] + a1[4 * r + 1]) + (a1[4 * r + 2] + a1[4 * r + 3]);
-        } else {
-          s.x = a0[r + 3 * hubs];
-          s.y = a1[r + 3 * hubs];
-        }
-        reinterpret_cast<double2*>(hot_out + (size_t)frec[u] * 12)[i % 6] = s;
-      }
+      if (i < n_hot * 6)
+        reinterpret_cast<double2*>(hot_out + (size_t)frec[u] * 12)[i % 6] = lpl_acc_sum(acc, n_slots, hubs, i / 6, i % 6);
     }
   }
   if (d.p2p_epoch && blockIdx.x == 0 && threadIdx.x == 0) *d.p2p_epoch += 1;  // one tick per term, read by the next kernels
@@ -1488,8 +1399,8 @@ __global__ __launch_bounds__(E0C_BLOCK) void e0_lpl(Dp d, double* hot_out) {
 
 // ------------------------------------------------------------------------------------------
 // K7 on the lane-per-landmark layout: get_Hll_inv_add_Hpp_b_pOSE / _poBA (landmark_block.hpp:510-572), the
-// landmark half of prepare_Hb_pOSE.  Same structure as e0_lpl (lane = landmark, row stream with a three-row
-// prefetch cursor, camera records and per-camera accumulators in LDS, cold observations through q4c): the forward
+// landmark half of prepare_Hb_pOSE.  Same structure as e0_lpl (lane = landmark, rows from an LplStream2,
+// camera records and per-camera accumulators in LDS, cold observations through q4c): the forward
 // pass accumulates Hll = Jl^T Jl and Jl^T r in registers, the lane then inverts Hll (+ lambda I for
 // POWER_SCHUR_COMPLEMENT), stores Hll^-1 and the per-term landmark records, and the backward pass adds
 // Jp^T (r - Jl w) into the camera accumulators.  The tile (Jl, r) is rebuilt from (P_c, x_l, u, v, sqrt(w), s_l):
@@ -1550,62 +1461,12 @@ __global__ __launch_bounds__(E0C_BLOCK) void prepare_lpl(Dp d, double* hot_out) 
   }
   __syncthreads();
   const int lane = threadIdx.x & 63;
-  const int t_begin = __builtin_amdgcn_readfirstlane(v.wg_tile_off[blockIdx.x]);
-  const int t_end = __builtin_amdgcn_readfirstlane(v.wg_tile_off[blockIdx.x + 1]);
-  auto grab = [&]() -> int {
-    int n = 0;
-    if (lane == 0) n = __hip_atomic_fetch_add(grab_ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    n = __builtin_amdgcn_readfirstlane(n);
-    const long long t = (long long)t_begin + n;
-    return t < t_end ? (int)t : t_end;
-  };
-  typedef const int __attribute__((address_space(4))) * cint_p;
-  const cint_p tiles = (cint_p)(uintptr_t)v.tile;
-  auto tile_info = [&](int t, int& row0, int& k, int& nh, int& fl) {
-    row0 = tiles[4 * t];
-    k = tiles[4 * t + 1];
-    nh = tiles[4 * t + 2];
-    fl = tiles[4 * t + 3];
-  };
-  LplCursor pc;
-  pc.t = grab();
-  pc.pass = 0;
-  pc.j = 0;
-  pc.row0 = 0;
-  pc.k = 1;
-  int c_t = pc.t, c_row0 = 0, c_k = 0, c_nh = 0, c_fl = 0, nx_t = t_end;
-  if (c_t < t_end) {
-    tile_info(c_t, c_row0, c_k, c_nh, c_fl);
-    pc.row0 = c_row0;
-    pc.k = c_k;
-    nx_t = grab();
-  }
-  auto issue = [&](LplRow& r) {
-    if (pc.t < t_end) {
-      const size_t i = ((size_t)pc.row0 + (pc.pass ? pc.k - 1 - pc.j : pc.j)) * WAVE + lane;
-      r.uv = v.uv[i];
-      r.cw = v.cw[i];
-      if (ROBUST) r.w = v.w[i];
-      if (++pc.j == pc.k) {
-        pc.j = 0;
-        if (++pc.pass == 2) {
-          pc.pass = 0;
-          pc.t = nx_t;
-          if (pc.t < t_end) {
-            int nh_, fl_;
-            tile_info(pc.t, pc.row0, pc.k, nh_, fl_);
-          }
-        }
-      }
-    }
-  };
-  LplRow n1, n2, n3;
-  n1.cw = n2.cw = n3.cw = -1;
-  n1.w = n2.w = n3.w = 1.0;
-  n1.uv = n2.uv = n3.uv = make_double2(0, 0);
-  issue(n1);
-  issue(n2);
-  issue(n3);
+  const LplTiles T(v, grab_ctr, lane);
+  const int t_end = T.t_end;
+  int c_t = T.grab(), c_row0 = 0, c_k = 0, c_nh = 0, c_fl = 0;
+  if (c_t < t_end) T.info(c_t, c_row0, c_k, c_nh, c_fl);
+  LplStream2<ROBUST> rows;
+  rows.start(T, v, c_t, c_row0, c_k, c_t < t_end ? T.grab() : t_end);
   while (c_t < t_end) {
     // the lane's landmark: coordinates and Jl column scale (gathers; once per tile)
     const int lm = v.lm_of[(size_t)c_t * WAVE + lane];
@@ -1614,10 +1475,7 @@ __global__ __launch_bounds__(E0C_BLOCK) void prepare_lpl(Dp d, double* hot_out) 
     const double hx = h4.x, hy = h4.y, hz = h4.z;
     double red[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     for (int j = 0; j < c_k; ++j) {
-      const LplRow cur = n1;
-      n1 = n2;
-      n2 = n3;
-      issue(n3);
+      const LplRow cur = rows.next(T, v);
       if (cur.cw == -1) continue;
       double P[12];
       if (cur.cw >= 0) prep_read_rec(hot + lpl_cw_slot(cur.cw) * PREP_STRIDE, P);
@@ -1665,10 +1523,7 @@ __global__ __launch_bounds__(E0C_BLOCK) void prepare_lpl(Dp d, double* hot_out) 
     }
     for (int jj = 0; jj < c_k; ++jj) {
       const int j = c_k - 1 - jj;
-      const LplRow cur = n1;
-      n1 = n2;
-      n2 = n3;
-      issue(n3);
+      const LplRow cur = rows.next(T, v);
       if (cur.cw == -1) continue;
       double P[12];
       if (cur.cw >= 0) prep_read_rec(hot + lpl_cw_slot(cur.cw) * PREP_STRIDE, P);
@@ -1691,27 +1546,15 @@ __global__ __launch_bounds__(E0C_BLOCK) void prepare_lpl(Dp d, double* hot_out) 
         d.q4c[d.q_rows ? lpl_cold_q(c_fl, c_nh, j, lane) : v.cpos[((size_t)c_row0 + j) * WAVE + lane]] = make_double4(q.x, q.y, q.z, 0);
       }
     }
-    c_t = nx_t;
+    c_t = rows.nx_t;
     if (c_t < t_end) {
-      tile_info(c_t, c_row0, c_k, c_nh, c_fl);
-      nx_t = grab();
+      T.info(c_t, c_row0, c_k, c_nh, c_fl);
+      rows.ahead(T.grab());
     }
   }
   __syncthreads();
-  for (int i = threadIdx.x; i < n_hot * 6; i += E0C_BLOCK) {
-    const int r = i / 6, m = 2 * (i % 6);
-    const double* a0 = acc + m * n_slots;
-    const double* a1 = a0 + n_slots;
-    double2 s;
-    if (r < hubs) {
-      s.x = (a0[4 * r] + a0[4 * r + 1]) + (a0[4 * r + 2] + a0[4 * r + 3]);
-      s.y = (a1[4 * r] + a1[4 * r + 1]) + (a1[4 * r + 2] + a1[4 * r + 3]);
-    } else {
-      s.x = a0[r + 3 * hubs];
-      s.y = a1[r + 3 * hubs];
-    }
-    reinterpret_cast<double2*>(hot_out + (size_t)v.wg_slot_rec[cam0 + r] * 12)[i % 6] = s;
-  }
+  for (int i = threadIdx.x; i < n_hot * 6; i += E0C_BLOCK)
+    reinterpret_cast<double2*>(hot_out + (size_t)v.wg_slot_rec[cam0 + i / 6] * 12)[i % 6] = lpl_acc_sum(acc, n_slots, hubs, i / 6, i % 6);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1746,81 +1589,23 @@ __global__ __launch_bounds__(E0C_BLOCK) void backsub_lpl(Dp d, double* part) {
   }
   __syncthreads();
   const int lane = threadIdx.x & 63;
-  const int t_begin = __builtin_amdgcn_readfirstlane(v.wg_tile_off[blockIdx.x]);
-  const int t_end = __builtin_amdgcn_readfirstlane(v.wg_tile_off[blockIdx.x + 1]);
-  auto grab = [&]() -> int {
-    int n = 0;
-    if (lane == 0) n = __hip_atomic_fetch_add(grab_ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    n = __builtin_amdgcn_readfirstlane(n);
-    const long long t = (long long)t_begin + n;
-    return t < t_end ? (int)t : t_end;
-  };
-  typedef const int __attribute__((address_space(4))) * cint_p;
-  const cint_p tiles = (cint_p)(uintptr_t)v.tile;
-  auto tile_info = [&](int t, int& row0, int& k, int& nh, int& fl) {
-    row0 = tiles[4 * t];
-    k = tiles[4 * t + 1];
-    nh = tiles[4 * t + 2];
-    fl = tiles[4 * t + 3];
-  };
-  LplCursor pc;
-  pc.t = grab();
-  pc.pass = 0;
-  pc.j = 0;
-  pc.row0 = 0;
-  pc.k = 1;
-  int c_t = pc.t, c_row0 = 0, c_k = 0, c_nh = 0, c_fl = 0, nx_t = t_end;
-  if (c_t < t_end) {
-    tile_info(c_t, c_row0, c_k, c_nh, c_fl);
-    pc.row0 = c_row0;
-    pc.k = c_k;
-    nx_t = grab();
-  }
-  auto issue = [&](LplRow& r) {
-    if (pc.t < t_end) {
-      const size_t i = ((size_t)pc.row0 + (pc.pass ? pc.k - 1 - pc.j : pc.j)) * WAVE + lane;
-      r.uv = v.uv[i];
-      r.cw = v.cw[i];
-      if (ROBUST) r.w = v.w[i];
-      if (++pc.j == pc.k) {
-        pc.j = 0;
-        if (++pc.pass == 2) {
-          pc.pass = 0;
-          pc.t = nx_t;
-          if (pc.t < t_end) {
-            int nh_, fl_;
-            tile_info(pc.t, pc.row0, pc.k, nh_, fl_);
-          }
-        }
-      }
-    }
-  };
-  // 12 consecutive doubles of a record (LDS) or of a camera-indexed global array (cold camera)
-  auto read12 = [&](const double2* hp, double4 (&o)[3]) {
-    const double2 b0 = hp[0], b1 = hp[1], b2 = hp[2], b3 = hp[3], b4 = hp[4], b5 = hp[5];
-    o[0] = make_double4(b0.x, b0.y, b1.x, b1.y);
-    o[1] = make_double4(b2.x, b2.y, b3.x, b3.y);
-    o[2] = make_double4(b4.x, b4.y, b5.x, b5.y);
-  };
-  // which: 0 P_new, 1 inc, 2 P_lin.  LDS pointer or global pointer, never a select of the two (a generic pointer turns
-  // the reads into flat_loads)
+  const LplTiles T(v, grab_ctr, lane);
+  const int t_end = T.t_end;
+  int c_t = T.grab(), c_row0 = 0, c_k = 0, c_nh = 0, c_fl = 0;
+  if (c_t < t_end) T.info(c_t, c_row0, c_k, c_nh, c_fl);
+  LplStream2<ROBUST> rows;
+  rows.start(T, v, c_t, c_row0, c_k, c_t < t_end ? T.grab() : t_end);
+  // which: 0 P_new, 1 inc, 2 P_lin, from the record (LDS) or from the camera-indexed global arrays (cold camera)
   auto read_part = [&](int cw, int which, double4 (&o)[3]) {
     if (cw >= 0) {
-      read12(hot + lpl_cw_slot(cw) * BACK_STRIDE + 6 * which, o);
+      lpl_read12(hot + lpl_cw_slot(cw) * BACK_STRIDE + 6 * which, o);
     } else {
       const int cam = d.hot_cams[-2 - cw];
       const double* src = which == 0 ? reinterpret_cast<const double*>(d.cams4)
                                      : which == 1 ? d.inc : reinterpret_cast<const double*>(d.cams_lin4);
-      read12(reinterpret_cast<const double2*>(src + 12 * (size_t)cam), o);
+      lpl_read12(reinterpret_cast<const double2*>(src + 12 * (size_t)cam), o);
     }
   };
-  LplRow n1, n2, n3;
-  n1.cw = n2.cw = n3.cw = -1;
-  n1.w = n2.w = n3.w = 1.0;
-  n1.uv = n2.uv = n3.uv = make_double2(0, 0);
-  issue(n1);
-  issue(n2);
-  issue(n3);
   double sc = 0;
   while (c_t < t_end) {
     const int lm = v.lm_of[(size_t)c_t * WAVE + lane];
@@ -1829,10 +1614,7 @@ __global__ __launch_bounds__(E0C_BLOCK) void backsub_lpl(Dp d, double* part) {
     const double4 h = v.lmx[li], hl = v.lml[li], s4 = v.lsc[li];
     double red[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     for (int j = 0; j < c_k; ++j) {
-      const LplRow cur = n1;
-      n1 = n2;
-      n2 = n3;
-      issue(n3);
+      const LplRow cur = rows.next(T, v);
       if (cur.cw == -1) continue;
       double4 pp[3];
       read_part(cur.cw, 0, pp);
@@ -1867,10 +1649,7 @@ __global__ __launch_bounds__(E0C_BLOCK) void backsub_lpl(Dp d, double* part) {
       if (lane == (sg & 255)) d.lms4[lm] = hn;
     }
     for (int jj = 0; jj < c_k; ++jj) {
-      const LplRow cur = n1;
-      n1 = n2;
-      n2 = n3;
-      issue(n3);
+      const LplRow cur = rows.next(T, v);
       if (cur.cw == -1) continue;
       double4 zz[3], pl[3];
       read_part(cur.cw, 1, zz);
@@ -1887,10 +1666,10 @@ __global__ __launch_bounds__(E0C_BLOCK) void backsub_lpl(Dp d, double* part) {
         sc -= ji * (0.5 * ji + sw * rr[r]);
       }
     }
-    c_t = nx_t;
+    c_t = rows.nx_t;
     if (c_t < t_end) {
-      tile_info(c_t, c_row0, c_k, c_nh, c_fl);
-      nx_t = grab();
+      T.info(c_t, c_row0, c_k, c_nh, c_fl);
+      rows.ahead(T.grab());
     }
   }
   double sv[1] = {sc};
@@ -1928,63 +1707,29 @@ __global__ __launch_bounds__(E0C_BLOCK) void lpl_pass(Dp d, double* part) {
   }
   __syncthreads();
   const int lane = threadIdx.x & 63;
-  const int t_begin = __builtin_amdgcn_readfirstlane(v.wg_tile_off[blockIdx.x]);
-  const int t_end = __builtin_amdgcn_readfirstlane(v.wg_tile_off[blockIdx.x + 1]);
-  auto grab = [&]() -> int {
-    int n = 0;
-    if (lane == 0) n = __hip_atomic_fetch_add(grab_ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    n = __builtin_amdgcn_readfirstlane(n);
-    const long long t = (long long)t_begin + n;
-    return t < t_end ? (int)t : t_end;
-  };
-  typedef const int __attribute__((address_space(4))) * cint_p;
-  const cint_p tiles = (cint_p)(uintptr_t)v.tile;
-  // single pass: the prefetch cursor walks tile after tile, three rows ahead (a tile has at least two rows here, so the
-  // cursor may need the tile after the next one: two tiles are taken ahead)
-  int c_t = grab(), q1 = c_t < t_end ? grab() : t_end, q2 = q1 < t_end ? grab() : t_end;
-  int pc_t = c_t, pc_ahead = 0, pc_j = 0, pc_row0 = 0, pc_k = 1;  // pc_ahead: 0 = c_t, 1 = q1, 2 = q2
-  if (pc_t < t_end) { pc_row0 = tiles[4 * pc_t]; pc_k = tiles[4 * pc_t + 1]; }
-  auto issue = [&](LplRow& r) {
-    if (pc_t < t_end) {
-      const size_t i = ((size_t)pc_row0 + pc_j) * WAVE + lane;
-      r.uv = v.uv[i];
-      r.cw = v.cw[i];
-      if (++pc_j == pc_k) {
-        pc_j = 0;
-        ++pc_ahead;
-        pc_t = pc_ahead == 1 ? q1 : pc_ahead == 2 ? q2 : t_end;
-        if (pc_t < t_end) { pc_row0 = tiles[4 * pc_t]; pc_k = tiles[4 * pc_t + 1]; }
-      }
-    }
-  };
-  LplRow n1, n2, n3;
-  n1.cw = n2.cw = n3.cw = -1;
-  n1.w = n2.w = n3.w = 1.0;
-  n1.uv = n2.uv = n3.uv = make_double2(0, 0);
-  issue(n1);
-  issue(n2);
-  issue(n3);
+  const LplTiles T(v, grab_ctr, lane);
+  const int t_end = T.t_end;
+  int c_t = T.grab();
+  LplStream1 rows;
+  rows.start(T, v, c_t);
   double sc[3] = {0, 0, 0};
   int bad = 0;
   while (c_t < t_end) {
-    const int c_row0 = tiles[4 * c_t], c_k = tiles[4 * c_t + 1], c_fl = tiles[4 * c_t + 3];
+    int c_row0, c_k, c_nh, c_fl;
+    T.info(c_t, c_row0, c_k, c_nh, c_fl);
     const double4 h = v.lmx[(size_t)c_t * WAVE + lane];
     if (MODE == 0) v.lml[(size_t)c_t * WAVE + lane] = h;  // the linearisation point, lane-ordered, is left behind
     double red[3] = {0, 0, 0};
     for (int j = 0; j < c_k; ++j) {
-      const LplRow cur = n1;
-      n1 = n2;
-      n2 = n3;
-      issue(n3);
+      const LplRow cur = rows.next(T, v);
       if (cur.cw == -1) continue;
       // (a select of an LDS and a global pointer: six flat_loads.  Measured against ds_read / global_load in two branches
       // -- profiles/r02_ablations.txt item 16 --: the branches join with a wait on both counters, which drains the row
       // prefetch every step: 50 instead of 44 us here; the two-pass kernels with their longer steps gain from the split)
       const double2* hp = cur.cw >= 0 ? hot + lpl_cw_slot(cur.cw) * PASS_STRIDE
                                       : reinterpret_cast<const double2*>(cams + 3 * (size_t)d.hot_cams[-2 - cur.cw]);
-      const double2 b0 = hp[0], b1 = hp[1], b2 = hp[2], b3 = hp[3], b4 = hp[4], b5 = hp[5];
-      const Cam P = {make_double4(b0.x, b0.y, b1.x, b1.y), make_double4(b2.x, b2.y, b3.x, b3.y),
-                     make_double4(b4.x, b4.y, b5.x, b5.y)};
+      Cam P;
+      lpl_read_cam(hp, P);
       double res[4];
       pose_residual(d, P, h, cur.uv.x, cur.uv.y, res);
       const double r2 = res[0] * res[0] + res[1] * res[1] + res[2] * res[2] + res[3] * res[3];
@@ -2019,10 +1764,7 @@ __global__ __launch_bounds__(E0C_BLOCK) void lpl_pass(Dp d, double* part) {
       // here: lanes_to_lm fills it when a lane-per-observation kernel or an export asks (povar_lm.hip: ensure_legacy)
       v.lsc[(size_t)c_t * WAVE + lane] = sc4;
     }
-    c_t = q1;
-    q1 = q2;
-    q2 = q1 < t_end ? grab() : t_end;
-    --pc_ahead;
+    c_t = rows.advance(T);
   }
   if (bad) atomicOr(&d.flags[0], 1);
   if (MODE == 1) {

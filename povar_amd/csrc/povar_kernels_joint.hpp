@@ -679,72 +679,12 @@ __global__ __launch_bounds__(E0C_BLOCK) void e0_lpl_h(Dp d, double* hot_out) {
   __syncthreads();
   if (done) return;
   const int lane = threadIdx.x & 63;
-  // The workgroup's tiles are sorted longest first; its wavefronts take them on demand (one LDS counter), so a
-  // wavefront's last tile is a short one.  The workgroups carry equal observation totals (lpl_layout.hpp).
-  const int t_begin = __builtin_amdgcn_readfirstlane(v.wg_tile_off[blockIdx.x]);
-  const int t_end = __builtin_amdgcn_readfirstlane(v.wg_tile_off[blockIdx.x + 1]);
-  auto grab = [&]() -> int {
-    int n = 0;
-    if (lane == 0) n = __hip_atomic_fetch_add(grab_ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    n = __builtin_amdgcn_readfirstlane(n);
-    const long long t = (long long)t_begin + n;
-    return t < t_end ? (int)t : t_end;
-  };
-
-  // tile table through the scalar cache (constant address space + wave-uniform index => s_load_dwordx4): a vector
-  // load here would put a vmcnt(0) drain inside the row pipeline
-  typedef const int __attribute__((address_space(4))) * cint_p;
-  const cint_p tiles = (cint_p)(uintptr_t)v.tile;
-  auto tile_info = [&](int t, int& row0, int& k, int& nh, int& fl) {
-    row0 = tiles[4 * t];
-    k = tiles[4 * t + 1];
-    nh = tiles[4 * t + 2];
-    fl = tiles[4 * t + 3];
-  };
-  LplCursor pc;
-  pc.t = grab();
-  pc.pass = 0;
-  pc.j = 0;
-  pc.row0 = 0;
-  pc.k = 1;
-  int c_t = pc.t, c_row0 = 0, c_k = 0, c_nh = 0, c_fl = 0;
-  // the tile after the one being consumed, taken when the consumer enters a tile: the prefetch cursor runs at most
-  // LPL_DEPTH = 3 rows ahead and a tile has at least 4 row steps, so it never needs more than this one
-  int nx_t = t_end;
-  if (c_t < t_end) {
-    tile_info(c_t, c_row0, c_k, c_nh, c_fl);
-    pc.row0 = c_row0;
-    pc.k = c_k;
-    nx_t = grab();
-  }
-  // request the row under the prefetch cursor and advance it
-  auto issue = [&](LplRow& r) {
-    if (pc.t < t_end) {
-      // the backward pass walks the rows in reverse: the rows read last are the ones most likely still in L2
-      const size_t i = ((size_t)pc.row0 + (pc.pass ? pc.k - 1 - pc.j : pc.j)) * WAVE + lane;
-      r.uv = v.uv[i];
-      r.cw = v.cw[i];
-      if (ROBUST) r.w = v.w[i];
-      if (++pc.j == pc.k) {
-        pc.j = 0;
-        if (++pc.pass == 2) {
-          pc.pass = 0;
-          pc.t = nx_t;
-          if (pc.t < t_end) {
-            int nh_, fl_;
-            tile_info(pc.t, pc.row0, pc.k, nh_, fl_);
-          }
-        }
-      }
-    }
-  };
-  LplRow n1, n2, n3;
-  n1.cw = n2.cw = n3.cw = -1;
-  n1.w = n2.w = n3.w = 1.0;
-  n1.uv = n2.uv = n3.uv = make_double2(0, 0);
-  issue(n1);
-  issue(n2);
-  issue(n3);
+  const LplTiles T(v, grab_ctr, lane);
+  const int t_end = T.t_end;
+  int c_t = T.grab(), c_row0 = 0, c_k = 0, c_nh = 0, c_fl = 0;
+  if (c_t < t_end) T.info(c_t, c_row0, c_k, c_nh, c_fl);
+  LplStream2<ROBUST> rows;
+  rows.start(T, v, c_t, c_row0, c_k, c_t < t_end ? T.grab() : t_end);
   // landmark record of the lane (step 2): X (4), Jl column scale s (4), Hll^-1 (6) = 14 entries of lmrec[tile][14][64];
   // the Householder vector of X (tangent basis N_l, landmark_block.hpp:227-269) is rebuilt once per tile
   auto load_rec = [&](int t, double4& X, double4& s4, double (&Hi)[6]) {
@@ -754,18 +694,7 @@ __global__ __launch_bounds__(E0C_BLOCK) void e0_lpl_h(Dp d, double* hot_out) {
 #pragma unroll
     for (int m = 0; m < 6; ++m) Hi[m] = rp[(8 + m) * WAVE];
   };
-  auto read_cam = [&](const double2* hp, Cam& P) {  // entries 12..23 of a record: P row-major
-    const double2 b0 = hp[6], b1 = hp[7], b2 = hp[8], b3 = hp[9], b4 = hp[10], b5 = hp[11];
-    P.r0 = make_double4(b0.x, b0.y, b1.x, b1.y);
-    P.r1 = make_double4(b2.x, b2.y, b3.x, b3.y);
-    P.r2 = make_double4(b4.x, b4.y, b5.x, b5.y);
-  };
-  auto read_z = [&](const double2* hp, double4 (&zz)[3]) {
-    const double2 a0 = hp[0], a1 = hp[1], a2 = hp[2], a3 = hp[3], a4 = hp[4], a5 = hp[5];
-    zz[0] = make_double4(a0.x, a0.y, a1.x, a1.y);
-    zz[1] = make_double4(a2.x, a2.y, a3.x, a3.y);
-    zz[2] = make_double4(a4.x, a4.y, a5.x, a5.y);
-  };
+  // a camera record: z (entries 0..11), then P row-major (12..23)
   double4 X = make_double4(0, 0, 0, 1), s4 = make_double4(1, 1, 1, 1);
   double Hi[6] = {0, 0, 0, 0, 0, 0};
   if (c_t < t_end) load_rec(c_t, X, s4, Hi);
@@ -774,13 +703,9 @@ __global__ __launch_bounds__(E0C_BLOCK) void e0_lpl_h(Dp d, double* hot_out) {
     house4(X, hw, hbeta);
     double red[3] = {0, 0, 0};
     for (int j = 0; j < c_k; ++j) {
-      const LplRow cur = n1;
-      n1 = n2;
-      n2 = n3;
-      issue(n3);
-      // The record is read through an LDS pointer or a global pointer, never through a select of the two: a generic
-      // pointer makes every read a flat_load (texture path into the LDS, both wait counters).  Rows [0, c_nh) have an
-      // LDS-resident camera in every lane: wave-uniform branch, LDS reads only.
+      const LplRow cur = rows.next(T, v);
+      // LDS pointer or global pointer, never a select of the two (lpl_read12).  Rows [0, c_nh) have an LDS-resident
+      // camera in every lane: wave-uniform branch, LDS reads only.
       auto fwd = [&](const Cam& P, const double4 (&zz)[3]) {
         const double sw = ROBUST ? sqrt(cur.w) : 1.0;
         const Hom h = hom_project(P, X, cur.uv.x, cur.uv.y);
@@ -795,18 +720,18 @@ __global__ __launch_bounds__(E0C_BLOCK) void e0_lpl_h(Dp d, double* hot_out) {
       double4 zz[3];
       if (j < c_nh) {
         const double2* hp = hot + lpl_cw_slot(cur.cw) * LPL_CAMREC_H;
-        read_z(hp, zz);
-        read_cam(hp, P);
+        lpl_read12(hp, zz);
+        lpl_read_cam(hp + 6, P);
         fwd(P, zz);
       } else if (cur.cw != -1) {
         if (cur.cw >= 0) {
           const double2* hp = hot + lpl_cw_slot(cur.cw) * LPL_CAMREC_H;
-          read_z(hp, zz);
-          read_cam(hp, P);
+          lpl_read12(hp, zz);
+          lpl_read_cam(hp + 6, P);
         } else {
           const double2* hp = rec_img + (size_t)(-2 - cur.cw) * (HOT_REC_STRIDE / 2);
-          read_z(hp, zz);
-          read_cam(hp, P);
+          lpl_read12(hp, zz);
+          lpl_read_cam(hp + 6, P);
         }
         fwd(P, zz);
       }
@@ -818,16 +743,13 @@ __global__ __launch_bounds__(E0C_BLOCK) void e0_lpl_h(Dp d, double* hot_out) {
     const double g[3] = {Hi[0] * red[0] + Hi[1] * red[1] + Hi[2] * red[2], Hi[1] * red[0] + Hi[3] * red[1] + Hi[4] * red[2],
                          Hi[2] * red[0] + Hi[4] * red[1] + Hi[5] * red[2]};
     // the next tile's record (Hll^-1 is dead by now; X and s are still needed: second set)
-    const int n_t = nx_t;
+    const int n_t = rows.nx_t;
     double4 nX = make_double4(0, 0, 0, 1), ns4 = make_double4(1, 1, 1, 1);
     double nHi[6] = {0, 0, 0, 0, 0, 0};
     if (n_t < t_end) load_rec(n_t, nX, ns4, nHi);
     for (int jj = 0; jj < c_k; ++jj) {
       const int j = c_k - 1 - jj;
-      const LplRow cur = n1;
-      n1 = n2;
-      n2 = n3;
-      issue(n3);
+      const LplRow cur = rows.next(T, v);
       auto bwd = [&](const Cam& P) -> double4 {
         const double sw = ROBUST ? sqrt(cur.w) : 1.0;
         const Hom h = hom_project(P, X, cur.uv.x, cur.uv.y);
@@ -848,23 +770,23 @@ __global__ __launch_bounds__(E0C_BLOCK) void e0_lpl_h(Dp d, double* hot_out) {
       };
       Cam P;
       if (j < c_nh) {  // wave-uniform: LDS only
-        read_cam(hot + lpl_cw_slot(cur.cw) * LPL_CAMREC_H, P);
+        lpl_read_cam(hot + lpl_cw_slot(cur.cw) * LPL_CAMREC_H + 6, P);
         scatter(bwd(P));
       } else if (cur.cw >= 0) {
-        read_cam(hot + lpl_cw_slot(cur.cw) * LPL_CAMREC_H, P);
+        lpl_read_cam(hot + lpl_cw_slot(cur.cw) * LPL_CAMREC_H + 6, P);
         scatter(bwd(P));
       } else if (cur.cw < -1) {
         // where q goes: row-major next to the other lanes' (graphs with many cold observations: the per-camera kernel
         // gathers, Dp::q_rows) or straight to its place in the camera-major cold view (few: one 32-byte store per lane)
         const int cold_at = d.q_rows ? lpl_cold_q(c_fl, c_nh, j, lane) : v.cpos[((size_t)c_row0 + j) * WAVE + lane];
-        read_cam(rec_img + (size_t)(-2 - cur.cw) * (HOT_REC_STRIDE / 2), P);
+        lpl_read_cam(rec_img + (size_t)(-2 - cur.cw) * (HOT_REC_STRIDE / 2) + 6, P);
         d.q4c[cold_at] = bwd(P);
       }
     }
     c_t = n_t;
     if (c_t < t_end) {
-      tile_info(c_t, c_row0, c_k, c_nh, c_fl);
-      nx_t = grab();
+      T.info(c_t, c_row0, c_k, c_nh, c_fl);
+      rows.ahead(T.grab());
     }
     X = nX;
     s4 = ns4;
@@ -885,20 +807,8 @@ __global__ __launch_bounds__(E0C_BLOCK) void e0_lpl_h(Dp d, double* hot_out) {
 #pragma unroll
     for (int u = 0; u < PASSES; ++u) {
       const int i = threadIdx.x + u * E0C_BLOCK;
-      if (i < n_hot * 6) {
-        const int r = i / 6, m = 2 * (i % 6);
-        const double* a0 = acc + m * n_slots;
-        const double* a1 = a0 + n_slots;
-        double2 s;
-        if (r < hubs) {
-          s.x = (a0[4 * r] + a0[4 * r + 1]) + (a0[4 * r + 2] + a0[4 * r + 3]);
-          s.y = (a1[4 * r] + a1[4 * r + 1]) + (a1[4 * r + 2] + a1[4 * r + 3]);
-        } else {
-          s.x = a0[r + 3 * hubs];
-          s.y = a1[r + 3 * hubs];
-        }
-        reinterpret_cast<double2*>(hot_out + (size_t)rec[u] * 12)[i % 6] = s;
-      }
+      if (i < n_hot * 6)
+        reinterpret_cast<double2*>(hot_out + (size_t)rec[u] * 12)[i % 6] = lpl_acc_sum(acc, n_slots, hubs, i / 6, i % 6);
     }
   }
   if (d.p2p_epoch && blockIdx.x == 0 && threadIdx.x == 0) *d.p2p_epoch += 1;  // one tick per term, read by the next kernels
@@ -929,68 +839,12 @@ __global__ __launch_bounds__(E0C_BLOCK) void prepare_lpl_h(Dp d, double* hot_out
   }
   __syncthreads();
   const int lane = threadIdx.x & 63;
-  const int t_begin = __builtin_amdgcn_readfirstlane(v.wg_tile_off[blockIdx.x]);
-  const int t_end = __builtin_amdgcn_readfirstlane(v.wg_tile_off[blockIdx.x + 1]);
-  auto grab = [&]() -> int {
-    int n = 0;
-    if (lane == 0) n = __hip_atomic_fetch_add(grab_ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    n = __builtin_amdgcn_readfirstlane(n);
-    const long long t = (long long)t_begin + n;
-    return t < t_end ? (int)t : t_end;
-  };
-  typedef const int __attribute__((address_space(4))) * cint_p;
-  const cint_p tiles = (cint_p)(uintptr_t)v.tile;
-  auto tile_info = [&](int t, int& row0, int& k, int& nh, int& fl) {
-    row0 = tiles[4 * t];
-    k = tiles[4 * t + 1];
-    nh = tiles[4 * t + 2];
-    fl = tiles[4 * t + 3];
-  };
-  LplCursor pc;
-  pc.t = grab();
-  pc.pass = 0;
-  pc.j = 0;
-  pc.row0 = 0;
-  pc.k = 1;
-  int c_t = pc.t, c_row0 = 0, c_k = 0, c_nh = 0, c_fl = 0, nx_t = t_end;
-  if (c_t < t_end) {
-    tile_info(c_t, c_row0, c_k, c_nh, c_fl);
-    pc.row0 = c_row0;
-    pc.k = c_k;
-    nx_t = grab();
-  }
-  auto issue = [&](LplRow& r) {
-    if (pc.t < t_end) {
-      const size_t i = ((size_t)pc.row0 + (pc.pass ? pc.k - 1 - pc.j : pc.j)) * WAVE + lane;
-      r.uv = v.uv[i];
-      r.cw = v.cw[i];
-      if (ROBUST) r.w = v.w[i];
-      if (++pc.j == pc.k) {
-        pc.j = 0;
-        if (++pc.pass == 2) {
-          pc.pass = 0;
-          pc.t = nx_t;
-          if (pc.t < t_end) {
-            int nh_, fl_;
-            tile_info(pc.t, pc.row0, pc.k, nh_, fl_);
-          }
-        }
-      }
-    }
-  };
-  auto read_cam = [&](const double2* hp, Cam& P) {
-    const double2 b0 = hp[0], b1 = hp[1], b2 = hp[2], b3 = hp[3], b4 = hp[4], b5 = hp[5];
-    P.r0 = make_double4(b0.x, b0.y, b1.x, b1.y);
-    P.r1 = make_double4(b2.x, b2.y, b3.x, b3.y);
-    P.r2 = make_double4(b4.x, b4.y, b5.x, b5.y);
-  };
-  LplRow n1, n2, n3;
-  n1.cw = n2.cw = n3.cw = -1;
-  n1.w = n2.w = n3.w = 1.0;
-  n1.uv = n2.uv = n3.uv = make_double2(0, 0);
-  issue(n1);
-  issue(n2);
-  issue(n3);
+  const LplTiles T(v, grab_ctr, lane);
+  const int t_end = T.t_end;
+  int c_t = T.grab(), c_row0 = 0, c_k = 0, c_nh = 0, c_fl = 0;
+  if (c_t < t_end) T.info(c_t, c_row0, c_k, c_nh, c_fl);
+  LplStream2<ROBUST> rows;
+  rows.start(T, v, c_t, c_row0, c_k, c_t < t_end ? T.grab() : t_end);
   while (c_t < t_end) {
     const int lm = v.lm_of[(size_t)c_t * WAVE + lane];
     const int sg = v.seg[(size_t)c_t * WAVE + lane];
@@ -999,15 +853,12 @@ __global__ __launch_bounds__(E0C_BLOCK) void prepare_lpl_h(Dp d, double* hot_out
     house4(X, hw, hbeta);
     double red[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     for (int j = 0; j < c_k; ++j) {
-      const LplRow cur = n1;
-      n1 = n2;
-      n2 = n3;
-      issue(n3);
+      const LplRow cur = rows.next(T, v);
       if (cur.cw == -1) continue;
       Cam P;
-      // LDS pointer or global pointer, never a select of the two (a generic pointer turns the reads into flat_loads)
-      if (cur.cw >= 0) read_cam(hot + lpl_cw_slot(cur.cw) * PREP_STRIDE, P);
-      else read_cam(rec_img + (size_t)(-2 - cur.cw) * (HOT_REC_STRIDE / 2) + 6, P);
+      // LDS pointer or global pointer, never a select of the two (lpl_read12)
+      if (cur.cw >= 0) lpl_read_cam(hot + lpl_cw_slot(cur.cw) * PREP_STRIDE, P);
+      else lpl_read_cam(rec_img + (size_t)(-2 - cur.cw) * (HOT_REC_STRIDE / 2) + 6, P);
       const double sw = ROBUST ? sqrt(cur.w) : 1.0;
       const Hom h = hom_project(P, X, cur.uv.x, cur.uv.y);
       double jl4[8], jl3[6];
@@ -1043,15 +894,12 @@ __global__ __launch_bounds__(E0C_BLOCK) void prepare_lpl_h(Dp d, double* hot_out
     }
     for (int jj = 0; jj < c_k; ++jj) {
       const int j = c_k - 1 - jj;
-      const LplRow cur = n1;
-      n1 = n2;
-      n2 = n3;
-      issue(n3);
+      const LplRow cur = rows.next(T, v);
       if (cur.cw == -1) continue;
       Cam P;
-      // LDS pointer or global pointer, never a select of the two (a generic pointer turns the reads into flat_loads)
-      if (cur.cw >= 0) read_cam(hot + lpl_cw_slot(cur.cw) * PREP_STRIDE, P);
-      else read_cam(rec_img + (size_t)(-2 - cur.cw) * (HOT_REC_STRIDE / 2) + 6, P);
+      // LDS pointer or global pointer, never a select of the two (lpl_read12)
+      if (cur.cw >= 0) lpl_read_cam(hot + lpl_cw_slot(cur.cw) * PREP_STRIDE, P);
+      else lpl_read_cam(rec_img + (size_t)(-2 - cur.cw) * (HOT_REC_STRIDE / 2) + 6, P);
       const double sw = ROBUST ? sqrt(cur.w) : 1.0;
       const Hom h = hom_project(P, X, cur.uv.x, cur.uv.y);
       double jl4[8], jl3[6];
@@ -1071,27 +919,15 @@ __global__ __launch_bounds__(E0C_BLOCK) void prepare_lpl_h(Dp d, double* hot_out
         d.q4c[d.q_rows ? lpl_cold_q(c_fl, c_nh, j, lane) : v.cpos[((size_t)c_row0 + j) * WAVE + lane]] = q;
       }
     }
-    c_t = nx_t;
+    c_t = rows.nx_t;
     if (c_t < t_end) {
-      tile_info(c_t, c_row0, c_k, c_nh, c_fl);
-      nx_t = grab();
+      T.info(c_t, c_row0, c_k, c_nh, c_fl);
+      rows.ahead(T.grab());
     }
   }
   __syncthreads();
-  for (int i = threadIdx.x; i < n_hot * 6; i += E0C_BLOCK) {
-    const int r = i / 6, m = 2 * (i % 6);
-    const double* a0 = acc + m * n_slots;
-    const double* a1 = a0 + n_slots;
-    double2 s;
-    if (r < hubs) {
-      s.x = (a0[4 * r] + a0[4 * r + 1]) + (a0[4 * r + 2] + a0[4 * r + 3]);
-      s.y = (a1[4 * r] + a1[4 * r + 1]) + (a1[4 * r + 2] + a1[4 * r + 3]);
-    } else {
-      s.x = a0[r + 3 * hubs];
-      s.y = a1[r + 3 * hubs];
-    }
-    reinterpret_cast<double2*>(hot_out + (size_t)v.wg_slot_rec[cam0 + r] * 12)[i % 6] = s;
-  }
+  for (int i = threadIdx.x; i < n_hot * 6; i += E0C_BLOCK)
+    reinterpret_cast<double2*>(hot_out + (size_t)v.wg_slot_rec[cam0 + i / 6] * 12)[i % 6] = lpl_acc_sum(acc, n_slots, hubs, i / 6, i % 6);
 }
 
 // b11_c = N_c^T y12_c for the per-camera sums of prepare_lpl_h (cam_cold_sum has applied sigma); y12 is scratch
@@ -1134,61 +970,29 @@ __global__ __launch_bounds__(E0C_BLOCK) void lpl_pass_h(Dp d, double* part) {
   }
   __syncthreads();
   const int lane = threadIdx.x & 63;
-  const int t_begin = __builtin_amdgcn_readfirstlane(v.wg_tile_off[blockIdx.x]);
-  const int t_end = __builtin_amdgcn_readfirstlane(v.wg_tile_off[blockIdx.x + 1]);
-  auto grab = [&]() -> int {
-    int n = 0;
-    if (lane == 0) n = __hip_atomic_fetch_add(grab_ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    n = __builtin_amdgcn_readfirstlane(n);
-    const long long t = (long long)t_begin + n;
-    return t < t_end ? (int)t : t_end;
-  };
-  typedef const int __attribute__((address_space(4))) * cint_p;
-  const cint_p tiles = (cint_p)(uintptr_t)v.tile;
-  int c_t = grab(), q1 = c_t < t_end ? grab() : t_end, q2 = q1 < t_end ? grab() : t_end;
-  int pc_t = c_t, pc_ahead = 0, pc_j = 0, pc_row0 = 0, pc_k = 1;
-  if (pc_t < t_end) { pc_row0 = tiles[4 * pc_t]; pc_k = tiles[4 * pc_t + 1]; }
-  auto issue = [&](LplRow& r) {
-    if (pc_t < t_end) {
-      const size_t i = ((size_t)pc_row0 + pc_j) * WAVE + lane;
-      r.uv = v.uv[i];
-      r.cw = v.cw[i];
-      if (++pc_j == pc_k) {
-        pc_j = 0;
-        ++pc_ahead;
-        pc_t = pc_ahead == 1 ? q1 : pc_ahead == 2 ? q2 : t_end;
-        if (pc_t < t_end) { pc_row0 = tiles[4 * pc_t]; pc_k = tiles[4 * pc_t + 1]; }
-      }
-    }
-  };
-  LplRow n1, n2, n3;
-  n1.cw = n2.cw = n3.cw = -1;
-  n1.w = n2.w = n3.w = 1.0;
-  n1.uv = n2.uv = n3.uv = make_double2(0, 0);
-  issue(n1);
-  issue(n2);
-  issue(n3);
+  const LplTiles T(v, grab_ctr, lane);
+  const int t_end = T.t_end;
+  int c_t = T.grab();
+  LplStream1 rows;
+  rows.start(T, v, c_t);
   double sc[6] = {0, 0, 0, 0, 0, 0};
   int bad = 0;
   while (c_t < t_end) {
-    const int c_row0 = tiles[4 * c_t], c_k = tiles[4 * c_t + 1], c_fl = tiles[4 * c_t + 3];
+    int c_row0, c_k, c_nh, c_fl;
+    T.info(c_t, c_row0, c_k, c_nh, c_fl);
     const double4 X = v.lmx[(size_t)c_t * WAVE + lane];
     if (MODE == 0) v.lml[(size_t)c_t * WAVE + lane] = X;  // the linearisation point, lane-ordered, is left behind
     double red[4] = {0, 0, 0, 0};
     for (int j = 0; j < c_k; ++j) {
-      const LplRow cur = n1;
-      n1 = n2;
-      n2 = n3;
-      issue(n3);
+      const LplRow cur = rows.next(T, v);
       if (cur.cw == -1) continue;
       // (a select of an LDS and a global pointer: six flat_loads.  Measured against ds_read / global_load in two branches
       // -- profiles/r02_ablations.txt item 16 --: the branches join with a wait on both counters, which drains the row
       // prefetch every step: 50 instead of 44 us here; the two-pass kernels with their longer steps gain from the split)
       const double2* hp = cur.cw >= 0 ? hot + lpl_cw_slot(cur.cw) * PASS_STRIDE
                                       : reinterpret_cast<const double2*>(cams + 3 * (size_t)d.hot_cams[-2 - cur.cw]);
-      const double2 b0 = hp[0], b1 = hp[1], b2 = hp[2], b3 = hp[3], b4 = hp[4], b5 = hp[5];
-      const Cam P = {make_double4(b0.x, b0.y, b1.x, b1.y), make_double4(b2.x, b2.y, b3.x, b3.y),
-                     make_double4(b4.x, b4.y, b5.x, b5.y)};
+      Cam P;
+      lpl_read_cam(hp, P);
       const Hom h = hom_project(P, X, cur.uv.x, cur.uv.y);
       const double r2 = h.r0 * h.r0 + h.r1 * h.r1;
       double e, w;
@@ -1214,10 +1018,7 @@ __global__ __launch_bounds__(E0C_BLOCK) void lpl_pass_h(Dp d, double* part) {
       v.lsc[(size_t)c_t * WAVE + lane] = make_double4(1.0 / (d.eps + sqrt(red[0])), 1.0 / (d.eps + sqrt(red[1])),
                                                       1.0 / (d.eps + sqrt(red[2])), 1.0 / (d.eps + sqrt(red[3])));
     }
-    c_t = q1;
-    q1 = q2;
-    q2 = q1 < t_end ? grab() : t_end;
-    --pc_ahead;
+    c_t = rows.advance(T);
   }
   if (bad) atomicOr(&d.flags[0], 1);
   if (MODE == 1) {
@@ -1250,80 +1051,28 @@ __global__ __launch_bounds__(E0C_BLOCK) void backsub_lpl_h(Dp d, double* part) {
         rec_img[(size_t)v.wg_cams[cam0 + i / HOT_REC_H] * (HOT_REC_STRIDE / 2) + i % HOT_REC_H];
   __syncthreads();
   const int lane = threadIdx.x & 63;
-  const int t_begin = __builtin_amdgcn_readfirstlane(v.wg_tile_off[blockIdx.x]);
-  const int t_end = __builtin_amdgcn_readfirstlane(v.wg_tile_off[blockIdx.x + 1]);
-  auto grab = [&]() -> int {
-    int n = 0;
-    if (lane == 0) n = __hip_atomic_fetch_add(grab_ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    n = __builtin_amdgcn_readfirstlane(n);
-    const long long t = (long long)t_begin + n;
-    return t < t_end ? (int)t : t_end;
-  };
-  typedef const int __attribute__((address_space(4))) * cint_p;
-  const cint_p tiles = (cint_p)(uintptr_t)v.tile;
-  auto tile_info = [&](int t, int& row0, int& k, int& nh, int& fl) {
-    row0 = tiles[4 * t];
-    k = tiles[4 * t + 1];
-    nh = tiles[4 * t + 2];
-    fl = tiles[4 * t + 3];
-  };
-  LplCursor pc;
-  pc.t = grab();
-  pc.pass = 0;
-  pc.j = 0;
-  pc.row0 = 0;
-  pc.k = 1;
-  int c_t = pc.t, c_row0 = 0, c_k = 0, c_nh = 0, c_fl = 0, nx_t = t_end;
-  if (c_t < t_end) {
-    tile_info(c_t, c_row0, c_k, c_nh, c_fl);
-    pc.row0 = c_row0;
-    pc.k = c_k;
-    nx_t = grab();
-  }
-  auto issue = [&](LplRow& r) {
-    if (pc.t < t_end) {
-      const size_t i = ((size_t)pc.row0 + (pc.pass ? pc.k - 1 - pc.j : pc.j)) * WAVE + lane;
-      r.uv = v.uv[i];
-      r.cw = v.cw[i];
-      if (ROBUST) r.w = v.w[i];
-      if (++pc.j == pc.k) {
-        pc.j = 0;
-        if (++pc.pass == 2) {
-          pc.pass = 0;
-          pc.t = nx_t;
-          if (pc.t < t_end) {
-            int nh_, fl_;
-            tile_info(pc.t, pc.row0, pc.k, nh_, fl_);
-          }
-        }
-      }
-    }
-  };
+  const LplTiles T(v, grab_ctr, lane);
+  const int t_end = T.t_end;
+  int c_t = T.grab(), c_row0 = 0, c_k = 0, c_nh = 0, c_fl = 0;
+  if (c_t < t_end) T.info(c_t, c_row0, c_k, c_nh, c_fl);
+  LplStream2<ROBUST> rows;
+  rows.start(T, v, c_t, c_row0, c_k, c_t < t_end ? T.grab() : t_end);
   // an observation's tile at the linearisation point and Jp * inc (z part of the record)
   auto obs = [&](const LplRow& cur, const double4& X, const double4& s4, const double (&hw)[4], double hbeta, Hom& h,
                  double (&jl4)[8], double (&jl3)[6], double& sw, double (&jpi)[2]) {
     // (select of an LDS and a global pointer: flat_loads; the split form spills here, see lpl_pass)
     const double2* hp = cur.cw >= 0 ? hot + lpl_cw_slot(cur.cw) * LPL_CAMREC_H
                                     : rec_img + (size_t)(-2 - cur.cw) * (HOT_REC_STRIDE / 2);
-    const double2 a0 = hp[0], a1 = hp[1], a2 = hp[2], a3 = hp[3], a4 = hp[4], a5 = hp[5];
-    const double2 b0 = hp[6], b1 = hp[7], b2 = hp[8], b3 = hp[9], b4 = hp[10], b5 = hp[11];
-    const double4 zz[3] = {make_double4(a0.x, a0.y, a1.x, a1.y), make_double4(a2.x, a2.y, a3.x, a3.y),
-                           make_double4(a4.x, a4.y, a5.x, a5.y)};
-    const Cam P = {make_double4(b0.x, b0.y, b1.x, b1.y), make_double4(b2.x, b2.y, b3.x, b3.y),
-                   make_double4(b4.x, b4.y, b5.x, b5.y)};
+    double4 zz[3];
+    Cam P;
+    lpl_read12(hp, zz);
+    lpl_read_cam(hp + 6, P);
     sw = ROBUST ? sqrt(cur.w) : 1.0;
     h = hom_project(P, X, cur.uv.x, cur.uv.y);
     hom_jl4(P, h, sw, s4, jl4);
     jl3_of_jl4(jl4, hw, hbeta, jl3);
     hom_jp_x(h, X, sw, zz, jpi);
   };
-  LplRow n1, n2, n3;
-  n1.cw = n2.cw = n3.cw = -1;
-  n1.w = n2.w = n3.w = 1.0;
-  n1.uv = n2.uv = n3.uv = make_double2(0, 0);
-  issue(n1);
-  issue(n2);
-  issue(n3);
   double sc = 0;
   while (c_t < t_end) {
     const int lm = v.lm_of[(size_t)c_t * WAVE + lane];
@@ -1333,10 +1082,7 @@ __global__ __launch_bounds__(E0C_BLOCK) void backsub_lpl_h(Dp d, double* part) {
     house4(X, hw, hbeta);
     double red[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     for (int j = 0; j < c_k; ++j) {
-      const LplRow cur = n1;
-      n1 = n2;
-      n2 = n3;
-      issue(n3);
+      const LplRow cur = rows.next(T, v);
       if (cur.cw == -1) continue;
       Hom h;
       double jl4[8], jl3[6], sw, jpi[2];
@@ -1356,10 +1102,7 @@ __global__ __launch_bounds__(E0C_BLOCK) void backsub_lpl_h(Dp d, double* part) {
       if (lane == (sg & 255)) d.lms4[lm] = Xc;
     }
     for (int jj = 0; jj < c_k; ++jj) {
-      const LplRow cur = n1;
-      n1 = n2;
-      n2 = n3;
-      issue(n3);
+      const LplRow cur = rows.next(T, v);
       if (cur.cw == -1) continue;
       Hom h;
       double jl4[8], jl3[6], sw, jpi[2];
@@ -1371,10 +1114,10 @@ __global__ __launch_bounds__(E0C_BLOCK) void backsub_lpl_h(Dp d, double* part) {
         sc -= ji * (0.5 * ji + rr[r]);
       }
     }
-    c_t = nx_t;
+    c_t = rows.nx_t;
     if (c_t < t_end) {
-      tile_info(c_t, c_row0, c_k, c_nh, c_fl);
-      nx_t = grab();
+      T.info(c_t, c_row0, c_k, c_nh, c_fl);
+      rows.ahead(T.grab());
     }
   }
   double sv[1] = {sc};

@@ -141,13 +141,21 @@ def _edge():
     return n_c + 1, lm_off, cam_idx, obs, cams
 
 
+# The row stream of e0_lpl (povar_kernels_lpl.hpp).  One workgroup: the edge graph's landmarks are at least 65 tiles over 16
+# wavefronts, so every wavefront takes later tiles from the counter, its prefetch cursor crosses tile boundaries three rows
+# ahead and ends in "no tile left"; K0 = 2 is the shortest tile the stream's invariant allows; 8 accumulators make most
+# observations cold, in both addressings of q4c.  (The default grid has more workgroups than tiles: wavefronts and workgroups
+# without any tile.)
+LPL_STREAM_RUNS = [("e0_lpl", r, {"POVAR_E0_WGS": "1"}, 0) for r in ("NONE", "HUBER")] + \
+    [("e0_lpl", "NONE", {"POVAR_E0_WGS": "1", "POVAR_LPL_K0": "2"}, 0)] + \
+    [("e0_lpl", "NONE", {"POVAR_HOT_ACC": "8", "POVAR_COLD_Q_ROWS": q}, 0) for q in ("0", "1")]
 EDGE_RUNS = [(f, "NONE", {}, 0) for f in C_FORM + PER_OBS] + [(f, "HUBER", {}, 0) for f in C_FORM] + \
     [(f, "NONE", {"POVAR_HOT_ACC": "8"}, 0) for f in CHUNK] + \
     [(f, "NONE", {"POVAR_CK_NB": "3", "POVAR_CK_HMAX": "5"}, 0) for f in CHUNK] + \
     [(f, "HUBER", {"POVAR_CK_NB": "3", "POVAR_CK_HMAX": "5"}, 0) for f in CHUNK] + \
     [(f, "NONE", {}, "FLAG_NO_PACKED_ROWS") for f in ("e0_ck", "e0_ck_f32")] + \
-    [("e0_ck_det", r, {"POVAR_E0_WGS": "1", "POVAR_CK_HMAX": "3"}, 0) for r in ("NONE", "HUBER")]
-# (the last two: one workgroup and chunks of at most 3 rows -- a batch of more than 16 tiles, so that a wavefront walks a
+    [("e0_ck_det", r, {"POVAR_E0_WGS": "1", "POVAR_CK_HMAX": "3"}, 0) for r in ("NONE", "HUBER")] + LPL_STREAM_RUNS
+# (the two of e0_ck_det: one workgroup and chunks of at most 3 rows -- a batch of more than 16 tiles, so that a wavefront walks a
 # SECOND tile and reloads its camera record between the passes and on the way back; every other edge run has 16 per batch)
 
 
@@ -163,8 +171,10 @@ def test_edge_graph_within_bound(monkeypatch, fam, robust, env, flag):
     if fam in ("e0_ck", "e0_ck_f32") and not env and not flag:
         li = ctx.layout_info()
         assert li.ck_packed == 1
-    if "POVAR_E0_WGS" in env:
+    if "POVAR_E0_WGS" in env and fam in CHUNK:
         assert ctx.layout_info().ck_tiles_max > 16, "no wavefront has a second tile in a batch"
+    if "POVAR_E0_WGS" in env and fam == "e0_lpl":
+        assert ctx.layout_info().grid == 1 and len(lm_off) - 1 > 16 * 64, "no wavefront takes a second tile from the counter"
     xs = _xs(n_c) + _xs(n_c, ctx)[2:]
     _run(ctx, fam, obs, robust, RB.EDGE_HUBER, xs, f"edge/{robust}/{env or flag or 'default'}")
     # exact zeros: the camera without observations

@@ -105,11 +105,17 @@ def _edge():
     return _EDGE[0]
 
 
+# The row stream of e0_lpl_h (povar_kernels_lpl.hpp), as in tests/test_gpu_e0_bounds.py: one workgroup (at least 65 tiles over
+# 16 wavefronts: later tiles from the counter, the prefetch cursor across tile boundaries and into "no tile left"), the shortest
+# tile the stream allows (K0 = 2), and mostly cold observations in both addressings of q4c
+LPL_STREAM_RUNS = [("e0_lpl_h", r, {"POVAR_E0_WGS": "1"}) for r in ("NONE", "HUBER")] + \
+    [("e0_lpl_h", "NONE", {"POVAR_E0_WGS": "1", "POVAR_LPL_K0": "2"})] + \
+    [("e0_lpl_h", "NONE", {"POVAR_HOT_ACC": "8", "POVAR_COLD_Q_ROWS": q}) for q in ("0", "1")]
 EDGE_RUNS = [(f, "NONE", {}) for f in ALL] + [(f, r, {}) for r in ("HUBER", "CAUCHY") for f in ALL] + \
     [(f, "NONE", e) for e in ({"POVAR_HOT_ACC": "8"}, {"POVAR_CK_NB": "3"}) for f in CHUNK] + \
     [(f, "NONE", {"POVAR_NO_FUSE": "1"}) for f in ("e0_ck_h", "e0_lpl_h")] + \
-    [("e0_ck_h_det", r, {"POVAR_E0_WGS": "1", "POVAR_CK_HMAX": "3"}) for r in ("NONE", "HUBER")]
-# (the last two: one workgroup and chunks of at most 3 rows -- more than 16 tiles in a batch, so that a wavefront walks a
+    [("e0_ck_h_det", r, {"POVAR_E0_WGS": "1", "POVAR_CK_HMAX": "3"}) for r in ("NONE", "HUBER")] + LPL_STREAM_RUNS
+# (the two of e0_ck_h_det: one workgroup and chunks of at most 3 rows -- more than 16 tiles in a batch, so that a wavefront walks a
 # SECOND tile and reloads its camera record between the passes and on the way back; every other edge run has 16 per batch)
 
 
@@ -118,7 +124,9 @@ EDGE_RUNS = [(f, "NONE", {}) for f in ALL] + [(f, r, {}) for r in ("HUBER", "CAU
 def test_edge_graph_terms_within_bound(monkeypatch, fam, robust, env):
     n_c, lm_off, cam_idx, obs, cams, lms_h = _edge()
     ctx = _context(monkeypatch, fam, n_c, lm_off, cam_idx, obs, cams, lms_h, robust, RB.EDGE_HUBER_H, env)
-    if "POVAR_E0_WGS" in env:
+    if "POVAR_E0_WGS" in env and fam == "e0_lpl_h":
+        assert ctx.layout_info().grid == 1 and len(lm_off) - 1 > 16 * 64, "no wavefront takes a second tile from the counter"
+    if "POVAR_E0_WGS" in env and fam in CHUNK:
         li = ctx.layout_info()
         assert li.ckh_chunks > 64 * 16 * li.ckh_batches * li.grid, "no wavefront has a second tile in a batch"
     _terms_within_bound(ctx, fam, obs, robust, RB.EDGE_HUBER_H, f"edge/{robust}/{'+'.join(f'{k}={v}' for k, v in env.items()) or 'default'}", unobserved=[n_c - 1])

@@ -1,0 +1,148 @@
+"""The lane-per-landmark stage kernels without a componentwise bound of their own -- lpl_pass[_h]<1> (the cost) and
+backsub_lpl[_h] (back substitution) -- against the CPU oracle on a layout that exercises their row stream
+(povar_kernels_lpl.hpp): ONE workgroup of shortest tiles (POVAR_E0_WGS=1, POVAR_LPL_K0=2).  1 500 landmarks are at least 24
+tiles over 16 wavefronts, so every wavefront takes later tiles from the LDS counter, its prefetch cursor crosses tile
+boundaries three rows ahead (lpl_pass: into the tile after the next) and ends in "no tile left".  The other lpl kernels of
+an LM iteration run on the way (lpl_pass[_h]<0>, prepare_lpl[_h], e0_lpl[_h]) and are held through the increment; their
+componentwise bounds on such layouts are in test_gpu_operand_bounds.py and test_gpu_e0[h]_bounds.py.
+
+The recipe and the tolerances are those of tests/test_gpu_step1.py (test_init_and_error, test_power_series_term_by_term,
+test_apply with POWER_VARPROJ) and of tests/test_gpu_step2.py (test_step2_against_oracle) for the same quantities, on
+medium_problem's recipe with 1 500 landmarks and 6 200 observations.  Measured on an MI355X at the commit before the
+shared row stream (c17c273) and at the one that adds it -- relative errors, worst of NONE / HUBER, before / after; every
+figure is printed as "LPLSTREAM ..." before it is asserted.  The commit before meets every tolerance, so none is widened:
+  step 1  cost 1.7e-15 / 1.9e-15, residual sum 2.8e-15 / 2.9e-15, increment 9.1e-14 / 9.0e-14 (20 terms), cameras 1.4e-15 / 1.4e-15,
+          landmarks 3.8e-11 / 3.8e-11, l_diff 7.9e-16 / 6.6e-16
+  step 2  cost 1.8e-15 / 1.9e-15, valid residual sum 1.2e-15 / 1.4e-15, increment 4.8e-15 / 5.0e-15 (10 terms),
+          cameras 7.4e-17 / 7.4e-17, landmarks 2.8e-14 / 2.8e-14, l_diff 1.3e-15 / 1.3e-15
+"""
+import os
+
+import numpy as np
+import pytest
+
+from conftest import rel
+
+pytestmark = pytest.mark.gpu
+ALPHA, LAM = 0.01, 1e-4
+ENV = {"POVAR_E0_V1": "0", "POVAR_E0_CK": "0", "POVAR_LPL_PLACE": "sync", "POVAR_E0_WGS": "1", "POVAR_LPL_K0": "2"}
+_OVERRIDES = ("POVAR_HOT_ACC", "POVAR_LPL_STRATEGY", "POVAR_LPL_NOGRID", "POVAR_LONG_SEPARATE", "POVAR_PREPARE_V1", "POVAR_RES",
+              "POVAR_COLD_Q_ROWS")
+_P = []
+
+
+def _problem():
+    from povar_amd import synth
+    if not _P:
+        _P.append(synth.make_problem(49, 1500, 6200, seed=49))
+    return _P[0]
+
+
+def _env(monkeypatch):
+    if os.environ.get("POVAR_DETERMINISTIC") == "1":
+        pytest.skip("POVAR_DETERMINISTIC=1 in the environment pins the per-observation stage kernels")
+    for k in _OVERRIDES:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in ENV.items():
+        monkeypatch.setenv(k, v)
+
+
+def _one_workgroup_of_lanes(ctx, p):
+    li = ctx.layout_info()
+    assert li.lane_per_landmark == 1 and li.grid == 1, (li.lane_per_landmark, li.grid)
+    assert p.n_lms >= 24 * 64 - 63
+
+
+def _check(label, figures):
+    """figures: (name, value, tolerance); all printed, then all asserted"""
+    for name, val, tol in figures:
+        print(f"LPLSTREAM {label} {name}={val:.3g} tol={tol:.3g}")
+    for name, val, tol in figures:
+        assert val < tol, (label, name, val, tol)
+
+
+@pytest.mark.parametrize("norm", ["NONE", "HUBER"])
+def test_step1_cost_and_back_substitution_on_one_workgroup(monkeypatch, norm):
+    from povar_amd import capi
+    from oracle import povar_oracle as O
+    M = 20
+    p = _problem()
+    _env(monkeypatch)
+    orc = O.Oracle(p.n_cams, p.lm_off, p.cam_idx, p.obs, robust_norm=norm, huber=30.0)
+    ctx = capi.Context(p.n_cams, p.lm_off, p.cam_idx, p.obs, robust_norm=norm, huber=30.0, e0_mode=capi.E0_IMPLICIT_LDSACC)
+    lms = orc.init_landmarks_pose(ALPHA, p.cams)
+    ctx.set_cameras(p.cams)
+    ctx.set_landmarks(lms)
+    _one_workgroup_of_lanes(ctx, p)
+    # lpl_pass<1>
+    ri, ro = ctx.error_pose(ALPHA), orc.error_pose(ALPHA, p.cams, lms)
+    assert ri.all_num_obs == ro.all_num_obs == p.n_obs and ri.valid_num_obs == ro.valid_num_obs and ri.is_numerically_valid == 1
+    fig = [("cost", abs(ri.all_error - ro.all_error) / ro.all_error, 1e-12),
+           ("residual_sum", abs(ri.all_residual_sum - ro.all_residual_sum) / ro.all_residual_sum, 1e-12)]
+    # lpl_pass<0>, prepare_lpl, e0_lpl
+    assert ctx.linearize_pose(ALPHA)
+    st, diag2, jls, sigma, ok = orc.stage1_pose(ALPHA, p.cams, lms)
+    orc.scale_jp_cols_pose(st, sigma)
+    hll, b, binv = orc.prepare_hb_pose(st, LAM, 0.0)
+    ref, _, _, _ = orc.solve_pose(st, hll, binv, b, M)
+    inc, it, _, rc = ctx.solve_pose(LAM, capi.POWER_VARPROJ, M)
+    assert rc == 0 and it == M
+    fig.append(("increment", rel(inc, ref), 1e-10))
+    # backsub_lpl
+    l_diff = ctx.apply_pose(capi.POWER_VARPROJ, ALPHA, ref)
+    inc_s = ref * sigma
+    cams_new = p.cams + inc_s.reshape(-1, 12)
+    ld, lms_new = orc.back_substitute_pose(ALPHA, st, cams_new, lms, inc_s * (1.0 / sigma))
+    fig += [("cameras", rel(ctx.get_cameras(), cams_new), 1e-14), ("landmarks", rel(ctx.get_landmarks(), lms_new), 1e-9),
+            ("l_diff", abs(l_diff - ld) / abs(ld), 1e-9)]
+    _one_workgroup_of_lanes(ctx, p)
+    ctx.close()
+    _check(f"step1/{norm}", fig)
+
+
+@pytest.mark.parametrize("norm", ["NONE", "HUBER"])
+def test_step2_cost_and_back_substitution_on_one_workgroup(monkeypatch, norm):
+    from povar_amd import capi
+    from oracle import povar_oracle as O
+    M = 10
+    p = _problem()
+    _env(monkeypatch)
+    rng = np.random.default_rng(11)
+    cams = rng.normal(size=(p.n_cams, 12))
+    cams[:, 8:11] *= 0.1
+    cams[:, 11] = 5 + rng.random(p.n_cams)
+    cams /= np.linalg.norm(cams, axis=1, keepdims=True)
+    lms_h = np.concatenate([rng.normal(size=(p.n_lms, 3)), np.ones((p.n_lms, 1))], 1)
+    obs = p.obs / 500.0
+    orc = O.Oracle(p.n_cams, p.lm_off, p.cam_idx, obs, robust_norm=norm, huber=0.5)
+    ctx = capi.Context(p.n_cams, p.lm_off, p.cam_idx, obs, robust_norm=norm, huber=0.5, e0_mode=capi.E0_IMPLICIT_LDSACC)
+    ctx.set_cameras(cams)
+    ctx.set_landmarks_homogeneous(lms_h)
+    _one_workgroup_of_lanes(ctx, p)
+    # lpl_pass_h<1>
+    ri, ro = ctx.error_homogeneous(), orc.error_homogeneous(cams, lms_h)
+    assert ri.all_num_obs == ro.all_num_obs and ri.valid_num_obs == ro.valid_num_obs
+    fig = [("cost", abs(ri.all_error - ro.all_error) / ro.all_error, 1e-12),
+           ("valid_residual_sum", abs(ri.valid_residual_sum - ro.valid_residual_sum) / ro.valid_residual_sum, 1e-12)]
+    # lpl_pass_h<0>, prepare_lpl_h, e0_lpl_h
+    assert ctx.linearize_homogeneous()
+    st_h, ok = orc.linearize_homogeneous(cams, lms_h)
+    diag2 = orc.jp_diag2_homogeneous(st_h)
+    jls = orc.scale_jl_cols_homogeneous(st_h)
+    sigma = 1.0 / (1e-5 + np.sqrt(diag2))
+    orc.scale_jp_cols_joint(st_h, sigma)
+    st_n = orc.linearize_nullspace(cams, lms_h, st_h)
+    hll, b, binv = orc.prepare_hb_joint(st_h, st_n, LAM)
+    ref, _, _, _ = orc.solve_joint(st_n, hll, binv, b, M)
+    inc, it, _, rc = ctx.solve_joint(LAM, M)
+    assert rc == 0 and it == M
+    fig.append(("increment", rel(inc, ref), 1e-10))
+    # backsub_lpl_h
+    ld = ctx.apply_joint(ref)
+    ld_o, lms_new = orc.back_substitute_joint(st_h, jls, LAM, cams, lms_h, ref)
+    cams_new = orc.apply_cam_inc_joint(cams, ref, sigma)
+    fig += [("cameras", rel(ctx.get_cameras(), cams_new), 1e-13), ("landmarks", rel(ctx.get_landmarks_homogeneous(), lms_new), 1e-10),
+            ("l_diff", abs(ld - ld_o) / abs(ld_o), 1e-9)]
+    _one_workgroup_of_lanes(ctx, p)
+    ctx.close()
+    _check(f"step2/{norm}", fig)

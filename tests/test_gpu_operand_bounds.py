@@ -40,9 +40,10 @@ FAMILIES = {
 }
 
 
-def _create(monkeypatch, fam, p):
+def _create(monkeypatch, fam, p, more_env=None):
     from povar_amd import capi
     env, mode, _ = FAMILIES[fam]
+    env = {**env, **(more_env or {})}
     if DET_ENV and fam != "det":
         pytest.skip("POVAR_DETERMINISTIC=1 in the environment pins the kernels of this case")
     for k in _OVERRIDES:
@@ -156,37 +157,48 @@ def edge_joint(robust):
     return OB.Joint(n_c, lm_off, cam_idx, obs, cams, X, RB.EDGE_LAM_H, robust, RB.EDGE_HUBER_H)
 
 
-def pose_context(monkeypatch, fam, p):
-    ctx = _create(monkeypatch, fam, p)
+def pose_context(monkeypatch, fam, p, env=None):
+    ctx = _create(monkeypatch, fam, p, env)
     ctx.set_cameras(p.cams)
     ctx.set_landmarks(p.lms)
     return ctx
 
 
-def joint_context(monkeypatch, fam, p):
-    ctx = _create(monkeypatch, fam, p)
+def joint_context(monkeypatch, fam, p, env=None):
+    ctx = _create(monkeypatch, fam, p, env)
     ctx.set_cameras(p.cams)
     ctx.set_landmarks_homogeneous(p.lms)
     return ctx
 
 
-@pytest.mark.parametrize("robust", ["NONE", "HUBER"])
-@pytest.mark.parametrize("fam", list(FAMILIES))
-def test_step1_operands_on_the_edge_graph(monkeypatch, fam, robust):
+# every family at its defaults, then the lpl family on the layouts that stress the row stream of lpl_pass[_h]<0> and
+# prepare_lpl[_h] (povar_kernels_lpl.hpp): one workgroup of shortest tiles (at least 65 tiles over 16 wavefronts: later tiles
+# from the counter, the prefetch cursor across tile boundaries and into "no tile left"), and 8 accumulators (mostly cold
+# observations).  Set after _create's deletions.
+LPL_STREAM_ENVS = ({"POVAR_E0_WGS": "1", "POVAR_LPL_K0": "2"}, {"POVAR_HOT_ACC": "8"})
+EDGE_CASES = [(f, r, {}) for r in ("NONE", "HUBER") for f in FAMILIES] + [("lpl", r, e) for e in LPL_STREAM_ENVS for r in ("NONE", "HUBER")]
+EDGE_IDS = ["-".join([f, r] + [f"{k}={v}" for k, v in e.items()]) for f, r, e in EDGE_CASES]
+
+
+@pytest.mark.parametrize("fam,robust,env", EDGE_CASES, ids=EDGE_IDS)
+def test_step1_operands_on_the_edge_graph(monkeypatch, fam, robust, env):
     p = edge_pose(robust)
     assert p.n_cams == 151 and p.n_lms == 4149 and len(p.cam_idx) == 14792 and (p.n_c == 0).sum() == 1
-    ctx = pose_context(monkeypatch, fam, p)
-    check_pose(ctx, p, fam, f"edge/{robust}")
+    ctx = pose_context(monkeypatch, fam, p, env)
+    if "POVAR_E0_WGS" in env:
+        assert ctx.layout_info().grid == 1
+    check_pose(ctx, p, fam, f"edge/{robust}" + "".join(f"/{k}={v}" for k, v in env.items()))
     ctx.close()
 
 
-@pytest.mark.parametrize("robust", ["NONE", "HUBER"])
-@pytest.mark.parametrize("fam", list(FAMILIES))
-def test_step2_operands_on_the_edge_graph(monkeypatch, fam, robust):
+@pytest.mark.parametrize("fam,robust,env", EDGE_CASES, ids=EDGE_IDS)
+def test_step2_operands_on_the_edge_graph(monkeypatch, fam, robust, env):
     p = edge_joint(robust)
     assert p.n_cams == 151 and (p.n_c == 0).sum() == 1
-    ctx = joint_context(monkeypatch, fam, p)
-    check_joint(ctx, p, fam, f"edge-joint/{robust}")
+    ctx = joint_context(monkeypatch, fam, p, env)
+    if "POVAR_E0_WGS" in env:
+        assert ctx.layout_info().grid == 1
+    check_joint(ctx, p, fam, f"edge-joint/{robust}" + "".join(f"/{k}={v}" for k, v in env.items()))
     ctx.close()
 
 
