@@ -21,6 +21,7 @@
 // lane, the forward pass alone needs ~120 of them, and with 8 or 12 wavefronts per workgroup it ran twice as long.)
 #pragma once
 
+#include "ck_layout.hpp"  // (CK_NONE)
 #include "povar_kernels.hpp"
 
 namespace povar {
@@ -84,6 +85,10 @@ __device__ inline void ck_group_barrier(int* cnt, int& gen, int group_waves, int
 __host__ __device__ inline int ck_rank(int x) { return x < 0 ? -1 : (x & 0xffff); }
 __host__ __device__ inline int ck_seg(int x) { return ((x >> 16) & 63) | (((x >> 22) & 63) << 8); }
 
+}  // namespace povar
+#include "povar_kernels_ck_parts.hpp"  // what the kernels of the family share: slot word, row walk, row stream
+namespace povar {
+
 // lpl_forward without the accumulation (red = ..., not red += ...: three fp64 adds per observation less)
 __device__ inline void ck_forward_math(const LplObs& o, const double* zz, const double* P3, double hx, double hy, double hz,
                                        double* red) {
@@ -145,16 +150,8 @@ __device__ inline void ck_obs_backward(const Dp& d, double2 uv, double w, const 
   }
 }
 
-// Streamed tile (rows read where they are used): D rows are in flight ahead of the row being worked on.  The D row
-// buffers are statically indexed -- the loop over the rows is unrolled by D -- so that a row's loads really have D
-// iterations to land.  (A rolled loop with a shift register of D buffers was built first: the register moves of
-// iteration j + 1 touch what iteration j has just requested, so every row waited for its predecessor's loads whatever
-// D was -- s_waitcnt vmcnt(0) at the top of the loop, 1400 cycles per row on the way back.)  D is even: the two
-// landmark slots of an li word then sit at a static shift.
+// Streamed tile (rows read where they are used): CkStream and its invariants are in povar_kernels_ck_parts.hpp.
 // buffer descriptors of the row arrays (wave-uniform: built once per kernel from kernel arguments)
-struct CkRows {
-  __amdgpu_buffer_rsrc_t uv, li, w;  // (w: step 2's e0_ck_h only)
-};
 __device__ inline CkRows ck_rows(const CkP& k) {
   CkRows R;
   R.uv = __builtin_amdgcn_make_buffer_rsrc(const_cast<double2*>(k.uv), 0, k.uv_bytes, 0x00020000);
@@ -162,60 +159,14 @@ __device__ inline CkRows ck_rows(const CkP& k) {
   R.w = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(k.w), 0, k.w ? (k.uv_packed ? k.uv_bytes : k.uv_bytes / 2) : 0, 0x00020000);
   return R;
 }
-template <int D, bool ROBUST, bool PK = false>
-struct CkStream {
-  double2 uv[D];
-  unsigned pk[D][2];  // (PK: the packed words.  They are decoded when the row is worked on, not when it is requested: a decode
-                      //  at the request makes the wavefront wait for the row there, and e0_ck requests a batch's first rows in
-                      //  front of the barrier that ends the batch before)
-  uint32_t w[D];
-  __device__ inline void clear() {
-#pragma unroll
-    for (int i = 0; i < D; ++i) {
-      uv[i] = make_double2(0, 0);
-      pk[i][0] = pk[i][1] = 0;
-      w[i] = 0xffffffffu;
-    }
-  }
-  __device__ inline double2 get(int i) const { return PK ? make_double2(ck_unpack_uv(pk[i][0]), ck_unpack_uv(pk[i][1])) : uv[i]; }
-  // buffer i <- row j of the tile (j clamped into the tile: a request past its end re-reads its last row -- a cache hit --
-  // so that every step issues the same loads and the wait counters can be exact: with loads under `if (j < h)` the
-  // compiler waited for all but the newest load, i.e. for the row it had requested one step earlier).
-  // The rows are read through buffer descriptors (CkRows): descriptor in SGPRs + the lane's constant 32-bit byte offset +
-  // the row's byte offset as the scalar offset -- no VALU instruction per load (a flat load took a 64-bit add each, two
-  // per row and pass in loops that are VALU-bound).
-  __device__ inline void load(const CkRows& R, int row0, int li0, int j, int h, int lane, int i) {
-    j = j < 0 ? 0 : (j >= h ? h - 1 : j);
-    const unsigned ul = (unsigned)lane;
-    const unsigned ro = (unsigned)(row0 + j) * (unsigned)(WAVE * 16), lo = (unsigned)(li0 + (j >> 1)) * (unsigned)(WAVE * 4);
-    if (PK) {  // packed image points: 8 bytes per observation
-      typedef unsigned __attribute__((ext_vector_type(2))) u2;
-      const u2 a = __builtin_amdgcn_raw_buffer_load_b64(R.uv, ul * 8u, ro >> 1, 0);
-      pk[i][0] = a.x;
-      pk[i][1] = a.y;
-    } else {
-      typedef unsigned __attribute__((ext_vector_type(4))) u4;
-      const u4 a = __builtin_amdgcn_raw_buffer_load_b128(R.uv, ul * 16u, ro, 0);
-      uv[i] = make_double2(__longlong_as_double(((long long)a.y << 32) | a.x), __longlong_as_double(((long long)a.w << 32) | a.z));
-    }
-    w[i] = __builtin_amdgcn_raw_buffer_load_b32(R.li, ul * 4u, lo, 0);
-  }
-  // step n of the walk is row n (DIR = +1) or row h - 1 - n (DIR = -1: the way back starts with the rows the way forward
-  // read last, the ones most likely still in the XCD's L2); buffer n % D holds it
-  template <int DIR>
-  __device__ inline void start(const CkRows& R, int row0, int li0, int h, int lane) {
-#pragma unroll
-    for (int i = 0; i < D; ++i) load(R, row0, li0, DIR > 0 ? i : h - 1 - i, h, lane, i);
-  }
-};
 // the rows of one tile (h >= 1); st has been started on the tile (steps 0 .. D-1 are in flight)
 template <int D, bool ROBUST, bool PK>
 __device__ inline void ck_forward_step(const Dp& d, const CkRows& k, CkStream<D, ROBUST, PK>& st, int row0, int li0, int h, int lane,
                                        const double* zz, const double* P3, const double* lh, double* lu, int S, int j, int i) {
   const double2 uv = st.get(i);
-  const uint32_t s = (st.w[i] >> (16 * (j & 1))) & 0xffffu;
+  const uint32_t s = ck_slot(st.w[i], j);
   st.load(k, row0, li0, j + D, h, lane, i);
-  if (s != 0xffffu) {
+  if (s != CK_NONE) {
     const double hx = lh[s], hy = lh[s + 1], hz = lh[s + 2];  // (s = 3 x slot: ck_layout.hpp)
     const double rw = ROBUST ? ck_huber_w(d, P3, hx, hy, hz, uv) : 1.0;
     ck_obs_forward(d, uv, rw, zz, P3, hx, hy, hz, lu, S, s);
@@ -224,23 +175,15 @@ __device__ inline void ck_forward_step(const Dp& d, const CkRows& k, CkStream<D,
 template <int D, bool ROBUST, bool PK>
 __device__ inline void ck_forward_rows(const Dp& d, const CkRows& k, CkStream<D, ROBUST, PK>& st, int row0, int li0, int h, int lane,
                                        const double* zz, const double* P3, const double* lh, double* lu, int S) {
-  int n0 = 0;
-#pragma nounroll
-  for (; n0 + D <= h; n0 += D) {
-#pragma unroll
-    for (int i = 0; i < D; ++i) ck_forward_step<D, ROBUST, PK>(d, k, st, row0, li0, h, lane, zz, P3, lh, lu, S, n0 + i, i);
-  }
-#pragma unroll
-  for (int i = 0; i < D - 1; ++i)  // the last h % D rows
-    if (n0 + i < h) ck_forward_step<D, ROBUST, PK>(d, k, st, row0, li0, h, lane, zz, P3, lh, lu, S, n0 + i, i);
+  ck_walk_rows<D, 1>(h, [&](int j, int i) { ck_forward_step<D, ROBUST, PK>(d, k, st, row0, li0, h, lane, zz, P3, lh, lu, S, j, i); });
 }
 template <int D, bool ROBUST, bool PK>
 __device__ inline void ck_backward_step(const Dp& d, const CkRows& k, CkStream<D, ROBUST, PK>& st, int row0, int li0, int h, int lane,
                                         const double* P3, const double* lh, const double* lg, int S, double* y, int j, int i) {
   const double2 uv = st.get(i);
-  const uint32_t s = (st.w[i] >> (16 * (j & 1))) & 0xffffu;
+  const uint32_t s = ck_slot(st.w[i], j);
   st.load(k, row0, li0, j - D, h, lane, i);
-  if (s != 0xffffu) {
+  if (s != CK_NONE) {
     const double hx = lh[s], hy = lh[s + 1], hz = lh[s + 2];
     const double rw = ROBUST ? ck_huber_w(d, P3, hx, hy, hz, uv) : 1.0;
     const double g[3] = {lg[s], lg[s + 1], lg[s + 2]};
@@ -250,15 +193,7 @@ __device__ inline void ck_backward_step(const Dp& d, const CkRows& k, CkStream<D
 template <int D, bool ROBUST, bool PK>
 __device__ inline void ck_backward_rows(const Dp& d, const CkRows& k, CkStream<D, ROBUST, PK>& st, int row0, int li0, int h, int lane,
                                         const double* P3, const double* lh, const double* lg, int S, double* y) {
-  int n0 = 0;
-#pragma nounroll
-  for (; n0 + D <= h; n0 += D) {
-#pragma unroll
-    for (int i = 0; i < D; ++i) ck_backward_step<D, ROBUST, PK>(d, k, st, row0, li0, h, lane, P3, lh, lg, S, y, h - 1 - (n0 + i), i);
-  }
-#pragma unroll
-  for (int i = 0; i < D - 1; ++i)
-    if (n0 + i < h) ck_backward_step<D, ROBUST, PK>(d, k, st, row0, li0, h, lane, P3, lh, lg, S, y, h - 1 - (n0 + i), i);
+  ck_walk_rows<D, -1>(h, [&](int j, int i) { ck_backward_step<D, ROBUST, PK>(d, k, st, row0, li0, h, lane, P3, lh, lg, S, y, j, i); });
 }
 
 // The way back over a tile that has lanes of cameras WITHOUT an accumulator slot, where those lanes leave q per observation in
@@ -273,8 +208,8 @@ __device__ inline void ck_backward_rows_cold(const Dp& d, const CkP& k, const Ck
     one.load(R, row0, li0, j, h, lane, 0);
     const int cp = cold_lane ? k.cpos[(size_t)(row0 + j) * WAVE + lane] : -1;
     const double2 uv = one.get(0);
-    const uint32_t s = (one.w[0] >> (16 * (j & 1))) & 0xffffu;
-    if (s != 0xffffu) {
+    const uint32_t s = ck_slot(one.w[0], j);
+    if (s != CK_NONE) {
       const double hx = lh[s], hy = lh[s + 1], hz = lh[s + 2];
       const double rw = ROBUST ? ck_huber_w(d, P3, hx, hy, hz, uv) : 1.0;
       const double g[3] = {lg[s], lg[s + 1], lg[s + 2]};
@@ -351,8 +286,6 @@ __device__ inline void ck_load_p(const Dp& d, int rank, double* P3) {
   }
 }
 
-// end of a tile's backward pass: the chunk sums go to the camera's accumulator in LDS (lanes that share one are summed
-// first) or, for a camera without a slot in this workgroup, to the chunk's own partial record
 // Partial records leave the kernel through PLAIN stores: the eight L2s gather a record's six 16-byte pieces (and the pieces of
 // neighbouring records) into whole lines and the release at the kernel's end writes them back in bulk.  Measured (round 6,
 // profiles/r06_experiments.txt B; venice-1778, us per term in the replayed graph): plain 60.4, write-through (sc1, aux 16: every
@@ -368,6 +301,15 @@ __device__ inline void ck_store_part(__amdgpu_buffer_rsrc_t pr, unsigned byte_of
   ck_u4 g;
   g.x = (unsigned)__double2loint(a); g.y = (unsigned)__double2hiint(a); g.z = (unsigned)__double2loint(b); g.w = (unsigned)__double2hiint(b);
   __builtin_amdgcn_raw_buffer_store_b128(g, pr, byte_off, 0, POVAR_CK_PART_AUX);
+}
+// end of the kernel (NW wavefronts): the accumulators -> this workgroup's partial records (camera-major behind PR)
+template <int NW>
+__device__ __forceinline__ void ck_store_accumulators(__amdgpu_buffer_rsrc_t PR, const CkP& k, int cam0, int n_acc, const double* acc) {
+  for (int i = threadIdx.x; i < n_acc * 6; i += NW * 64) {
+    const int r = i / 6, m = 2 * (i % 6);
+    const int rec = k.slot_rec[cam0 + r];
+    ck_store_part(PR, (unsigned)rec * 96u + 16u * (unsigned)(i % 6), acc[r * CK_ACC_STRIDE + m], acc[r * CK_ACC_STRIDE + m + 1]);
+  }
 }
 // end of a tile's backward pass: the chunk sums go to the camera's accumulator in LDS (lanes that share one are summed
 // first) or, for a camera without a slot in this workgroup, to the chunk's own partial record
@@ -770,12 +712,7 @@ __global__ __launch_bounds__(NW * 64) void e0_ck(Dp d, CkP k, double* part_out) 
   }
   if (NG > 1) ck_barrier();  // every group is done: the accumulators are complete
   // ---- accumulators -> this workgroup's partial records (camera-major in part_out)
-  const __amdgpu_buffer_rsrc_t PR = ck_part_rsrc(part_out);
-  for (int i = threadIdx.x; i < n_acc * 6; i += NW * 64) {
-    const int r = i / 6, m = 2 * (i % 6);
-    const int rec = k.slot_rec[cam0 + r];
-    ck_store_part(PR, (unsigned)rec * 96u + 16u * (unsigned)(i % 6), acc[r * CK_ACC_STRIDE + m], acc[r * CK_ACC_STRIDE + m + 1]);
-  }
+  ck_store_accumulators<NW>(ck_part_rsrc(part_out), k, cam0, n_acc, acc);
   if (d.p2p_epoch && blockIdx.x == 0 && threadIdx.x == 0) *d.p2p_epoch += 1;  // one tick per term (as e0_lpl)
 }
 

@@ -101,21 +101,10 @@ struct CkdJoint {
   template <int D, bool ROBUST> __device__ static inline Obs obs(const Stream<D, ROBUST>& st, int i) { return ROBUST ? st.rw[i] : 1.0; }
   template <bool ROBUST> __device__ static inline void load_cam(const Dp& d, int rank, Cam& c) { ckh_load_rec(d, rank, c.zz, c.P); }
   template <bool ROBUST> __device__ static inline void load_cam_back(const Dp& d, int rank, Cam& c) { ckh_load_cam(d, rank, c.P); }
-  // J4^T t, t = sw D (Z X): the arithmetic of ckh_obs_forward (povar_kernels_ck_joint.hpp) without its adds -- a copy, the
-  // same expressions in the same order: e0_ck_h's helper stays as it is
+  // J4^T t, t = sw D (Z X): what e0_ck_h adds (ckh_forward_math)
   template <bool ROBUST>
   __device__ static inline void contribution(const Dp&, const Cam& c, Obs rw, const double* lx, uint32_t s, double (&v)[NC]) {
-    const povar::Cam& P = c.P;
-    const double4 X = make_double4(lx[s], lx[CKH_STRIDE + s], lx[2 * CKH_STRIDE + s], lx[3 * CKH_STRIDE + s]);
-    const double sw = ROBUST ? sqrt(rw) : 1.0;
-    const Hom hp = ckh_project(P, X);
-    double t[2];
-    hom_jp_x(hp, X, sw, c.zz, t);
-    const double e0 = sw * hp.D00 * t[0], e1 = sw * hp.D00 * t[1], e2 = sw * (hp.D02 * t[0] + hp.D12 * t[1]);
-    v[0] = P.r0.x * e0 + P.r1.x * e1 + P.r2.x * e2;
-    v[1] = P.r0.y * e0 + P.r1.y * e1 + P.r2.y * e2;
-    v[2] = P.r0.z * e0 + P.r1.z * e1 + P.r2.z * e2;
-    v[3] = P.r0.w * e0 + P.r1.w * e1 + P.r2.w * e2;
+    ckh_forward_math<ROBUST>(c.P, c.zz, rw, lx, s, [&](int m, double x) { v[m] = x; });
   }
   // U4 -> G4 (ckh_landmark_step reads U4 where the sums were)
   __device__ static inline void landmark_step(double* lx, double* lu, int s, const double (&u)[NC], const double (&rec)[NG]) {
@@ -145,11 +134,11 @@ __host__ __device__ inline size_t ckh_lds_bytes_det(int n_acc) { return ckd_lds_
 template <class Step, int D, bool ROBUST, int PASS>
 __device__ inline void ckd_forward_rows(const Dp& d, const CkRows& R, typename Step::template Stream<D, ROBUST>& st, int row0, int li0, int h,
                                         int lane, const typename Step::Cam& c, const double* lx, double* lu, const short* lexp) {
-  auto step = [&](int j, int i) {
+  ck_walk_rows<D, 1>(h, [&](int j, int i) {
     const typename Step::Obs o = Step::template obs<D, ROBUST>(st, i);
-    const uint32_t s = (st.w[i] >> (16 * (j & 1))) & 0xffffu;
+    const uint32_t s = ck_slot(st.w[i], j);
     st.load(R, row0, li0, j + D, h, lane, i);
-    if (s != 0xffffu) {
+    if (s != CK_NONE) {
       double v[Step::NC];
       Step::template contribution<ROBUST>(d, c, o, lx, s, v);
       if (PASS == 0) {
@@ -165,16 +154,7 @@ __device__ inline void ckd_forward_rows(const Dp& d, const CkRows& R, typename S
                                  __HIP_MEMORY_SCOPE_WORKGROUP);
       }
     }
-  };
-  int n0 = 0;
-#pragma nounroll
-  for (; n0 + D <= h; n0 += D) {
-#pragma unroll
-    for (int i = 0; i < D; ++i) step(n0 + i, i);
-  }
-#pragma unroll
-  for (int i = 0; i < D - 1; ++i)
-    if (n0 + i < h) step(n0 + i, i);
+  });
 }
 
 // NW wavefronts per workgroup (the count the layout's tiles were scheduled for and its tickets numbered for), SD rows in flight

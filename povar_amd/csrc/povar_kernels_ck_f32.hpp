@@ -35,9 +35,6 @@ __host__ __device__ inline size_t ck32_lds_bytes(int slots, int n_acc) {
   return 16 + (size_t)slots * 24 + (size_t)n_acc * CK_ACC_STRIDE * 8 + 64;
 }
 
-// a packed image coordinate in fp32: k micro-units (the packing verified that k * 10^-6 is the file's number)
-__device__ inline float ck32_unpack(unsigned k) { return (float)(int)k * 1e-6f; }
-
 struct Ck32Obs {
   float w, cu, cv, cuv;
   __device__ inline void set(float sb2, float2 uv, float w_) {
@@ -60,31 +57,7 @@ __device__ inline float ck32_huber_w(float sb2, float sa2, float t, const float*
   return r2 < t * t ? 1.0f : t * y;
 }
 
-struct Ck32Rows {
-  __amdgpu_buffer_rsrc_t uv, li;
-};
-
-// D rows in flight (as CkStream: statically indexed buffers, a request past the tile's end re-reads its last row)
-template <int D, bool PK>
-struct Ck32Stream {
-  float2 uv[D];
-  uint32_t w[D];
-  __device__ inline void load(const Ck32Rows& R, int row0, int li0, int j, int h, int lane, int i) {
-    j = j < 0 ? 0 : (j >= h ? h - 1 : j);
-    const unsigned ro = (unsigned)(row0 + j) * (unsigned)(WAVE * 8), lo = (unsigned)(li0 + (j >> 1)) * (unsigned)(WAVE * 4);
-    typedef unsigned __attribute__((ext_vector_type(2))) u2;
-    const u2 a = __builtin_amdgcn_raw_buffer_load_b64(R.uv, (unsigned)lane * 8u, ro, 0);
-    if (PK) uv[i] = make_float2(ck32_unpack(a.x), ck32_unpack(a.y));
-    else uv[i] = make_float2(__uint_as_float(a.x), __uint_as_float(a.y));
-    w[i] = __builtin_amdgcn_raw_buffer_load_b32(R.li, (unsigned)lane * 4u, lo, 0);
-  }
-  template <int DIR>
-  __device__ inline void start(const Ck32Rows& R, int row0, int li0, int h, int lane) {
-#pragma unroll
-    for (int i = 0; i < D; ++i) load(R, row0, li0, DIR > 0 ? i : h - 1 - i, h, lane, i);
-  }
-};
-
+// (the rows: Ck32Stream, povar_kernels_ck_parts.hpp -- float2 image points or the packed words through CkRows::uv)
 struct Ck32Scal {
   float sb2, sa2, huber;
 };
@@ -126,33 +99,24 @@ __device__ inline void ck32_obs_backward(const Ck32Scal& sc, float2 uv, const fl
 }
 
 template <int D, bool ROBUST, bool PK>
-__device__ inline void ck32_forward_rows(const Ck32Scal& sc, const Ck32Rows& R, Ck32Stream<D, PK>& st, int row0, int li0, int h, int lane,
+__device__ inline void ck32_forward_rows(const Ck32Scal& sc, const CkRows& R, Ck32Stream<D, PK>& st, int row0, int li0, int h, int lane,
                                          const float* zz, const float* P, const float* lh, float* lu) {
-  auto step = [&](int j, int i) {
+  ck_walk_rows<D, 1>(h, [&](int j, int i) {
     const float2 uv = st.uv[i];
-    const uint32_t s = (st.w[i] >> (16 * (j & 1))) & 0xffffu;
+    const uint32_t s = ck_slot(st.w[i], j);
     st.load(R, row0, li0, j + D, h, lane, i);
-    if (s != 0xffffu) ck32_obs_forward<ROBUST>(sc, uv, zz, P, lh, lu, s);
-  };
-  int n0 = 0;
-#pragma nounroll
-  for (; n0 + D <= h; n0 += D) {
-#pragma unroll
-    for (int i = 0; i < D; ++i) step(n0 + i, i);
-  }
-#pragma unroll
-  for (int i = 0; i < D - 1; ++i)
-    if (n0 + i < h) step(n0 + i, i);
+    if (s != CK_NONE) ck32_obs_forward<ROBUST>(sc, uv, zz, P, lh, lu, s);
+  });
 }
 
 template <int D, bool ROBUST, bool PK>
-__device__ inline void ck32_backward_rows(const Ck32Scal& sc, const Ck32Rows& R, Ck32Stream<D, PK>& st, int row0, int li0, int h, int lane,
+__device__ inline void ck32_backward_rows(const Ck32Scal& sc, const CkRows& R, Ck32Stream<D, PK>& st, int row0, int li0, int h, int lane,
                                           const float* P, const float* lh, const float* lg, float* y) {
-  auto step = [&](int j, int i) {
+  ck_walk_rows<D, -1>(h, [&](int j, int i) {
     const float2 uv = st.uv[i];
-    const uint32_t s = (st.w[i] >> (16 * (j & 1))) & 0xffffu;
+    const uint32_t s = ck_slot(st.w[i], j);
     st.load(R, row0, li0, j - D, h, lane, i);
-    if (s != 0xffffu) {
+    if (s != CK_NONE) {
       float hh[3], q[3];
       ck32_obs_backward<ROBUST>(sc, uv, P, lh, lg, s, hh, q);
 #pragma unroll
@@ -163,29 +127,20 @@ __device__ inline void ck32_backward_rows(const Ck32Scal& sc, const Ck32Rows& R,
         y[4 * m + 3] += q[m];
       }
     }
-  };
-  int n0 = 0;
-#pragma nounroll
-  for (; n0 + D <= h; n0 += D) {
-#pragma unroll
-    for (int i = 0; i < D; ++i) step(h - 1 - (n0 + i), i);
-  }
-#pragma unroll
-  for (int i = 0; i < D - 1; ++i)
-    if (n0 + i < h) step(h - 1 - (n0 + i), i);
+  });
 }
 
 // the way back over a tile with lanes of cameras WITHOUT an accumulator slot that leave q in the cold view (ck_backward_rows_cold):
 // rows read where they are used, q stored as the fp64 double4 the per-camera kernel reads
 template <bool PK>
-__device__ inline void ck32_backward_rows_cold(const Ck32Scal& sc, const CkP& k, const Ck32Rows& R, int row0, int li0, int h, int lane,
+__device__ inline void ck32_backward_rows_cold(const Ck32Scal& sc, const CkP& k, const CkRows& R, int row0, int li0, int h, int lane,
                                                const float* P, const float* lh, const float* lg, bool cold_lane, float* y) {
   for (int j = h - 1; j >= 0; --j) {
     Ck32Stream<1, PK> one;
     one.load(R, row0, li0, j, h, lane, 0);
     const int cp = cold_lane ? k.cpos[(size_t)(row0 + j) * WAVE + lane] : -1;
-    const uint32_t s = (one.w[0] >> (16 * (j & 1))) & 0xffffu;
-    if (s != 0xffffu) {
+    const uint32_t s = ck_slot(one.w[0], j);
+    if (s != CK_NONE) {
       float hh[3], q[3];
       ck32_obs_backward<false>(sc, one.uv[0], P, lh, lg, s, hh, q);
       if (cp >= 0) {
@@ -242,7 +197,7 @@ __global__ __launch_bounds__(CK32_NW * 64) void e0_ck_f32(Dp d, CkP k, Ck32 f, d
   const int t0 = __builtin_amdgcn_readfirstlane(v.wg_tile_off[blockIdx.x]);
   const int t1 = __builtin_amdgcn_readfirstlane(v.wg_tile_off[blockIdx.x + 1]);
   if (done) return;  // wave-uniform, before any barrier and any side effect
-  Ck32Rows R;
+  CkRows R;
   R.uv = __builtin_amdgcn_make_buffer_rsrc(PK ? (void*)k.uv : (void*)f.uv, 0, f.uv_bytes, 0x00020000);
   R.li = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(k.li), 0, k.li_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t PR = __builtin_amdgcn_make_buffer_rsrc(part_out, 0, f.part_bytes, 0x00020000);
@@ -270,15 +225,15 @@ __global__ __launch_bounds__(CK32_NW * 64) void e0_ck_f32(Dp d, CkP k, Ck32 f, d
     // ---- forward
     int q_t = 0;
     for (int t = tile_of(tb0, 0); t < tb1; t = tile_of(tb0, ++q_t)) {
-      const int4 tl = k.tile[t];
-      const int rank = ck_rank(k.lane_meta[(size_t)t * WAVE + lane].x);
+      const CkTile tl = CkTile::of(k.tile[t]);
+      const int rank = CkLaneMeta::rank_of(k, t, lane);
       const int rk = rank < 0 ? 0 : rank;
       float zz[12], P[12];
       ck32_load_p<ROBUST>(f, rk, P);
       Ck32Stream<SD, PK> st;
-      st.template start<1>(R, tl.x, tl.w, tl.y, lane);
+      st.template start<1>(R, tl.row0, tl.li0, tl.h, lane);
       ck32_load_z(d, rk, zz);
-      ck32_forward_rows<SD, ROBUST, PK>(sc, R, st, tl.x, tl.w, tl.y, lane, zz, P, lh, lu);
+      ck32_forward_rows<SD, ROBUST, PK>(sc, R, st, tl.row0, tl.li0, tl.h, lane, zz, P, lh, lu);
     }
     ck_barrier();
     // ---- g = G u per landmark slot
@@ -296,28 +251,28 @@ __global__ __launch_bounds__(CK32_NW * 64) void e0_ck_f32(Dp d, CkP k, Ck32 f, d
     // ---- backward: the wavefront's tiles in reverse
     for (int q = q_t - 1; q >= 0; --q) {
       const int t = tile_of(tb0, q);
-      const int4 tl = k.tile[t];
-      const int2 me = k.lane_meta[(size_t)t * WAVE + lane];
-      const int rank = ck_rank(me.x), seg = ck_seg(me.x), acc_slot = me.y;
+      const CkTile tl = CkTile::of(k.tile[t]);
+      const CkLaneMeta me = CkLaneMeta::load(k, t, lane);
+      const int rank = me.rank, seg = me.seg, acc_slot = me.acc;
       float P[12];
       ck32_load_p<ROBUST>(f, rank < 0 ? 0 : rank, P);
       float y[12];
 #pragma unroll
       for (int m = 0; m < 12; ++m) y[m] = 0;
       // (2 = CK_FLAG_COLD; as in e0_ck, not with a robust norm: the layout keeps the records for those)
-      const bool cold_q = !ROBUST && k.cpos != nullptr && (tl.z & 2) != 0;
+      const bool cold_q = !ROBUST && k.cpos != nullptr && (tl.fl & 2) != 0;
       if (cold_q) {
-        ck32_backward_rows_cold<PK>(sc, k, R, tl.x, tl.w, tl.y, lane, P, lh, lu, rank >= 0 && acc_slot < 0, y);
+        ck32_backward_rows_cold<PK>(sc, k, R, tl.row0, tl.li0, tl.h, lane, P, lh, lu, rank >= 0 && acc_slot < 0, y);
       } else {
         Ck32Stream<SD, PK> st;
-        st.template start<-1>(R, tl.x, tl.w, tl.y, lane);
-        ck32_backward_rows<SD, ROBUST, PK>(sc, R, st, tl.x, tl.w, tl.y, lane, P, lh, lu, y);
+        st.template start<-1>(R, tl.row0, tl.li0, tl.h, lane);
+        ck32_backward_rows<SD, ROBUST, PK>(sc, R, st, tl.row0, tl.li0, tl.h, lane, P, lh, lu, y);
       }
       // the chunk's sum leaves fp32 here: lanes of one camera are summed in fp64, then its accumulator or its own record
       double yd[12];
 #pragma unroll
       for (int m = 0; m < 12; ++m) yd[m] = (double)y[m];
-      if (tl.z & 1) seg_scan_steps<12>(yd, lane, seg & 255, 4);  // (inclusive scan: the run's total is in its LAST lane)
+      if (tl.fl & 1) seg_scan_steps<12>(yd, lane, seg & 255, 4);  // (inclusive scan: the run's total is in its LAST lane)
       if (rank >= 0) {
         if (acc_slot >= 0) {
           if (lane == ((seg >> 8) & 255)) {
@@ -336,11 +291,7 @@ __global__ __launch_bounds__(CK32_NW * 64) void e0_ck_f32(Dp d, CkP k, Ck32 f, d
   }
   if (k.nb == 0) ck_barrier();
   // ---- accumulators -> this workgroup's partial records (camera-major in part_out)
-  for (int i = threadIdx.x; i < n_acc * 6; i += NW * 64) {
-    const int r = i / 6, m = 2 * (i % 6);
-    const int rec = k.slot_rec[cam0 + r];
-    ck_store_part(PR, (unsigned)rec * 96u + 16u * (unsigned)(i % 6), acc[r * CK_ACC_STRIDE + m], acc[r * CK_ACC_STRIDE + m + 1]);
-  }
+  ck_store_accumulators<NW>(PR, k, cam0, n_acc, acc);
   if (d.p2p_epoch && blockIdx.x == 0 && threadIdx.x == 0) *d.p2p_epoch += 1;  // one tick per term (as e0_ck)
 }
 

@@ -38,34 +38,7 @@ constexpr int CKH_STRIDE_WIDE = 2048;   // the same with fewer accumulators besi
 constexpr int CKH_REC = 14;        // = LPL_REC_H: doubles per landmark lane in V2::lmrec (step 2): X (4), s (4), Hll^-1 (6)
 __host__ __device__ inline size_t ckh_lds_bytes(int n_acc, int stride = CKH_STRIDE) { return 16 + (size_t)8 * stride * 8 + (size_t)n_acc * CK_ACC_STRIDE * 8 + 64; }
 
-// rows of a tile: the landmark-slot words (two 16-bit slots per word) and, with a robust norm, the weights
-template <int D, bool ROBUST>
-struct CkStreamH {
-  uint32_t w[D];
-  double rw[D];
-  __device__ inline void clear() {
-#pragma unroll
-    for (int i = 0; i < D; ++i) {
-      w[i] = 0xffffffffu;
-      rw[i] = 1.0;
-    }
-  }
-  __device__ inline void load(const CkRows& R, int row0, int li0, int j, int h, int lane, int i) {
-    j = j < 0 ? 0 : (j >= h ? h - 1 : j);
-    const unsigned ul = (unsigned)lane;
-    w[i] = __builtin_amdgcn_raw_buffer_load_b32(R.li, ul * 4u, (unsigned)(li0 + (j >> 1)) * (unsigned)(WAVE * 4), 0);
-    if (ROBUST) {
-      typedef unsigned __attribute__((ext_vector_type(2))) u2;
-      const u2 b = __builtin_amdgcn_raw_buffer_load_b64(R.w, ul * 8u, (unsigned)(row0 + j) * (unsigned)(WAVE * 8), 0);
-      rw[i] = __longlong_as_double(((long long)b.y << 32) | b.x);
-    }
-  }
-  template <int DIR>
-  __device__ inline void start(const CkRows& R, int row0, int li0, int h, int lane) {
-#pragma unroll
-    for (int i = 0; i < D; ++i) load(R, row0, li0, DIR > 0 ? i : h - 1 - i, h, lane, i);
-  }
-};
+// (rows of a tile: the landmark-slot words and, with a robust norm, the weights -- CkStreamH, povar_kernels_ck_parts.hpp)
 
 __device__ inline void ckh_load_rec(const Dp& d, int rank, double4 (&zz)[3], Cam& P) {
   const double2* r = reinterpret_cast<const double2*>(d.hot_rec + (size_t)rank * HOT_REC_STRIDE);
@@ -101,19 +74,28 @@ __device__ inline Hom ckh_project(const Cam& P, const double4& X) {
 }
 // J4 = sw D P with D = [D00 0 D02; 0 D00 D12] (hom_jl4 with unit column scale) is never formed:
 //   J4^T t = P^T (D^T t),   J4 g = D (P g)       (12 + 4 operations each instead of 16 + 8)
-// one observation forward: U4_l += J4^T t,  t = sw D (Z X)
-template <bool ROBUST, int CKH_STRIDE = povar::CKH_STRIDE>
-__device__ inline void ckh_obs_forward(const Cam& P, const double4 (&zz)[3], double w, const double* lx, double* lu, uint32_t s) {
+// one observation's contribution to U4_l: J4^T t,  t = sw D (Z X), handed to sum(component, value) one component at a time --
+// each is formed in front of what the caller does with it (e0_ck_h, series_res_h: an LDS add; e0_ck_h_det: kept for the
+// fixed-point grid).  Its expressions and their order are what the error models "ckh" and "det" of tests/rounding_bounds.py describe.
+template <bool ROBUST, int CKH_STRIDE = povar::CKH_STRIDE, class Sum>
+__device__ inline void ckh_forward_math(const Cam& P, const double4 (&zz)[3], double w, const double* lx, uint32_t s, Sum&& sum) {
   const double4 X = make_double4(lx[s], lx[CKH_STRIDE + s], lx[2 * CKH_STRIDE + s], lx[3 * CKH_STRIDE + s]);
   const double sw = ROBUST ? sqrt(w) : 1.0;
   const Hom h = ckh_project(P, X);
   double t[2];
   hom_jp_x(h, X, sw, zz, t);
   const double e0 = sw * h.D00 * t[0], e1 = sw * h.D00 * t[1], e2 = sw * (h.D02 * t[0] + h.D12 * t[1]);
-  __hip_atomic_fetch_add(lu + s, P.r0.x * e0 + P.r1.x * e1 + P.r2.x * e2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  __hip_atomic_fetch_add(lu + CKH_STRIDE + s, P.r0.y * e0 + P.r1.y * e1 + P.r2.y * e2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  __hip_atomic_fetch_add(lu + 2 * CKH_STRIDE + s, P.r0.z * e0 + P.r1.z * e1 + P.r2.z * e2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  __hip_atomic_fetch_add(lu + 3 * CKH_STRIDE + s, P.r0.w * e0 + P.r1.w * e1 + P.r2.w * e2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  sum(0, P.r0.x * e0 + P.r1.x * e1 + P.r2.x * e2);
+  sum(1, P.r0.y * e0 + P.r1.y * e1 + P.r2.y * e2);
+  sum(2, P.r0.z * e0 + P.r1.z * e1 + P.r2.z * e2);
+  sum(3, P.r0.w * e0 + P.r1.w * e1 + P.r2.w * e2);
+}
+// one observation forward: U4_l += J4^T t
+template <bool ROBUST, int CKH_STRIDE = povar::CKH_STRIDE>
+__device__ inline void ckh_obs_forward(const Cam& P, const double4 (&zz)[3], double w, const double* lx, double* lu, uint32_t s) {
+  ckh_forward_math<ROBUST, CKH_STRIDE>(P, zz, w, lx, s, [&](int m, double v) {
+    __hip_atomic_fetch_add(lu + m * CKH_STRIDE + s, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  });
 }
 // one observation backward: y_c += X (x) q,  q = hom_q(J4 G4)
 template <bool ROBUST, int CKH_STRIDE = povar::CKH_STRIDE>
@@ -134,40 +116,22 @@ __device__ inline void ckh_obs_backward(const Cam& P, double w, const double* lx
 template <int D, bool ROBUST, int CKH_STRIDE = povar::CKH_STRIDE>
 __device__ inline void ckh_forward_rows(const CkRows& R, CkStreamH<D, ROBUST>& st, int row0, int li0, int h, int lane,
                                         const Cam& P, const double4 (&zz)[3], const double* lx, double* lu) {
-  auto step = [&](int j, int i) {
-    const uint32_t s = (st.w[i] >> (16 * (j & 1))) & 0xffffu;
+  ck_walk_rows<D, 1>(h, [&](int j, int i) {
+    const uint32_t s = ck_slot(st.w[i], j);
     const double rw = ROBUST ? st.rw[i] : 1.0;
     st.load(R, row0, li0, j + D, h, lane, i);
-    if (s != 0xffffu) ckh_obs_forward<ROBUST, CKH_STRIDE>(P, zz, rw, lx, lu, s);
-  };
-  int n0 = 0;
-#pragma nounroll
-  for (; n0 + D <= h; n0 += D) {
-#pragma unroll
-    for (int i = 0; i < D; ++i) step(n0 + i, i);
-  }
-#pragma unroll
-  for (int i = 0; i < D - 1; ++i)
-    if (n0 + i < h) step(n0 + i, i);
+    if (s != CK_NONE) ckh_obs_forward<ROBUST, CKH_STRIDE>(P, zz, rw, lx, lu, s);
+  });
 }
 template <int D, bool ROBUST, int CKH_STRIDE = povar::CKH_STRIDE>
 __device__ inline void ckh_backward_rows(const CkRows& R, CkStreamH<D, ROBUST>& st, int row0, int li0, int h, int lane,
                                          const Cam& P, const double* lx, const double* lg, double (&y)[12]) {
-  auto step = [&](int j, int i) {
-    const uint32_t s = (st.w[i] >> (16 * (j & 1))) & 0xffffu;
+  ck_walk_rows<D, -1>(h, [&](int j, int i) {
+    const uint32_t s = ck_slot(st.w[i], j);
     const double rw = ROBUST ? st.rw[i] : 1.0;
     st.load(R, row0, li0, j - D, h, lane, i);
-    if (s != 0xffffu) ckh_obs_backward<ROBUST, CKH_STRIDE>(P, rw, lx, lg, s, y);
-  };
-  int n0 = 0;
-#pragma nounroll
-  for (; n0 + D <= h; n0 += D) {
-#pragma unroll
-    for (int i = 0; i < D; ++i) step(h - 1 - (n0 + i), i);
-  }
-#pragma unroll
-  for (int i = 0; i < D - 1; ++i)
-    if (n0 + i < h) step(h - 1 - (n0 + i), i);
+    if (s != CK_NONE) ckh_obs_backward<ROBUST, CKH_STRIDE>(P, rw, lx, lg, s, y);
+  });
 }
 
 // Between the passes, per landmark slot (the lane that owns it): U4 -> G4 = s .* (N_l Hll^-1 N_l^T (s .* U4)).
@@ -211,9 +175,7 @@ __global__ __launch_bounds__(NW * 64) void e0_ck_h(Dp d, CkP k, double* part_out
   const int t0 = __builtin_amdgcn_readfirstlane(v.wg_tile_off[blockIdx.x]);
   const int t1 = __builtin_amdgcn_readfirstlane(v.wg_tile_off[blockIdx.x + 1]);
   for (int i = threadIdx.x; i < n_acc * CK_ACC_STRIDE; i += NW * 64) acc[i] = 0;
-  typedef const int __attribute__((address_space(4))) * cint_p;
-  const cint_p tiles = (cint_p)(uintptr_t)k.tile;
-  const cint_p bt = (cint_p)(uintptr_t)k.bt_off;
+  const CkTile::table_p tiles = CkTile::table(k), bt = (CkTile::table_p)(uintptr_t)k.bt_off;  // (both through the scalar cache)
   if (done) return;  // wave-uniform, before any barrier and any side effect
   auto tile_of = [&](int tb0, int q) { return tb0 + q * NW + ((q & 1) ? NW - 1 - wave : wave); };
   constexpr int HM = 32 / NW > 0 ? 32 / NW : 1;  // slot tiles per wavefront whose X is requested a phase ahead
@@ -243,7 +205,7 @@ __global__ __launch_bounds__(NW * 64) void e0_ck_h(Dp d, CkP k, double* part_out
     rank_next = 0;
     if (b < k.nb) {
       const int tb0 = bt_of(b, b == 0), tb1 = bt_of(b + 1, b == 0);
-      if (tb0 + wave < tb1) rank_next = ck_rank(k.lane_meta[(size_t)(tb0 + wave) * WAVE + lane].x);
+      if (tb0 + wave < tb1) rank_next = CkLaneMeta::rank_of(k, tb0 + wave, lane);
     }
   };
   request_first_meta(0, lane0);
@@ -261,15 +223,15 @@ __global__ __launch_bounds__(NW * 64) void e0_ck_h(Dp d, CkP k, double* part_out
     P.r0 = P.r1 = P.r2 = make_double4(0, 0, 0, 0);
     CkStreamH<SD, ROBUST> st;
     st.clear();
-    int row0 = 0, h = 0, fl = 0, li0 = 0;
+    CkTile tl = {0, 0, 0, 0};
     int tn = tile_of(tb0, 1);
     int rank_n = 0;
     // ---- the way forward starts: record and first rows of the first tile
     if (t < tb1) {
-      row0 = tiles[4 * t]; h = tiles[4 * t + 1]; fl = tiles[4 * t + 2]; li0 = tiles[4 * t + 3];  // (the whole header at once: below)
-      if (tn < tb1) rank_n = ck_rank(k.lane_meta[(size_t)tn * WAVE + lane].x);
+      tl = CkTile::load(tiles, t);  // (the whole header at once: below)
+      if (tn < tb1) rank_n = CkLaneMeta::rank_of(k, tn, lane);
       ckh_load_rec(d, rank < 0 ? 0 : rank, zz, P);
-      st.template start<1>(R, row0, li0, h, lane);
+      st.template start<1>(R, tl.row0, tl.li0, tl.h, lane);
     }
     // ---- X of the batch into LDS (requested a phase ago), U4 = 0
 #pragma unroll
@@ -296,22 +258,21 @@ __global__ __launch_bounds__(NW * 64) void e0_ck_h(Dp d, CkP k, double* part_out
     ck_barrier();
     // ---- forward
     while (t < tb1) {
-      ckh_forward_rows<SD, ROBUST, CKH_STRIDE>(R, st, row0, li0, h, lane, P, zz, lx, lu);
+      ckh_forward_rows<SD, ROBUST, CKH_STRIDE>(R, st, tl.row0, tl.li0, tl.h, lane, P, zz, lx, lu);
       if (tn >= tb1) break;  // (t, q_t, rank, P stay on the last tile: the way back starts there)
       t = tn;
       ++q_t;
       rank = rank_n;
       tn = tile_of(tb0, q_t + 1);
-      row0 = tiles[4 * t]; h = tiles[4 * t + 1]; fl = tiles[4 * t + 2]; li0 = tiles[4 * t + 3];
-      if (tn < tb1) rank_n = ck_rank(k.lane_meta[(size_t)tn * WAVE + lane].x);
+      tl = CkTile::load(tiles, t);
+      if (tn < tb1) rank_n = CkLaneMeta::rank_of(k, tn, lane);
       ckh_load_rec(d, rank < 0 ? 0 : rank, zz, P);
-      st.template start<1>(R, row0, li0, h, lane);
+      st.template start<1>(R, tl.row0, tl.li0, tl.h, lane);
     }
     // ---- the way back starts before the barriers in front of it
     asm volatile("" : "+v"(lane));
-    int acc_slot = 0, seg = 0;
     int tp = q_t > 0 ? tile_of(tb0, q_t - 1) : tb1;
-    int rank_p = 0, acc_p = 0, seg_p = 0;
+    CkLaneMeta me = {rank, 0, 0}, mp = {0, 0, 0};  // the lane in tile t and in tp
     double rec[HM][10];  // s (4) and Hll^-1 (6) of the wavefront's landmark slots
 #pragma unroll
     for (int q = 0; q < HM; ++q) {
@@ -325,16 +286,11 @@ __global__ __launch_bounds__(NW * 64) void e0_ck_h(Dp d, CkP k, double* part_out
       }
     }
     if (t < tb1) {
-      const int2 me = k.lane_meta[(size_t)t * WAVE + lane];
-      seg = ck_seg(me.x);
-      acc_slot = me.y;  // (fl came with the tile's header: a scalar load HERE is a miss in front of the barrier's lgkmcnt(0) --
-      if (tp < tb1) {   //  ~ 2.6 k cycles per batch in e0_ck's stamps, profiles/r06_e0_ck_phase_stamps.txt)
-        const int2 mp = k.lane_meta[(size_t)tp * WAVE + lane];
-        rank_p = ck_rank(mp.x);
-        seg_p = ck_seg(mp.x);
-        acc_p = mp.y;
-      }
-      st.template start<-1>(R, row0, li0, h, lane);
+      // (tl.fl came with the tile's header: a scalar load HERE is a miss in front of the barrier's lgkmcnt(0) --
+      //  ~ 2.6 k cycles per batch in e0_ck's stamps, profiles/r06_e0_ck_phase_stamps.txt)
+      me = CkLaneMeta::load(k, t, lane);
+      if (tp < tb1) mp = CkLaneMeta::load(k, tp, lane);
+      st.template start<-1>(R, tl.row0, tl.li0, tl.h, lane);
     }
     ck_barrier();
     request_first_meta(b + 1, lane);
@@ -358,32 +314,22 @@ __global__ __launch_bounds__(NW * 64) void e0_ck_h(Dp d, CkP k, double* part_out
       double y[12];
 #pragma unroll
       for (int m = 0; m < 12; ++m) y[m] = 0;
-      ckh_backward_rows<SD, ROBUST, CKH_STRIDE>(R, st, row0, li0, h, lane, P, lx, lu, y);
-      ck_flush_tile(y, fl, lane, rank, acc_slot, seg, acc, n_acc, part_out);
+      ckh_backward_rows<SD, ROBUST, CKH_STRIDE>(R, st, tl.row0, tl.li0, tl.h, lane, P, lx, lu, y);
+      ck_flush_tile(y, tl.fl, lane, me.rank, me.acc, me.seg, acc, n_acc, part_out);
       if (tp >= tb1) break;
       t = tp;
       --q_t;
-      rank = rank_p; acc_slot = acc_p; seg = seg_p;
+      me = mp;
       tp = q_t > 0 ? tile_of(tb0, q_t - 1) : tb1;
-      row0 = tiles[4 * t]; h = tiles[4 * t + 1]; fl = tiles[4 * t + 2]; li0 = tiles[4 * t + 3];
-      if (tp < tb1) {
-        const int2 mp = k.lane_meta[(size_t)tp * WAVE + lane];
-        rank_p = ck_rank(mp.x);
-        seg_p = ck_seg(mp.x);
-        acc_p = mp.y;
-      }
-      ckh_load_cam(d, rank < 0 ? 0 : rank, P);
-      st.template start<-1>(R, row0, li0, h, lane);
+      tl = CkTile::load(tiles, t);
+      if (tp < tb1) mp = CkLaneMeta::load(k, tp, lane);
+      ckh_load_cam(d, me.rank < 0 ? 0 : me.rank, P);
+      st.template start<-1>(R, tl.row0, tl.li0, tl.h, lane);
     }
     ck_barrier();  // the next batch overwrites X and U4; after the last one: the accumulators are complete
   }
   // ---- accumulators -> this workgroup's partial records (camera-major in part_out)
-  const __amdgpu_buffer_rsrc_t PR = ck_part_rsrc(part_out);
-  for (int i = threadIdx.x; i < n_acc * 6; i += NW * 64) {
-    const int r = i / 6, m = 2 * (i % 6);
-    const int rc = k.slot_rec[cam0 + r];
-    ck_store_part(PR, (unsigned)rc * 96u + 16u * (unsigned)(i % 6), acc[r * CK_ACC_STRIDE + m], acc[r * CK_ACC_STRIDE + m + 1]);
-  }
+  ck_store_accumulators<NW>(ck_part_rsrc(part_out), k, cam0, n_acc, acc);
   if (d.p2p_epoch && blockIdx.x == 0 && threadIdx.x == 0) *d.p2p_epoch += 1;  // one tick per term (as e0_lpl_h)
 }
 

@@ -131,8 +131,8 @@ def main():
     s = sub(s, "    if (EARLY) request_first_tile(lane, tile_of(tb0_next, 0) < tb1_next);\n    group_barrier();  // the next batch overwrites h~ and u; after the last one: the accumulators are complete\n",
             "    CK_STAMP(8 * (b / NG) + 7);\n    if (EARLY) request_first_tile(lane, tile_of(tb0_next, 0) < tb1_next);\n"
             "    group_barrier();  // the next batch overwrites h~ and u; after the last one: the accumulators are complete\n")
-    s = sub(s, "  // ---- accumulators -> this workgroup's partial records (camera-major in part_out)\n  const __amdgpu_buffer_rsrc_t PR",
-            "  CK_STAMP(8 * (k.nb / NG));\n  // ---- accumulators -> this workgroup's partial records (camera-major in part_out)\n  const __amdgpu_buffer_rsrc_t PR")
+    s = sub(s, "  // ---- accumulators -> this workgroup's partial records (camera-major in part_out)\n  ck_store_accumulators<NW>(ck_part_rsrc(part_out)",
+            "  CK_STAMP(8 * (k.nb / NG));\n  // ---- accumulators -> this workgroup's partial records (camera-major in part_out)\n  ck_store_accumulators<NW>(ck_part_rsrc(part_out)")
     s = sub(s, "  if (d.p2p_epoch && blockIdx.x == 0 && threadIdx.x == 0) *d.p2p_epoch += 1;  // one tick per term (as e0_lpl)",
             "  CK_STAMP(8 * (k.nb / NG) + 1);\n  if (d.p2p_epoch && blockIdx.x == 0 && threadIdx.x == 0) *d.p2p_epoch += 1;  // one tick per term (as e0_lpl)")
     open(p, "w").write(s)
