@@ -1,5 +1,6 @@
 """Exact rational arithmetic for small step-1 problems, straight from the REFERENCE's formulas (not from either restatement):
-test infrastructure that holds the C oracle and the HIP path to the mathematically exact E0 x and b.
+test infrastructure that holds the C oracle and the HIP path to the mathematically exact E0 x and b, and the
+long-double references of tests/step_bounds.py to the exact cost (trivial norm) and POWER_VARPROJ landmark re-solve.
 
 Inputs are IEEE doubles, i.e. exact rationals; everything below is `fractions.Fraction` arithmetic, no rounding anywhere.
 
@@ -47,13 +48,14 @@ class ExactStep1:
         self.n_cams = int(n_cams)
         al = F(float(alpha))
         self.D2 = [1 - al, 1 - al, al, al]
-        self.lm = []
+        self.lm, self.x = [], []
         for l in range(len(lm_off) - 1):
             x = [F(float(t)) for t in lms[l]]
+            self.x.append(x)
             ob = []
             for i in range(int(lm_off[l]), int(lm_off[l + 1])):
                 c = int(cam_idx[i])
-                P = [F(float(t)) for t in cams[c]]
+                P = [t if isinstance(t, F) else F(float(t)) for t in cams[c]]  # (Fractions: cameras that are no doubles)
                 ob.append((c,) + _rows(P, x, F(float(obs[i][0])), F(float(obs[i][1]))))
             H = [[sum(self.D2[r] * Jl0[r][a] * Jl0[r][b] for _, _, Jl0, _ in ob for r in range(4)) for b in range(3)] for a in range(3)]
             self.lm.append((ob, _inv3(H)))
@@ -111,6 +113,19 @@ class ExactStep1:
                 s = [self.D2[r] * (r0[r] - sum(Jl0[r][a] * w[a] for a in range(3))) for r in range(4)]
                 for j in range(12):
                     out[12 * c + j] += sum(Jp0[r][j] * s[r] for r in range(4))
+        return out
+
+    def cost_none(self):
+        """compute_error_pOSE with the trivial norm: sum_i 0.5 |r_i|^2 (bal_bundle_adjustment_helper.cpp:117-154)."""
+        return sum(F(1, 2) * self.D2[r] * r0[r] ** 2 for ob, _ in self.lm for _, _, _, r0 in ob for r in range(4))
+
+    def varproj_resolve(self):
+        """back_substitute_pOSE's landmark re-solve (landmark_block.hpp:670-707) at THIS object's cameras (the caller builds it
+        with the updated ones): x_new = x - (Jl^T Jl)^-1 Jl^T r of the unweighted, unscaled rows, [n_lms][3]."""
+        out = []
+        for l, (ob, Hi) in enumerate(self.lm):
+            g = [sum(self.D2[r] * Jl0[r][a] * r0[r] for _, _, Jl0, r0 in ob for r in range(4)) for a in range(3)]
+            out.append([self.x[l][a] - sum(Hi[a][b] * g[b] for b in range(3)) for a in range(3)])
         return out
 
 

@@ -1,5 +1,6 @@
-"""The lane-per-landmark stage kernels without a componentwise bound of their own -- lpl_pass[_h]<1> (the cost) and
-backsub_lpl[_h] (back substitution) -- against the CPU oracle on a layout that exercises their row stream
+"""The lane-per-landmark stage kernels of the two ends of an LM iteration -- lpl_pass[_h]<1> (the cost) and backsub_lpl[_h]
+(back substitution); their componentwise bounds are in test_gpu_step_bounds.py -- against the CPU oracle, normwise, on a
+layout that exercises their row stream
 (povar_kernels_lpl.hpp): ONE workgroup of shortest tiles (POVAR_E0_WGS=1, POVAR_LPL_K0=2).  1 500 landmarks are at least 24
 tiles over 16 wavefronts, so every wavefront takes later tiles from the LDS counter, its prefetch cursor crosses tile
 boundaries three rows ahead (lpl_pass: into the tile after the next) and ends in "no tile left".  The other lpl kernels of
