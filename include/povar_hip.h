@@ -256,6 +256,41 @@ int povar_solve_joint_sc_method(povar_ctx* ctx, double lambda, int32_t method, i
  * per-term E0 kernels the series and RIPCG use; x, y: 11 n_cams.  An error when the system prepared last is step 1's. */
 int povar_right_mul_e0_joint(povar_ctx* ctx, const double* x, double* y);
 
+/* ---- marginal covariance of the cameras.  The reference has no counterpart (it reports no uncertainty; Ceres answers the
+ * same question with ceres::Covariance).  Both calls return, per camera, the diagonal block of the inverse of the reduced
+ * camera system of their step, computed from the dense factor of CHOLESKY / RICHOLESKY (S = R^T R on the device, W = R^-1 in
+ * place on the fp64 matrix cores, block_c = sum_k W[J_c, k] W[J_c, k]^T; needs the memory of those solvers plus a 64-column
+ * panel).  The blocks are the inverse INFORMATION of the linearised problem in the library's residual units: the caller
+ * multiplies by their own noise variance.
+ *   gauge  POVAR_COV_FREE_GAUGE: lambda must be 0.  The blocks of the pseudo-inverse S(0)^+ of the undamped system, i.e. the
+ *          free-gauge, minimum-norm covariance, as (S0 + Q Q^T)^-1 - Q Q^T with Q an orthonormal basis of the gauge null space
+ *          of S0, built on the host in closed form from the linearisation point: step 1 the 12-dimensional affine gauge
+ *          X -> A X that keeps the last homogeneous coordinate (per camera vec(-P_c G) / sigma_c, G = e_i e_j^T, i < 3),
+ *          step 2 the 15-dimensional projective gauge (G = e_i e_j^T, (i, j) != (3, 3), the camera's own scale absorbed,
+ *          projected on the tangent space N_c).  A system that is singular beyond its gauge is reported: after the
+ *          factorisation of A = S0 + Q Q^T the smallest pivot R_kk^2 is compared with sqrt(u) max_k A_kk, u = 2^-53.
+ *          POVAR_COV_DAMPED: lambda > 0.  The blocks of S(lambda)^-1 for exactly the matrix CHOLESKY / RICHOLESKY assemble at
+ *          that lambda (step 1 without landmark damping, step 2 with it, as povar_prepare_joint leaves it); positive
+ *          definiteness by CHOLESKY's own rule.
+ *   coords POVAR_COV_SOLVER_COORDS: the solver's Jacobi-scaled coordinates, dim x dim row-major with dim = 12 (pose) or 11
+ *          (joint: tangent coordinates of N_c), at stride 144 per camera -- the layout of POVAR_BUF_SC_BLOCKDIAG; the rest of
+ *          the 144 is zero.  POVAR_COV_CAMERA_COORDS: always 12 x 12, the block T carried through the map that
+ *          povar_apply_pose / povar_apply_joint apply to an increment: D T D with D = diag(sigma_c) (pose), D N_c T N_c^T D
+ *          (joint; rank 11: the direction of P_c itself is not a degree of freedom).
+ * Every block is symmetric bit for bit.  cov: 144 n_cams doubles.
+ * Precondition: the step's linearisation is in force (povar_linearize_pose / povar_linearize_homogeneous); otherwise, for
+ * an unknown enum value and for a lambda the mode does not take, an argument error (< 0).  The call prepares the system itself
+ * (as povar_solve_pose_sc / povar_solve_joint_sc_method do): the system prepared before, the inspection buffers of the
+ * explicit-SC solvers and the increment buffer are overwritten.  Not positive definite, or singular (free gauge): every entry of
+ * cov is NaN and the call returns POVAR_NUMERIC_FAILURE.  Not enough device memory: the error of CHOLESKY / RICHOLESKY.
+ * On a sharded context every rank calls; the assembly is all-reduced and every rank inverts the same matrix. ---- */
+enum { POVAR_COV_FREE_GAUGE = 0, POVAR_COV_DAMPED = 1 };
+enum { POVAR_COV_CAMERA_COORDS = 0, POVAR_COV_SOLVER_COORDS = 1 };
+/* after povar_linearize_pose: the 12 n_cams system of step 1 */
+int povar_camera_covariance_pose(povar_ctx* ctx, double lambda, int32_t gauge, int32_t coords, double* cov /*144 n_cams*/);
+/* after povar_linearize_homogeneous: the 11 n_cams tangent system of step 2 */
+int povar_camera_covariance_joint(povar_ctx* ctx, double lambda, int32_t gauge, int32_t coords, double* cov /*144 n_cams*/);
+
 /* ---- inspection of internal state in the reference's layouts (parity tests) ---- */
 enum {
   POVAR_BUF_DIAG2 = 0,     /* get_Jp_diag2_pOSE, 12 n_cams (linearization_varproj.hpp:183-222) */

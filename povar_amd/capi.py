@@ -24,6 +24,9 @@ NUMERIC_FAILURE = 1
  BUF_JL_COL_SCALE_H, BUF_B_JOINT, BUF_B_INV_JOINT, BUF_NC_HOUSEHOLDER, BUF_SC_PRECOND,
  BUF_SC_BLOCKDIAG) = range(13)
 SC_PCG, SC_CHOLESKY = 0, 1
+# povar_camera_covariance_pose / _joint (include/povar_hip.h: POVAR_COV_*)
+COV_FREE_GAUGE, COV_DAMPED = 0, 1
+COV_CAMERA_COORDS, COV_SOLVER_COORDS = 0, 1
 
 
 class Options(C.Structure):
@@ -295,6 +298,18 @@ class Context:
         y = np.zeros(11 * self.n_cams)
         self._chk(self.L.povar_right_mul_e0_joint(self.h, _p(x), _p(y)))
         return y
+
+    def camera_covariance(self, step=1, lam=0.0, gauge=COV_FREE_GAUGE, coords=COV_CAMERA_COORDS):
+        """Per-camera marginal covariance (inverse information) of the step linearised last: (blocks, rc).  blocks is
+        [n_cams, 12, 12] in camera coordinates, [n_cams, dim, dim] (dim = 12 for step 1, 11 for step 2) in the solver's;
+        rc = NUMERIC_FAILURE comes with all-NaN blocks (include/povar_hip.h)."""
+        if step not in (1, 2):
+            raise ValueError("camera_covariance: step is 1 or 2")
+        out = np.zeros((self.n_cams, 144))
+        fn = self.L.povar_camera_covariance_pose if step == 1 else self.L.povar_camera_covariance_joint
+        rc = self._chk(fn(self.h, C.c_double(lam), C.c_int32(gauge), C.c_int32(coords), _p(out)), allow_numeric=True)
+        dim = 11 if (step == 2 and coords == COV_SOLVER_COORDS) else 12
+        return out[:, :dim * dim].reshape(self.n_cams, dim, dim).copy(), rc
 
     def apply_joint(self, inc):
         inc = np.ascontiguousarray(inc, dtype=np.float64)

@@ -126,6 +126,27 @@ void check_options(const SolverOptions& o) {
   }
 }
 
+// --camera-covariance-path: n_cams on the first line, then one line of 144 numbers (12 x 12 row-major) per camera
+void write_camera_covariance(Linearizor& linearizor, const BalProblem& bal_problem, const SolverOptions& so, bool step2) {
+  Linearizor::VecX cov;
+  const int rc = linearizor.camera_covariance(step2, so.alpha, cov);
+  if (rc < 0) {
+    std::fprintf(stderr, "FATAL: this linearizor does not serve --camera-covariance-path\n");
+    std::abort();
+  }
+  if (rc != 0) std::printf("\t[WARN] camera covariance: the reduced system is singular beyond its gauge, the blocks are NaN\n");
+  std::FILE* f = std::fopen(so.camera_covariance_path.c_str(), "w");
+  if (!f) {
+    std::fprintf(stderr, "FATAL: cannot write %s\n", so.camera_covariance_path.c_str());
+    std::abort();
+  }
+  const int n_cams = bal_problem.num_cameras();
+  std::fprintf(f, "%d\n", n_cams);
+  for (int c = 0; c < n_cams; ++c)
+    for (int k = 0; k < 144; ++k) std::fprintf(f, "%.17g%c", cov[144 * (size_t)c + k], k == 143 ? '\n' : ' ');
+  std::fclose(f);
+}
+
 void optimize_lm(BalProblem& bal_problem, const SolverOptions& so, SolverSummary& summary, const Timer& timer_total,
                  bool step2) {
   Timer timer_preprocessor;
@@ -303,6 +324,9 @@ void optimize_lm(BalProblem& bal_problem, const SolverOptions& so, SolverSummary
   summary.minimizer_time_in_seconds = timer_minimizer.elapsed();
   summary.total_time_in_seconds = timer_total.elapsed();
   finish_solve(summary, so);
+  // not in the reference: the cameras' marginal covariance at the final accepted state of the last step that ran
+  if (!so.camera_covariance_path.empty() && step2 == (so.max_num_iterations_step_2 > 0))
+    write_camera_covariance(*linearizor, bal_problem, so, step2);
   std::printf("Final Cost: %s\n", error_summary_oneline(summary.final_cost, so.use_projection_validity_check()).c_str());
   std::printf("%s: %s\n", summary.termination_type == CONVERGENCE ? "CONVERGENCE" : "NO_CONVERGENCE", summary.message.c_str());
   std::fflush(stdout);

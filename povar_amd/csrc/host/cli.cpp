@@ -92,6 +92,7 @@ bool parse_bal_app_arguments(int argc, char** argv, BalAppOptions& o) {
   flag["fp32-terms"] = &o.solver.fp32_terms;
   integer("device", &o.solver.device);
   integer("gpus", &o.solver.gpus);
+  str("camera-covariance-path", &o.solver.camera_covariance_path);
 
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -103,7 +104,10 @@ bool parse_bal_app_arguments(int argc, char** argv, BalAppOptions& o) {
       std::printf("\n  --solver-type-step-1 PCG | POWER_SCHUR_COMPLEMENT | POWER_VARPROJ | CHOLESKY\n"
                   "  --solver-type-step-2 RIPOBA | RIPCG | RICHOLESKY\n"
                   "      RICHOLESKY is not a value of the reference: the direct solve of the joint system (dense Cholesky on the\n"
-                  "      device), the limit RIPOBA and RIPCG approach\n");
+                  "      device), the limit RIPOBA and RIPCG approach\n"
+                  "  --camera-covariance-path FILE\n"
+                  "      not an option of the reference: at the final accepted state of the last step that ran, the free-gauge marginal\n"
+                  "      covariance (inverse information) of every camera: n_cams, then 144 numbers (12 x 12, row-major) per camera\n");
       return false;
     }
     if (a.rfind("--", 0) != 0) {
@@ -126,6 +130,10 @@ bool parse_bal_app_arguments(int argc, char** argv, BalAppOptions& o) {
     if (!it->second(v)) { std::fprintf(stderr, "invalid value '%s' for '--%s'\n", v.c_str(), a.c_str()); return false; }
   }
   if (o.dataset.input.empty()) { std::fprintf(stderr, "missing --input\n"); return false; }
+  if (o.solver.gpus > 1 && !o.solver.camera_covariance_path.empty()) {
+    std::fprintf(stderr, "--gpus > 1 does not serve --camera-covariance-path (the dense factor is inverted on one device)\n");
+    return false;
+  }
   return true;
 }
 

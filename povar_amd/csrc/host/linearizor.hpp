@@ -112,6 +112,14 @@ class Linearizor {
   virtual double apply_joint(VecX&& inc) = 0;
   virtual double apply(const SolverOptions& solver_options, double alpha, VecX&& inc) = 0;
   virtual void finish_iteration() = 0;
+  // Not in the reference: the free-gauge marginal covariance of every camera at the current state, camera coordinates,
+  // 144 n_cams numbers (povar_camera_covariance_pose after linearize_pOSE(alpha), or povar_camera_covariance_joint after
+  // linearize_projective_space_homogeneous).  Returns the library's status: 0, or POVAR_NUMERIC_FAILURE (1) with all-NaN blocks
+  // for a system that is singular beyond its gauge.  Linearizors other than the single-device HIP one do not serve it.
+  virtual int camera_covariance(bool step2, double alpha, VecX& cov) {
+    (void)step2; (void)alpha; (void)cov;
+    return -1;
+  }
 };
 
 // hook for alternative implementations (the tests register an oracle-backed one)

@@ -170,6 +170,21 @@ class LinearizorPowerVarprojHip : public Linearizor, public StateMirror {
     IF_SET(it_summary_)->stage1_time_in_seconds = e;
     IF_SET(summary_)->num_jacobian_evaluations += 1;
   }
+  int camera_covariance(bool step2, double alpha, VecX& cov) override {
+    cov.assign(144 * (size_t)bal_problem_.num_cameras(), 0.0);
+    // the library calls themselves: this runs after the LM loop, when the iteration summary start_iteration handed over is
+    // gone and the solver summary is finished -- no timing or evaluation count is booked
+    const int rc_lin = step2 ? povar_linearize_homogeneous(ctx_) : povar_linearize_pose(ctx_, alpha);
+    check(rc_lin, "povar_linearize (camera covariance)");
+    if (rc_lin == POVAR_NUMERIC_FAILURE) {
+      std::fprintf(stderr, "FATAL: did not expect numerical failure during linearization\n");
+      std::abort();
+    }
+    const int rc = step2 ? povar_camera_covariance_joint(ctx_, 0.0, POVAR_COV_FREE_GAUGE, POVAR_COV_CAMERA_COORDS, cov.data())
+                         : povar_camera_covariance_pose(ctx_, 0.0, POVAR_COV_FREE_GAUGE, POVAR_COV_CAMERA_COORDS, cov.data());
+    check(rc, "povar_camera_covariance");
+    return rc;
+  }
   VecX solve(const SolverOptions& so, double lambda, double) override {
     VecX inc(12 * (size_t)bal_problem_.num_cameras());
     Timer t;

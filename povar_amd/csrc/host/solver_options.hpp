@@ -62,6 +62,10 @@ struct SolverOptions {
   // shard r runs on device (device + r) mod device count; one exchange step per power-series term (RCCL, or an in-process
   // all-reduce when shards share a device)
   int gpus = 1;
+  // not in the reference: after the last step that ran, at its final accepted state, linearise and write the free-gauge
+  // marginal covariance of every camera in camera coordinates (povar_camera_covariance_pose / _joint): n_cams on the first
+  // line, then 144 numbers (12 x 12 row-major, %.17g) per camera.  Empty: nothing is written.  One device only.
+  std::string camera_covariance_path;
 
   // solver_options.cpp:41-51
   bool use_projection_validity_check() const { return optimized_cost != OptimizedCost::ERROR; }

@@ -259,6 +259,9 @@ struct povar_ctx {
   DevBuf<double> sc_dense, sc_xpad;      // CHOLESKY / RICHOLESKY: augmented S (povar_kernels_chol.hpp) and the padded solution,
                                          // grown to the larger of the two systems a context solves (run_cholesky)
   DevBuf<int> sc_lm_slot0, sc_lm_cnt, sc_info;
+  // camera covariance (povar_camera_covariance_*), grown on demand and kept: the gauge basis Q, (max A_kk, min R_kk^2), the
+  // N x 64 scratch panel of the triangular inverse, the [n_cams][144] blocks
+  DevBuf<double> sc_cov_q, sc_cov_stat, sc_cov_panel, sc_cov_blocks;
 
   Dp d{};
   bool new_linearization_point = false;  // linearizor_power_varproj.cpp:75, 192, 240

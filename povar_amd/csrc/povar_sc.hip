@@ -1,5 +1,6 @@
 // povar_sc.hip -- explicit-Schur-complement solvers (LinearizorSC: PCG, CHOLESKY, RIPCG).
 #include "povar_ctx.hpp"
+#include "povar_kernels_cov.hpp"
 
 // ------------------------------------------------------------------------------------------
 // explicit-Schur-complement solvers (LinearizorSC: PCG, CHOLESKY, RIPCG)
@@ -52,10 +53,10 @@ int e0_dense(povar_ctx* c) {
   return 0;
 }
 
-// solve_direct_pOSE (linearization_sc.hpp:236-245): accum = LLT(S).solve(-b) with the dense S,
-// factored by the kernels of povar_kernels_chol.hpp.  dim = 12: step 1's system; dim = 11: the joint tangent system of
-// step 2 (RICHOLESKY; not in the reference).  A context that solves both keeps one dense buffer, sized for the larger.
-int run_cholesky(povar_ctx* c, int dim, int32_t* num_iterations, int32_t* termination) {
+// First half, shared with the covariance calls below: assembly of the augmented matrix and its factorisation, R left in
+// sc_dense.  Q (device, n x nq row-major; null for the solvers) is the free-gauge term: A = S + Q Q^T, added on rank 0 before
+// the all-reduce; `stat` (device, 2 doubles; null for the solvers) then receives max_k A_kk and min_k R_kk^2.
+static int chol_factor(povar_ctx* c, int dim, const double* Q, int nq, double* stat) {
   const int n = dim * c->n_cams;
   const int N = (n + CH_NB - 1) / CH_NB * CH_NB;
   const int64_t ld = (int64_t)N + CH_T;
@@ -94,6 +95,7 @@ int run_cholesky(povar_ctx* c, int dim, int32_t* num_iterations, int32_t* termin
     else
       hipLaunchKernelGGL(sc_dense_diag<12>, dim3(c->n_cams), dim3(256), 0, c->stream, c->d, (const double*)c->sc.bmat, M, ld, N);
     if (N > n) hipLaunchKernelGGL(chol_pad, dim3(1), dim3(64), 0, c->stream, M, ld, n, N);
+    if (Q) hipLaunchKernelGGL(cov_add_qqt, dim3(N / CH_NB, N / CH_NB), dim3(256), 0, c->stream, M, ld, n, Q, nq);
   }
   if (c->n_lms > 0) {
     if (dim == 11)
@@ -105,6 +107,7 @@ int run_cholesky(povar_ctx* c, int dim, int32_t* num_iterations, int32_t* termin
   }
   HIP_TRY(hipGetLastError());
   if (int rc = allreduce(c, M, count)) return rc;
+  if (stat) hipLaunchKernelGGL(cov_diag_scan, dim3(1), dim3(256), 0, c->stream, (const double*)M, ld, n, 0, stat);
   for (int K0 = 0; K0 < N; K0 += CH_OB) {
     const int kdepth = std::min(CH_OB, N - K0), R0 = K0 + kdepth;
     for (int k0 = K0; k0 < R0; k0 += CH_NB) {
@@ -119,6 +122,20 @@ int run_cholesky(povar_ctx* c, int dim, int32_t* num_iterations, int32_t* termin
       hipLaunchKernelGGL(chol_syrk_outer, dim3((unsigned)((N - R0) / CH_T + 1), (unsigned)((N - R0 + CH_T - 1) / CH_T)),
                          dim3(256), 0, c->stream, M, ld, K0, kdepth);
   }
+  if (stat) hipLaunchKernelGGL(cov_diag_scan, dim3(1), dim3(256), 0, c->stream, (const double*)M, ld, n, 1, stat);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// solve_direct_pOSE (linearization_sc.hpp:236-245): accum = LLT(S).solve(-b) with the dense S,
+// factored by the kernels of povar_kernels_chol.hpp.  dim = 12: step 1's system; dim = 11: the joint tangent system of
+// step 2 (RICHOLESKY; not in the reference).  A context that solves both keeps one dense buffer, sized for the larger.
+int run_cholesky(povar_ctx* c, int dim, int32_t* num_iterations, int32_t* termination) {
+  if (int rc = chol_factor(c, dim, nullptr, 0, nullptr)) return rc;
+  const int n = dim * c->n_cams;
+  const int N = (n + CH_NB - 1) / CH_NB * CH_NB;
+  const int64_t ld = (int64_t)N + CH_T;
+  double* M = c->sc_dense.p;
   if (c->sc_xpad.n < (size_t)N) {
     if (c->sc_xpad.p) {
       HIP_TRY(hipStreamSynchronize(c->stream));
@@ -191,7 +208,191 @@ int run_pcg(povar_ctx* c, int32_t min_it, int32_t max_it, double eta, int32_t* n
   return 0;
 }
 
+// ------------------------------------------------------------------------------------------
+// marginal camera covariance (povar_camera_covariance_pose / _joint; not in the reference)
+// ------------------------------------------------------------------------------------------
+namespace {
+// a scratch buffer of the covariance calls, grown to `count` doubles and kept (counted in povar_device_bytes); no memory:
+// the error of CHOLESKY / RICHOLESKY
+int cov_buffer(povar_ctx* c, DevBuf<double>& buf, size_t count, int dim) {
+  if (buf.p && buf.n >= count) return 0;
+  if (buf.p) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->bytes -= buf.n * sizeof(double);
+    buf.release();
+  }
+  if (buf.alloc(count, &c->bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    buf.p = nullptr;
+    buf.n = 0;
+    return fail(-1, std::string(dim == 11 ? "RICHOLESKY" : "CHOLESKY") + ": not enough device memory for the covariance scratch of " +
+                        std::to_string(dim * c->n_cams) + " rows (" + std::to_string(count * sizeof(double) >> 20) + " MiB)");
+  }
+  return 0;
+}
+
+// Orthonormal basis Q (n x nq, row-major) of the gauge null space of the undamped reduced system, in the solver's
+// Jacobi-scaled coordinates, from the linearisation point P_c, sigma_c and the reflectors (w, beta):
+//   step 1 (dim 12, nq 12): the affine gauge X -> A X that keeps the last homogeneous coordinate: generators
+//           G = e_i e_j^T, i < 3:  v_c = vec(-P_c G) / sigma_c;
+//   step 2 (dim 11, nq 15): the projective gauge, generators (i, j) != (3, 3), the per-camera scale absorbed: with
+//           g = vec(-P_c G), h0 = the reflector's first column, a = -(h0 . g / sigma_c) / (h0 . P_c / sigma_c):
+//           x_c = N_c^T ((g + a P_c) / sigma_c).
+// Orthonormalised by twice-applied modified Gram-Schmidt in fp64.  false: the columns are numerically dependent.
+bool gauge_basis(int n_cams, int dim, const std::vector<double>& P, const std::vector<double>& sg, const std::vector<double>& ncw,
+                 std::vector<double>& Q, int& nq) {
+  nq = dim == 12 ? 12 : 15;
+  const size_t n = (size_t)dim * n_cams;
+  std::vector<std::vector<double>> V(nq, std::vector<double>(n));
+  for (int col = 0; col < nq; ++col) {
+    const int gi = col / 4, gj = col % 4;  // G = e_gi e_gj^T; step 1 stops at gi = 2, step 2 at (3, 2)
+    for (int c = 0; c < n_cams; ++c) {
+      const double* p = P.data() + 12 * (size_t)c;
+      const double* s = sg.data() + 12 * (size_t)c;
+      double g[12];
+      for (int r = 0; r < 3; ++r)
+        for (int j = 0; j < 4; ++j) g[4 * r + j] = j == gj ? -p[4 * r + gi] : 0.0;
+      if (dim == 12) {
+        for (int k = 0; k < 12; ++k) V[col][12 * (size_t)c + k] = g[k] / s[k];
+        continue;
+      }
+      const double* w = ncw.data() + 13 * (size_t)c;
+      const double beta = w[12];
+      double hg = 0, hp = 0;
+      for (int k = 0; k < 12; ++k) {
+        const double h0 = (k == 0 ? 1.0 : 0.0) - beta * w[k] * w[0];
+        hg += h0 * (g[k] / s[k]);
+        hp += h0 * (p[k] / s[k]);
+      }
+      const double a = -hg / hp;
+      double y[12], wy = 0;
+      for (int k = 0; k < 12; ++k) {
+        y[k] = (g[k] + a * p[k]) / s[k];
+        wy += w[k] * y[k];
+      }
+      for (int j = 0; j < 11; ++j) V[col][11 * (size_t)c + j] = y[j + 1] - beta * w[j + 1] * wy;
+    }
+  }
+  auto dot = [&](const std::vector<double>& x, const std::vector<double>& y) {
+    double s = 0;
+    for (size_t i = 0; i < n; ++i) s += x[i] * y[i];
+    return s;
+  };
+  for (int k = 0; k < nq; ++k) {
+    const double norm0 = std::sqrt(dot(V[k], V[k]));
+    for (int pass = 0; pass < 2; ++pass)
+      for (int j = 0; j < k; ++j) {
+        const double t = dot(V[j], V[k]);
+        for (size_t i = 0; i < n; ++i) V[k][i] -= t * V[j][i];
+      }
+    const double norm = std::sqrt(dot(V[k], V[k]));
+    if (!(norm > 1e-8 * norm0) || !std::isfinite(norm)) return false;
+    for (size_t i = 0; i < n; ++i) V[k][i] /= norm;
+  }
+  Q.assign(n * nq, 0.0);
+  for (int k = 0; k < nq; ++k)
+    for (size_t i = 0; i < n; ++i) Q[i * nq + k] = V[k][i];
+  return true;
+}
+}  // namespace
+
+// Diagonal blocks of S(lambda)^-1 (POVAR_COV_DAMPED) or of the pseudo-inverse S(0)^+ = (S0 + Q Q^T)^-1 - Q Q^T
+// (POVAR_COV_FREE_GAUGE), through the factorisation of CHOLESKY / RICHOLESKY: A = R^T R, W = R^-1 in place, blocks of W W^T.
+static int camera_covariance(povar_ctx* c, int dim, double lambda, int32_t gauge, int32_t coords, double* cov) {
+  const char* who = dim == 12 ? "povar_camera_covariance_pose" : "povar_camera_covariance_joint";
+  if (int rc = check_ctx(c)) return rc;
+  if (!cov) return fail(-1, std::string(who) + ": null argument");
+  if (gauge != POVAR_COV_FREE_GAUGE && gauge != POVAR_COV_DAMPED) return fail(-1, std::string(who) + ": unknown gauge");
+  if (coords != POVAR_COV_CAMERA_COORDS && coords != POVAR_COV_SOLVER_COORDS) return fail(-1, std::string(who) + ": unknown coords");
+  if (gauge == POVAR_COV_FREE_GAUGE && lambda != 0.0) return fail(-1, std::string(who) + ": POVAR_COV_FREE_GAUGE takes lambda = 0");
+  if (gauge == POVAR_COV_DAMPED && !(lambda > 0.0)) return fail(-1, std::string(who) + ": POVAR_COV_DAMPED takes lambda > 0");
+  // the system as the direct solvers prepare it (an argument error without the step's linearisation)
+  if (int rc = dim == 12 ? povar_prepare_pose(c, lambda, POVAR_POWER_VARPROJ) : povar_prepare_joint(c, lambda)) return rc;
+  ensure_legacy(c);
+  if (int rc = ensure_sc(c)) return rc;
+  if (int rc = dim == 12 ? build_schur_jacobi<false>(c, lambda) : build_schur_jacobi<true>(c, lambda)) return rc;
+  const size_t nc = c->n_cams;
+  const int n = dim * c->n_cams;
+  const int N = (n + CH_NB - 1) / CH_NB * CH_NB;
+  const int64_t ld = (int64_t)N + CH_T;
+  const size_t out_count = 144 * nc;
+  auto all_nan = [&]() {
+    std::fill(cov, cov + out_count, std::nan(""));
+    return POVAR_NUMERIC_FAILURE;
+  };
+  TimeScope ts(c, 2);
+  const bool free_gauge = gauge == POVAR_COV_FREE_GAUGE;
+  const double* q = nullptr;
+  int nq = 0;
+  if (free_gauge) {
+    std::vector<double> P(12 * nc), sg(12 * nc), ncw(13 * nc), Q;
+    HIP_TRY(hipMemcpyAsync(P.data(), c->cams_lin4.p, 12 * nc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(sg.data(), c->sigma.p, 12 * nc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (dim == 11) HIP_TRY(hipMemcpyAsync(ncw.data(), c->ncw.p, 13 * nc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (!gauge_basis(c->n_cams, dim, P, sg, ncw, Q, nq)) return all_nan();
+    if (int rc = cov_buffer(c, c->sc_cov_q, Q.size(), dim)) return rc;
+    if (int rc = cov_buffer(c, c->sc_cov_stat, 2, dim)) return rc;
+    HIP_TRY(hipMemcpyAsync(c->sc_cov_q.p, Q.data(), Q.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (Q is pageable host memory that goes out of scope)
+    q = c->sc_cov_q.p;
+  }
+  // (the pivot scan belongs to the free gauge: the damped mode judges by chol_diag's info alone)
+  if (int rc = chol_factor(c, dim, q, nq, free_gauge ? c->sc_cov_stat.p : nullptr)) return rc;
+  int info = 0;
+  double st[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(&info, c->sc_info.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (free_gauge) HIP_TRY(hipMemcpyAsync(st, c->sc_cov_stat.p, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (info != 0) return all_nan();  // not positive definite: CHOLESKY's own rule
+  if (free_gauge) {
+    // a gauge-only system keeps pivots of the order of its smallest eigenvalue; further degeneracy leaves rounding
+    // noise of the order u max A_kk: the threshold sqrt(u) max A_kk sits in the gap
+    const double thr = std::sqrt(std::ldexp(1.0, -53)) * st[0];
+    if (!(st[1] >= thr)) return all_nan();
+  }
+  double* M = c->sc_dense.p;
+  if (int rc = cov_buffer(c, c->sc_cov_panel, (size_t)N * CH_NB, dim)) return rc;
+  if (int rc = cov_buffer(c, c->sc_cov_blocks, out_count, dim)) return rc;
+  double* panel = c->sc_cov_panel.p;
+  double* blocks = c->sc_cov_blocks.p;
+  // W = R^-1 in place, block column by block column (povar_kernels_cov.hpp)
+  for (int j = 0; j < N / CH_NB; ++j) {
+    const int64_t k0 = (int64_t)j * CH_NB;
+    hipLaunchKernelGGL(cov_diag_inv, dim3(1), dim3(64), 0, c->stream, M, ld, (int)k0);
+    if (j == 0) continue;
+    hipLaunchKernelGGL(cov_trmm, dim3(j), dim3(256), 0, c->stream, (const double*)(M + k0), ld, (const double*)(M + k0 * ld + k0), ld,
+                       panel, (int64_t)CH_NB, 0, 1, 1.0);
+    hipLaunchKernelGGL(cov_trmm, dim3(j), dim3(256), 0, c->stream, (const double*)M, ld, (const double*)panel, (int64_t)CH_NB,
+                       M + k0, ld, 1, j, -1.0);
+  }
+  HIP_TRY(hipMemsetAsync(blocks, 0, out_count * sizeof(double), c->stream));
+  if (dim == 12) {
+    hipLaunchKernelGGL(cov_gram<12>, dim3(c->n_cams), dim3(256), 0, c->stream, (const double*)M, ld, n, blocks);
+    hipLaunchKernelGGL(cov_finish<12>, dim3(c->n_cams), dim3(256), 0, c->stream, blocks, q, nq,
+                       (const double*)c->sigma.p, (const double*)c->ncw.p, coords);
+  } else {
+    hipLaunchKernelGGL(cov_gram<11>, dim3(c->n_cams), dim3(256), 0, c->stream, (const double*)M, ld, n, blocks);
+    hipLaunchKernelGGL(cov_finish<11>, dim3(c->n_cams), dim3(256), 0, c->stream, blocks, q, nq,
+                       (const double*)c->sigma.p, (const double*)c->ncw.p, coords);
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(cov, blocks, out_count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (size_t i = 0; i < out_count; ++i)
+    if (!std::isfinite(cov[i])) return all_nan();
+  return 0;
+}
+
 extern "C" {
+
+int povar_camera_covariance_pose(povar_ctx* c, double lambda, int32_t gauge, int32_t coords, double* cov) {
+  return camera_covariance(c, 12, lambda, gauge, coords, cov);
+}
+
+int povar_camera_covariance_joint(povar_ctx* c, double lambda, int32_t gauge, int32_t coords, double* cov) {
+  return camera_covariance(c, 11, lambda, gauge, coords, cov);
+}
 
 int povar_set_jl_col_scaling(povar_ctx* c, int32_t enable) {
   if (int rc = check_ctx(c)) return rc;

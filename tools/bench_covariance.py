@@ -1,0 +1,88 @@
+#!/usr/bin/env python3
+"""Times the camera covariance (povar_camera_covariance_pose / _joint) against the direct solve it shares its factorisation
+with (povar_solve_pose_sc / povar_solve_joint_sc_method with POVAR_SC_CHOLESKY) on a synthetic BAL shape, one process, one
+context.  Device times (povar_timings.solve_ms: hipEvents on the context's stream around assembly + factorisation + back
+substitution, or assembly + factorisation + inverse + per-camera Gram); every call is warmed once, then timed REPS times,
+the median is reported.  The covariance is timed in both modes: free gauge (lambda = 0) and damped (lambda as given); a shape
+that is singular beyond its gauge returns after the factorisation, which the line then says.
+At this size a dense reference is out of reach; the two size-independent checks are printed instead: bitwise symmetry of every
+block, and (step 2, camera coordinates) the null-vector residual |block (h0 / sigma_c)| / (|block| |h0 / sigma_c|).
+usage: bench_covariance.py [shape] [lambda] [reps]"""
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from povar_amd import capi, synth  # noqa: E402
+
+
+def main():
+    shape = sys.argv[1] if len(sys.argv) > 1 else "venice-1778"
+    lam = float(sys.argv[2]) if len(sys.argv) > 2 else 1e-2
+    reps = int(sys.argv[3]) if len(sys.argv) > 3 else 3
+    p = synth.make_bal_problem(shape)
+    ctx = capi.Context(p.n_cams, p.lm_off, p.cam_idx, p.obs / 500.0, e0_mode=capi.E0_IMPLICIT_LDSACC)
+    ctx.layout_finalize()
+    ctx.timings_enable(True)
+
+    def timed(call):
+        out = call()  # warm-up: code objects, the dense buffer
+        ms = []
+        for _ in range(reps):
+            t0 = ctx.timings()
+            out = call()
+            t1 = ctx.timings()
+            assert t1.solve_calls - t0.solve_calls == 1
+            ms.append(t1.solve_ms - t0.solve_ms)
+        return out, float(np.median(ms))
+
+    def report(step, dim, solver, solve):
+        (x, it, st, rc), ms_solve = timed(solve)
+        assert rc == 0 and it == 0
+        print(f"step {step} {solver} n = {dim * p.n_cams}: {ms_solve:.1f} ms per factorisation + solve (device, median of {reps})", flush=True)
+        for name, gauge, lm in (("free gauge", capi.COV_FREE_GAUGE, 0.0), ("damped", capi.COV_DAMPED, lam)):
+            (cov, rc), ms = timed(lambda: ctx.camera_covariance(step=step, lam=lm, gauge=gauge, coords=capi.COV_CAMERA_COORDS))
+            line = f"step {step} covariance, {name} (lambda {lm:g}): {ms:.1f} ms per call, ratio to {solver} {ms / ms_solve:.2f}"
+            if rc != 0:
+                print(line + f" -- rc {rc}: singular beyond the gauge, the call ended after the factorisation", flush=True)
+                assert np.all(np.isnan(cov))
+                continue
+            sym = np.array_equal(cov, cov.transpose(0, 2, 1))
+            ev = np.linalg.eigvalsh(cov)
+            line += f"; blocks bitwise symmetric: {sym}; smallest eigenvalue / largest, worst camera: {(ev[:, 0] / ev[:, -1]).min():.2e}"
+            if step == 2:
+                sigma = ctx.get_buffer(capi.BUF_POSE_SCALING).reshape(-1, 12)
+                ncw = ctx.get_buffer(capi.BUF_NC_HOUSEHOLDER).reshape(-1, 13)
+                h0 = -ncw[:, 12:13] * ncw[:, :12] * ncw[:, 0:1]
+                h0[:, 0] += 1.0
+                v = h0 / sigma
+                r = np.linalg.norm(np.einsum("cij,cj->ci", cov, v), axis=1) / (np.linalg.norm(cov, axis=(1, 2)) * np.linalg.norm(v, axis=1))
+                line += f"; null-vector residual, worst camera: {r.max():.2e}"
+            print(line, flush=True)
+
+    # step 1 in the units of the normalised observations (the first two rows of every P divided by 500)
+    cams1 = p.cams.copy()
+    cams1[:, :8] /= 500.0
+    ctx.set_cameras(cams1)
+    ctx.init_landmarks_pose(0.01)
+    ctx.set_jl_col_scaling(False)
+    assert ctx.linearize_pose(0.01)
+    report(1, 12, "CHOLESKY", lambda: ctx.solve_pose_sc(lam, capi.SC_CHOLESKY))
+    # step 2: the state of the at-size tests (random normalised cameras, X_w = 1 landmarks)
+    rng = np.random.default_rng(11)
+    cams = rng.normal(size=(p.n_cams, 12))
+    cams[:, 8:11] *= 0.1
+    cams[:, 11] = 5 + rng.random(p.n_cams)
+    cams /= np.linalg.norm(cams, axis=1, keepdims=True)
+    lms_h = np.concatenate([rng.normal(size=(p.n_lms, 3)), np.ones((p.n_lms, 1))], 1)
+    ctx.set_cameras(cams)
+    ctx.set_landmarks_homogeneous(lms_h)
+    assert ctx.linearize_homogeneous()
+    report(2, 11, "RICHOLESKY", lambda: ctx.solve_joint_sc(lam, method=capi.SC_CHOLESKY))
+    print("device MiB:", ctx.device_bytes() >> 20)
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
