@@ -306,7 +306,18 @@ enum {
   POVAR_BUF_NC_HOUSEHOLDER, /* per camera (w[12], beta): N_c = (I - beta w w^T)[:, 1:], 13 n_cams */
   POVAR_BUF_SC_PRECOND,    /* Schur-Jacobi inv_blocks of the last povar_solve_*_sc (preconditioner.hpp:80-107),
                               144 n_cams (step 1) or 121 n_cams (step 2) */
-  POVAR_BUF_SC_BLOCKDIAG   /* B_c = Hpp_c + lambda I of the last povar_solve_*_sc, same sizes */
+  POVAR_BUF_SC_BLOCKDIAG,  /* B_c = Hpp_c + lambda I of the last povar_solve_*_sc, same sizes */
+  POVAR_BUF_SC_FACTOR      /* the factored augmented matrix of the last successful CHOLESKY / RICHOLESKY solve and its two
+                              triangular solves: N x (N + 2) doubles row-major, N = dim n_cams rounded up to 64 (dim = 12
+                              for step 1, 11 for step 2).  Row i: M[i, 0:N] (row i of the upper factor R in the columns
+                              j >= i, S = R^T R; the columns j < i are unspecified), then y_i (R^T y = -b: column N of the
+                              augmented matrix after the factorisation) and x_i (R x = y; the increment is x[0:dim n_cams]).
+                              Rows and columns past dim n_cams are the padding: identity in R, 0 in y and x.
+                              Precondition: the last call that wrote the dense matrix was a CHOLESKY / RICHOLESKY solve
+                              that found it positive definite; any other state (no direct solve yet, a failed
+                              factorisation, a povar_camera_covariance_* call since, which inverts R in place) is an argument
+                              error.  PCG / RIPCG and the power series leave the factor alone.  On a sharded context every
+                              rank holds the all-reduced matrix. */
 };
 int povar_get_buffer(povar_ctx* ctx, int32_t which, double* out, int64_t n);
 

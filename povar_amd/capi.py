@@ -22,7 +22,7 @@ NO_CONVERGENCE, SUCCESS, FAILURE = 0, 1, 2
 NUMERIC_FAILURE = 1
 (BUF_DIAG2, BUF_POSE_SCALING, BUF_JL_COL_SCALE, BUF_HLL_INV, BUF_B, BUF_B_INV, BUF_STORAGE,
  BUF_JL_COL_SCALE_H, BUF_B_JOINT, BUF_B_INV_JOINT, BUF_NC_HOUSEHOLDER, BUF_SC_PRECOND,
- BUF_SC_BLOCKDIAG) = range(13)
+ BUF_SC_BLOCKDIAG, BUF_SC_FACTOR) = range(14)
 SC_PCG, SC_CHOLESKY = 0, 1
 # povar_camera_covariance_pose / _joint (include/povar_hip.h: POVAR_COV_*)
 COV_FREE_GAUGE, COV_DAMPED = 0, 1
@@ -364,6 +364,11 @@ class Context:
             out = np.zeros(n)
             self._chk(self.L.povar_get_buffer(self.h, C.c_int32(which), _p(out), C.c_int64(n)))
             return out
+        if which == BUF_SC_FACTOR:  # [N, N + 2]: R (upper), y, x; N = dim n_cams rounded up to 64
+            N = ((11 if joint else 12) * self.n_cams + 63) // 64 * 64
+            out = np.zeros(N * (N + 2))
+            self._chk(self.L.povar_get_buffer(self.h, C.c_int32(which), _p(out), C.c_int64(out.size)))
+            return out.reshape(N, N + 2)
         n = {BUF_DIAG2: 12 * self.n_cams, BUF_POSE_SCALING: 12 * self.n_cams,
              BUF_JL_COL_SCALE: 3 * self.n_lms, BUF_HLL_INV: 9 * self.n_lms, BUF_B: 12 * self.n_cams,
              BUF_B_INV: 144 * self.n_cams, BUF_STORAGE: 64 * self.n_obs,

@@ -259,6 +259,8 @@ struct povar_ctx {
   DevBuf<double> sc_dense, sc_xpad;      // CHOLESKY / RICHOLESKY: augmented S (povar_kernels_chol.hpp) and the padded solution,
                                          // grown to the larger of the two systems a context solves (run_cholesky)
   DevBuf<int> sc_lm_slot0, sc_lm_cnt, sc_info;
+  int sc_factor_dim = 0;                 // POVAR_BUF_SC_FACTOR: the system whose R, y (sc_dense) and x (sc_xpad) are in place:
+  int sc_factor_n = 0;                   // 12 (step 1) or 11 (step 2) and dim * n_cams; 0: none (chol_factor, camera_covariance)
   // camera covariance (povar_camera_covariance_*), grown on demand and kept: the gauge basis Q, (max A_kk, min R_kk^2), the
   // N x 64 scratch panel of the triangular inverse, the [n_cams][144] blocks
   DevBuf<double> sc_cov_q, sc_cov_stat, sc_cov_panel, sc_cov_blocks;

@@ -599,6 +599,21 @@ int povar_get_buffer(povar_ctx* c, int32_t which, double* out, int64_t n) {
       if (!c->sc_s.p) return fail(-1, "povar_get_buffer: no explicit-SC solve yet");
       return read_cam_blocks(c, which == POVAR_BUF_SC_PRECOND ? c->sc_minv.p : c->sc_bmat.p, dim2, out);
     }
+    case POVAR_BUF_SC_FACTOR: {
+      if (c->sc_factor_dim == 0 || !c->sc_dense.p || !c->sc_xpad.p)
+        return fail(-1, "povar_get_buffer: POVAR_BUF_SC_FACTOR: no factor in place (the last call that wrote the dense matrix "
+                        "must be a CHOLESKY / RICHOLESKY solve that found it positive definite)");
+      const size_t N = ((size_t)c->sc_factor_n + CH_NB - 1) / CH_NB * CH_NB;
+      if ((size_t)n != N * (N + 2)) return fail(-1, "povar_get_buffer: wrong size");
+      const size_t ld = N + CH_T;  // row stride of the augmented matrix (chol_factor, povar_sc.hip)
+      std::vector<double> xh(N);
+      HIP_TRY(hipMemcpy2DAsync(out, (N + 2) * sizeof(double), c->sc_dense.p, ld * sizeof(double), (N + 1) * sizeof(double), N,
+                               hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipMemcpyAsync(xh.data(), c->sc_xpad.p, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      for (size_t i = 0; i < N; ++i) out[i * (N + 2) + N + 1] = xh[i];
+      return 0;
+    }
     case POVAR_BUF_JL_COL_SCALE_H: {
       if ((size_t)n != 4 * nl) return fail(-1, "povar_get_buffer: wrong size");
       HIP_TRY(hipMemcpyAsync(out, c->jl_scale4.p, nl * sizeof(double4), hipMemcpyDeviceToHost, c->stream));

@@ -57,6 +57,7 @@ int e0_dense(povar_ctx* c) {
 // sc_dense.  Q (device, n x nq row-major; null for the solvers) is the free-gauge term: A = S + Q Q^T, added on rank 0 before
 // the all-reduce; `stat` (device, 2 doubles; null for the solvers) then receives max_k A_kk and min_k R_kk^2.
 static int chol_factor(povar_ctx* c, int dim, const double* Q, int nq, double* stat) {
+  c->sc_factor_dim = c->sc_factor_n = 0;  // (run_cholesky sets it again once the factorisation has succeeded)
   const int n = dim * c->n_cams;
   const int N = (n + CH_NB - 1) / CH_NB * CH_NB;
   const int64_t ld = (int64_t)N + CH_T;
@@ -162,6 +163,8 @@ int run_cholesky(povar_ctx* c, int dim, int32_t* num_iterations, int32_t* termin
     HIP_TRY(hipStreamSynchronize(c->stream));
   } else {
     HIP_TRY(hipMemcpyAsync(c->accum.p, x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    c->sc_factor_dim = dim;
+    c->sc_factor_n = n;
   }
   if (num_iterations) *num_iterations = 0;  // LinearizationSC::Summary default (linearization_sc.hpp:71-81)
   if (termination) *termination = POVAR_LINEAR_SOLVER_SUCCESS;
@@ -339,6 +342,7 @@ static int camera_covariance(povar_ctx* c, int dim, double lambda, int32_t gauge
   }
   // (the pivot scan belongs to the free gauge: the damped mode judges by chol_diag's info alone)
   if (int rc = chol_factor(c, dim, q, nq, free_gauge ? c->sc_cov_stat.p : nullptr)) return rc;
+  c->sc_factor_dim = c->sc_factor_n = 0;  // (R becomes R^-1 below: not the factor POVAR_BUF_SC_FACTOR hands out)
   int info = 0;
   double st[2] = {0, 0};
   HIP_TRY(hipMemcpyAsync(&info, c->sc_info.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));

@@ -380,6 +380,8 @@ def pose_operands(p, sigma_dev=None, mutate=None, u=U64):
         b = b.copy()
         b.reshape(-1)[i] *= LD(fac)
     R.put("B", b.reshape(-1), (_f(sig) * EY + _ab(Y) * Esig + u * _ab(b)).reshape(-1))
+    # (the chain's own numbers, for tests/sc_bounds.py: per observation w, rho; per landmark s, Hi; per camera sigma, moments)
+    R.aux["chain"] = dict(w=w, rho=rho, s=s, Es=Es, Hi=Hi_b, EHi=EHi, sig=sig, Esig=Esig, G=G, Gm=Gm, EG=EG, sb2=sb2)
     # ---- B_INV parts: B_ref with the device's sigma
     if sigma_dev is not None:
         sd = np.asarray(sigma_dev, dtype=F).reshape(-1, 12)
@@ -545,6 +547,9 @@ def joint_operands(p, sigma_dev=None, mutate=None, u=U64):
         b11 = b11.copy()
         b11.reshape(-1)[i] *= LD(fac)
     R.put("B_JOINT", b11.reshape(-1), (_nt12(cwa, cba, Ey12, +1) + (g(15, u) + dnc) * b11m).reshape(-1))
+    # (the chain's own numbers, for tests/sc_bounds.py)
+    R.aux["chain"] = dict(sw=sw, rho=rho, D=D, A=A, E=E, jl3=jl3, jl3a=jl3a, ejl3=ejl3, Hi=Hi_b, EHi=EHi, sig=sig, Esig=Esig,
+                          G=G, Gm=Gm, EG=EG, cw=cw, cb=cb)
     # ---- B_INV_JOINT parts
     if sigma_dev is not None:
         sd = np.asarray(sigma_dev, dtype=F).reshape(-1, 12)

@@ -6,6 +6,7 @@ The oracle forms the dense joint system block by block as add_Hb_joint does (get
 and factors it with the kernels of step 1's CHOLESKY.  On every shape used here S is positive definite with
 cond(S) <= 7.7e4 for NONE and HUBER at lambda = 1e-4 and 1.0, and the oracle's Cholesky agrees with an LU solve to 4.3e-12,
 so the bounds of a direct solve are those of test_cholesky_pose: rel(inc, ref) < 1e-8 and rel(S inc, -b) < 1e-9.
+(The assembly, the factor and both triangular solves are held entry by entry in tests/test_gpu_sc_bounds.py.)
 """
 import threading
 

@@ -7,6 +7,7 @@ matrix-free (B p - E0 p with the per-term E0 kernels) and forms only its block d
 in different orders, and CG amplifies rounding with the iteration count, so the tolerance is
 1e-9 relative for a handful of iterations (the reference's default eta = 1e-2 stops after 3-6) and
 1e-6 after tens of iterations; iteration counts and termination types must be identical.
+(The direct solves, the block diagonal and the preconditioner are held entry by entry in tests/test_gpu_sc_bounds.py.)
 """
 import numpy as np
 import pytest
