@@ -291,6 +291,42 @@ int povar_camera_covariance_pose(povar_ctx* ctx, double lambda, int32_t gauge, i
 /* after povar_linearize_homogeneous: the 11 n_cams tangent system of step 2 */
 int povar_camera_covariance_joint(povar_ctx* ctx, double lambda, int32_t gauge, int32_t coords, double* cov /*144 n_cams*/);
 
+/* ---- marginal covariance of the landmarks: the other half of the question (ceres::Covariance serves both).  With
+ * H = [[Hpp + lambda I, Hpl], [Hlp, Hll + lambda_l I]] in the solver's Jacobi-scaled coordinates (lambda_l = 0 in step 1, the
+ * system CHOLESKY assembles; lambda_l = lambda in step 2, as povar_prepare_joint leaves the tangent Hll^-1), C the camera
+ * covariance the calls above take blocks of and F_l = Hpl[:, l] Hll_l^-1, the block of landmark l is
+ *       Sigma_l = Hll_l^-1 + F_l^T C F_l.
+ * From the same factor: W = R^-1 as above, then C = W W^T off the diagonal too (a third n^3 / 3 pass on the fp64 matrix
+ * cores, in place: no further n^2 buffer) and one workgroup per requested landmark that contracts the blocks C[c_i, c_j] of
+ * its camera pairs.  Given C a block is reproducible: the contraction uses no atomics (the assembly of S does).
+ *   gauge  POVAR_COV_DAMPED: C = S(lambda)^-1 and Sigma_l is exactly the (l, l) block of H^-1.
+ *          POVAR_COV_FREE_GAUGE (lambda = 0): C = S(0)^+.  This is the covariance with the gauge fixed on the cameras: minimum
+ *          norm over the camera parameters, i.e. under the constraint Q^T x_cameras = 0 -- the gauge the camera call fixes,
+ *          so the two calls describe one consistent joint covariance.  It is NOT the landmark block of the pseudo-inverse
+ *          of the full H (minimum norm over cameras and landmarks together), which differs from it at order one.
+ *          Same lambda rules, pivot rule and errors as the camera calls.
+ *   coords POVAR_COV_SOLVER_COORDS: the 3 x 3 block in the scaled coordinates (step 2: the tangent coordinates of N_l) in
+ *          the first 9 numbers of the landmark's stride, the rest zero.  POVAR_COV_LANDMARK_COORDS: the block carried through
+ *          the map back-substitution applies to a landmark increment: pose: D Sigma D, D = diag(s_l) the Jl column scale
+ *          (ones with povar_set_jl_col_scaling(0)), 3 x 3; joint: the 4 x 4 D4 N_l Sigma N_l^T D4 with N_l the reflector
+ *          basis of X_l (rank 3, null vector X_l / s_l).
+ *   lm_ids indices into the context's own landmarks (on a sharded context: of the rank's shard), n_ids of them, duplicates
+ *          allowed, an id out of range is an argument error; NULL: every landmark of the context in order (n_ids ignored).
+ *   lm_cov row-major blocks at stride 9 (pose) or 16 (joint) per requested landmark, symmetric bit for bit.
+ *   cam_cov NULL, or 144 n_cams doubles: the camera blocks of the same call in the same coords, as the camera calls return
+ *          them (one factorisation and one inversion serve both); n_ids = 0 with cam_cov given is allowed.
+ * Preconditions, side effects (POVAR_BUF_SC_FACTOR is an argument error afterwards), the sharded rule and the failure modes
+ * are those of the camera calls; on POVAR_NUMERIC_FAILURE every entry of lm_cov and cam_cov is NaN. ---- */
+enum { POVAR_COV_LANDMARK_COORDS = 0 }; /* = POVAR_COV_CAMERA_COORDS: the parameter's own coordinates */
+/* after povar_linearize_pose: 3 x 3 per landmark, row-major at stride 9 */
+int povar_landmark_covariance_pose(povar_ctx* ctx, double lambda, int32_t gauge, int32_t coords,
+                                   const int32_t* lm_ids /* NULL = all landmarks of the context */, int32_t n_ids,
+                                   double* lm_cov, double* cam_cov /* 144 n_cams or NULL */);
+/* after povar_linearize_homogeneous: stride 16 per landmark */
+int povar_landmark_covariance_joint(povar_ctx* ctx, double lambda, int32_t gauge, int32_t coords,
+                                    const int32_t* lm_ids /* NULL = all landmarks of the context */, int32_t n_ids,
+                                    double* lm_cov, double* cam_cov /* 144 n_cams or NULL */);
+
 /* ---- inspection of internal state in the reference's layouts (parity tests) ---- */
 enum {
   POVAR_BUF_DIAG2 = 0,     /* get_Jp_diag2_pOSE, 12 n_cams (linearization_varproj.hpp:183-222) */
@@ -315,7 +351,7 @@ enum {
                               Rows and columns past dim n_cams are the padding: identity in R, 0 in y and x.
                               Precondition: the last call that wrote the dense matrix was a CHOLESKY / RICHOLESKY solve
                               that found it positive definite; any other state (no direct solve yet, a failed
-                              factorisation, a povar_camera_covariance_* call since, which inverts R in place) is an argument
+                              factorisation, a povar_*_covariance_* call since, which inverts R in place) is an argument
                               error.  PCG / RIPCG and the power series leave the factor alone.  On a sharded context every
                               rank holds the all-reduced matrix. */
 };

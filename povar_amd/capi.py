@@ -27,6 +27,7 @@ SC_PCG, SC_CHOLESKY = 0, 1
 # povar_camera_covariance_pose / _joint (include/povar_hip.h: POVAR_COV_*)
 COV_FREE_GAUGE, COV_DAMPED = 0, 1
 COV_CAMERA_COORDS, COV_SOLVER_COORDS = 0, 1
+COV_LANDMARK_COORDS = 0  # povar_landmark_covariance_pose / _joint: the same number as COV_CAMERA_COORDS
 
 
 class Options(C.Structure):
@@ -310,6 +311,32 @@ class Context:
         rc = self._chk(fn(self.h, C.c_double(lam), C.c_int32(gauge), C.c_int32(coords), _p(out)), allow_numeric=True)
         dim = 11 if (step == 2 and coords == COV_SOLVER_COORDS) else 12
         return out[:, :dim * dim].reshape(self.n_cams, dim, dim).copy(), rc
+
+    def landmark_covariance(self, step=1, lam=0.0, gauge=COV_FREE_GAUGE, coords=COV_LANDMARK_COORDS, ids=None,
+                            with_cameras=False):
+        """Marginal covariance of landmarks (all of the context's, or those of `ids`: indices into its own landmarks,
+        duplicates allowed) of the step linearised last: (blocks, rc), or (blocks, cam_blocks, rc) with_cameras.  blocks is
+        [n, 3, 3] in step 1 and in the solver's coordinates, [n, 4, 4] in step 2's landmark coordinates; cam_blocks as
+        camera_covariance returns them, from the same factorisation.  rc = NUMERIC_FAILURE comes with all-NaN blocks."""
+        if step not in (1, 2):
+            raise ValueError("landmark_covariance: step is 1 or 2")
+        stride = 9 if step == 1 else 16
+        if ids is None:
+            n, ids_p = self.n_lms, None
+        else:
+            ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+            n, ids_p = ids.shape[0], _p(ids)
+        out = np.zeros((n, stride))
+        cam = np.zeros((self.n_cams, 144)) if with_cameras else None
+        fn = self.L.povar_landmark_covariance_pose if step == 1 else self.L.povar_landmark_covariance_joint
+        rc = self._chk(fn(self.h, C.c_double(lam), C.c_int32(gauge), C.c_int32(coords), ids_p, C.c_int32(n),
+                          _p(out) if n else None, _p(cam) if with_cameras else None), allow_numeric=True)
+        d = 4 if (step == 2 and coords == COV_LANDMARK_COORDS) else 3
+        blocks = out[:, :d * d].reshape(n, d, d).copy()
+        if not with_cameras:
+            return blocks, rc
+        dim = 11 if (step == 2 and coords == COV_SOLVER_COORDS) else 12
+        return blocks, cam[:, :dim * dim].reshape(self.n_cams, dim, dim).copy(), rc
 
     def apply_joint(self, inc):
         inc = np.ascontiguousarray(inc, dtype=np.float64)

@@ -147,6 +147,36 @@ void write_camera_covariance(Linearizor& linearizor, const BalProblem& bal_probl
   std::fclose(f);
 }
 
+// --landmark-covariance-path: n_lms on the first line, then one line of 9 (step 1) or 16 (step 2) numbers per landmark in
+// file order; together with --camera-covariance-path one call serves both files
+void write_covariances(Linearizor& linearizor, const BalProblem& bal_problem, const SolverOptions& so, bool step2) {
+  if (so.landmark_covariance_path.empty()) {
+    write_camera_covariance(linearizor, bal_problem, so, step2);
+    return;
+  }
+  const bool with_cameras = !so.camera_covariance_path.empty();
+  Linearizor::VecX lm_cov, cam_cov;
+  const int rc = linearizor.landmark_covariance(step2, so.alpha, lm_cov, with_cameras ? &cam_cov : nullptr);
+  if (rc < 0) {
+    std::fprintf(stderr, "FATAL: this linearizor does not serve --landmark-covariance-path\n");
+    std::abort();
+  }
+  if (rc != 0) std::printf("\t[WARN] landmark covariance: the reduced system is singular beyond its gauge, the blocks are NaN\n");
+  auto write = [](const std::string& path, int count, int stride, const Linearizor::VecX& v) {
+    std::FILE* f = std::fopen(path.c_str(), "w");
+    if (!f) {
+      std::fprintf(stderr, "FATAL: cannot write %s\n", path.c_str());
+      std::abort();
+    }
+    std::fprintf(f, "%d\n", count);
+    for (int i = 0; i < count; ++i)
+      for (int k = 0; k < stride; ++k) std::fprintf(f, "%.17g%c", v[(size_t)stride * i + k], k == stride - 1 ? '\n' : ' ');
+    std::fclose(f);
+  };
+  write(so.landmark_covariance_path, bal_problem.num_landmarks(), step2 ? 16 : 9, lm_cov);
+  if (with_cameras) write(so.camera_covariance_path, bal_problem.num_cameras(), 144, cam_cov);
+}
+
 void optimize_lm(BalProblem& bal_problem, const SolverOptions& so, SolverSummary& summary, const Timer& timer_total,
                  bool step2) {
   Timer timer_preprocessor;
@@ -324,9 +354,9 @@ void optimize_lm(BalProblem& bal_problem, const SolverOptions& so, SolverSummary
   summary.minimizer_time_in_seconds = timer_minimizer.elapsed();
   summary.total_time_in_seconds = timer_total.elapsed();
   finish_solve(summary, so);
-  // not in the reference: the cameras' marginal covariance at the final accepted state of the last step that ran
-  if (!so.camera_covariance_path.empty() && step2 == (so.max_num_iterations_step_2 > 0))
-    write_camera_covariance(*linearizor, bal_problem, so, step2);
+  // not in the reference: the marginal covariance of cameras and / or landmarks at the final accepted state of the last step that ran
+  if ((!so.camera_covariance_path.empty() || !so.landmark_covariance_path.empty()) && step2 == (so.max_num_iterations_step_2 > 0))
+    write_covariances(*linearizor, bal_problem, so, step2);
   std::printf("Final Cost: %s\n", error_summary_oneline(summary.final_cost, so.use_projection_validity_check()).c_str());
   std::printf("%s: %s\n", summary.termination_type == CONVERGENCE ? "CONVERGENCE" : "NO_CONVERGENCE", summary.message.c_str());
   std::fflush(stdout);

@@ -93,6 +93,7 @@ bool parse_bal_app_arguments(int argc, char** argv, BalAppOptions& o) {
   integer("device", &o.solver.device);
   integer("gpus", &o.solver.gpus);
   str("camera-covariance-path", &o.solver.camera_covariance_path);
+  str("landmark-covariance-path", &o.solver.landmark_covariance_path);
 
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -107,7 +108,10 @@ bool parse_bal_app_arguments(int argc, char** argv, BalAppOptions& o) {
                   "      device), the limit RIPOBA and RIPCG approach\n"
                   "  --camera-covariance-path FILE\n"
                   "      not an option of the reference: at the final accepted state of the last step that ran, the free-gauge marginal\n"
-                  "      covariance (inverse information) of every camera: n_cams, then 144 numbers (12 x 12, row-major) per camera\n");
+                  "      covariance (inverse information) of every camera: n_cams, then 144 numbers (12 x 12, row-major) per camera\n"
+                  "  --landmark-covariance-path FILE\n"
+                  "      likewise for every landmark (gauge fixed on the cameras): n_lms, then 9 numbers (3 x 3, after step 1) or 16\n"
+                  "      (4 x 4 homogeneous, after step 2) per landmark; with --camera-covariance-path one call serves both files\n");
       return false;
     }
     if (a.rfind("--", 0) != 0) {

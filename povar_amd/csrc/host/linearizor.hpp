@@ -120,6 +120,13 @@ class Linearizor {
     (void)step2; (void)alpha; (void)cov;
     return -1;
   }
+  // Likewise for the landmarks (povar_landmark_covariance_pose / _joint, free gauge, landmark coordinates): lm_cov gets the
+  // blocks in file order at stride 9 (step 1: 3 x 3) or 16 (step 2: 4 x 4); cam_cov, when given, the camera blocks of the
+  // same call (one factorisation and one inversion serve both).  The N-shard linearizor serves it without cam_cov.
+  virtual int landmark_covariance(bool step2, double alpha, VecX& lm_cov, VecX* cam_cov) {
+    (void)step2; (void)alpha; (void)lm_cov; (void)cam_cov;
+    return -1;
+  }
 };
 
 // hook for alternative implementations (the tests register an oracle-backed one)

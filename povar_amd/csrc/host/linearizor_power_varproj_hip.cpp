@@ -185,6 +185,22 @@ class LinearizorPowerVarprojHip : public Linearizor, public StateMirror {
     check(rc, "povar_camera_covariance");
     return rc;
   }
+  int landmark_covariance(bool step2, double alpha, VecX& lm_cov, VecX* cam_cov) override {
+    lm_cov.assign((step2 ? 16 : 9) * (size_t)bal_problem_.num_landmarks(), 0.0);
+    if (cam_cov) cam_cov->assign(144 * (size_t)bal_problem_.num_cameras(), 0.0);
+    // (as camera_covariance: after the LM loop, nothing is booked)
+    const int rc_lin = step2 ? povar_linearize_homogeneous(ctx_) : povar_linearize_pose(ctx_, alpha);
+    check(rc_lin, "povar_linearize (landmark covariance)");
+    if (rc_lin == POVAR_NUMERIC_FAILURE) {
+      std::fprintf(stderr, "FATAL: did not expect numerical failure during linearization\n");
+      std::abort();
+    }
+    double* cam = cam_cov ? cam_cov->data() : nullptr;
+    const int rc = step2 ? povar_landmark_covariance_joint(ctx_, 0.0, POVAR_COV_FREE_GAUGE, POVAR_COV_LANDMARK_COORDS, nullptr, 0, lm_cov.data(), cam)
+                         : povar_landmark_covariance_pose(ctx_, 0.0, POVAR_COV_FREE_GAUGE, POVAR_COV_LANDMARK_COORDS, nullptr, 0, lm_cov.data(), cam);
+    check(rc, "povar_landmark_covariance");
+    return rc;
+  }
   VecX solve(const SolverOptions& so, double lambda, double) override {
     VecX inc(12 * (size_t)bal_problem_.num_cameras());
     Timer t;
@@ -535,6 +551,31 @@ class LinearizorPowerVarprojHipMulti : public Linearizor, public StateMirror {
       if (rc == POVAR_NUMERIC_FAILURE) failed.store(1);
     });
     after_linearize(failed.load());
+  }
+  int landmark_covariance(bool step2, double alpha, VecX& lm_cov, VecX* cam_cov) override {
+    if (cam_cov) return -1;  // (the camera file is the single-device linearizor's)
+    const size_t stride = step2 ? 16 : 9;
+    lm_cov.assign(stride * (size_t)bal_problem_.num_landmarks(), 0.0);
+    std::atomic<int> failed{0}, status{0};
+    // every shard linearises and calls (the assembly is all-reduced, every rank inverts the same matrix) and writes the
+    // blocks of its own landmarks at their place in file order
+    all([&](Shard& s, int) {
+      const int rc_lin = step2 ? povar_linearize_homogeneous(s.ctx) : povar_linearize_pose(s.ctx, alpha);
+      check(rc_lin, "povar_linearize (landmark covariance)");
+      if (rc_lin == POVAR_NUMERIC_FAILURE) failed.store(1);
+    });
+    if (failed.load()) {
+      std::fprintf(stderr, "FATAL: did not expect numerical failure during linearization\n");
+      std::abort();
+    }
+    all([&](Shard& s, int) {
+      double* out = lm_cov.data() + stride * (size_t)s.lb;
+      const int rc = step2 ? povar_landmark_covariance_joint(s.ctx, 0.0, POVAR_COV_FREE_GAUGE, POVAR_COV_LANDMARK_COORDS, nullptr, 0, out, nullptr)
+                           : povar_landmark_covariance_pose(s.ctx, 0.0, POVAR_COV_FREE_GAUGE, POVAR_COV_LANDMARK_COORDS, nullptr, 0, out, nullptr);
+      check(rc, "povar_landmark_covariance");
+      if (rc != 0) status.store(rc);
+    });
+    return status.load();
   }
   VecX solve(const SolverOptions& so, double lambda, double) override {
     const size_t n = 12 * (size_t)bal_problem_.num_cameras();

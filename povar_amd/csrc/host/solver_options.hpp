@@ -66,6 +66,11 @@ struct SolverOptions {
   // marginal covariance of every camera in camera coordinates (povar_camera_covariance_pose / _joint): n_cams on the first
   // line, then 144 numbers (12 x 12 row-major, %.17g) per camera.  Empty: nothing is written.  One device only.
   std::string camera_covariance_path;
+  // likewise the free-gauge marginal covariance of every landmark in landmark coordinates (povar_landmark_covariance_pose /
+  // _joint): n_lms on the first line, then 9 (after step 1: 3 x 3) or 16 (after step 2: 4 x 4) numbers per landmark in file
+  // order.  With camera_covariance_path one library call serves both files.  Served with --gpus N too: every shard writes its
+  // own landmarks.
+  std::string landmark_covariance_path;
 
   // solver_options.cpp:41-51
   bool use_projection_validity_check() const { return optimized_cost != OptimizedCost::ERROR; }

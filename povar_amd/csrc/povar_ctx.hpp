@@ -260,10 +260,12 @@ struct povar_ctx {
                                          // grown to the larger of the two systems a context solves (run_cholesky)
   DevBuf<int> sc_lm_slot0, sc_lm_cnt, sc_info;
   int sc_factor_dim = 0;                 // POVAR_BUF_SC_FACTOR: the system whose R, y (sc_dense) and x (sc_xpad) are in place:
-  int sc_factor_n = 0;                   // 12 (step 1) or 11 (step 2) and dim * n_cams; 0: none (chol_factor, camera_covariance)
+  int sc_factor_n = 0;                   // 12 (step 1) or 11 (step 2) and dim * n_cams; 0: none (chol_factor, the covariance calls)
   // camera covariance (povar_camera_covariance_*), grown on demand and kept: the gauge basis Q, (max A_kk, min R_kk^2), the
   // N x 64 scratch panel of the triangular inverse, the [n_cams][144] blocks
   DevBuf<double> sc_cov_q, sc_cov_stat, sc_cov_panel, sc_cov_blocks;
+  DevBuf<double> sc_cov_lm;              // povar_landmark_covariance_*: the requested landmark blocks and their ids, kept likewise
+  DevBuf<int> sc_cov_ids;
 
   Dp d{};
   bool new_linearization_point = false;  // linearizor_power_varproj.cpp:75, 192, 240

@@ -10,8 +10,14 @@
 // W overwrites R in place, block column by block column from the left: when column j is formed, W[0:j, 0:j] is final
 // (the leading block of the inverse of a triangular matrix is the inverse of its leading block) and R[0:j, j] is still
 // untouched.  cov_trmm is the n^3/3 part and runs on v_mfma_f64_16x16x4_f64 with the fragment layout of chol_syrk.
+//
+// Landmark covariance (povar_landmark_covariance_pose / _joint) goes on from W:
+//   cov_lauum      C = W W^T: the strictly lower 64 x 64 blocks into M, the diagonal blocks into the scratch panel     MFMA
+//   cov_at         entry (r, c) of C in that layout
+//   lm_cov         Sigma_l = Hll^-1 + sum_ij G_i^T K_ij G_j - T_l^T T_l, then the map to landmark coordinates   workgroup per landmark
 #pragma once
 #include "povar_kernels_chol.hpp"
+#include "povar_kernels_sc.hpp"
 
 namespace povar {
 
@@ -238,6 +244,297 @@ __global__ __launch_bounds__(256) void cov_finish(double* blk, const double* Q, 
   v = sg[i] * v * sg[j];
   o[12 * i + j] = v;
   o[12 * j + i] = v;
+}
+
+// C = W W^T after the W loop: C[I][J] = sum_{K >= I} W[I][K] W[J][K]^T for the 64 x 64 blocks I >= J (W upper block
+// triangular, K >= I >= J).  The strictly lower blocks go to their natural place in M, the N / 64 diagonal blocks to the
+// N x 64 scratch panel (free once the W loop has ended: block I at rows 64 I), so no n^2 buffer is needed.
+// One launch reads only the upper block triangle of M (blocks [I][K], [J][K] with K >= I >= J) and writes only the strictly
+// lower one and the panel: no workgroup reads what another workgroup of the launch writes, and W itself stays in place.
+// The K = I block of W[I][.] (and of W[J][.] when J = I) is masked below its diagonal, as cov_gram masks.
+// Both operands are row-major along K (an A B^T product), so both sit in LDS as cov_trmm's A tile (stride CV_ALDS) and
+// both fragments read A[i + (l & 15)][kk + (l >> 4)]; 4 wavefronts, each a 32 x 32 quadrant = 2 x 2 MFMA tiles; the global
+// loads of block K + 1 are in flight under the MFMAs of block K.  A tile of block row I takes N / 64 - I K steps: the
+// linear blockIdx walks the rows I upwards (tile t = I (I + 1) / 2 + J), so the long tiles start first.
+// grid = nb (nb + 1) / 2 with nb = N / 64.  66 KiB of static LDS: two workgroups per CU.
+POVAR_KERNEL __launch_bounds__(256) void cov_lauum(double* M, int64_t ld, double* panel, int nb) {
+  __shared__ double As[CH_NB][CV_ALDS];
+  __shared__ double Bs[CH_NB][CV_ALDS];
+  const int t = blockIdx.x;
+  int I = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+  while ((I + 1) * (I + 2) / 2 <= t) ++I;
+  while (I * (I + 1) / 2 > t) --I;
+  const int J = t - I * (I + 1) / 2;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int wi = (w >> 1) * 32, wj = (w & 1) * 32;
+  const int lr = lane >> 4, lc = lane & 15;
+  ch_d4 acc[2][2];
+#pragma unroll
+  for (int x = 0; x < 2; ++x)
+#pragma unroll
+    for (int y = 0; y < 2; ++y) acc[x][y] = ch_d4{0, 0, 0, 0};
+  const double* arow = M + (int64_t)I * CH_NB * ld;
+  const double* brow = M + (int64_t)J * CH_NB * ld;
+  constexpr int NLD = CH_NB * CH_NB / 2 / 256;  // double2 per thread and operand
+  double2 ra[NLD], rb[NLD];
+  auto fetch = [&](int kb) {
+#pragma unroll
+    for (int u = 0; u < NLD; ++u) {
+      const int e = threadIdx.x + 256 * u;
+      const int p = e >> 5, q = (e & 31) * 2;
+      ra[u] = *reinterpret_cast<const double2*>(arow + (int64_t)p * ld + (int64_t)kb * CH_NB + q);
+      rb[u] = *reinterpret_cast<const double2*>(brow + (int64_t)p * ld + (int64_t)kb * CH_NB + q);
+      if (kb == I) {  // the diagonal block of W: upper triangular
+        if (q < p) ra[u].x = 0.0;
+        if (q + 1 < p) ra[u].y = 0.0;
+      }
+      if (kb == J) {
+        if (q < p) rb[u].x = 0.0;
+        if (q + 1 < p) rb[u].y = 0.0;
+      }
+    }
+  };
+  fetch(I);
+  for (int kb = I; kb < nb; ++kb) {
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < NLD; ++u) {
+      const int e = threadIdx.x + 256 * u;
+      const int p = e >> 5, q = (e & 31) * 2;
+      As[p][q] = ra[u].x; As[p][q + 1] = ra[u].y;
+      Bs[p][q] = rb[u].x; Bs[p][q + 1] = rb[u].y;
+    }
+    __syncthreads();
+    if (kb + 1 < nb) fetch(kb + 1);
+#pragma unroll 4
+    for (int kk = 0; kk < CH_NB; kk += 4) {
+      const double a0 = As[wi + lc][kk + lr], a1 = As[wi + 16 + lc][kk + lr];
+      const double b0 = Bs[wj + lc][kk + lr], b1 = Bs[wj + 16 + lc][kk + lr];
+      acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
+      acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
+      acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
+      acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
+    }
+  }
+  double* crow = I == J ? panel + (int64_t)I * CH_NB * CH_NB : M + (int64_t)I * CH_NB * ld + (int64_t)J * CH_NB;
+  const int64_t ldc = I == J ? (int64_t)CH_NB : ld;
+#pragma unroll
+  for (int x = 0; x < 2; ++x)
+#pragma unroll
+    for (int y = 0; y < 2; ++y)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) crow[(int64_t)(wi + 16 * x + lr + 4 * r) * ldc + wj + 16 * y + lc] = acc[x][y][r];
+}
+
+// Entry (r, c) of the symmetric C = W W^T as cov_lauum leaves it: the one place that knows the layout (a camera block of
+// 12 or 11 rows straddles the 64-edges, so a block's entries may come from up to four tiles).
+__device__ inline double cov_at(const double* M, int64_t ld, const double* panel, int r, int c) {
+  if (r < c) { const int t = r; r = c; c = t; }
+  if ((r >> 6) == (c >> 6)) return panel[(int64_t)r * CH_NB + (c & 63)];
+  return M[(int64_t)r * ld + c];
+}
+
+// Per-landmark contraction.  With C the camera covariance (S(lambda)^-1, or S0^+ = (S0 + Q Q^T)^-1 - Q Q^T), E_i the
+// DIM x 3 block of Hpl of observation i and G_i = F_i Hll^-1 (scd_stage / scdh_stage):
+//   Sigma_l = Hll^-1 + sum_{i,j in obs(l)} (E_i Hll^-1)^T C[c_i, c_j] (E_j Hll^-1),    E_i Hll^-1 = sum_a u_a G_i[a][:],
+//   u_a = sigma_ci o (e_a (x) h) (DIM = 12) or N_ci^T (sigma_ci o (e_a (x) X)) (DIM = 11: the staged U),
+// so a camera pair costs the 3 x 3 bilinear form K_ij[a][b] = u_a^T C[c_i, c_j] v_b (DIM^2 entries of C through cov_at, a
+// 16-lane group per pair) and G_i^T K_ij G_j, plus its transpose for i != j (pairs i <= j only).  C here is (S0 + Q Q^T)^-1
+// in the free gauge; the - Q Q^T part is T_l^T T_l with T_l = sum_i Q[rows of c_i, :]^T (E_i Hll^-1) (nq x 3), gathered per
+// observation by 64 threads (column k of Q, every fourth observation) and subtracted once.
+// One workgroup per requested landmark (ids null: landmark blockIdx.x), the observations staged in chunks with the two
+// chunk loops of sc_dense_offdiag[_h].  No atomics: every thread keeps its own partial, one fixed-order workgroup sum,
+// so the block is reproducible given C.  Then + Hll^-1 and the coords map:
+//   coords = 1 (solver):    Sigma (3 x 3) in the first 9 of the stride, the rest zero;
+//   coords = 0 (landmark):  the block carried through the map back-substitution applies to a landmark increment:
+//                           DIM = 12: D Sigma D, D = diag(s_l) (stride 9); DIM = 11: the 4 x 4 D4 N_l Sigma N_l^T D4 with
+//                           N_l = (I - beta w w^T)[:, 1:] from house4(X_l) (stride 16; rank 3, null vector X_l / s_l).
+// The upper triangle is written mirrored: every block is symmetric bit for bit.
+template <int DIM> struct LmCovObs;
+template <> struct LmCovObs<12> { typedef ScdObs T; static constexpr int CHUNK = SCD_CHUNK; };
+template <> struct LmCovObs<11> { typedef ScdObsH T; static constexpr int CHUNK = SCDH_CHUNK; };
+
+// u[a] = entry r of u_a of a staged observation
+__device__ inline void lm_cov_u(const ScdObs& o, const double* sigma, const double (&h)[4], int r, double (&u)[3]) {
+  const double v = sigma[12 * (size_t)o.cam + r] * h[r & 3];
+  u[0] = (r >> 2) == 0 ? v : 0.0;
+  u[1] = (r >> 2) == 1 ? v : 0.0;
+  u[2] = (r >> 2) == 2 ? v : 0.0;
+}
+__device__ inline void lm_cov_u(const ScdObsH& o, const double*, const double (&)[4], int r, double (&u)[3]) {
+  u[0] = o.U[r];
+  u[1] = o.U[11 + r];
+  u[2] = o.U[22 + r];
+}
+
+template <int DIM>
+__global__ __launch_bounds__(256) void lm_cov(Dp d, const double* ncw, const int* lm_slot0, const int* lm_cnt, const int* ids,
+                                              const double* M, int64_t ld, const double* panel, const double* Q, int nq,
+                                              int coords, double* out) {
+  typedef typename LmCovObs<DIM>::T Obs;
+  constexpr int CHUNK = LmCovObs<DIM>::CHUNK;
+  constexpr int STRIDE = DIM == 12 ? 9 : 16;
+  __shared__ Obs oi[CHUNK], oj[CHUNK];
+  __shared__ double sh[4 * 9];
+  __shared__ double shT[4][16][3];
+  const int lm = ids ? ids[blockIdx.x] : (int)blockIdx.x;
+  const int s0 = lm_slot0[lm], k = lm_cnt[lm];
+  double h[4], s4[4], Hi[9], hw[4] = {0, 0, 0, 0}, hbeta = 0;
+  double4 X = make_double4(0, 0, 0, 0), s = make_double4(0, 0, 0, 0);
+  if constexpr (DIM == 12) {
+    const double4* rec = reinterpret_cast<const double4*>(d.lmrec) + 3 * (size_t)lm;
+    const double4 r0 = rec[0], r1 = rec[1], r2 = rec[2];
+    h[0] = r0.x; h[1] = r0.y; h[2] = r0.z; h[3] = 1.0;
+    s4[0] = r0.w; s4[1] = r1.x; s4[2] = r1.y; s4[3] = 0.0;
+    const double t9[9] = {r1.z, r1.w, r2.x, r1.w, r2.y, r2.z, r2.x, r2.z, r2.w};
+#pragma unroll
+    for (int e = 0; e < 9; ++e) Hi[e] = t9[e];
+  } else {
+    const double4* rec = reinterpret_cast<const double4*>(d.lmrec) + 4 * (size_t)lm;
+    X = rec[0];
+    s = rec[1];
+    const double4 r2 = rec[2], r3 = rec[3];
+    h[0] = X.x; h[1] = X.y; h[2] = X.z; h[3] = X.w;
+    s4[0] = s.x; s4[1] = s.y; s4[2] = s.z; s4[3] = s.w;
+    const double t9[9] = {r2.x, r2.y, r2.z, r2.y, r2.w, r3.x, r2.z, r3.x, r3.y};
+#pragma unroll
+    for (int e = 0; e < 9; ++e) Hi[e] = t9[e];
+    house4(X, hw, hbeta);
+  }
+  auto stage = [&](int slot, Obs& o) {
+    if constexpr (DIM == 12) scd_stage(d, slot, s4, Hi, o);
+    else scdh_stage(d, ncw, slot, X, s, Hi, hw, hbeta, o);
+  };
+  const int grp = threadIdx.x >> 4, gl = threadIdx.x & 15;
+  double acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  double tacc[3] = {0, 0, 0};  // threads < 64: T_l[k = t & 15][:] over the observations t >> 4, + 4, ...
+  for (int ic = 0; ic < k; ic += CHUNK) {
+    const int ni = min(CHUNK, k - ic);
+    __syncthreads();
+    if ((int)threadIdx.x < ni) stage(s0 + ic + threadIdx.x, oi[threadIdx.x]);
+    for (int jc = ic; jc < k; jc += CHUNK) {
+      const int nj = min(CHUNK, k - jc);
+      __syncthreads();
+      if ((int)threadIdx.x < nj) stage(s0 + jc + threadIdx.x, oj[threadIdx.x]);
+      __syncthreads();
+      if (nq > 0 && jc == ic && threadIdx.x < 64 && gl < nq) {
+        for (int i = grp; i < ni; i += 4) {
+          const Obs& a = oi[i];
+          const double* qrow = Q + (size_t)DIM * a.cam * nq + gl;
+          double ta[3] = {0, 0, 0};
+          for (int r = 0; r < DIM; ++r) {
+            double u[3];
+            lm_cov_u(a, d.sigma, h, r, u);
+            const double qv = qrow[(size_t)r * nq];
+            ta[0] += qv * u[0];
+            ta[1] += qv * u[1];
+            ta[2] += qv * u[2];
+          }
+#pragma unroll
+          for (int b = 0; b < 3; ++b) tacc[b] += ta[0] * a.G[b] + ta[1] * a.G[3 + b] + ta[2] * a.G[6 + b];
+        }
+      }
+      // (the trip count and the shuffles are uniform over the workgroup; a group without a pair adds zeros)
+      for (int p0 = 0; p0 < ni * nj; p0 += 16) {
+        const int pp = p0 + grp;
+        const int i = pp / nj, j = pp - i * nj;
+        const bool live = pp < ni * nj && !(ic == jc && i > j);  // pairs i <= j: the transpose stands for the other half
+        double K[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        if (live) {
+          const Obs& a = oi[i];
+          const Obs& b = oj[j];
+          for (int e = gl; e < DIM * DIM; e += 16) {
+            const int r = e / DIM, c = e - DIM * r;
+            const double cv = cov_at(M, ld, panel, DIM * a.cam + r, DIM * b.cam + c);
+            double u[3], v[3];
+            lm_cov_u(a, d.sigma, h, r, u);
+            lm_cov_u(b, d.sigma, h, c, v);
+#pragma unroll
+            for (int x = 0; x < 3; ++x)
+#pragma unroll
+              for (int y = 0; y < 3; ++y) K[3 * x + y] += u[x] * cv * v[y];
+          }
+        }
+#pragma unroll
+        for (int m = 8; m >= 1; m >>= 1)
+#pragma unroll
+          for (int e = 0; e < 9; ++e) K[e] += shfl_xor_d(K[e], m);
+        if (live && gl == 0) {
+          const Obs& a = oi[i];
+          const Obs& b = oj[j];
+          double KG[9], P[9];  // K G_j, then G_i^T (K G_j)
+#pragma unroll
+          for (int x = 0; x < 3; ++x)
+#pragma unroll
+            for (int y = 0; y < 3; ++y) KG[3 * x + y] = K[3 * x] * b.G[y] + K[3 * x + 1] * b.G[3 + y] + K[3 * x + 2] * b.G[6 + y];
+#pragma unroll
+          for (int x = 0; x < 3; ++x)
+#pragma unroll
+            for (int y = 0; y < 3; ++y) P[3 * x + y] = a.G[x] * KG[y] + a.G[3 + x] * KG[3 + y] + a.G[6 + x] * KG[6 + y];
+          const bool same = ic == jc && i == j;
+#pragma unroll
+          for (int x = 0; x < 3; ++x)
+#pragma unroll
+            for (int y = 0; y < 3; ++y) acc[3 * x + y] += same ? P[3 * x + y] : P[3 * x + y] + P[3 * y + x];
+        }
+      }
+    }
+  }
+  block_sum<9, 256>(acc, sh);
+  if (threadIdx.x < 64) {
+#pragma unroll
+    for (int b = 0; b < 3; ++b) shT[grp][gl][b] = tacc[b];
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double Sg[9];
+#pragma unroll
+  for (int x = 0; x < 3; ++x)
+#pragma unroll
+    for (int y = x; y < 3; ++y) {
+      double tt = 0;
+      for (int q = 0; q < nq; ++q) {
+        const double tx = ((shT[0][q][x] + shT[1][q][x]) + shT[2][q][x]) + shT[3][q][x];
+        const double ty = ((shT[0][q][y] + shT[1][q][y]) + shT[2][q][y]) + shT[3][q][y];
+        tt += tx * ty;
+      }
+      const double v = Hi[3 * x + y] + acc[3 * x + y] - tt;
+      Sg[3 * x + y] = v;
+      Sg[3 * y + x] = v;
+    }
+  double* o = out + (size_t)STRIDE * blockIdx.x;
+  if (coords == 1) {
+#pragma unroll
+    for (int e = 0; e < STRIDE; ++e) o[e] = e < 9 ? Sg[e] : 0.0;
+    return;
+  }
+  if constexpr (DIM == 12) {
+#pragma unroll
+    for (int x = 0; x < 3; ++x)
+#pragma unroll
+      for (int y = x; y < 3; ++y) {
+        const double v = s4[x] * Sg[3 * x + y] * s4[y];
+        o[3 * x + y] = v;
+        o[3 * y + x] = v;
+      }
+  } else {
+    double Nl[4][3];  // N_l[i][p] = delta(i, p + 1) - beta w_i w_{p+1}
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int p = 0; p < 3; ++p) Nl[i][p] = (i == p + 1 ? 1.0 : 0.0) - hbeta * hw[i] * hw[p + 1];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = i; j < 4; ++j) {
+        double v = 0;
+#pragma unroll
+        for (int p = 0; p < 3; ++p) v += Nl[i][p] * (Sg[3 * p] * Nl[j][0] + Sg[3 * p + 1] * Nl[j][1] + Sg[3 * p + 2] * Nl[j][2]);
+        v = s4[i] * v * s4[j];
+        o[4 * i + j] = v;
+        o[4 * j + i] = v;
+      }
+  }
 }
 
 }  // namespace povar

@@ -1,4 +1,6 @@
 // povar_sc.hip -- explicit-Schur-complement solvers (LinearizorSC: PCG, CHOLESKY, RIPCG).
+#include <optional>
+
 #include "povar_ctx.hpp"
 #include "povar_kernels_cov.hpp"
 
@@ -212,16 +214,17 @@ int run_pcg(povar_ctx* c, int32_t min_it, int32_t max_it, double eta, int32_t* n
 }
 
 // ------------------------------------------------------------------------------------------
-// marginal camera covariance (povar_camera_covariance_pose / _joint; not in the reference)
+// marginal covariance of cameras and landmarks (povar_camera_covariance_* / povar_landmark_covariance_*; not in the reference)
 // ------------------------------------------------------------------------------------------
 namespace {
 // a scratch buffer of the covariance calls, grown to `count` doubles and kept (counted in povar_device_bytes); no memory:
 // the error of CHOLESKY / RICHOLESKY
-int cov_buffer(povar_ctx* c, DevBuf<double>& buf, size_t count, int dim) {
+template <typename T>
+int cov_buffer(povar_ctx* c, DevBuf<T>& buf, size_t count, int dim) {
   if (buf.p && buf.n >= count) return 0;
   if (buf.p) {
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->bytes -= buf.n * sizeof(double);
+    c->bytes -= buf.n * sizeof(T);
     buf.release();
   }
   if (buf.alloc(count, &c->bytes) != hipSuccess) {
@@ -229,7 +232,7 @@ int cov_buffer(povar_ctx* c, DevBuf<double>& buf, size_t count, int dim) {
     buf.p = nullptr;
     buf.n = 0;
     return fail(-1, std::string(dim == 11 ? "RICHOLESKY" : "CHOLESKY") + ": not enough device memory for the covariance scratch of " +
-                        std::to_string(dim * c->n_cams) + " rows (" + std::to_string(count * sizeof(double) >> 20) + " MiB)");
+                        std::to_string(dim * c->n_cams) + " rows (" + std::to_string(count * sizeof(T) >> 20) + " MiB)");
   }
   return 0;
 }
@@ -299,12 +302,21 @@ bool gauge_basis(int n_cams, int dim, const std::vector<double>& P, const std::v
 }
 }  // namespace
 
-// Diagonal blocks of S(lambda)^-1 (POVAR_COV_DAMPED) or of the pseudo-inverse S(0)^+ = (S0 + Q Q^T)^-1 - Q Q^T
-// (POVAR_COV_FREE_GAUGE), through the factorisation of CHOLESKY / RICHOLESKY: A = R^T R, W = R^-1 in place, blocks of W W^T.
-static int camera_covariance(povar_ctx* c, int dim, double lambda, int32_t gauge, int32_t coords, double* cov) {
-  const char* who = dim == 12 ? "povar_camera_covariance_pose" : "povar_camera_covariance_joint";
+// What the covariance calls share: the argument checks, the prepared system, the gauge basis, the factorisation of
+// CHOLESKY / RICHOLESKY (A = S(lambda), or S0 + Q Q^T in the free gauge), the pivot rule and W = R^-1 in place.
+struct CovInverse {
+  int n = 0, N = 0;           // dim * n_cams and its multiple of 64
+  int64_t ld = 0;
+  const double* q = nullptr;  // device: the gauge basis (free gauge), n x nq row-major
+  int nq = 0;
+};
+// 0: W is in the upper block triangle of sc_dense, the scratch panel is allocated and free;  POVAR_NUMERIC_FAILURE: not
+// positive definite, or singular beyond the gauge (the caller fills its outputs with NaN);  < 0: an error.  `ts` is the call's
+// one solve-stage timing: it opens here, once the system is prepared, and closes when the caller is done.
+static int cov_inverse(povar_ctx* c, int dim, const char* who, bool have_out, double lambda, int32_t gauge, int32_t coords,
+                       CovInverse& f, std::optional<TimeScope>& ts) {
   if (int rc = check_ctx(c)) return rc;
-  if (!cov) return fail(-1, std::string(who) + ": null argument");
+  if (!have_out) return fail(-1, std::string(who) + ": null argument");
   if (gauge != POVAR_COV_FREE_GAUGE && gauge != POVAR_COV_DAMPED) return fail(-1, std::string(who) + ": unknown gauge");
   if (coords != POVAR_COV_CAMERA_COORDS && coords != POVAR_COV_SOLVER_COORDS) return fail(-1, std::string(who) + ": unknown coords");
   if (gauge == POVAR_COV_FREE_GAUGE && lambda != 0.0) return fail(-1, std::string(who) + ": POVAR_COV_FREE_GAUGE takes lambda = 0");
@@ -315,53 +327,45 @@ static int camera_covariance(povar_ctx* c, int dim, double lambda, int32_t gauge
   if (int rc = ensure_sc(c)) return rc;
   if (int rc = dim == 12 ? build_schur_jacobi<false>(c, lambda) : build_schur_jacobi<true>(c, lambda)) return rc;
   const size_t nc = c->n_cams;
-  const int n = dim * c->n_cams;
-  const int N = (n + CH_NB - 1) / CH_NB * CH_NB;
-  const int64_t ld = (int64_t)N + CH_T;
-  const size_t out_count = 144 * nc;
-  auto all_nan = [&]() {
-    std::fill(cov, cov + out_count, std::nan(""));
-    return POVAR_NUMERIC_FAILURE;
-  };
-  TimeScope ts(c, 2);
+  f.n = dim * c->n_cams;
+  f.N = (f.n + CH_NB - 1) / CH_NB * CH_NB;
+  f.ld = (int64_t)f.N + CH_T;
+  ts.emplace(c, 2);
   const bool free_gauge = gauge == POVAR_COV_FREE_GAUGE;
-  const double* q = nullptr;
-  int nq = 0;
   if (free_gauge) {
     std::vector<double> P(12 * nc), sg(12 * nc), ncw(13 * nc), Q;
     HIP_TRY(hipMemcpyAsync(P.data(), c->cams_lin4.p, 12 * nc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(sg.data(), c->sigma.p, 12 * nc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (dim == 11) HIP_TRY(hipMemcpyAsync(ncw.data(), c->ncw.p, 13 * nc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (!gauge_basis(c->n_cams, dim, P, sg, ncw, Q, nq)) return all_nan();
+    if (!gauge_basis(c->n_cams, dim, P, sg, ncw, Q, f.nq)) return POVAR_NUMERIC_FAILURE;
     if (int rc = cov_buffer(c, c->sc_cov_q, Q.size(), dim)) return rc;
     if (int rc = cov_buffer(c, c->sc_cov_stat, 2, dim)) return rc;
     HIP_TRY(hipMemcpyAsync(c->sc_cov_q.p, Q.data(), Q.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));  // (Q is pageable host memory that goes out of scope)
-    q = c->sc_cov_q.p;
+    f.q = c->sc_cov_q.p;
   }
   // (the pivot scan belongs to the free gauge: the damped mode judges by chol_diag's info alone)
-  if (int rc = chol_factor(c, dim, q, nq, free_gauge ? c->sc_cov_stat.p : nullptr)) return rc;
+  if (int rc = chol_factor(c, dim, f.q, f.nq, free_gauge ? c->sc_cov_stat.p : nullptr)) return rc;
   c->sc_factor_dim = c->sc_factor_n = 0;  // (R becomes R^-1 below: not the factor POVAR_BUF_SC_FACTOR hands out)
   int info = 0;
   double st[2] = {0, 0};
   HIP_TRY(hipMemcpyAsync(&info, c->sc_info.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   if (free_gauge) HIP_TRY(hipMemcpyAsync(st, c->sc_cov_stat.p, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  if (info != 0) return all_nan();  // not positive definite: CHOLESKY's own rule
+  if (info != 0) return POVAR_NUMERIC_FAILURE;  // not positive definite: CHOLESKY's own rule
   if (free_gauge) {
     // a gauge-only system keeps pivots of the order of its smallest eigenvalue; further degeneracy leaves rounding
     // noise of the order u max A_kk: the threshold sqrt(u) max A_kk sits in the gap
     const double thr = std::sqrt(std::ldexp(1.0, -53)) * st[0];
-    if (!(st[1] >= thr)) return all_nan();
+    if (!(st[1] >= thr)) return POVAR_NUMERIC_FAILURE;
   }
   double* M = c->sc_dense.p;
-  if (int rc = cov_buffer(c, c->sc_cov_panel, (size_t)N * CH_NB, dim)) return rc;
-  if (int rc = cov_buffer(c, c->sc_cov_blocks, out_count, dim)) return rc;
+  const int64_t ld = f.ld;
+  if (int rc = cov_buffer(c, c->sc_cov_panel, (size_t)f.N * CH_NB, dim)) return rc;
   double* panel = c->sc_cov_panel.p;
-  double* blocks = c->sc_cov_blocks.p;
   // W = R^-1 in place, block column by block column (povar_kernels_cov.hpp)
-  for (int j = 0; j < N / CH_NB; ++j) {
+  for (int j = 0; j < f.N / CH_NB; ++j) {
     const int64_t k0 = (int64_t)j * CH_NB;
     hipLaunchKernelGGL(cov_diag_inv, dim3(1), dim3(64), 0, c->stream, M, ld, (int)k0);
     if (j == 0) continue;
@@ -370,21 +374,92 @@ static int camera_covariance(povar_ctx* c, int dim, double lambda, int32_t gauge
     hipLaunchKernelGGL(cov_trmm, dim3(j), dim3(256), 0, c->stream, (const double*)M, ld, (const double*)panel, (int64_t)CH_NB,
                        M + k0, ld, 1, j, -1.0);
   }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// Diagonal blocks of W W^T, less Q_J Q_J^T in the free gauge, in `coords`, into the host's cov (144 n_cams).  Reads the
+// upper block triangle of sc_dense only.  POVAR_NUMERIC_FAILURE: a block is not finite.
+static int cov_camera_blocks(povar_ctx* c, int dim, const CovInverse& f, int32_t coords, double* cov) {
+  const size_t out_count = 144 * (size_t)c->n_cams;
+  if (int rc = cov_buffer(c, c->sc_cov_blocks, out_count, dim)) return rc;
+  const double* M = c->sc_dense.p;
+  double* blocks = c->sc_cov_blocks.p;
   HIP_TRY(hipMemsetAsync(blocks, 0, out_count * sizeof(double), c->stream));
   if (dim == 12) {
-    hipLaunchKernelGGL(cov_gram<12>, dim3(c->n_cams), dim3(256), 0, c->stream, (const double*)M, ld, n, blocks);
-    hipLaunchKernelGGL(cov_finish<12>, dim3(c->n_cams), dim3(256), 0, c->stream, blocks, q, nq,
+    hipLaunchKernelGGL(cov_gram<12>, dim3(c->n_cams), dim3(256), 0, c->stream, M, f.ld, f.n, blocks);
+    hipLaunchKernelGGL(cov_finish<12>, dim3(c->n_cams), dim3(256), 0, c->stream, blocks, f.q, f.nq,
                        (const double*)c->sigma.p, (const double*)c->ncw.p, coords);
   } else {
-    hipLaunchKernelGGL(cov_gram<11>, dim3(c->n_cams), dim3(256), 0, c->stream, (const double*)M, ld, n, blocks);
-    hipLaunchKernelGGL(cov_finish<11>, dim3(c->n_cams), dim3(256), 0, c->stream, blocks, q, nq,
+    hipLaunchKernelGGL(cov_gram<11>, dim3(c->n_cams), dim3(256), 0, c->stream, M, f.ld, f.n, blocks);
+    hipLaunchKernelGGL(cov_finish<11>, dim3(c->n_cams), dim3(256), 0, c->stream, blocks, f.q, f.nq,
                        (const double*)c->sigma.p, (const double*)c->ncw.p, coords);
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(cov, blocks, out_count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   for (size_t i = 0; i < out_count; ++i)
-    if (!std::isfinite(cov[i])) return all_nan();
+    if (!std::isfinite(cov[i])) return POVAR_NUMERIC_FAILURE;
+  return 0;
+}
+
+// Diagonal blocks of S(lambda)^-1 (POVAR_COV_DAMPED) or of the pseudo-inverse S(0)^+ = (S0 + Q Q^T)^-1 - Q Q^T
+// (POVAR_COV_FREE_GAUGE), through the factorisation of CHOLESKY / RICHOLESKY: A = R^T R, W = R^-1 in place, blocks of W W^T.
+static int camera_covariance(povar_ctx* c, int dim, double lambda, int32_t gauge, int32_t coords, double* cov) {
+  const char* who = dim == 12 ? "povar_camera_covariance_pose" : "povar_camera_covariance_joint";
+  CovInverse f;
+  std::optional<TimeScope> ts;
+  int rc = cov_inverse(c, dim, who, cov != nullptr, lambda, gauge, coords, f, ts);
+  if (rc == 0) rc = cov_camera_blocks(c, dim, f, coords, cov);
+  if (rc == POVAR_NUMERIC_FAILURE) std::fill(cov, cov + 144 * (size_t)c->n_cams, std::nan(""));
+  return rc;
+}
+
+// Landmark blocks Sigma_l = Hll^-1 + F_l^T C F_l of the requested landmarks (and, on request, the camera blocks of the
+// same C): the camera call's W, then C = W W^T off the diagonal too (cov_lauum) and the per-landmark contraction (lm_cov).
+static int landmark_covariance(povar_ctx* c, int dim, double lambda, int32_t gauge, int32_t coords, const int32_t* lm_ids,
+                               int32_t n_ids, double* lm_cov_out, double* cam_cov) {
+  const char* who = dim == 12 ? "povar_landmark_covariance_pose" : "povar_landmark_covariance_joint";
+  if (int rc = check_ctx(c)) return rc;
+  const int n_out = lm_ids ? n_ids : c->n_lms;
+  if (n_out < 0) return fail(-1, std::string(who) + ": negative n_ids");
+  for (int i = 0; lm_ids && i < n_out; ++i)
+    if (lm_ids[i] < 0 || lm_ids[i] >= c->n_lms) return fail(-1, std::string(who) + ": landmark id out of range");
+  const int stride = dim == 12 ? 9 : 16;
+  const size_t lm_count = (size_t)stride * (size_t)n_out, cam_count = 144 * (size_t)c->n_cams;
+  CovInverse f;
+  std::optional<TimeScope> ts;
+  int rc = cov_inverse(c, dim, who, lm_cov_out != nullptr || n_out == 0, lambda, gauge, coords, f, ts);
+  auto all_nan = [&]() {
+    std::fill(lm_cov_out, lm_cov_out + lm_count, std::nan(""));
+    if (cam_cov) std::fill(cam_cov, cam_cov + cam_count, std::nan(""));
+    return POVAR_NUMERIC_FAILURE;
+  };
+  if (rc == 0 && cam_cov) rc = cov_camera_blocks(c, dim, f, coords, cam_cov);
+  if (rc == POVAR_NUMERIC_FAILURE) return all_nan();
+  if (rc != 0 || n_out == 0) return rc;
+  if (int rc2 = cov_buffer(c, c->sc_cov_lm, lm_count, dim)) return rc2;
+  if (lm_ids) {
+    if (int rc2 = cov_buffer(c, c->sc_cov_ids, (size_t)n_out, dim)) return rc2;
+    HIP_TRY(hipMemcpyAsync(c->sc_cov_ids.p, lm_ids, (size_t)n_out * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  }
+  const int* ids = lm_ids ? c->sc_cov_ids.p : nullptr;
+  double* M = c->sc_dense.p;
+  const int nb = f.N / CH_NB;
+  hipLaunchKernelGGL(cov_lauum, dim3((unsigned)(nb * (nb + 1) / 2)), dim3(256), 0, c->stream, M, f.ld, c->sc_cov_panel.p, nb);
+  if (dim == 12)
+    hipLaunchKernelGGL(lm_cov<12>, dim3(n_out), dim3(256), 0, c->stream, c->d, (const double*)c->ncw.p, (const int*)c->sc_lm_slot0.p,
+                       (const int*)c->sc_lm_cnt.p, ids, (const double*)M, f.ld, (const double*)c->sc_cov_panel.p, f.q, f.nq, coords,
+                       c->sc_cov_lm.p);
+  else
+    hipLaunchKernelGGL(lm_cov<11>, dim3(n_out), dim3(256), 0, c->stream, c->d, (const double*)c->ncw.p, (const int*)c->sc_lm_slot0.p,
+                       (const int*)c->sc_lm_cnt.p, ids, (const double*)M, f.ld, (const double*)c->sc_cov_panel.p, f.q, f.nq, coords,
+                       c->sc_cov_lm.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(lm_cov_out, c->sc_cov_lm.p, lm_count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));  // (also: lm_ids is the caller's memory)
+  for (size_t i = 0; i < lm_count; ++i)
+    if (!std::isfinite(lm_cov_out[i])) return all_nan();
   return 0;
 }
 
@@ -396,6 +471,16 @@ int povar_camera_covariance_pose(povar_ctx* c, double lambda, int32_t gauge, int
 
 int povar_camera_covariance_joint(povar_ctx* c, double lambda, int32_t gauge, int32_t coords, double* cov) {
   return camera_covariance(c, 11, lambda, gauge, coords, cov);
+}
+
+int povar_landmark_covariance_pose(povar_ctx* c, double lambda, int32_t gauge, int32_t coords, const int32_t* lm_ids, int32_t n_ids,
+                                   double* lm_cov, double* cam_cov) {
+  return landmark_covariance(c, 12, lambda, gauge, coords, lm_ids, n_ids, lm_cov, cam_cov);
+}
+
+int povar_landmark_covariance_joint(povar_ctx* c, double lambda, int32_t gauge, int32_t coords, const int32_t* lm_ids, int32_t n_ids,
+                                    double* lm_cov, double* cam_cov) {
+  return landmark_covariance(c, 11, lambda, gauge, coords, lm_ids, n_ids, lm_cov, cam_cov);
 }
 
 int povar_set_jl_col_scaling(povar_ctx* c, int32_t enable) {

@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
-"""Times the camera covariance (povar_camera_covariance_pose / _joint) against the direct solve it shares its factorisation
+"""Times the camera covariance (povar_camera_covariance_pose / _joint) and the landmark covariance of every landmark
+(povar_landmark_covariance_pose / _joint) against the direct solve they share their factorisation
 with (povar_solve_pose_sc / povar_solve_joint_sc_method with POVAR_SC_CHOLESKY) on a synthetic BAL shape, one process, one
 context.  Device times (povar_timings.solve_ms: hipEvents on the context's stream around assembly + factorisation + back
-substitution, or assembly + factorisation + inverse + per-camera Gram); every call is warmed once, then timed REPS times,
+substitution, or assembly + factorisation + inverse + per-camera Gram, or -- the landmark call -- assembly + factorisation +
+inverse + W W^T + per-landmark contraction + the copy of the blocks to the host); every call is warmed once, then timed REPS times,
 the median is reported.  The covariance is timed in both modes: free gauge (lambda = 0) and damped (lambda as given); a shape
 that is singular beyond its gauge returns after the factorisation, which the line then says.
 At this size a dense reference is out of reach; the two size-independent checks are printed instead: bitwise symmetry of every
@@ -60,6 +62,14 @@ def main():
                 r = np.linalg.norm(np.einsum("cij,cj->ci", cov, v), axis=1) / (np.linalg.norm(cov, axis=(1, 2)) * np.linalg.norm(v, axis=1))
                 line += f"; null-vector residual, worst camera: {r.max():.2e}"
             print(line, flush=True)
+            mib_cam = ctx.device_bytes() >> 20
+            (blocks, rc), ms_lm = timed(lambda: ctx.landmark_covariance(step=step, lam=lm, gauge=gauge, coords=capi.COV_LANDMARK_COORDS))
+            assert rc == 0
+            ev = np.linalg.eigvalsh(blocks)
+            print(f"step {step} landmark covariance, all {p.n_lms} landmarks, {name} (lambda {lm:g}): {ms_lm:.1f} ms per call, ratio to the "
+                  f"camera call {ms_lm / ms:.2f}, to {solver} {ms_lm / ms_solve:.2f}; blocks bitwise symmetric: "
+                  f"{np.array_equal(blocks, blocks.transpose(0, 2, 1))}; eigenvalue {1 if step == 1 else 2} / largest, worst landmark: "
+                  f"{(ev[:, 0 if step == 1 else 1] / ev[:, -1]).min():.2e}; device MiB {mib_cam} -> {ctx.device_bytes() >> 20}", flush=True)
 
     # step 1 in the units of the normalised observations (the first two rows of every P divided by 500)
     cams1 = p.cams.copy()
