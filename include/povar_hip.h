@@ -343,7 +343,7 @@ enum {
   POVAR_BUF_SC_PRECOND,    /* Schur-Jacobi inv_blocks of the last povar_solve_*_sc (preconditioner.hpp:80-107),
                               144 n_cams (step 1) or 121 n_cams (step 2) */
   POVAR_BUF_SC_BLOCKDIAG,  /* B_c = Hpp_c + lambda I of the last povar_solve_*_sc, same sizes */
-  POVAR_BUF_SC_FACTOR      /* the factored augmented matrix of the last successful CHOLESKY / RICHOLESKY solve and its two
+  POVAR_BUF_SC_FACTOR,     /* the factored augmented matrix of the last successful CHOLESKY / RICHOLESKY solve and its two
                               triangular solves: N x (N + 2) doubles row-major, N = dim n_cams rounded up to 64 (dim = 12
                               for step 1, 11 for step 2).  Row i: M[i, 0:N] (row i of the upper factor R in the columns
                               j >= i, S = R^T R; the columns j < i are unspecified), then y_i (R^T y = -b: column N of the
@@ -354,7 +354,28 @@ enum {
                               factorisation, a povar_*_covariance_* call since, which inverts R in place) is an argument
                               error.  PCG / RIPCG and the power series leave the factor alone.  On a sharded context every
                               rank holds the all-reduced matrix. */
+  POVAR_BUF_COV_FACTOR,    /* the four POVAR_BUF_COV_* hand out what the last povar_*_covariance_* call left on the device.
+                              Precondition of all four: the last call that wrote the dense matrix was a covariance call
+                              that returned 0; any other state (no such call yet, POVAR_NUMERIC_FAILURE, a CHOLESKY /
+                              RICHOLESKY solve since) is an argument error.  N = dim n_cams rounded up to 64, n = dim n_cams.
+                              COV_FACTOR: N x N row-major, the augmented matrix's first N columns after the factorisation: the
+                              upper factor R (A = R^T R, A = S(lambda) or S0 + Q Q^T) the inversion started from, in the
+                              columns j >= i; the columns j < i are unspecified; rows and columns past n are the identity's.
+                              It is a copy made before W overwrites R, only while povar_set_cov_inspect is on: an argument
+                              error when the switch was off during that call. */
+  POVAR_BUF_COV_INVERSE,   /* N x N row-major, the dense matrix after the call.  The upper block triangle of 64 x 64 blocks
+                              holds W = R^-1 (upper triangular: zero below the diagonal inside the diagonal blocks, the
+                              identity on the padding).  After a landmark call with n_ids > 0 the strictly lower 64 x 64 blocks
+                              hold C = W W^T; after a camera call they are unspecified. */
+  POVAR_BUF_COV_PANEL,     /* N x 64 row-major: rows 64 I .. 64 I + 63 are the diagonal block I of C = W W^T.  Valid after a
+                              landmark call with n_ids > 0 only; an argument error after a camera call. */
+  POVAR_BUF_COV_GAUGE      /* n x nq row-major (nq = 12 pose, 15 joint): the orthonormal gauge basis Q of the last covariance
+                              call, in the solver's coordinates.  An argument error when that call was POVAR_COV_DAMPED. */
 };
+/* enable = 1: every later povar_*_covariance_* call keeps a device copy of its factor R for POVAR_BUF_COV_FACTOR (8 N^2 bytes
+ * more, counted in povar_device_bytes; not enough memory: the error of CHOLESKY / RICHOLESKY).  0 (default): no allocation,
+ * no copy.  For tests that hold the stages of the covariance path to their own rounding-error bounds. */
+int povar_set_cov_inspect(povar_ctx* ctx, int32_t enable);
 int povar_get_buffer(povar_ctx* ctx, int32_t which, double* out, int64_t n);
 
 /* ---- measurement ---- */

@@ -22,7 +22,7 @@ NO_CONVERGENCE, SUCCESS, FAILURE = 0, 1, 2
 NUMERIC_FAILURE = 1
 (BUF_DIAG2, BUF_POSE_SCALING, BUF_JL_COL_SCALE, BUF_HLL_INV, BUF_B, BUF_B_INV, BUF_STORAGE,
  BUF_JL_COL_SCALE_H, BUF_B_JOINT, BUF_B_INV_JOINT, BUF_NC_HOUSEHOLDER, BUF_SC_PRECOND,
- BUF_SC_BLOCKDIAG, BUF_SC_FACTOR) = range(14)
+ BUF_SC_BLOCKDIAG, BUF_SC_FACTOR, BUF_COV_FACTOR, BUF_COV_INVERSE, BUF_COV_PANEL, BUF_COV_GAUGE) = range(18)
 SC_PCG, SC_CHOLESKY = 0, 1
 # povar_camera_covariance_pose / _joint (include/povar_hip.h: POVAR_COV_*)
 COV_FREE_GAUGE, COV_DAMPED = 0, 1
@@ -275,6 +275,10 @@ class Context:
     def set_jl_col_scaling(self, enable):
         self._chk(self.L.povar_set_jl_col_scaling(self.h, C.c_int32(1 if enable else 0)))
 
+    def set_cov_inspect(self, enable):
+        """Keep the factor R of every later covariance call for BUF_COV_FACTOR (include/povar_hip.h)."""
+        self._chk(self.L.povar_set_cov_inspect(self.h, C.c_int32(1 if enable else 0)))
+
     def solve_pose_sc(self, lam, method=SC_PCG, min_iterations=0, max_iterations=500, eta=1e-2):
         inc = np.zeros(12 * self.n_cams)
         it, st = C.c_int32(), C.c_int32()
@@ -396,6 +400,14 @@ class Context:
             out = np.zeros(N * (N + 2))
             self._chk(self.L.povar_get_buffer(self.h, C.c_int32(which), _p(out), C.c_int64(out.size)))
             return out.reshape(N, N + 2)
+        if which in (BUF_COV_FACTOR, BUF_COV_INVERSE, BUF_COV_PANEL, BUF_COV_GAUGE):
+            dim = 11 if joint else 12  # [N, N], [N, N], [N, 64], [n, nq]; N = n = dim n_cams rounded up to 64
+            n = dim * self.n_cams
+            N = (n + 63) // 64 * 64
+            shape = {BUF_COV_FACTOR: (N, N), BUF_COV_INVERSE: (N, N), BUF_COV_PANEL: (N, 64), BUF_COV_GAUGE: (n, 15 if joint else 12)}[which]
+            out = np.zeros(shape)
+            self._chk(self.L.povar_get_buffer(self.h, C.c_int32(which), _p(out), C.c_int64(out.size)))
+            return out
         n = {BUF_DIAG2: 12 * self.n_cams, BUF_POSE_SCALING: 12 * self.n_cams,
              BUF_JL_COL_SCALE: 3 * self.n_lms, BUF_HLL_INV: 9 * self.n_lms, BUF_B: 12 * self.n_cams,
              BUF_B_INV: 144 * self.n_cams, BUF_STORAGE: 64 * self.n_obs,

@@ -266,6 +266,14 @@ struct povar_ctx {
   DevBuf<double> sc_cov_q, sc_cov_stat, sc_cov_panel, sc_cov_blocks;
   DevBuf<double> sc_cov_lm;              // povar_landmark_covariance_*: the requested landmark blocks and their ids, kept likewise
   DevBuf<int> sc_cov_ids;
+  // inspection of the covariance path (povar_set_cov_inspect, POVAR_BUF_COV_*).  sc_cov_kind: what the last call that wrote
+  // the dense matrix left there: 0 nothing to hand out (chol_factor, a failure), 1 a camera call's W, 2 a landmark call's W, C
+  // and panel; sc_cov_n as sc_factor_n (dim * n_cams of that call); sc_cov_nq: columns of the gauge basis of that call (0:
+  // damped); sc_cov_kept: that call copied its R into sc_cov_r (N x N, row-major, allocated only with the switch on)
+  int cov_inspect = 0;
+  int sc_cov_kind = 0, sc_cov_n = 0, sc_cov_nq = 0;
+  bool sc_cov_kept = false;
+  DevBuf<double> sc_cov_r;
 
   Dp d{};
   bool new_linearization_point = false;  // linearizor_power_varproj.cpp:75, 192, 240

@@ -154,9 +154,10 @@ POVAR_KERNEL __launch_bounds__(256) void cov_trmm(const double* A, int64_t lda, 
 }
 
 // Solver-coordinate block of camera c: T[a][b] = sum_k W[J_a][k] W[J_b][k], J_a = DIM c + a, over the columns
-// k < n (the padding columns of these rows are zero: they contribute nothing).  W is upper triangular, but below the
-// diagonal M still holds what the assembly left there (a camera block that straddles a 64-panel edge), so entries with
-// k < row are masked, not read.  One workgroup per camera: thread t walks columns DIM c + t, + 256, ... (coalesced row
+// k < n (the padding columns of these rows are zero: they contribute nothing).  W is upper triangular.  Inside a 64 x 64
+// diagonal block cov_diag_inv has stored its zeros below the diagonal, but the strictly lower 64 x 64 blocks of M still
+// hold what the assembly left there (or C, after cov_lauum), and a camera block that straddles a 64-edge reaches into
+// one: entries with k < row are masked, not read.  One workgroup per camera: thread t walks columns DIM c + t, + 256, ... (coalesced row
 // reads), keeps the DIM (DIM + 1) / 2 products of the upper triangle, one deterministic workgroup sum, mirrored on
 // the way out so the block is symmetric bit for bit.  out: DIM x DIM row-major at stride 144.
 template <int DIM>

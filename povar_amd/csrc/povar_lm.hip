@@ -614,6 +614,35 @@ int povar_get_buffer(povar_ctx* c, int32_t which, double* out, int64_t n) {
       for (size_t i = 0; i < N; ++i) out[i * (N + 2) + N + 1] = xh[i];
       return 0;
     }
+    case POVAR_BUF_COV_FACTOR:
+    case POVAR_BUF_COV_INVERSE:
+    case POVAR_BUF_COV_PANEL:
+    case POVAR_BUF_COV_GAUGE: {
+      if (c->sc_cov_kind == 0 || !c->sc_dense.p)
+        return fail(-1, "povar_get_buffer: POVAR_BUF_COV_*: no covariance in place (the last call that wrote the dense matrix "
+                        "must be a povar_*_covariance_* call that returned 0)");
+      const size_t N = ((size_t)c->sc_cov_n + CH_NB - 1) / CH_NB * CH_NB;
+      const size_t ld = N + CH_T;  // row stride of the augmented matrix (chol_factor, povar_sc.hip)
+      if (which == POVAR_BUF_COV_GAUGE) {
+        if (c->sc_cov_nq == 0 || !c->sc_cov_q.p) return fail(-1, "povar_get_buffer: POVAR_BUF_COV_GAUGE: the last covariance call was damped");
+        return copy(c->sc_cov_q.p, (size_t)c->sc_cov_n * (size_t)c->sc_cov_nq);
+      }
+      if (which == POVAR_BUF_COV_PANEL) {
+        if (c->sc_cov_kind != 2 || !c->sc_cov_panel.p)
+          return fail(-1, "povar_get_buffer: POVAR_BUF_COV_PANEL: the last covariance call was not a landmark call with landmarks");
+        return copy(c->sc_cov_panel.p, N * CH_NB);
+      }
+      if (which == POVAR_BUF_COV_FACTOR && (!c->sc_cov_kept || !c->sc_cov_r.p))
+        return fail(-1, "povar_get_buffer: POVAR_BUF_COV_FACTOR: povar_set_cov_inspect was off during the last covariance call");
+      if ((size_t)n != N * N) return fail(-1, "povar_get_buffer: wrong size");
+      if (which == POVAR_BUF_COV_FACTOR)
+        HIP_TRY(hipMemcpyAsync(out, c->sc_cov_r.p, N * N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+      else
+        HIP_TRY(hipMemcpy2DAsync(out, N * sizeof(double), c->sc_dense.p, ld * sizeof(double), N * sizeof(double), N, hipMemcpyDeviceToHost,
+                                 c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      return 0;
+    }
     case POVAR_BUF_JL_COL_SCALE_H: {
       if ((size_t)n != 4 * nl) return fail(-1, "povar_get_buffer: wrong size");
       HIP_TRY(hipMemcpyAsync(out, c->jl_scale4.p, nl * sizeof(double4), hipMemcpyDeviceToHost, c->stream));

@@ -60,6 +60,7 @@ int e0_dense(povar_ctx* c) {
 // the all-reduce; `stat` (device, 2 doubles; null for the solvers) then receives max_k A_kk and min_k R_kk^2.
 static int chol_factor(povar_ctx* c, int dim, const double* Q, int nq, double* stat) {
   c->sc_factor_dim = c->sc_factor_n = 0;  // (run_cholesky sets it again once the factorisation has succeeded)
+  c->sc_cov_kind = c->sc_cov_n = 0;  // (a covariance call sets it again once it has returned its blocks)
   const int n = dim * c->n_cams;
   const int N = (n + CH_NB - 1) / CH_NB * CH_NB;
   const int64_t ld = (int64_t)N + CH_T;
@@ -331,6 +332,7 @@ static int cov_inverse(povar_ctx* c, int dim, const char* who, bool have_out, do
   f.N = (f.n + CH_NB - 1) / CH_NB * CH_NB;
   f.ld = (int64_t)f.N + CH_T;
   ts.emplace(c, 2);
+  c->sc_cov_kind = 0;  // (from here on Q, the dense matrix and the panel are rewritten: POVAR_BUF_COV_* wait for cov_done)
   const bool free_gauge = gauge == POVAR_COV_FREE_GAUGE;
   if (free_gauge) {
     std::vector<double> P(12 * nc), sg(12 * nc), ncw(13 * nc), Q;
@@ -364,6 +366,13 @@ static int cov_inverse(povar_ctx* c, int dim, const char* who, bool have_out, do
   const int64_t ld = f.ld;
   if (int rc = cov_buffer(c, c->sc_cov_panel, (size_t)f.N * CH_NB, dim)) return rc;
   double* panel = c->sc_cov_panel.p;
+  c->sc_cov_kept = false;
+  if (c->cov_inspect) {  // povar_set_cov_inspect: keep the R the inversion starts from (POVAR_BUF_COV_FACTOR)
+    if (int rc = cov_buffer(c, c->sc_cov_r, (size_t)f.N * f.N, dim)) return rc;
+    HIP_TRY(hipMemcpy2DAsync(c->sc_cov_r.p, (size_t)f.N * sizeof(double), M, (size_t)ld * sizeof(double), (size_t)f.N * sizeof(double),
+                             (size_t)f.N, hipMemcpyDeviceToDevice, c->stream));
+    c->sc_cov_kept = true;
+  }
   // W = R^-1 in place, block column by block column (povar_kernels_cov.hpp)
   for (int j = 0; j < f.N / CH_NB; ++j) {
     const int64_t k0 = (int64_t)j * CH_NB;
@@ -403,6 +412,13 @@ static int cov_camera_blocks(povar_ctx* c, int dim, const CovInverse& f, int32_t
   return 0;
 }
 
+// a covariance call has returned 0: what POVAR_BUF_COV_* may hand out (kind 1: a camera call, 2: a landmark call)
+static void cov_done(povar_ctx* c, const CovInverse& f, int kind) {
+  c->sc_cov_kind = kind;
+  c->sc_cov_n = f.n;
+  c->sc_cov_nq = f.nq;
+}
+
 // Diagonal blocks of S(lambda)^-1 (POVAR_COV_DAMPED) or of the pseudo-inverse S(0)^+ = (S0 + Q Q^T)^-1 - Q Q^T
 // (POVAR_COV_FREE_GAUGE), through the factorisation of CHOLESKY / RICHOLESKY: A = R^T R, W = R^-1 in place, blocks of W W^T.
 static int camera_covariance(povar_ctx* c, int dim, double lambda, int32_t gauge, int32_t coords, double* cov) {
@@ -412,6 +428,7 @@ static int camera_covariance(povar_ctx* c, int dim, double lambda, int32_t gauge
   int rc = cov_inverse(c, dim, who, cov != nullptr, lambda, gauge, coords, f, ts);
   if (rc == 0) rc = cov_camera_blocks(c, dim, f, coords, cov);
   if (rc == POVAR_NUMERIC_FAILURE) std::fill(cov, cov + 144 * (size_t)c->n_cams, std::nan(""));
+  if (rc == 0) cov_done(c, f, 1);
   return rc;
 }
 
@@ -437,6 +454,7 @@ static int landmark_covariance(povar_ctx* c, int dim, double lambda, int32_t gau
   };
   if (rc == 0 && cam_cov) rc = cov_camera_blocks(c, dim, f, coords, cam_cov);
   if (rc == POVAR_NUMERIC_FAILURE) return all_nan();
+  if (rc == 0 && n_out == 0) cov_done(c, f, 1);  // (no landmark: cov_lauum does not run)
   if (rc != 0 || n_out == 0) return rc;
   if (int rc2 = cov_buffer(c, c->sc_cov_lm, lm_count, dim)) return rc2;
   if (lm_ids) {
@@ -460,6 +478,7 @@ static int landmark_covariance(povar_ctx* c, int dim, double lambda, int32_t gau
   HIP_TRY(hipStreamSynchronize(c->stream));  // (also: lm_ids is the caller's memory)
   for (size_t i = 0; i < lm_count; ++i)
     if (!std::isfinite(lm_cov_out[i])) return all_nan();
+  cov_done(c, f, 2);
   return 0;
 }
 
@@ -481,6 +500,12 @@ int povar_landmark_covariance_pose(povar_ctx* c, double lambda, int32_t gauge, i
 int povar_landmark_covariance_joint(povar_ctx* c, double lambda, int32_t gauge, int32_t coords, const int32_t* lm_ids, int32_t n_ids,
                                     double* lm_cov, double* cam_cov) {
   return landmark_covariance(c, 11, lambda, gauge, coords, lm_ids, n_ids, lm_cov, cam_cov);
+}
+
+int povar_set_cov_inspect(povar_ctx* c, int32_t enable) {
+  if (int rc = check_ctx(c)) return rc;
+  c->cov_inspect = enable ? 1 : 0;
+  return 0;
 }
 
 int povar_set_jl_col_scaling(povar_ctx* c, int32_t enable) {

@@ -23,6 +23,20 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, n), f"{n} declared in povar_hip.h but not exported"
 
 
+def test_buffer_ids_of_the_header_and_the_ctypes_mirror_agree():
+    """POVAR_BUF_* in the header's order against capi.BUF_* (the covariance inspection ids included), and the setter that
+    goes with them."""
+    from povar_amd import capi
+    text = open(os.path.join(ROOT, "include", "povar_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    body = re.search(r"enum\s*\{\s*(POVAR_BUF_DIAG2\b.*?)\}", text, flags=re.S).group(1)
+    names = re.findall(r"\bPOVAR_(BUF_[A-Z0-9_]+)", body)
+    assert len(names) == 18 and names[-4:] == ["BUF_COV_FACTOR", "BUF_COV_INVERSE", "BUF_COV_PANEL", "BUF_COV_GAUGE"]
+    for k, n in enumerate(names):
+        assert getattr(capi, n) == k, n
+    assert hasattr(capi.lib(), "povar_set_cov_inspect") and hasattr(capi.Context, "set_cov_inspect")
+
+
 def test_no_gpu_fails_loudly():
     """No CPU fallback: without a HIP device povar_create must return an error, never a context."""
     from povar_amd import capi, synth
