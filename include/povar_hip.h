@@ -327,6 +327,39 @@ int povar_landmark_covariance_joint(povar_ctx* ctx, double lambda, int32_t gauge
                                     const int32_t* lm_ids /* NULL = all landmarks of the context */, int32_t n_ids,
                                     double* lm_cov, double* cam_cov /* 144 n_cams or NULL */);
 
+/* ---- per-observation leverage and covariance of the predicted image point: the block of the hat matrix J H^+ J^T of every
+ * observation of the requested landmarks, J = [Jp Jl] the weighted Jacobian of the step (d = 4 residual rows per observation in
+ * step 1, d = 2 in step 2).  With y = P_c X_l the projected homogeneous point, Syy_i the 3 x 3 covariance of y that the joint
+ * covariance of camera c_i and landmark l implies (the camera-landmark cross terms included, which neither call above
+ * exposes), each observation gets one row of 4 doubles
+ *       (h, c_uu, c_uv, c_vv):   h = tr(J_i H^+ J_i^T), the leverage in the weighted residual metric the step minimises
+ *                                (d - h is the redundancy number of the observation; 0 <= h <= d);
+ *                                [[c_uu, c_uv], [c_uv, c_vv]] the covariance of the predicted image point (y0 / y2, y1 / y2),
+ *                                unweighted (step 2: h = w_i (c_uu + c_vv) with w_i the robust weight).
+ * These values do not depend on the gauge, on the Jacobi scaling or on povar_set_jl_col_scaling: there is no coords argument
+ * and no caveat about where the gauge is fixed.  In the free gauge, over all observations of an unsharded context,
+ *       sum_i h_i = rank J = DIM n_cams + 3 n_lms - nq     (DIM = 12, nq = 12 in step 1; DIM = 11, nq = 15 in step 2).
+ * From the same factor as the landmark calls: C = W W^T, Sigma_l (without the gauge correction, which cancels in J C J^T) and
+ * one more workgroup per landmark; given C a row is reproducible (no atomics).
+ *   gauge, lambda   the camera calls' rules.  POVAR_COV_DAMPED: h = tr(J_i H(lambda)^-1 J_i^T).
+ *   lm_ids, n_ids   as the landmark calls'.
+ *   obs_cov, n_rows 4 n_rows doubles.  The rows are the observations of the requested landmarks in the caller's CSR order:
+ *                   NULL: every observation of the context in order; a list: the tracks concatenated in list order, duplicates
+ *                   allowed.  n_rows must be the number of rows the request produces, else an argument error.  On a sharded
+ *                   context each rank returns its shard's observations.
+ * Preconditions, the pivot rule, side effects (on the dense matrix, POVAR_BUF_SC_FACTOR and POVAR_BUF_COV_*), the sharded rule
+ * and the memory errors are those of the landmark calls.  On POVAR_NUMERIC_FAILURE every entry is NaN.  The status judges the
+ * factorisation only: an observation with y2 == 0 (a point in the camera's principal plane) gets non-finite c_* by IEEE
+ * rules with status 0, and its h is unaffected in step 1 (step 2's linearisation already reports such a point). ---- */
+/* after povar_linearize_pose */
+int povar_observation_covariance_pose(povar_ctx* ctx, double lambda, int32_t gauge,
+                                      const int32_t* lm_ids /* NULL = all landmarks of the context */, int32_t n_ids,
+                                      double* obs_cov /* 4 n_rows */, int64_t n_rows);
+/* after povar_linearize_homogeneous */
+int povar_observation_covariance_joint(povar_ctx* ctx, double lambda, int32_t gauge,
+                                       const int32_t* lm_ids /* NULL = all landmarks of the context */, int32_t n_ids,
+                                       double* obs_cov /* 4 n_rows */, int64_t n_rows);
+
 /* ---- inspection of internal state in the reference's layouts (parity tests) ---- */
 enum {
   POVAR_BUF_DIAG2 = 0,     /* get_Jp_diag2_pOSE, 12 n_cams (linearization_varproj.hpp:183-222) */

@@ -342,6 +342,27 @@ class Context:
         dim = 11 if (step == 2 and coords == COV_SOLVER_COORDS) else 12
         return blocks, cam[:, :dim * dim].reshape(self.n_cams, dim, dim).copy(), rc
 
+    def observation_covariance(self, step=1, lam=0.0, gauge=COV_FREE_GAUGE, lm_ids=None):
+        """Leverage and predicted-point covariance of every observation of the context (or of the landmarks `lm_ids`: their
+        tracks concatenated in list order, duplicates allowed) at the step linearised last: (rows, rc) with rows [n, 4] =
+        (h, c_uu, c_uv, c_vv) per observation in the caller's CSR order.  Gauge- and scaling-invariant: no coords.
+        rc = NUMERIC_FAILURE comes with all-NaN rows."""
+        if step not in (1, 2):
+            raise ValueError("observation_covariance: step is 1 or 2")
+        if lm_ids is None:
+            n_ids, ids_p, n_rows = 0, None, self.n_obs
+        else:
+            lm_ids = np.ascontiguousarray(lm_ids, dtype=np.int32).reshape(-1)
+            if np.any(lm_ids < 0) or np.any(lm_ids >= self.n_lms):
+                raise PovarError("observation_covariance: landmark id out of range")
+            n_ids, ids_p = lm_ids.shape[0], _p(lm_ids)
+            n_rows = int(np.diff(self.lm_off)[lm_ids].sum())
+        out = np.zeros((n_rows, 4))
+        fn = self.L.povar_observation_covariance_pose if step == 1 else self.L.povar_observation_covariance_joint
+        rc = self._chk(fn(self.h, C.c_double(lam), C.c_int32(gauge), ids_p, C.c_int32(n_ids), _p(out) if n_rows else None,
+                          C.c_int64(n_rows)), allow_numeric=True)
+        return out, rc
+
     def apply_joint(self, inc):
         inc = np.ascontiguousarray(inc, dtype=np.float64)
         ld = C.c_double()

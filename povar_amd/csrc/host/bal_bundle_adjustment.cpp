@@ -177,6 +177,32 @@ void write_covariances(Linearizor& linearizor, const BalProblem& bal_problem, co
   if (with_cameras) write(so.camera_covariance_path, bal_problem.num_cameras(), 144, cam_cov);
 }
 
+// --observation-covariance-path: n_obs on the first line, then one line per observation in file order: landmark, camera and
+// the row (h, c_uu, c_uv, c_vv) of povar_observation_covariance_pose / _joint; a call of its own
+void write_observation_covariance(Linearizor& linearizor, const BalProblem& bal_problem, const SolverOptions& so, bool step2) {
+  Linearizor::VecX cov;
+  const int rc = linearizor.observation_covariance(step2, so.alpha, cov);
+  if (rc < 0) {
+    std::fprintf(stderr, "FATAL: this linearizor does not serve --observation-covariance-path\n");
+    std::abort();
+  }
+  if (rc != 0) std::printf("\t[WARN] observation covariance: the reduced system is singular beyond its gauge, the rows are NaN\n");
+  std::FILE* f = std::fopen(so.observation_covariance_path.c_str(), "w");
+  if (!f) {
+    std::fprintf(stderr, "FATAL: cannot write %s\n", so.observation_covariance_path.c_str());
+    std::abort();
+  }
+  std::vector<int> lm_off, cam_idx;
+  std::vector<double> obs;
+  bal_problem.flatten(lm_off, cam_idx, obs);
+  std::fprintf(f, "%zu\n", cam_idx.size());
+  for (int l = 0; l < bal_problem.num_landmarks(); ++l)
+    for (int i = lm_off[l]; i < lm_off[l + 1]; ++i)
+      std::fprintf(f, "%d %d %.17g %.17g %.17g %.17g\n", l, cam_idx[i], cov[4 * (size_t)i], cov[4 * (size_t)i + 1], cov[4 * (size_t)i + 2],
+                   cov[4 * (size_t)i + 3]);
+  std::fclose(f);
+}
+
 void optimize_lm(BalProblem& bal_problem, const SolverOptions& so, SolverSummary& summary, const Timer& timer_total,
                  bool step2) {
   Timer timer_preprocessor;
@@ -357,6 +383,8 @@ void optimize_lm(BalProblem& bal_problem, const SolverOptions& so, SolverSummary
   // not in the reference: the marginal covariance of cameras and / or landmarks at the final accepted state of the last step that ran
   if ((!so.camera_covariance_path.empty() || !so.landmark_covariance_path.empty()) && step2 == (so.max_num_iterations_step_2 > 0))
     write_covariances(*linearizor, bal_problem, so, step2);
+  if (!so.observation_covariance_path.empty() && step2 == (so.max_num_iterations_step_2 > 0))
+    write_observation_covariance(*linearizor, bal_problem, so, step2);
   std::printf("Final Cost: %s\n", error_summary_oneline(summary.final_cost, so.use_projection_validity_check()).c_str());
   std::printf("%s: %s\n", summary.termination_type == CONVERGENCE ? "CONVERGENCE" : "NO_CONVERGENCE", summary.message.c_str());
   std::fflush(stdout);

@@ -94,6 +94,7 @@ bool parse_bal_app_arguments(int argc, char** argv, BalAppOptions& o) {
   integer("gpus", &o.solver.gpus);
   str("camera-covariance-path", &o.solver.camera_covariance_path);
   str("landmark-covariance-path", &o.solver.landmark_covariance_path);
+  str("observation-covariance-path", &o.solver.observation_covariance_path);
 
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -111,7 +112,11 @@ bool parse_bal_app_arguments(int argc, char** argv, BalAppOptions& o) {
                   "      covariance (inverse information) of every camera: n_cams, then 144 numbers (12 x 12, row-major) per camera\n"
                   "  --landmark-covariance-path FILE\n"
                   "      likewise for every landmark (gauge fixed on the cameras): n_lms, then 9 numbers (3 x 3, after step 1) or 16\n"
-                  "      (4 x 4 homogeneous, after step 2) per landmark; with --camera-covariance-path one call serves both files\n");
+                  "      (4 x 4 homogeneous, after step 2) per landmark; with --camera-covariance-path one call serves both files\n"
+                  "  --observation-covariance-path FILE\n"
+                  "      likewise for every observation, independent of the gauge: n_obs, then one line per observation in file order:\n"
+                  "      landmark camera h c_uu c_uv c_vv -- the leverage h (redundancy number: 4 - h after step 1, 2 - h after step 2)\n"
+                  "      and the 2 x 2 covariance of the predicted image point\n");
       return false;
     }
     if (a.rfind("--", 0) != 0) {

@@ -127,6 +127,12 @@ class Linearizor {
     (void)step2; (void)alpha; (void)lm_cov; (void)cam_cov;
     return -1;
   }
+  // Likewise for the observations (povar_observation_covariance_pose / _joint, free gauge): obs_cov gets 4 numbers per
+  // observation in file order (h, c_uu, c_uv, c_vv).  The N-shard linearizor serves it too.
+  virtual int observation_covariance(bool step2, double alpha, VecX& obs_cov) {
+    (void)step2; (void)alpha; (void)obs_cov;
+    return -1;
+  }
 };
 
 // hook for alternative implementations (the tests register an oracle-backed one)

@@ -201,6 +201,21 @@ class LinearizorPowerVarprojHip : public Linearizor, public StateMirror {
     check(rc, "povar_landmark_covariance");
     return rc;
   }
+  int observation_covariance(bool step2, double alpha, VecX& obs_cov) override {
+    const int64_t n_obs = bal_problem_.num_observations();
+    obs_cov.assign(4 * (size_t)n_obs, 0.0);
+    // (as camera_covariance: after the LM loop, nothing is booked)
+    const int rc_lin = step2 ? povar_linearize_homogeneous(ctx_) : povar_linearize_pose(ctx_, alpha);
+    check(rc_lin, "povar_linearize (observation covariance)");
+    if (rc_lin == POVAR_NUMERIC_FAILURE) {
+      std::fprintf(stderr, "FATAL: did not expect numerical failure during linearization\n");
+      std::abort();
+    }
+    const int rc = step2 ? povar_observation_covariance_joint(ctx_, 0.0, POVAR_COV_FREE_GAUGE, nullptr, 0, obs_cov.data(), n_obs)
+                         : povar_observation_covariance_pose(ctx_, 0.0, POVAR_COV_FREE_GAUGE, nullptr, 0, obs_cov.data(), n_obs);
+    check(rc, "povar_observation_covariance");
+    return rc;
+  }
   VecX solve(const SolverOptions& so, double lambda, double) override {
     VecX inc(12 * (size_t)bal_problem_.num_cameras());
     Timer t;
@@ -496,6 +511,8 @@ class LinearizorPowerVarprojHipMulti : public Linearizor, public StateMirror {
       std::vector<int> off(lm_off.begin() + s.lb, lm_off.begin() + s.le + 1);
       const int ob = off.front();
       for (int& v : off) v -= ob;
+      s.ob = ob;
+      s.on = off.back();
       povar_options or_ = o;
       or_.device = (options.device + r) % n_dev;
       check(povar_create(&s.ctx, bal_problem.num_cameras(), s.le - s.lb, (int64_t)off.back(), off.data(), cam_idx.data() + ob,
@@ -577,6 +594,28 @@ class LinearizorPowerVarprojHipMulti : public Linearizor, public StateMirror {
     });
     return status.load();
   }
+  int observation_covariance(bool step2, double alpha, VecX& obs_cov) override {
+    obs_cov.assign(4 * (size_t)bal_problem_.num_observations(), 0.0);
+    std::atomic<int> failed{0}, status{0};
+    // as landmark_covariance: every shard linearises and calls, and writes the rows of its own observations at their place
+    all([&](Shard& s, int) {
+      const int rc_lin = step2 ? povar_linearize_homogeneous(s.ctx) : povar_linearize_pose(s.ctx, alpha);
+      check(rc_lin, "povar_linearize (observation covariance)");
+      if (rc_lin == POVAR_NUMERIC_FAILURE) failed.store(1);
+    });
+    if (failed.load()) {
+      std::fprintf(stderr, "FATAL: did not expect numerical failure during linearization\n");
+      std::abort();
+    }
+    all([&](Shard& s, int) {
+      double* out = obs_cov.data() + 4 * (size_t)s.ob;
+      const int rc = step2 ? povar_observation_covariance_joint(s.ctx, 0.0, POVAR_COV_FREE_GAUGE, nullptr, 0, out, s.on)
+                           : povar_observation_covariance_pose(s.ctx, 0.0, POVAR_COV_FREE_GAUGE, nullptr, 0, out, s.on);
+      check(rc, "povar_observation_covariance");
+      if (rc != 0) status.store(rc);
+    });
+    return status.load();
+  }
   VecX solve(const SolverOptions& so, double lambda, double) override {
     const size_t n = 12 * (size_t)bal_problem_.num_cameras();
     std::vector<VecX> inc(shards_.size(), VecX(n));
@@ -650,6 +689,7 @@ class LinearizorPowerVarprojHipMulti : public Linearizor, public StateMirror {
   struct Shard {
     povar_ctx* ctx = nullptr;
     int32_t lb = 0, le = 0;
+    int64_t ob = 0, on = 0;  // its observations in file order: the first one and their number
   };
   template <class F>
   void all(F&& f) {

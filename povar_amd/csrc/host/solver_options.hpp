@@ -71,6 +71,10 @@ struct SolverOptions {
   // order.  With camera_covariance_path one library call serves both files.  Served with --gpus N too: every shard writes its
   // own landmarks.
   std::string landmark_covariance_path;
+  // leverage and predicted-point covariance of every observation (povar_observation_covariance_pose / _joint, free gauge):
+  // n_obs on the first line, then one line per observation in file order: landmark camera h c_uu c_uv c_vv (%.17g).  A call
+  // of its own, independent of the two paths above; served with --gpus N too: every shard writes its own observations.
+  std::string observation_covariance_path;
 
   // solver_options.cpp:41-51
   bool use_projection_validity_check() const { return optimized_cost != OptimizedCost::ERROR; }

@@ -1004,7 +1004,7 @@ void povar_destroy(povar_ctx* c) {
   c->inc.release(); c->item_part.release(); c->item_partG.release(); c->norm_part.release();
   c->norms.release(); c->part.release(); c->scal.release(); c->stage.release(); c->cm_h.release(); c->lmrec.release(); c->ncw.release(); c->cc_h.release(); c->cc_part.release(); c->hot_part.release(); c->hot_rec.release(); c->zimg.release();
   c->sc_dense.release(); c->sc_xpad.release(); c->sc_lm_slot0.release(); c->sc_lm_cnt.release(); c->sc_info.release();
-  c->sc_cov_q.release(); c->sc_cov_stat.release(); c->sc_cov_panel.release(); c->sc_cov_blocks.release(); c->sc_cov_lm.release(); c->sc_cov_ids.release(); c->sc_cov_r.release();
+  c->sc_cov_q.release(); c->sc_cov_stat.release(); c->sc_cov_panel.release(); c->sc_cov_blocks.release(); c->sc_cov_lm.release(); c->sc_cov_ids.release(); c->sc_cov_r.release(); c->sc_cov_obs.release(); c->sc_cov_row0.release();
   c->sc_dm_part.release(); c->sc_dm.release(); c->sc_bmat.release(); c->sc_minv.release(); c->sc_x.release();
   c->sc_r.release(); c->sc_p.release(); c->sc_q.release(); c->sc_zv.release(); c->sc_part.release(); c->sc_s.release();
   c->cc_cam_range.release(); c->cold_pos.release(); c->q4c.release();

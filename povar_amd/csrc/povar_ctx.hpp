@@ -266,6 +266,8 @@ struct povar_ctx {
   DevBuf<double> sc_cov_q, sc_cov_stat, sc_cov_panel, sc_cov_blocks;
   DevBuf<double> sc_cov_lm;              // povar_landmark_covariance_*: the requested landmark blocks and their ids, kept likewise
   DevBuf<int> sc_cov_ids;
+  DevBuf<double> sc_cov_obs;             // povar_observation_covariance_*: the rows (4 per observation) and the first row of
+  DevBuf<int> sc_cov_row0;               // every requested landmark, kept likewise (Sigma_l without the gauge part goes to sc_cov_lm)
   // inspection of the covariance path (povar_set_cov_inspect, POVAR_BUF_COV_*).  sc_cov_kind: what the last call that wrote
   // the dense matrix left there: 0 nothing to hand out (chol_factor, a failure), 1 a camera call's W, 2 a landmark call's W, C
   // and panel; sc_cov_n as sc_factor_n (dim * n_cams of that call); sc_cov_nq: columns of the gauge basis of that call (0:

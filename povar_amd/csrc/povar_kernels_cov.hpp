@@ -15,6 +15,8 @@
 //   cov_lauum      C = W W^T: the strictly lower 64 x 64 blocks into M, the diagonal blocks into the scratch panel     MFMA
 //   cov_at         entry (r, c) of C in that layout
 //   lm_cov         Sigma_l = Hll^-1 + sum_ij G_i^T K_ij G_j - T_l^T T_l, then the map to landmark coordinates   workgroup per landmark
+// Observation leverage and predicted-point covariance (povar_observation_covariance_pose / _joint) go on from Sigma_l:
+//   obs_cov        (h_i, c_uu, c_uv, c_vv) of every observation of a landmark from K_ii, R_i = sum_j K_ij G_j and Sigma_l   workgroup per landmark
 #pragma once
 #include "povar_kernels_chol.hpp"
 #include "povar_kernels_sc.hpp"
@@ -535,6 +537,180 @@ __global__ __launch_bounds__(256) void lm_cov(Dp d, const double* ncw, const int
         o[4 * i + j] = v;
         o[4 * j + i] = v;
       }
+  }
+}
+
+// Per-observation block of the hat matrix J H^+ J^T (povar_observation_covariance_pose / _joint).  With y = P_c X_l the
+// projected homogeneous point of observation i of landmark l, dy = U_i^T dp_c + L_i dl (U_i the three vectors lm_cov_u
+// reads; L_i = P3 diag(s) (DIM = 12) or P diag(s4) N_l (DIM = 11)) and M_i the 3 x 3 Gram matrix of the weighted residual
+// Jacobian with respect to y (w C, or w Dm^T Dm: F_i = M_i L_i), the covariance of y is
+//   Syy_i = K_ii - R_i L_i^T - L_i R_i^T + L_i Sigma_l L_i^T,   K_ij = U_i^T C[c_i, c_j] U_j,   R_i = sum_{j in obs(l)} K_ij G_j
+// (- C F_l is the camera-landmark cross covariance), and the row is
+//   h_i = tr(M_i Syy_i)  (leverage)   and   J Syy_i J^T,  J = d(y0 / y2, y1 / y2) / dy  (2 x 2: c_uu, c_uv, c_vv; unweighted).
+// C is (S0 + Q Q^T)^-1 as it stands in the free gauge: [Q; -Hll^-1 Hlp Q] lies in the null space of J, so the - Q Q^T
+// part cancels in Syy_i -- provided Sigma_l carries none of it either: `sig` is lm_cov's output with nq = 0, coords = 1
+// (9 numbers at stride 9 / 16), and no Q is read here.
+// One workgroup per requested landmark, staged as lm_cov stages; a 16-lane group owns observation i and walks every j of
+// the track (all k^2 pairs: K_ji = K_ij^T is not reused), each lane keeping its share of the DIM^2 entries of every K_ij:
+// R_i is linear in K_ij, so the lanes' partial R_i and K_ii stay in registers and meet in one butterfly after the walk --
+// no atomics, a fixed order, the row reproducible given C.  Lane 0 of the group then forms the row at
+// out + 4 (row0[blockIdx.x] + i): the rows of a landmark in the order of its observations.  y2 = 0 leaves c_* non-finite
+// by IEEE rules (DIM = 12: h_i does not depend on J).
+template <int DIM>
+__global__ __launch_bounds__(256) void obs_cov(Dp d, const double* ncw, const int* lm_slot0, const int* lm_cnt, const int* ids,
+                                               const int* row0, const double* M, int64_t ld, const double* panel,
+                                               const double* sig, double* out) {
+  typedef typename LmCovObs<DIM>::T Obs;
+  constexpr int CHUNK = LmCovObs<DIM>::CHUNK;
+  constexpr int STRIDE = DIM == 12 ? 9 : 16;
+  __shared__ Obs oi[CHUNK], oj[CHUNK];
+  const int lm = ids ? ids[blockIdx.x] : (int)blockIdx.x;
+  const int s0 = lm_slot0[lm], k = lm_cnt[lm];
+  double h[4], s4[4], Hi[9], hw[4] = {0, 0, 0, 0}, hbeta = 0;
+  double4 X = make_double4(0, 0, 0, 0), s = make_double4(0, 0, 0, 0);
+  if constexpr (DIM == 12) {
+    const double4* rec = reinterpret_cast<const double4*>(d.lmrec) + 3 * (size_t)lm;
+    const double4 r0 = rec[0], r1 = rec[1], r2 = rec[2];
+    h[0] = r0.x; h[1] = r0.y; h[2] = r0.z; h[3] = 1.0;
+    s4[0] = r0.w; s4[1] = r1.x; s4[2] = r1.y; s4[3] = 0.0;
+    const double t9[9] = {r1.z, r1.w, r2.x, r1.w, r2.y, r2.z, r2.x, r2.z, r2.w};
+#pragma unroll
+    for (int e = 0; e < 9; ++e) Hi[e] = t9[e];
+  } else {
+    const double4* rec = reinterpret_cast<const double4*>(d.lmrec) + 4 * (size_t)lm;
+    X = rec[0];
+    s = rec[1];
+    const double4 r2 = rec[2], r3 = rec[3];
+    h[0] = X.x; h[1] = X.y; h[2] = X.z; h[3] = X.w;
+    s4[0] = s.x; s4[1] = s.y; s4[2] = s.z; s4[3] = s.w;
+    const double t9[9] = {r2.x, r2.y, r2.z, r2.y, r2.w, r3.x, r2.z, r3.x, r3.y};
+#pragma unroll
+    for (int e = 0; e < 9; ++e) Hi[e] = t9[e];
+    house4(X, hw, hbeta);
+  }
+  auto stage = [&](int slot, Obs& o) {
+    if constexpr (DIM == 12) scd_stage(d, slot, s4, Hi, o);
+    else scdh_stage(d, ncw, slot, X, s, Hi, hw, hbeta, o);
+  };
+  const int grp = threadIdx.x >> 4, gl = threadIdx.x & 15;
+  int staged = -1;  // the chunk oj holds: a track of one chunk stages it once
+  for (int ic = 0; ic < k; ic += CHUNK) {
+    const int ni = min(CHUNK, k - ic);
+    __syncthreads();
+    if ((int)threadIdx.x < ni) stage(s0 + ic + threadIdx.x, oi[threadIdx.x]);
+    __syncthreads();
+    // (the trip counts, the barriers and the shuffles are uniform over the workgroup; a group without an observation adds zeros)
+    for (int i0 = 0; i0 < ni; i0 += 16) {
+      const int i = i0 + grp;
+      const bool live = i < ni;
+      double R[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, Kii[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+      for (int jc = 0; jc < k; jc += CHUNK) {
+        const int nj = min(CHUNK, k - jc);
+        if (staged != jc) {
+          __syncthreads();
+          if ((int)threadIdx.x < nj) stage(s0 + jc + threadIdx.x, oj[threadIdx.x]);
+          __syncthreads();
+          staged = jc;
+        }
+        if (!live) continue;
+        const Obs& a = oi[i];
+        for (int j = 0; j < nj; ++j) {
+          const Obs& b = oj[j];
+          double K[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+          for (int e = gl; e < DIM * DIM; e += 16) {
+            const int r = e / DIM, c = e - DIM * r;
+            const double cv = cov_at(M, ld, panel, DIM * a.cam + r, DIM * b.cam + c);
+            double u[3], v[3];
+            lm_cov_u(a, d.sigma, h, r, u);
+            lm_cov_u(b, d.sigma, h, c, v);
+#pragma unroll
+            for (int x = 0; x < 3; ++x)
+#pragma unroll
+              for (int y = 0; y < 3; ++y) K[3 * x + y] += u[x] * cv * v[y];
+          }
+#pragma unroll
+          for (int x = 0; x < 3; ++x)
+#pragma unroll
+            for (int y = 0; y < 3; ++y) R[3 * x + y] += K[3 * x] * b.G[y] + K[3 * x + 1] * b.G[3 + y] + K[3 * x + 2] * b.G[6 + y];
+          if (jc == ic && j == i) {
+#pragma unroll
+            for (int e = 0; e < 9; ++e) Kii[e] = K[e];
+          }
+        }
+      }
+#pragma unroll
+      for (int m = 8; m >= 1; m >>= 1)
+#pragma unroll
+        for (int e = 0; e < 9; ++e) {
+          R[e] += shfl_xor_d(R[e], m);
+          Kii[e] += shfl_xor_d(Kii[e], m);
+        }
+      if (!live || gl != 0) continue;
+      // the row of observation ic + i: L_i, M_i and y from the linearisation point, as the staging reads them
+      const int slot = s0 + ic + i;
+      const Cam P = load_cam(d.cams_lin4, oi[i].cam);
+      const double2 uv = d.uv[slot];
+      const double sw = d.robust ? d.sw[slot] : 1.0;
+      const double w = sw * sw;
+      const double4 pr[3] = {P.r0, P.r1, P.r2};
+      double L[9], Mi[9], yv[3];
+#pragma unroll
+      for (int x = 0; x < 3; ++x) {
+        const double p4[4] = {pr[x].x, pr[x].y, pr[x].z, pr[x].w};
+        yv[x] = p4[0] * h[0] + p4[1] * h[1] + p4[2] * h[2] + p4[3] * h[3];
+        if constexpr (DIM == 12) {
+#pragma unroll
+          for (int y = 0; y < 3; ++y) L[3 * x + y] = p4[y] * s4[y];
+        } else {  // a row of P diag(s4) N_l, N_l = (I - beta w w^T)[:, 1:]
+          const double q4[4] = {p4[0] * s4[0], p4[1] * s4[1], p4[2] * s4[2], p4[3] * s4[3]};
+          const double aw = q4[0] * hw[0] + q4[1] * hw[1] + q4[2] * hw[2] + q4[3] * hw[3];
+#pragma unroll
+          for (int y = 0; y < 3; ++y) L[3 * x + y] = q4[y + 1] - hbeta * aw * hw[y + 1];
+        }
+      }
+      if constexpr (DIM == 12) {
+        const double sb2 = d.sb * d.sb;
+        const double cu = sb2 * uv.x, cv = sb2 * uv.y, cuv = sb2 * (uv.x * uv.x + uv.y * uv.y);
+        const double C9[9] = {1, 0, -cu, 0, 1, -cv, -cu, -cv, cuv};
+#pragma unroll
+        for (int e = 0; e < 9; ++e) Mi[e] = w * C9[e];
+      } else {
+        const Hom hp = hom_project(P, X, uv.x, uv.y);
+        const double m9[9] = {hp.D00 * hp.D00, 0, hp.D00 * hp.D02, 0, hp.D00 * hp.D00, hp.D00 * hp.D12,
+                              hp.D00 * hp.D02, hp.D00 * hp.D12, hp.D02 * hp.D02 + hp.D12 * hp.D12};
+#pragma unroll
+        for (int e = 0; e < 9; ++e) Mi[e] = w * m9[e];
+      }
+      const double* Sg = sig + (size_t)STRIDE * blockIdx.x;
+      double SL[9], Syy[9];  // Sigma_l L_i^T, then the upper triangle of Syy_i, mirrored
+#pragma unroll
+      for (int x = 0; x < 3; ++x)
+#pragma unroll
+        for (int y = 0; y < 3; ++y) SL[3 * x + y] = Sg[3 * x] * L[3 * y] + Sg[3 * x + 1] * L[3 * y + 1] + Sg[3 * x + 2] * L[3 * y + 2];
+#pragma unroll
+      for (int x = 0; x < 3; ++x)
+#pragma unroll
+        for (int y = x; y < 3; ++y) {
+          const double rl = R[3 * x] * L[3 * y] + R[3 * x + 1] * L[3 * y + 1] + R[3 * x + 2] * L[3 * y + 2];
+          const double lr = L[3 * x] * R[3 * y] + L[3 * x + 1] * R[3 * y + 1] + L[3 * x + 2] * R[3 * y + 2];
+          const double lsl = L[3 * x] * SL[y] + L[3 * x + 1] * SL[3 + y] + L[3 * x + 2] * SL[6 + y];
+          const double v = Kii[3 * x + y] - rl - lr + lsl;
+          Syy[3 * x + y] = v;
+          Syy[3 * y + x] = v;
+        }
+      double lev = 0;
+#pragma unroll
+      for (int e = 0; e < 9; ++e) lev += Mi[e] * Syy[e];  // (both symmetric)
+      const double iz = 1.0 / yv[2];
+      const double j0 = -yv[0] * iz * iz, j1 = -yv[1] * iz * iz;  // J = [[iz, 0, j0], [0, iz, j1]]
+      const double a0[3] = {iz * Syy[0] + j0 * Syy[6], iz * Syy[1] + j0 * Syy[7], iz * Syy[2] + j0 * Syy[8]};  // J Syy
+      const double a1[3] = {iz * Syy[3] + j1 * Syy[6], iz * Syy[4] + j1 * Syy[7], iz * Syy[5] + j1 * Syy[8]};
+      double* o = out + 4 * ((size_t)row0[blockIdx.x] + ic + i);
+      o[0] = lev;
+      o[1] = a0[0] * iz + a0[2] * j0;
+      o[2] = a0[1] * iz + a0[2] * j1;
+      o[3] = a1[1] * iz + a1[2] * j1;
+    }
   }
 }
 

@@ -432,6 +432,21 @@ static int camera_covariance(povar_ctx* c, int dim, double lambda, int32_t gauge
   return rc;
 }
 
+// C = W W^T off the diagonal too (cov_lauum), then the blocks of the n_out requested landmarks into sc_cov_lm (lm_cov)
+static void cov_lm_launch(povar_ctx* c, int dim, const CovInverse& f, const int* ids, int n_out, const double* q, int nq, int32_t coords) {
+  double* M = c->sc_dense.p;
+  const int nb = f.N / CH_NB;
+  hipLaunchKernelGGL(cov_lauum, dim3((unsigned)(nb * (nb + 1) / 2)), dim3(256), 0, c->stream, M, f.ld, c->sc_cov_panel.p, nb);
+  if (dim == 12)
+    hipLaunchKernelGGL(lm_cov<12>, dim3(n_out), dim3(256), 0, c->stream, c->d, (const double*)c->ncw.p, (const int*)c->sc_lm_slot0.p,
+                       (const int*)c->sc_lm_cnt.p, ids, (const double*)M, f.ld, (const double*)c->sc_cov_panel.p, q, nq, coords,
+                       c->sc_cov_lm.p);
+  else
+    hipLaunchKernelGGL(lm_cov<11>, dim3(n_out), dim3(256), 0, c->stream, c->d, (const double*)c->ncw.p, (const int*)c->sc_lm_slot0.p,
+                       (const int*)c->sc_lm_cnt.p, ids, (const double*)M, f.ld, (const double*)c->sc_cov_panel.p, q, nq, coords,
+                       c->sc_cov_lm.p);
+}
+
 // Landmark blocks Sigma_l = Hll^-1 + F_l^T C F_l of the requested landmarks (and, on request, the camera blocks of the
 // same C): the camera call's W, then C = W W^T off the diagonal too (cov_lauum) and the per-landmark contraction (lm_cov).
 static int landmark_covariance(povar_ctx* c, int dim, double lambda, int32_t gauge, int32_t coords, const int32_t* lm_ids,
@@ -461,23 +476,71 @@ static int landmark_covariance(povar_ctx* c, int dim, double lambda, int32_t gau
     if (int rc2 = cov_buffer(c, c->sc_cov_ids, (size_t)n_out, dim)) return rc2;
     HIP_TRY(hipMemcpyAsync(c->sc_cov_ids.p, lm_ids, (size_t)n_out * sizeof(int), hipMemcpyHostToDevice, c->stream));
   }
-  const int* ids = lm_ids ? c->sc_cov_ids.p : nullptr;
-  double* M = c->sc_dense.p;
-  const int nb = f.N / CH_NB;
-  hipLaunchKernelGGL(cov_lauum, dim3((unsigned)(nb * (nb + 1) / 2)), dim3(256), 0, c->stream, M, f.ld, c->sc_cov_panel.p, nb);
-  if (dim == 12)
-    hipLaunchKernelGGL(lm_cov<12>, dim3(n_out), dim3(256), 0, c->stream, c->d, (const double*)c->ncw.p, (const int*)c->sc_lm_slot0.p,
-                       (const int*)c->sc_lm_cnt.p, ids, (const double*)M, f.ld, (const double*)c->sc_cov_panel.p, f.q, f.nq, coords,
-                       c->sc_cov_lm.p);
-  else
-    hipLaunchKernelGGL(lm_cov<11>, dim3(n_out), dim3(256), 0, c->stream, c->d, (const double*)c->ncw.p, (const int*)c->sc_lm_slot0.p,
-                       (const int*)c->sc_lm_cnt.p, ids, (const double*)M, f.ld, (const double*)c->sc_cov_panel.p, f.q, f.nq, coords,
-                       c->sc_cov_lm.p);
+  cov_lm_launch(c, dim, f, lm_ids ? c->sc_cov_ids.p : nullptr, n_out, f.q, f.nq, coords);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(lm_cov_out, c->sc_cov_lm.p, lm_count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));  // (also: lm_ids is the caller's memory)
   for (size_t i = 0; i < lm_count; ++i)
     if (!std::isfinite(lm_cov_out[i])) return all_nan();
+  cov_done(c, f, 2);
+  return 0;
+}
+
+// Per-observation leverage and predicted-point covariance of the requested landmarks' observations: the landmark call's C,
+// Sigma_l without the gauge correction (lm_cov with nq = 0 in solver coordinates, into sc_cov_lm) and the per-landmark
+// contraction obs_cov, which reads no Q: the gauge part of C cancels in J C J^T only if no term carries the correction.
+static int observation_covariance(povar_ctx* c, int dim, double lambda, int32_t gauge, const int32_t* lm_ids, int32_t n_ids,
+                                  double* obs_cov_out, int64_t n_rows) {
+  const char* who = dim == 12 ? "povar_observation_covariance_pose" : "povar_observation_covariance_joint";
+  if (int rc = check_ctx(c)) return rc;
+  const int n_out = lm_ids ? n_ids : c->n_lms;
+  if (n_out < 0) return fail(-1, std::string(who) + ": negative n_ids");
+  std::vector<int> row0((size_t)n_out);
+  int64_t rows = 0;
+  for (int i = 0; i < n_out; ++i) {
+    const int l = lm_ids ? lm_ids[i] : i;
+    if (l < 0 || l >= c->n_lms) return fail(-1, std::string(who) + ": landmark id out of range");
+    if (rows > INT32_MAX) return fail(-1, std::string(who) + ": more than 2^31 rows requested");
+    row0[i] = (int)rows;
+    rows += c->lm_off[l + 1] - c->lm_off[l];
+  }
+  if (n_rows != rows) return fail(-1, std::string(who) + ": n_rows is " + std::to_string(n_rows) + ", the request produces " + std::to_string(rows));
+  const size_t count = 4 * (size_t)rows;
+  CovInverse f;
+  std::optional<TimeScope> ts;
+  int rc = cov_inverse(c, dim, who, obs_cov_out != nullptr || rows == 0, lambda, gauge, POVAR_COV_SOLVER_COORDS, f, ts);
+  auto all_nan = [&]() {
+    std::fill(obs_cov_out, obs_cov_out + count, std::nan(""));
+    return POVAR_NUMERIC_FAILURE;
+  };
+  if (rc == POVAR_NUMERIC_FAILURE) return all_nan();
+  if (rc == 0 && rows == 0) cov_done(c, f, 1);  // (no observation: cov_lauum does not run)
+  if (rc != 0 || rows == 0) return rc;
+  if (int rc2 = cov_buffer(c, c->sc_cov_lm, (size_t)(dim == 12 ? 9 : 16) * (size_t)n_out, dim)) return rc2;
+  if (int rc2 = cov_buffer(c, c->sc_cov_row0, (size_t)n_out, dim)) return rc2;
+  if (int rc2 = cov_buffer(c, c->sc_cov_obs, count, dim)) return rc2;
+  if (lm_ids) {
+    if (int rc2 = cov_buffer(c, c->sc_cov_ids, (size_t)n_out, dim)) return rc2;
+    HIP_TRY(hipMemcpyAsync(c->sc_cov_ids.p, lm_ids, (size_t)n_out * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  }
+  HIP_TRY(hipMemcpyAsync(c->sc_cov_row0.p, row0.data(), (size_t)n_out * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  // (rows of a landmark without observations do not exist; every other entry is written)
+  const int* ids = lm_ids ? c->sc_cov_ids.p : nullptr;
+  cov_lm_launch(c, dim, f, ids, n_out, nullptr, 0, POVAR_COV_SOLVER_COORDS);
+  if (dim == 12)
+    hipLaunchKernelGGL(obs_cov<12>, dim3(n_out), dim3(256), 0, c->stream, c->d, (const double*)c->ncw.p, (const int*)c->sc_lm_slot0.p,
+                       (const int*)c->sc_lm_cnt.p, ids, (const int*)c->sc_cov_row0.p, (const double*)c->sc_dense.p, f.ld,
+                       (const double*)c->sc_cov_panel.p, (const double*)c->sc_cov_lm.p, c->sc_cov_obs.p);
+  else
+    hipLaunchKernelGGL(obs_cov<11>, dim3(n_out), dim3(256), 0, c->stream, c->d, (const double*)c->ncw.p, (const int*)c->sc_lm_slot0.p,
+                       (const int*)c->sc_lm_cnt.p, ids, (const int*)c->sc_cov_row0.p, (const double*)c->sc_dense.p, f.ld,
+                       (const double*)c->sc_cov_panel.p, (const double*)c->sc_cov_lm.p, c->sc_cov_obs.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(obs_cov_out, c->sc_cov_obs.p, count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));  // (also: lm_ids and row0 are host memory that goes out of scope)
+  // the status judges the factorisation: a leverage that is not finite means C is not; c_* may be non-finite at y2 = 0
+  for (size_t i = 0; i < count; i += 4)
+    if (!std::isfinite(obs_cov_out[i])) return all_nan();
   cov_done(c, f, 2);
   return 0;
 }
@@ -500,6 +563,16 @@ int povar_landmark_covariance_pose(povar_ctx* c, double lambda, int32_t gauge, i
 int povar_landmark_covariance_joint(povar_ctx* c, double lambda, int32_t gauge, int32_t coords, const int32_t* lm_ids, int32_t n_ids,
                                     double* lm_cov, double* cam_cov) {
   return landmark_covariance(c, 11, lambda, gauge, coords, lm_ids, n_ids, lm_cov, cam_cov);
+}
+
+int povar_observation_covariance_pose(povar_ctx* c, double lambda, int32_t gauge, const int32_t* lm_ids, int32_t n_ids, double* obs_cov,
+                                      int64_t n_rows) {
+  return observation_covariance(c, 12, lambda, gauge, lm_ids, n_ids, obs_cov, n_rows);
+}
+
+int povar_observation_covariance_joint(povar_ctx* c, double lambda, int32_t gauge, const int32_t* lm_ids, int32_t n_ids, double* obs_cov,
+                                       int64_t n_rows) {
+  return observation_covariance(c, 11, lambda, gauge, lm_ids, n_ids, obs_cov, n_rows);
 }
 
 int povar_set_cov_inspect(povar_ctx* c, int32_t enable) {

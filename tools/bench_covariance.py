@@ -1,14 +1,17 @@
 #!/usr/bin/env python3
-"""Times the camera covariance (povar_camera_covariance_pose / _joint) and the landmark covariance of every landmark
-(povar_landmark_covariance_pose / _joint) against the direct solve they share their factorisation
+"""Times the camera covariance (povar_camera_covariance_pose / _joint), the landmark covariance of every landmark
+(povar_landmark_covariance_pose / _joint) and the leverage / predicted-point covariance of every observation
+(povar_observation_covariance_pose / _joint) against the direct solve they share their factorisation
 with (povar_solve_pose_sc / povar_solve_joint_sc_method with POVAR_SC_CHOLESKY) on a synthetic BAL shape, one process, one
 context.  Device times (povar_timings.solve_ms: hipEvents on the context's stream around assembly + factorisation + back
 substitution, or assembly + factorisation + inverse + per-camera Gram, or -- the landmark call -- assembly + factorisation +
-inverse + W W^T + per-landmark contraction + the copy of the blocks to the host); every call is warmed once, then timed REPS times,
+inverse + W W^T + per-landmark contraction + the copy of the blocks to the host; the observation call: the landmark call's stages with
+Sigma_l kept on the device, + the per-observation contraction + the copy of the rows); every call is warmed once, then timed REPS times,
 the median is reported.  The covariance is timed in both modes: free gauge (lambda = 0) and damped (lambda as given); a shape
 that is singular beyond its gauge returns after the factorisation, which the line then says.
 At this size a dense reference is out of reach; the two size-independent checks are printed instead: bitwise symmetry of every
-block, and (step 2, camera coordinates) the null-vector residual |block (h0 / sigma_c)| / (|block| |h0 / sigma_c|).
+block, (step 2, camera coordinates) the null-vector residual |block (h0 / sigma_c)| / (|block| |h0 / sigma_c|), and for the
+observation rows of the free gauge sum_i h_i against rank J = dim n_cams + 3 n_lms - nq.
 usage: bench_covariance.py [shape] [lambda] [reps]"""
 import os
 import sys
@@ -70,6 +73,16 @@ def main():
                   f"camera call {ms_lm / ms:.2f}, to {solver} {ms_lm / ms_solve:.2f}; blocks bitwise symmetric: "
                   f"{np.array_equal(blocks, blocks.transpose(0, 2, 1))}; eigenvalue {1 if step == 1 else 2} / largest, worst landmark: "
                   f"{(ev[:, 0 if step == 1 else 1] / ev[:, -1]).min():.2e}; device MiB {mib_cam} -> {ctx.device_bytes() >> 20}", flush=True)
+            mib_lm = ctx.device_bytes() >> 20
+            (rows, rc), ms_obs = timed(lambda: ctx.observation_covariance(step=step, lam=lm, gauge=gauge))
+            assert rc == 0
+            line = (f"step {step} observation covariance, all {rows.shape[0]} observations, {name} (lambda {lm:g}): {ms_obs:.1f} ms per call, "
+                    f"ratio to the landmark call {ms_obs / ms_lm:.2f}, to {solver} {ms_obs / ms_solve:.2f}; leverage in "
+                    f"[{rows[:, 0].min():.3g}, {rows[:, 0].max():.3g}] (d = {4 if step == 1 else 2})")
+            if gauge == capi.COV_FREE_GAUGE:
+                rank = dim * p.n_cams + 3 * p.n_lms - (12 if step == 1 else 15)
+                line += f"; sum h = {np.sum(rows[:, 0].astype(np.longdouble)):.6f}, rank J = {rank}"
+            print(line + f"; finite c_*: {bool(np.all(np.isfinite(rows[:, 1:])))}; device MiB {mib_lm} -> {ctx.device_bytes() >> 20}", flush=True)
 
     # step 1 in the units of the normalised observations (the first two rows of every P divided by 500)
     cams1 = p.cams.copy()
