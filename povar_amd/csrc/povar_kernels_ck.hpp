@@ -84,6 +84,8 @@ __device__ inline void ck_group_barrier(int* cnt, int& gen, int group_waves, int
 // lane metadata word: rank | first << 16 | last << 22 (negative: empty lane); seg comes out as first | last << 8
 __host__ __device__ inline int ck_rank(int x) { return x < 0 ? -1 : (x & 0xffff); }
 __host__ __device__ inline int ck_seg(int x) { return ((x >> 16) & 63) | (((x >> 22) & 63) << 8); }
+// ... its rank as the index of a record gather: an empty lane gathers record 0 (and adds nothing: ck_flush_tile)
+__host__ __device__ inline int ck_word_rank0(int x) { return x < 0 ? 0 : (x & 0xffff); }
 
 }  // namespace povar
 #include "povar_kernels_ck_parts.hpp"  // what the kernels of the family share: slot word, row walk, row stream
@@ -404,6 +406,14 @@ __global__ __launch_bounds__(NW * 64) void e0_ck(Dp d, CkP k, double* part_out) 
       }
     }
   };
+  // h~ has arrived: stated where it costs nothing -- at the end of a batch's way back, a whole pass after the request, and on
+  // the path that requests nothing behind it.  With the ranks carried as raw words no decode waits for the next batch's first
+  // requests any more, and h~ is requested right behind them: left to the first use in the LDS set-up at the head of the batch
+  // loop, the wait came out as s_waitcnt vmcnt(0) there -- every batch's first barrier behind its first tile's gathers and rows.
+  auto wait_h = [&]() {
+#pragma unroll
+    for (int q = 0; q < HM; ++q) asm volatile("" : "+v"(hn[q][0]), "+v"(hn[q][1]), "+v"(hn[q][2]));
+  };
   // The tile ranges of the workgroup's batches: from LDS after the first batch (sixteen spare ints behind the accumulators),
   // and the next batch's first requests are issued BEHIND the barrier that ends the way forward: every scalar load -- each
   // workgroup's first touch of its bt_off entries is a miss all the way -- counts against the lgkmcnt(0) in front of a
@@ -420,7 +430,15 @@ __global__ __launch_bounds__(NW * 64) void e0_ck(Dp d, CkP k, double* part_out) 
   // The next batch's first tile (tile_of(tb0, 0)): its tile range, the camera ranks of the wavefront's first and (EARLY) second
   // tile and (EARLY) the first tile's header, requested with hn.  The header comes through a VECTOR load (a wave-uniform address; made scalar by
   // readfirstlane where it is used): a scalar load would count against the lgkmcnt(0) of the barriers in front of its use.
-  int tb0_next = 0, tb1_next = 0, rank_next = 0, rank_next2 = 0;
+  //
+  // Lane metadata crosses the barriers as the RAW word it was loaded as (meta_next / meta_next2 here, me / mp / mpp on the way
+  // back) and is decoded -- ck_rank, ck_seg, the sign of the accumulator word -- where rank, run and slot are first read: a
+  // decode at the load is a vector instruction on the loaded register, i.e. an s_waitcnt right behind the request, and the
+  // counters retire in issue order: the wavefront then waits there for everything it requested before the word, too
+  // (profiles/e0_ck_meta_words_isa.txt).  The second tile's word is loaded unconditionally, from the first tile's address
+  // where there is no second tile (a scalar select of the address; the word is then never read): a load under the condition
+  // came out as a v_cndmask on the loaded register.
+  int tb0_next = 0, tb1_next = 0, meta_next = 0, meta_next2 = 0;
   ck_u4 hdr_next = {0, 0, 0, 0};
   auto request_first_meta = [&](int b, int lane, bool ranks) {
     tb0_next = tb1_next = 0;
@@ -429,16 +447,16 @@ __global__ __launch_bounds__(NW * 64) void e0_ck(Dp d, CkP k, double* part_out) 
       tb1_next = bt_of(b + 1, b == grp);
     }
     if (!ranks) return;  // (the first batch of an EARLY instantiation: its ranks and header came from CkP::first_meta / first_hdr)
-    rank_next = rank_next2 = 0;
+    meta_next = meta_next2 = 0;
     hdr_next = ck_u4{0, 0, 0, 0};
     if (b < k.nb) {
       const int tf = tile_of(tb0_next, 0), tf2 = tile_of(tb0_next, 1);
-      if (tf < tb1_next && !EARLY) rank_next = ck_rank(k.lane_meta[(size_t)tf * WAVE + lane].x);
+      if (tf < tb1_next && !EARLY) meta_next = k.lane_meta[(size_t)tf * WAVE + lane].x;
       if (tf < tb1_next && EARLY) {
         const __amdgpu_buffer_rsrc_t TR = __builtin_amdgcn_make_buffer_rsrc(const_cast<int4*>(k.tile), 0, 0x7ffffff0, 0x00020000);
         hdr_next = __builtin_amdgcn_raw_buffer_load_b128(TR, 0u, (unsigned)tf * 16u, 0);
-        rank_next = ck_rank(k.lane_meta[(size_t)tf * WAVE + lane].x);
-        if (tf2 < tb1_next) rank_next2 = ck_rank(k.lane_meta[(size_t)tf2 * WAVE + lane].x);
+        meta_next = k.lane_meta[(size_t)tf * WAVE + lane].x;
+        meta_next2 = k.lane_meta[(size_t)(tf2 < tb1_next ? tf2 : tf) * WAVE + lane].x;
       }
     }
   };
@@ -454,7 +472,7 @@ __global__ __launch_bounds__(NW * 64) void e0_ck(Dp d, CkP k, double* part_out) 
   int row0 = 0, h = 0, fl = 0, li0 = 0;
   auto request_first_tile = [&](int lane, bool have) {
     const int tf = tile_of(tb0_next, 0);
-    const int rk = rank_next < 0 ? 0 : rank_next;
+    const int rk = ck_word_rank0(meta_next);
     if (have && EARLY) {
       row0 = __builtin_amdgcn_readfirstlane((int)hdr_next.x);
       h = __builtin_amdgcn_readfirstlane((int)hdr_next.y);
@@ -466,11 +484,12 @@ __global__ __launch_bounds__(NW * 64) void e0_ck(Dp d, CkP k, double* part_out) 
     } else if (have) {  // (the order of the batch head: Z last, the youngest request)
       const int tf2 = tile_of(tb0_next, 1);
       row0 = tiles[4 * tf]; h = tiles[4 * tf + 1]; fl = tiles[4 * tf + 2]; li0 = tiles[4 * tf + 3];
-      if (tf2 < tb1_next) rank_next2 = ck_rank(k.lane_meta[(size_t)tf2 * WAVE + lane].x);
+      meta_next2 = k.lane_meta[(size_t)(tf2 < tb1_next ? tf2 : tf) * WAVE + lane].x;
       ck_load_p<ROBUST>(d, rk, P3);
       st.template start<1>(R, row0, li0, h, lane);
       ck_load_z_img(d, rk, zz);
-    } else {  // (every value defined on this path too: see the batch loop)
+    } else {  // (every value defined on this path too: see the batch loop; no request behind h~ on it: see wait_h)
+      wait_h();
 #pragma unroll
       for (int e = 0; e < 12; ++e) zz[e] = P3[e] = 0;
       st.clear();
@@ -490,9 +509,13 @@ __global__ __launch_bounds__(NW * 64) void e0_ck(Dp d, CkP k, double* part_out) 
     const __amdgpu_buffer_rsrc_t HR = __builtin_amdgcn_make_buffer_rsrc(const_cast<int4*>(k.first_hdr), 0, 0x7ffffff0, 0x00020000);
     hdr_next = __builtin_amdgcn_raw_buffer_load_b128(HR, 0u, fs * 16u, 0);
     request_h(grp, lane0);
+    // (the table packs two ranks, 0xffff: none; as metadata words: the rank, or negative.  The rank is the gathers' address: the
+    //  decode HERE is a wait for fm and, the counters retiring in order, for h~ in front of the first gather.  It stays: with h~
+    //  requested behind that wait the batch's first barrier opened 0.9 k cycles later -- h~ comes from HBM, and the LDS set-up
+    //  then waited for the gathers in front of that barrier too (profiles/e0_ck_meta_words_bench_ab.txt, "entry"))
     const int r1 = fm.x & 0xffff, r2 = (fm.x >> 16) & 0xffff;
-    rank_next = r1 == 0xffff ? -1 : r1;
-    rank_next2 = r2 == 0xffff ? -1 : r2;
+    meta_next = r1 == 0xffff ? -1 : r1;
+    meta_next2 = r2 == 0xffff ? -1 : r2;
     request_first_tile(lane0, __builtin_amdgcn_readfirstlane(fm.y) >= 0);
     request_first_meta(grp, lane0, false);
   } else {
@@ -514,7 +537,7 @@ __global__ __launch_bounds__(NW * 64) void e0_ck(Dp d, CkP k, double* part_out) 
     const int tb0 = tb0_next, tb1 = tb1_next;
     int q_t = 0;  // round of the tile walk
     int t = tile_of(tb0, 0);
-    int rank = rank_next;
+    int mw = meta_next;  // the lane's metadata word in tile t (raw: see request_first_meta)
     // (Order of the requests: the rows of a tile are requested after everything else of its phase.  The wait counters
     // retire in issue order; with younger loads pending behind the rows, the compiler's merge of the loop-entry and
     // back-edge states at the head of the row loop came out as s_waitcnt vmcnt(0): every row waited for the row
@@ -526,7 +549,7 @@ __global__ __launch_bounds__(NW * 64) void e0_ck(Dp d, CkP k, double* part_out) 
     // four wavefronts with a second tile the tail of every pass.
     int tn = tile_of(tb0, 1);
     if (!EARLY) request_first_tile(lane, t < tb1);
-    int rank_n = rank_next2, rank_nn = 0;
+    int mw_n = meta_next2, mw_nn = 0;
     double zn[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, Pn[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     CkStream<SD, ROBUST, PK> stn;
     stn.clear();
@@ -561,8 +584,8 @@ __global__ __launch_bounds__(NW * 64) void e0_ck(Dp d, CkP k, double* part_out) 
       if (DB && tn < tb1) {
         const int tnn = tile_of(tb0, q_t + 2);
         row0n = tiles[4 * tn]; hnx = tiles[4 * tn + 1]; fln = tiles[4 * tn + 2]; li0n = tiles[4 * tn + 3];
-        if (tnn < tb1) rank_nn = ck_rank(k.lane_meta[(size_t)tnn * WAVE + lane].x);
-        const int rk = rank_n < 0 ? 0 : rank_n;
+        if (tnn < tb1) mw_nn = k.lane_meta[(size_t)tnn * WAVE + lane].x;
+        const int rk = ck_word_rank0(mw_n);
         ck_load_z_img(d, rk, zn);
         ck_load_p<ROBUST>(d, rk, Pn);
         stn.template start<1>(R, row0n, li0n, hnx, lane);
@@ -577,10 +600,10 @@ __global__ __launch_bounds__(NW * 64) void e0_ck(Dp d, CkP k, double* part_out) 
     // ---- forward
     while (t < tb1) {
       ck_forward_rows<SD, ROBUST, PK>(d, R, st, row0, li0, h, lane, zz, P3, lh, lu, S);
-      if (tn >= tb1) break;  // (t, q_t, rank, P3 stay on the last tile: the way back starts there)
+      if (tn >= tb1) break;  // (t, q_t, P3 stay on the last tile: the way back starts there)
       t = tn;
       ++q_t;
-      rank = rank_n;
+      mw = mw_n;
       tn = tile_of(tb0, q_t + 1);
       if (DB) {
 #pragma unroll
@@ -589,12 +612,12 @@ __global__ __launch_bounds__(NW * 64) void e0_ck(Dp d, CkP k, double* part_out) 
         for (int e = 0; e < (ROBUST ? 12 : 9); ++e) P3[e] = Pn[e];
         st = stn;
         row0 = row0n; h = hnx; fl = fln; li0 = li0n;
-        rank_n = rank_nn;
+        mw_n = mw_nn;
         request_next_fwd();
       } else {
         row0 = tiles[4 * t]; h = tiles[4 * t + 1]; fl = tiles[4 * t + 2]; li0 = tiles[4 * t + 3];
-        if (tn < tb1) rank_n = ck_rank(k.lane_meta[(size_t)tn * WAVE + lane].x);
-        const int rk = rank < 0 ? 0 : rank;
+        if (tn < tb1) mw_n = k.lane_meta[(size_t)tn * WAVE + lane].x;
+        const int rk = ck_word_rank0(mw);
         ck_load_z_img(d, rk, zz);
         ck_load_p<ROBUST>(d, rk, P3);
         st.template start<1>(R, row0, li0, h, lane);
@@ -603,9 +626,10 @@ __global__ __launch_bounds__(NW * 64) void e0_ck(Dp d, CkP k, double* part_out) 
     // ---- the way back starts before the barriers in front of it: accumulator metadata and last rows of the tile the
     // wavefront has just left (its P3 is in registers), G of its landmark slots, and the next batch's first requests
     asm volatile("" : "+v"(lane));  // (the two passes share no per-lane address register)
-    int acc_slot = 0, seg = 0;
     int tp = q_t > 0 ? tile_of(tb0, q_t - 1) : tb1;
-    int rank_p = 0, acc_p = 0, seg_p = 0, rank_pp = 0, acc_pp = 0, seg_pp = 0;
+    // the lane's metadata in tile t, in tp and (DB) in the one before: the raw words -- nothing in front of the next barrier reads
+    // them, so that a wavefront arrives there without having waited for G, which is older than they are
+    int2 me = make_int2(mw, 0), mp = make_int2(0, 0), mpp = make_int2(0, 0);
     double G[HM][6];
 #pragma unroll
     for (int q = 0; q < HM; ++q) {
@@ -619,18 +643,18 @@ __global__ __launch_bounds__(NW * 64) void e0_ck(Dp d, CkP k, double* part_out) 
       }
     }
     if (t < tb1) {
-      const int2 me = k.lane_meta[(size_t)t * WAVE + lane];
-      seg = ck_seg(me.x);
-      acc_slot = me.y;  // (fl: the tile's header word came with row0 / h / li0 -- a scalar load HERE sits in front of the barrier's
-      if (tp < tb1) {   //  lgkmcnt(0): 2.6 k cycles per batch in the stamps of round 6, profiles/r06_e0_ck_phase_stamps.txt)
-        const int2 mp = k.lane_meta[(size_t)tp * WAVE + lane];
-        rank_p = ck_rank(mp.x);
-        seg_p = ck_seg(mp.x);
-        acc_p = mp.y;
-      }
+      // (fl: the tile's header word came with row0 / h / li0 -- a scalar load HERE sits in front of the barrier's lgkmcnt(0):
+      //  2.6 k cycles per batch in the stamps of round 6, profiles/r06_e0_ck_phase_stamps.txt)
+      me = k.lane_meta[(size_t)t * WAVE + lane];
+      if (tp < tb1) mp = k.lane_meta[(size_t)tp * WAVE + lane];
       st.template start<-1>(R, row0, li0, h, lane);
     }
     group_barrier();
+    // (G is waited for HERE, in front of the next batch's requests: it was requested before the barrier and is older than
+    //  everything in flight; behind them, the count of its wait is the merge of the paths with and without a next batch and
+    //  without h~ -- a wait for the requests just issued, one exposed round trip per batch)
+#pragma unroll
+    for (int q = 0; q < HM; ++q) asm volatile("" : "+v"(G[q][0]), "+v"(G[q][1]), "+v"(G[q][2]), "+v"(G[q][3]), "+v"(G[q][4]), "+v"(G[q][5]));
     request_first_meta(b + NG, lane, true);  // the next batch is started from here: its coordinates and first metadata are in
     request_h(b + NG, lane);           // flight during the way back (behind the barrier: see lbt)
     // ---- g = G u per landmark slot (over u)
@@ -659,13 +683,8 @@ __global__ __launch_bounds__(NW * 64) void e0_ck(Dp d, CkP k, double* part_out) 
       if (DB && tp < tb1) {
         const int tpp = q_t > 1 ? tile_of(tb0, q_t - 2) : tb1;
         row0n = tiles[4 * tp]; hnx = tiles[4 * tp + 1]; fln = tiles[4 * tp + 2]; li0n = tiles[4 * tp + 3];
-        if (tpp < tb1) {
-          const int2 mp = k.lane_meta[(size_t)tpp * WAVE + lane];
-          rank_pp = ck_rank(mp.x);
-          seg_pp = ck_seg(mp.x);
-          acc_pp = mp.y;
-        }
-        ck_load_p<ROBUST>(d, rank_p < 0 ? 0 : rank_p, Pn);
+        if (tpp < tb1) mpp = k.lane_meta[(size_t)tpp * WAVE + lane];
+        ck_load_p<ROBUST>(d, ck_word_rank0(mp.x), Pn);  // (behind the barrier that ends the way forward: mp is decoded here)
         stn.template start<-1>(R, row0n, li0n, hnx, lane);
       }
     };
@@ -680,34 +699,32 @@ __global__ __launch_bounds__(NW * 64) void e0_ck(Dp d, CkP k, double* part_out) 
       //  cold loop beside their row loops -- ten spilled per lane at batch level, 30 MB of scratch traffic per launch -- and gain
       //  nothing from the cold view; povar_create.hip keeps the records for them)
       const bool cold_q = !ROBUST && k.cpos != nullptr && (fl & 2) != 0;
-      if (cold_q) ck_backward_rows_cold<ROBUST, PK>(d, k, R, row0, li0, h, lane, P3, lh, lu, rank >= 0 && acc_slot < 0, y);
+      if (cold_q) ck_backward_rows_cold<ROBUST, PK>(d, k, R, row0, li0, h, lane, P3, lh, lu, me.x >= 0 && me.y < 0, y);
       else ck_backward_rows<SD, ROBUST, PK>(d, R, st, row0, li0, h, lane, P3, lh, lu, S, y);
-      ck_flush_tile(y, fl, lane, rank, acc_slot, seg, acc, n_acc, cold_q ? nullptr : part_out);
+      ck_flush_tile(y, fl, lane, ck_rank(me.x), me.y, ck_seg(me.x), acc, n_acc, cold_q ? nullptr : part_out);  // (me: decoded here)
       if (tp >= tb1) break;
       t = tp;
       --q_t;
-      rank = rank_p; acc_slot = acc_p; seg = seg_p;
+      me = mp;
       tp = q_t > 0 ? tile_of(tb0, q_t - 1) : tb1;
       if (DB) {
 #pragma unroll
         for (int e = 0; e < (ROBUST ? 12 : 9); ++e) P3[e] = Pn[e];
         st = stn;
         row0 = row0n; h = hnx; fl = fln; li0 = li0n;
-        rank_p = rank_pp; acc_p = acc_pp; seg_p = seg_pp;
+        mp = mpp;
         request_next_bwd();
       } else {
         row0 = tiles[4 * t]; h = tiles[4 * t + 1]; fl = tiles[4 * t + 2]; li0 = tiles[4 * t + 3];
-        if (tp < tb1) {
-          const int2 mp = k.lane_meta[(size_t)tp * WAVE + lane];
-          rank_p = ck_rank(mp.x);
-          seg_p = ck_seg(mp.x);
-          acc_p = mp.y;
-        }
-        ck_load_p<ROBUST>(d, rank < 0 ? 0 : rank, P3);
+        if (tp < tb1) mp = k.lane_meta[(size_t)tp * WAVE + lane];
+        ck_load_p<ROBUST>(d, ck_word_rank0(me.x), P3);
         st.template start<-1>(R, row0, li0, h, lane);
       }
     }
-    if (EARLY) request_first_tile(lane, tile_of(tb0_next, 0) < tb1_next);
+    if (EARLY) {
+      wait_h();
+      request_first_tile(lane, tile_of(tb0_next, 0) < tb1_next);
+    }
     group_barrier();  // the next batch overwrites h~ and u; after the last one: the accumulators are complete
   }
   if (NG > 1) ck_barrier();  // every group is done: the accumulators are complete

@@ -200,12 +200,14 @@ __global__ __launch_bounds__(NW * 64) void e0_ck_h(Dp d, CkP k, double* part_out
   auto bt_of = [&](int i, bool first) {
     return (bt_lds && !first) ? __builtin_amdgcn_readfirstlane(lbt[i]) : bt[blockIdx.x * k.nb + i];
   };
-  int rank_next = 0;
+  // (lane metadata crosses the barriers as the raw words of CkP::lane_meta and is decoded where rank, run and slot are first
+  //  read, as in e0_ck: a decode at the load is a wait right behind the request -- and for everything requested before it)
+  int meta_next = 0;
   auto request_first_meta = [&](int b, int lane) {
-    rank_next = 0;
+    meta_next = 0;
     if (b < k.nb) {
       const int tb0 = bt_of(b, b == 0), tb1 = bt_of(b + 1, b == 0);
-      if (tb0 + wave < tb1) rank_next = CkLaneMeta::rank_of(k, tb0 + wave, lane);
+      if (tb0 + wave < tb1) meta_next = k.lane_meta[(size_t)(tb0 + wave) * WAVE + lane].x;
     }
   };
   request_first_meta(0, lane0);
@@ -217,7 +219,7 @@ __global__ __launch_bounds__(NW * 64) void e0_ck_h(Dp d, CkP k, double* part_out
     const int tb0 = bt_of(b, b == 0), tb1 = bt_of(b + 1, b == 0);
     int q_t = 0;
     int t = tile_of(tb0, 0);
-    int rank = rank_next;
+    int mw = meta_next;  // the lane's metadata word in tile t
     double4 zz[3] = {make_double4(0, 0, 0, 0), make_double4(0, 0, 0, 0), make_double4(0, 0, 0, 0)};
     Cam P;
     P.r0 = P.r1 = P.r2 = make_double4(0, 0, 0, 0);
@@ -225,12 +227,12 @@ __global__ __launch_bounds__(NW * 64) void e0_ck_h(Dp d, CkP k, double* part_out
     st.clear();
     CkTile tl = {0, 0, 0, 0};
     int tn = tile_of(tb0, 1);
-    int rank_n = 0;
+    int mw_n = 0;
     // ---- the way forward starts: record and first rows of the first tile
     if (t < tb1) {
       tl = CkTile::load(tiles, t);  // (the whole header at once: below)
-      if (tn < tb1) rank_n = CkLaneMeta::rank_of(k, tn, lane);
-      ckh_load_rec(d, rank < 0 ? 0 : rank, zz, P);
+      ckh_load_rec(d, ck_word_rank0(mw), zz, P);  // (mw is decoded here: the next tile's word is requested behind the gather,
+      if (tn < tb1) mw_n = k.lane_meta[(size_t)tn * WAVE + lane].x;  //  not in front of the wait for this one)
       st.template start<1>(R, tl.row0, tl.li0, tl.h, lane);
     }
     // ---- X of the batch into LDS (requested a phase ago), U4 = 0
@@ -259,20 +261,20 @@ __global__ __launch_bounds__(NW * 64) void e0_ck_h(Dp d, CkP k, double* part_out
     // ---- forward
     while (t < tb1) {
       ckh_forward_rows<SD, ROBUST, CKH_STRIDE>(R, st, tl.row0, tl.li0, tl.h, lane, P, zz, lx, lu);
-      if (tn >= tb1) break;  // (t, q_t, rank, P stay on the last tile: the way back starts there)
+      if (tn >= tb1) break;  // (t, q_t, P stay on the last tile: the way back starts there)
       t = tn;
       ++q_t;
-      rank = rank_n;
+      mw = mw_n;
       tn = tile_of(tb0, q_t + 1);
       tl = CkTile::load(tiles, t);
-      if (tn < tb1) rank_n = CkLaneMeta::rank_of(k, tn, lane);
-      ckh_load_rec(d, rank < 0 ? 0 : rank, zz, P);
+      if (tn < tb1) mw_n = k.lane_meta[(size_t)tn * WAVE + lane].x;
+      ckh_load_rec(d, ck_word_rank0(mw), zz, P);
       st.template start<1>(R, tl.row0, tl.li0, tl.h, lane);
     }
     // ---- the way back starts before the barriers in front of it
     asm volatile("" : "+v"(lane));
     int tp = q_t > 0 ? tile_of(tb0, q_t - 1) : tb1;
-    CkLaneMeta me = {rank, 0, 0}, mp = {0, 0, 0};  // the lane in tile t and in tp
+    int2 me = make_int2(mw, 0), mp = make_int2(0, 0);  // the lane in tile t and in tp: raw, nothing in front of the barrier reads them
     double rec[HM][10];  // s (4) and Hll^-1 (6) of the wavefront's landmark slots
 #pragma unroll
     for (int q = 0; q < HM; ++q) {
@@ -288,11 +290,17 @@ __global__ __launch_bounds__(NW * 64) void e0_ck_h(Dp d, CkP k, double* part_out
     if (t < tb1) {
       // (tl.fl came with the tile's header: a scalar load HERE is a miss in front of the barrier's lgkmcnt(0) --
       //  ~ 2.6 k cycles per batch in e0_ck's stamps, profiles/r06_e0_ck_phase_stamps.txt)
-      me = CkLaneMeta::load(k, t, lane);
-      if (tp < tb1) mp = CkLaneMeta::load(k, tp, lane);
+      me = k.lane_meta[(size_t)t * WAVE + lane];
+      if (tp < tb1) mp = k.lane_meta[(size_t)tp * WAVE + lane];
       st.template start<-1>(R, tl.row0, tl.li0, tl.h, lane);
     }
     ck_barrier();
+    // (the landmark records are waited for HERE, in front of the next batch's requests: see e0_ck)
+#pragma unroll
+    for (int q = 0; q < HM; ++q) {
+#pragma unroll
+      for (int e = 0; e < 10; ++e) asm volatile("" : "+v"(rec[q][e]));
+    }
     request_first_meta(b + 1, lane);
     request_x(b + 1, lane);
     // ---- per landmark slot: U4 -> G4
@@ -315,15 +323,15 @@ __global__ __launch_bounds__(NW * 64) void e0_ck_h(Dp d, CkP k, double* part_out
 #pragma unroll
       for (int m = 0; m < 12; ++m) y[m] = 0;
       ckh_backward_rows<SD, ROBUST, CKH_STRIDE>(R, st, tl.row0, tl.li0, tl.h, lane, P, lx, lu, y);
-      ck_flush_tile(y, tl.fl, lane, me.rank, me.acc, me.seg, acc, n_acc, part_out);
+      ck_flush_tile(y, tl.fl, lane, ck_rank(me.x), me.y, ck_seg(me.x), acc, n_acc, part_out);  // (me: decoded here)
       if (tp >= tb1) break;
       t = tp;
       --q_t;
       me = mp;
       tp = q_t > 0 ? tile_of(tb0, q_t - 1) : tb1;
       tl = CkTile::load(tiles, t);
-      if (tp < tb1) mp = CkLaneMeta::load(k, tp, lane);
-      ckh_load_cam(d, me.rank < 0 ? 0 : me.rank, P);
+      if (tp < tb1) mp = k.lane_meta[(size_t)tp * WAVE + lane];
+      ckh_load_cam(d, ck_word_rank0(me.x), P);
       st.template start<-1>(R, tl.row0, tl.li0, tl.h, lane);
     }
     ck_barrier();  // the next batch overwrites X and U4; after the last one: the accumulators are complete

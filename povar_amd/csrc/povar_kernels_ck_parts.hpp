@@ -2,8 +2,9 @@
 // e0_ck_f32 (.._ck_f32.hpp), e0_ck_det / e0_ck_h_det (.._ck_det.hpp).  Pieces, not a walker: every kernel keeps its batch loop
 // and phases, the order of its requests, its `asm volatile("" : "+v"(lane))` fences and its arithmetic.  Here: the slot word
 // (ck_slot), the row walk (ck_walk_rows), the row stream (CkRowStream + payloads; aliases CkStream, CkStreamH, Ck32Stream),
-// a tile's header and a lane's metadata (CkTile, CkLaneMeta: e0_ck_h and e0_ck_f32 -- in e0_ck and the det pair they moved
-// s_waitcnt counts, registers and e0_ck's s_waitcnt order, profiles/ck_parts_isa.txt: those keep their own text).
+// a tile's header (CkTile: e0_ck_h and e0_ck_f32 -- in e0_ck and the det pair it moved s_waitcnt counts, registers and
+// e0_ck's s_waitcnt order, profiles/ck_parts_isa.txt: those keep their own text) and a lane's DECODED metadata (CkLaneMeta:
+// e0_ck_f32; e0_ck and e0_ck_h carry the raw words across their barriers and decode at first use, povar_kernels_ck.hpp).
 // Included by povar_kernels_ck.hpp behind WAVE, CK_NONE, CkP, ck_rank / ck_seg and ck_unpack_uv, never on its own.  Every
 // function is __forceinline__ and every member a value: tile headers stay in SGPRs, the row buffers in VGPRs.
 //

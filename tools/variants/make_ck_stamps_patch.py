@@ -120,17 +120,16 @@ def main():
     s = sub(s, "      ck_forward_rows<SD, ROBUST, PK>(d, R, st, row0, li0, h, lane, zz, P3, lh, lu, S);\n",
             "      ck_forward_rows<SD, ROBUST, PK>(d, R, st, row0, li0, h, lane, zz, P3, lh, lu, S);\n      if (b < NG) CK_STAMP(20 + 2 * q_t);\n")
     s = sub(s, "    // ---- the way back starts before the barriers in front of it:", "    CK_STAMP(8 * (b / NG) + 4);\n    // ---- the way back starts before the barriers in front of it:")
-    s = sub(s, "      st.template start<-1>(R, row0, li0, h, lane);\n    }\n    group_barrier();\n    request_first_meta(b + NG, lane, true);",
+    s = sub(s, "      st.template start<-1>(R, row0, li0, h, lane);\n    }\n    group_barrier();\n    // (G is waited for HERE,",
             "      CK_STAMP(24 + 4 * (b / NG));      // G + metadata of the way back requested\n"
             "      st.template start<-1>(R, row0, li0, h, lane);\n    }\n"
             "    CK_STAMP(25 + 4 * (b / NG));        // ... and its first rows\n"
             "    asm volatile(\"s_waitcnt lgkmcnt(0)\" ::: \"memory\");\n"
             "    CK_STAMP(26 + 4 * (b / NG));        // LDS atomics + scalar loads drained (what the barrier's lgkmcnt(0) waits for)\n"
-            "    group_barrier();\n    CK_STAMP(8 * (b / NG) + 5);\n    request_first_meta(b + NG, lane, true);")
+            "    group_barrier();\n    CK_STAMP(8 * (b / NG) + 5);\n    // (G is waited for HERE,")
     s = sub(s, "    request_next_bwd();\n    group_barrier();\n", "    request_next_bwd();\n    group_barrier();\n    CK_STAMP(8 * (b / NG) + 6);\n")
-    s = sub(s, "    if (EARLY) request_first_tile(lane, tile_of(tb0_next, 0) < tb1_next);\n    group_barrier();  // the next batch overwrites h~ and u; after the last one: the accumulators are complete\n",
-            "    CK_STAMP(8 * (b / NG) + 7);\n    if (EARLY) request_first_tile(lane, tile_of(tb0_next, 0) < tb1_next);\n"
-            "    group_barrier();  // the next batch overwrites h~ and u; after the last one: the accumulators are complete\n")
+    s = sub(s, "    if (EARLY) {\n      wait_h();\n      request_first_tile(lane, tile_of(tb0_next, 0) < tb1_next);\n    }\n",
+            "    CK_STAMP(8 * (b / NG) + 7);\n    if (EARLY) {\n      wait_h();\n      request_first_tile(lane, tile_of(tb0_next, 0) < tb1_next);\n    }\n")
     s = sub(s, "  // ---- accumulators -> this workgroup's partial records (camera-major in part_out)\n  ck_store_accumulators<NW>(ck_part_rsrc(part_out)",
             "  CK_STAMP(8 * (k.nb / NG));\n  // ---- accumulators -> this workgroup's partial records (camera-major in part_out)\n  ck_store_accumulators<NW>(ck_part_rsrc(part_out)")
     s = sub(s, "  if (d.p2p_epoch && blockIdx.x == 0 && threadIdx.x == 0) *d.p2p_epoch += 1;  // one tick per term (as e0_lpl)",
