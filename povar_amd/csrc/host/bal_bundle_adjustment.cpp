@@ -126,72 +126,57 @@ void check_options(const SolverOptions& o) {
   }
 }
 
-// --camera-covariance-path: n_cams on the first line, then one line of 144 numbers (12 x 12 row-major) per camera
-void write_camera_covariance(Linearizor& linearizor, const BalProblem& bal_problem, const SolverOptions& so, bool step2) {
-  Linearizor::VecX cov;
-  const int rc = linearizor.camera_covariance(step2, so.alpha, cov);
-  if (rc < 0) {
-    std::fprintf(stderr, "FATAL: this linearizor does not serve --camera-covariance-path\n");
-    std::abort();
-  }
-  if (rc != 0) std::printf("\t[WARN] camera covariance: the reduced system is singular beyond its gauge, the blocks are NaN\n");
-  std::FILE* f = std::fopen(so.camera_covariance_path.c_str(), "w");
+// The three covariance options (not in the reference) share how a file is opened, how blocks are written and how a
+// linearizor's status is reported.
+std::FILE* open_for_writing(const std::string& path) {
+  std::FILE* f = std::fopen(path.c_str(), "w");
   if (!f) {
-    std::fprintf(stderr, "FATAL: cannot write %s\n", so.camera_covariance_path.c_str());
+    std::fprintf(stderr, "FATAL: cannot write %s\n", path.c_str());
     std::abort();
   }
-  const int n_cams = bal_problem.num_cameras();
-  std::fprintf(f, "%d\n", n_cams);
-  for (int c = 0; c < n_cams; ++c)
-    for (int k = 0; k < 144; ++k) std::fprintf(f, "%.17g%c", cov[144 * (size_t)c + k], k == 143 ? '\n' : ' ');
+  return f;
+}
+
+// count on the first line, then one line of `stride` numbers per item
+void write_blocks(const std::string& path, int count, int stride, const Linearizor::VecX& v) {
+  std::FILE* f = open_for_writing(path);
+  std::fprintf(f, "%d\n", count);
+  for (int i = 0; i < count; ++i)
+    for (int k = 0; k < stride; ++k) std::fprintf(f, "%.17g%c", v[(size_t)stride * i + k], k == stride - 1 ? '\n' : ' ');
   std::fclose(f);
 }
 
+// rc of Linearizor::<what>_covariance: below zero the linearizor does not serve the option, above zero its `items` are NaN
+void report_covariance_status(int rc, const char* what, const char* items) {
+  if (rc < 0) {
+    std::fprintf(stderr, "FATAL: this linearizor does not serve --%s-covariance-path\n", what);
+    std::abort();
+  }
+  if (rc != 0) std::printf("\t[WARN] %s covariance: the reduced system is singular beyond its gauge, the %s are NaN\n", what, items);
+}
+
+// --camera-covariance-path: n_cams on the first line, then one line of 144 numbers (12 x 12 row-major) per camera
 // --landmark-covariance-path: n_lms on the first line, then one line of 9 (step 1) or 16 (step 2) numbers per landmark in
 // file order; together with --camera-covariance-path one call serves both files
 void write_covariances(Linearizor& linearizor, const BalProblem& bal_problem, const SolverOptions& so, bool step2) {
+  Linearizor::VecX lm_cov, cam_cov;
   if (so.landmark_covariance_path.empty()) {
-    write_camera_covariance(linearizor, bal_problem, so, step2);
+    report_covariance_status(linearizor.camera_covariance(step2, so.alpha, cam_cov), "camera", "blocks");
+    write_blocks(so.camera_covariance_path, bal_problem.num_cameras(), 144, cam_cov);
     return;
   }
   const bool with_cameras = !so.camera_covariance_path.empty();
-  Linearizor::VecX lm_cov, cam_cov;
-  const int rc = linearizor.landmark_covariance(step2, so.alpha, lm_cov, with_cameras ? &cam_cov : nullptr);
-  if (rc < 0) {
-    std::fprintf(stderr, "FATAL: this linearizor does not serve --landmark-covariance-path\n");
-    std::abort();
-  }
-  if (rc != 0) std::printf("\t[WARN] landmark covariance: the reduced system is singular beyond its gauge, the blocks are NaN\n");
-  auto write = [](const std::string& path, int count, int stride, const Linearizor::VecX& v) {
-    std::FILE* f = std::fopen(path.c_str(), "w");
-    if (!f) {
-      std::fprintf(stderr, "FATAL: cannot write %s\n", path.c_str());
-      std::abort();
-    }
-    std::fprintf(f, "%d\n", count);
-    for (int i = 0; i < count; ++i)
-      for (int k = 0; k < stride; ++k) std::fprintf(f, "%.17g%c", v[(size_t)stride * i + k], k == stride - 1 ? '\n' : ' ');
-    std::fclose(f);
-  };
-  write(so.landmark_covariance_path, bal_problem.num_landmarks(), step2 ? 16 : 9, lm_cov);
-  if (with_cameras) write(so.camera_covariance_path, bal_problem.num_cameras(), 144, cam_cov);
+  report_covariance_status(linearizor.landmark_covariance(step2, so.alpha, lm_cov, with_cameras ? &cam_cov : nullptr), "landmark", "blocks");
+  write_blocks(so.landmark_covariance_path, bal_problem.num_landmarks(), step2 ? 16 : 9, lm_cov);
+  if (with_cameras) write_blocks(so.camera_covariance_path, bal_problem.num_cameras(), 144, cam_cov);
 }
 
 // --observation-covariance-path: n_obs on the first line, then one line per observation in file order: landmark, camera and
 // the row (h, c_uu, c_uv, c_vv) of povar_observation_covariance_pose / _joint; a call of its own
 void write_observation_covariance(Linearizor& linearizor, const BalProblem& bal_problem, const SolverOptions& so, bool step2) {
   Linearizor::VecX cov;
-  const int rc = linearizor.observation_covariance(step2, so.alpha, cov);
-  if (rc < 0) {
-    std::fprintf(stderr, "FATAL: this linearizor does not serve --observation-covariance-path\n");
-    std::abort();
-  }
-  if (rc != 0) std::printf("\t[WARN] observation covariance: the reduced system is singular beyond its gauge, the rows are NaN\n");
-  std::FILE* f = std::fopen(so.observation_covariance_path.c_str(), "w");
-  if (!f) {
-    std::fprintf(stderr, "FATAL: cannot write %s\n", so.observation_covariance_path.c_str());
-    std::abort();
-  }
+  report_covariance_status(linearizor.observation_covariance(step2, so.alpha, cov), "observation", "rows");
+  std::FILE* f = open_for_writing(so.observation_covariance_path);
   std::vector<int> lm_off, cam_idx;
   std::vector<double> obs;
   bal_problem.flatten(lm_off, cam_idx, obs);

@@ -115,20 +115,20 @@ class Linearizor {
   // Not in the reference: the free-gauge marginal covariance of every camera at the current state, camera coordinates,
   // 144 n_cams numbers (povar_camera_covariance_pose after linearize_pOSE(alpha), or povar_camera_covariance_joint after
   // linearize_projective_space_homogeneous).  Returns the library's status: 0, or POVAR_NUMERIC_FAILURE (1) with all-NaN blocks
-  // for a system that is singular beyond its gauge.  Linearizors other than the single-device HIP one do not serve it.
+  // for a system that is singular beyond its gauge.  Only the HIP linearizor on a single device serves it.
   virtual int camera_covariance(bool step2, double alpha, VecX& cov) {
     (void)step2; (void)alpha; (void)cov;
     return -1;
   }
   // Likewise for the landmarks (povar_landmark_covariance_pose / _joint, free gauge, landmark coordinates): lm_cov gets the
   // blocks in file order at stride 9 (step 1: 3 x 3) or 16 (step 2: 4 x 4); cam_cov, when given, the camera blocks of the
-  // same call (one factorisation and one inversion serve both).  The N-shard linearizor serves it without cam_cov.
+  // same call (one factorisation and one inversion serve both).  Sharded, the HIP linearizor serves it without cam_cov.
   virtual int landmark_covariance(bool step2, double alpha, VecX& lm_cov, VecX* cam_cov) {
     (void)step2; (void)alpha; (void)lm_cov; (void)cam_cov;
     return -1;
   }
   // Likewise for the observations (povar_observation_covariance_pose / _joint, free gauge): obs_cov gets 4 numbers per
-  // observation in file order (h, c_uu, c_uv, c_vv).  The N-shard linearizor serves it too.
+  // observation in file order (h, c_uu, c_uv, c_vv).  Sharded, the HIP linearizor serves it too.
   virtual int observation_covariance(bool step2, double alpha, VecX& obs_cov) {
     (void)step2; (void)alpha; (void)obs_cov;
     return -1;

@@ -91,7 +91,7 @@ def test_bal_gpus_n_matches_one_device(tmp_path, gpus):
 @pytest.mark.gpu
 @pytest.mark.parametrize("graph_comm", ["0", "1"])
 def test_bal_rccl_branch_of_the_shard_team_with_one_rank(tmp_path, graph_comm):
-    """The RCCL branch of LinearizorPowerVarprojHipMulti on the one GPU there is: POVAR_FORCE_MULTI=1
+    """The RCCL branch of the sharded LinearizorPowerVarprojHip on the one GPU there is: POVAR_FORCE_MULTI=1
     routes `bal --gpus 1` through the shard team -- ncclCommInitRank on the worker thread, every exchange step of the run
     an ncclAllReduce of one rank on the context's stream, with POVAR_GRAPH_COMM=1 inside the captured term loop -- against
     plain `bal`: identical accept / reject sequences and iteration counts, every cost to 1e-9."""

@@ -274,7 +274,7 @@ def test_bal_venice_known_answer(tmp_path):
     exp, std = chi2_floor(p.n_cams, p.n_lms, p.n_obs)
     assert abs(d["cost"][-1] - exp) <= 5 * std, (d["cost"][-1], exp, std)
     assert d["_static"]["solver"]["termination_type"] == "CONVERGENCE"
-    # the same run over TWO shard contexts of one process (`bal --gpus 2`: LinearizorPowerVarprojHipMulti, landmark shards of
+    # the same run over TWO shard contexts of one process (`bal --gpus 2`: the sharded LinearizorPowerVarprojHip, landmark shards of
     # 2.5 M observations each, one exchange per power-series term; on a one-GPU box through the in-process all-reduce): the
     # same iterations, every cost to 1e-9, the same floor
     log2 = str(tmp_path / "hip2.json")
