@@ -29,6 +29,7 @@
 
 #include "povar_kernels.hpp"
 #include "povar_kernels_joint.hpp"
+#include "povar_kernels_lpl.hpp"
 #include "povar_kernels_cam.hpp"
 #include "povar_kernels_sc.hpp"
 #include "povar_kernels_chol.hpp"

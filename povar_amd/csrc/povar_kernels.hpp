@@ -1228,185 +1228,21 @@ __device__ inline void lpl_read_p3(const double2* h, double* P3) {
 #define POVAR_LPL_HUBS 16
 #endif
 constexpr int LPL_HUBS = POVAR_LPL_HUBS;
-__host__ __device__ inline int lpl_hubs(int n_hot) { return n_hot < LPL_HUBS ? n_hot : LPL_HUBS; }
+__host__ __device__ constexpr int lpl_hubs(int n_hot) { return n_hot < LPL_HUBS ? n_hot : LPL_HUBS; }
 // cw >= 0 packs the LDS slot (low 16 bits) and, for a hub, the accumulator replica the host chose (bits 16-17)
 __host__ __device__ inline int lpl_cw_slot(int cw) { return cw & 0xffff; }
 __host__ __device__ inline int lpl_acc_slot(int cw, int hubs) {
   const int slot = cw & 0xffff;
   return slot < hubs ? 4 * slot + ((cw >> 16) & 3) : slot + 3 * hubs;
 }
-__host__ __device__ inline size_t lpl_lds_bytes(int n_hot) {
+__host__ __device__ constexpr size_t lpl_lds_bytes(int n_hot) {
   return (size_t)n_hot * HOT_REC * sizeof(double2) + (size_t)(n_hot + 3 * lpl_hubs(n_hot)) * 96 + 16;
 }
 // where a cold observation of row j, lane `lane` leaves its q in Dp::q4c (fl, nh: tile.w, tile.z; lpl_layout.hpp)
 __device__ inline int lpl_cold_q(int fl, int nh, int j, int lane) { return ((fl >> 4) + (j - nh)) * WAVE + lane; }
 
-}  // namespace povar
-#include "povar_kernels_lpl.hpp"  // tile source, row streams, accumulator flush and record readers of the kernels below
-namespace povar {
-
-// The rows come from an LplStream2 (three rows ahead, across the pass and tile boundaries).  The next tile's landmark record
-// is requested when the backward pass starts: G is dead by then (g = G u is formed), so only the three coordinates need a
-// second set of registers.
-template <bool ROBUST>
-__global__ __launch_bounds__(E0C_BLOCK) void e0_lpl(Dp d, double* hot_out) {
-  const int done = d.flags[1];  // requested first, tested after the LDS staging (no global side effects before)
-  extern __shared__ double2 hot[];  // [n_hot][HOT_REC] records, then acc[12][n_slots], then the tile counter
-  const V2& v = d.v2;
-  // this workgroup's camera slots: the records of the cameras it keeps in LDS (lpl_layout.hpp) and their accumulators
-  const int cam0 = v.wg_cam_off[blockIdx.x];
-  const int n_hot = v.wg_cam_off[blockIdx.x + 1] - cam0;
-  const int hubs = v.hubs, n_slots = n_hot + 3 * hubs;
-  double* acc = reinterpret_cast<double*>(hot + n_hot * HOT_REC);
-  int* grab_ctr = reinterpret_cast<int*>(acc + n_slots * 12);
-  for (int i = threadIdx.x; i < n_slots * 12; i += E0C_BLOCK) acc[i] = 0;
-  // the first tile of every wavefront is dealt statically (tiles are sorted longest first: the same tiles the first
-  // sixteen grabs would return), the counter serves the later ones
-  if (threadIdx.x == 0) *grab_ctr = E0C_BLOCK / WAVE;
-  const double2* rec_img = reinterpret_cast<const double2*>(d.hot_rec);
-  // staging, part 1: slot -> camera rank (the record pieces, a second dependent round trip, are requested further down:
-  // the wavefront's first rows and landmark record go out in between, so the three latencies overlap instead of adding
-  // up -- they are the fixed cost of a launch, a third of the kernel on an 8-GPU shard)
-  constexpr int PASSES = (HOT_ACC_MAX * HOT_REC + E0C_BLOCK - 1) / E0C_BLOCK;
-  int rk[PASSES];
-#pragma unroll
-  for (int u = 0; u < PASSES; ++u) {
-    const int i = threadIdx.x + u * E0C_BLOCK;
-    rk[u] = i < n_hot * HOT_REC ? v.wg_cams[cam0 + i / HOT_REC] : 0;
-  }
-  // where the accumulators go at the end (partial record of each slot): requested now, used after the last tile
-  constexpr int FPASSES = (HOT_ACC_MAX * 6 + E0C_BLOCK - 1) / E0C_BLOCK;
-  int frec[FPASSES];
-#pragma unroll
-  for (int u = 0; u < FPASSES; ++u) {
-    const int i = threadIdx.x + u * E0C_BLOCK;
-    frec[u] = i < n_hot * 6 ? v.wg_slot_rec[cam0 + i / 6] : 0;
-  }
-  const int lane = threadIdx.x & 63;
-  const LplTiles T(v, grab_ctr, lane);
-  const int t_end = T.t_end;
-  int c_t = T.nth(__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))), c_row0 = 0, c_k = 0, c_nh = 0, c_fl = 0;
-  if (c_t < t_end) T.info(c_t, c_row0, c_k, c_nh, c_fl);
-  // the first rows go out now; the tile after this one is taken behind the staging barrier below (the counter lives in LDS)
-  LplStream2<ROBUST> rows;
-  rows.start(T, v, c_t, c_row0, c_k, t_end);
-  double hx = 0, hy = 0, hz = 0, G00 = 0, G01 = 0, G02 = 0, G11 = 0, G12 = 0, G22 = 0;
-  if (c_t < t_end) {
-    const double* rp = v.lmrec + ((size_t)c_t * 9) * WAVE + lane;
-    hx = rp[0]; hy = rp[WAVE]; hz = rp[2 * WAVE];
-    G00 = rp[3 * WAVE]; G01 = rp[4 * WAVE]; G02 = rp[5 * WAVE]; G11 = rp[6 * WAVE]; G12 = rp[7 * WAVE]; G22 = rp[8 * WAVE];
-  }
-  {
-    // staging, part 2: the record pieces into LDS
-    double2 piece[PASSES];
-#pragma unroll
-    for (int u = 0; u < PASSES; ++u) {
-      const int i = threadIdx.x + u * E0C_BLOCK;
-      piece[u] = rec_img[(size_t)rk[u] * (HOT_REC_STRIDE / 2) + i % HOT_REC];
-    }
-#pragma unroll
-    for (int u = 0; u < PASSES; ++u) {
-      const int i = threadIdx.x + u * E0C_BLOCK;
-      if (i < n_hot * HOT_REC) hot[i] = piece[u];
-    }
-  }
-  __syncthreads();
-  if (done) return;
-  if (c_t < t_end) rows.ahead(T.grab());
-  while (c_t < t_end) {
-    double red[3] = {0, 0, 0};
-    for (int j = 0; j < c_k; ++j) {
-      const LplRow cur = rows.next(T, v);
-      double zz[12], P3[9];
-      LplObs o;
-      o.set(d, cur.uv, ROBUST ? cur.w : 1.0);
-      if (j < c_nh) {  // wave-uniform: every lane has an observation of an LDS-resident camera in this row
-        const double2* h = hot + lpl_cw_slot(cur.cw) * HOT_REC;
-        lpl_read_zz(h, zz);
-        lpl_read_p3(h, P3);
-        lpl_forward(o, zz, P3, hx, hy, hz, red);
-      } else if (cur.cw != -1) {
-        if (cur.cw >= 0) {
-          const double2* h = hot + lpl_cw_slot(cur.cw) * HOT_REC;
-          lpl_read_zz(h, zz);
-          lpl_read_p3(h, P3);
-        } else {  // cold: camera with popularity rank -2 - cw, record from the rank-ordered image (L2)
-          const double2* h = rec_img + (size_t)(-2 - cur.cw) * (HOT_REC_STRIDE / 2);
-          lpl_read_zz(h, zz);
-          lpl_read_p3(h, P3);
-        }
-        lpl_forward(o, zz, P3, hx, hy, hz, red);
-      }
-    }
-    if (c_fl & 1) {  // landmarks dealt over several lanes: sum their partial u = Jl^T t (segmented wavefront scan)
-      const int sg = v.seg[(size_t)c_t * WAVE + lane];
-      seg_reduce_steps<3>(red, lane, sg & 255, (sg >> 8) & 255, 4);
-    }
-    const double g[3] = {G00 * red[0] + G01 * red[1] + G02 * red[2], G01 * red[0] + G11 * red[1] + G12 * red[2],
-                         G02 * red[0] + G12 * red[1] + G22 * red[2]};
-    // the next tile's record: G into its own (now dead) registers, the coordinates into a second set
-    const int n_t = rows.nx_t;
-    double nhx = 0, nhy = 0, nhz = 0;
-    if (n_t < t_end) {
-      const double* rp = v.lmrec + ((size_t)n_t * 9) * WAVE + lane;
-      nhx = rp[0]; nhy = rp[WAVE]; nhz = rp[2 * WAVE];
-      G00 = rp[3 * WAVE]; G01 = rp[4 * WAVE]; G02 = rp[5 * WAVE]; G11 = rp[6 * WAVE]; G12 = rp[7 * WAVE]; G22 = rp[8 * WAVE];
-    }
-    for (int jj = 0; jj < c_k; ++jj) {
-      const int j = c_k - 1 - jj;
-      const LplRow cur = rows.next(T, v);
-      double P3[9], q[3];
-      LplObs o;
-      o.set(d, cur.uv, ROBUST ? cur.w : 1.0);
-      if (j < c_nh || cur.cw >= 0) {
-        lpl_read_p3(hot + lpl_cw_slot(cur.cw) * HOT_REC, P3);
-        lpl_backward(o, P3, g, q);
-        double* a = acc + lpl_acc_slot(cur.cw, hubs);  // acc[m][slot]: consecutive slots on consecutive banks
-        const double val[12] = {hx * q[0], hy * q[0], hz * q[0], q[0], hx * q[1], hy * q[1],
-                                hz * q[1], q[1], hx * q[2], hy * q[2], hz * q[2], q[2]};
-#pragma unroll
-        for (int m = 0; m < 12; ++m)
-          __hip_atomic_fetch_add(a + m * n_slots, val[m], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      } else if (cur.cw < -1) {
-        // where q goes: row-major next to the other lanes' (graphs with many cold observations: the per-camera kernel
-        // gathers, Dp::q_rows) or straight to its place in the camera-major cold view (few: one 32-byte store per lane)
-        const int cold_at = d.q_rows ? lpl_cold_q(c_fl, c_nh, j, lane) : v.cpos[((size_t)c_row0 + j) * WAVE + lane];
-        lpl_read_p3(rec_img + (size_t)(-2 - cur.cw) * (HOT_REC_STRIDE / 2), P3);
-        lpl_backward(o, P3, g, q);
-        d.q4c[cold_at] = make_double4(q[0], q[1], q[2], 0);
-      }
-    }
-    c_t = n_t;
-    if (c_t < t_end) {
-      T.info(c_t, c_row0, c_k, c_nh, c_fl);
-      rows.ahead(T.grab());
-    }
-    hx = nhx; hy = nhy; hz = nhz;
-  }
-  __syncthreads();
-  // accumulators -> this workgroup's partial records (camera-major in hot_out: the per-camera kernel reads one run);
-  // 16-byte stores; the record indices were requested in the prologue
-  {
-#pragma unroll
-    for (int u = 0; u < FPASSES; ++u) {
-      const int i = threadIdx.x + u * E0C_BLOCK;
-      if (i < n_hot * 6)
-        reinterpret_cast<double2*>(hot_out + (size_t)frec[u] * 12)[i % 6] = lpl_acc_sum(acc, n_slots, hubs, i / 6, i % 6);
-    }
-  }
-  if (d.p2p_epoch && blockIdx.x == 0 && threadIdx.x == 0) *d.p2p_epoch += 1;  // one tick per term, read by the next kernels
-}
-
-// ------------------------------------------------------------------------------------------
-// K7 on the lane-per-landmark layout: get_Hll_inv_add_Hpp_b_pOSE / _poBA (landmark_block.hpp:510-572), the
-// landmark half of prepare_Hb_pOSE.  Same structure as e0_lpl (lane = landmark, rows from an LplStream2,
-// camera records and per-camera accumulators in LDS, cold observations through q4c): the forward
-// pass accumulates Hll = Jl^T Jl and Jl^T r in registers, the lane then inverts Hll (+ lambda I for
-// POWER_SCHUR_COMPLEMENT), stores Hll^-1 and the per-term landmark records, and the backward pass adds
-// Jp^T (r - Jl w) into the camera accumulators.  The tile (Jl, r) is rebuilt from (P_c, x_l, u, v, sqrt(w), s_l):
-// nothing per observation is read besides the 20-byte row.  Replaces lm_regular<OpPrepare> + cm_scatter +
-// cam_sum_items (214 + 109 + 6 us on venice-1778) for the LDSACC mode.
-// ------------------------------------------------------------------------------------------
+// Camera records of the other lane-per-landmark kernels (prepare_lpl, backsub_lpl, lpl_pass and their step-2 twins,
+// povar_kernels_lpl.hpp): lengths, LDS strides and launch sizes, and the step-1 tile prepare_lpl rebuilds per observation.
 constexpr int PREP_REC = 6;  // double2 per camera record: P[:, :3] row-major (9), then the translation column (3)
 // LDS strides of the records are odd numbers of 16-byte quads: slot -> bank-quad class is then a bijection mod 16, the
 // relation the row placement of the layout assumes (an even stride leaves 8, 4 or 2 classes: built-in conflicts)
@@ -1439,343 +1275,17 @@ __device__ inline void prep_read_rec(const double2* h, double* P) {
     P[2 * j + 1] = v.y;
   }
 }
-__host__ __device__ inline size_t prep_lds_bytes(int n_hot) {
+__host__ __device__ constexpr size_t prep_lds_bytes(int n_hot) {
   return (size_t)n_hot * PREP_STRIDE * sizeof(double2) + (size_t)(n_hot + 3 * lpl_hubs(n_hot)) * 96 + 16;
 }
 
-template <bool ROBUST>
-__global__ __launch_bounds__(E0C_BLOCK) void prepare_lpl(Dp d, double* hot_out) {
-  extern __shared__ double2 hot[];  // [n_hot][PREP_REC] records, then acc[12][n_slots], then the tile counter
-  const V2& v = d.v2;
-  const int cam0 = v.wg_cam_off[blockIdx.x];
-  const int n_hot = v.wg_cam_off[blockIdx.x + 1] - cam0;
-  const int hubs = v.hubs, n_slots = n_hot + 3 * hubs;
-  double* acc = reinterpret_cast<double*>(hot + n_hot * PREP_STRIDE);
-  int* grab_ctr = reinterpret_cast<int*>(acc + n_slots * 12);
-  for (int i = threadIdx.x; i < n_slots * 12; i += E0C_BLOCK) acc[i] = 0;
-  if (threadIdx.x == 0) *grab_ctr = 0;
-  const double2* rec_img = reinterpret_cast<const double2*>(d.hot_rec);
-  for (int i = threadIdx.x; i < n_hot * PREP_REC; i += E0C_BLOCK) {
-    const int r = i / PREP_REC, j = i - r * PREP_REC;
-    hot[r * PREP_STRIDE + j] = rec_img[(size_t)v.wg_cams[cam0 + r] * (HOT_REC_STRIDE / 2) + 6 + j];  // entries 12..23 of the image
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & 63;
-  const LplTiles T(v, grab_ctr, lane);
-  const int t_end = T.t_end;
-  int c_t = T.grab(), c_row0 = 0, c_k = 0, c_nh = 0, c_fl = 0;
-  if (c_t < t_end) T.info(c_t, c_row0, c_k, c_nh, c_fl);
-  LplStream2<ROBUST> rows;
-  rows.start(T, v, c_t, c_row0, c_k, c_t < t_end ? T.grab() : t_end);
-  while (c_t < t_end) {
-    // the lane's landmark: coordinates and Jl column scale (gathers; once per tile)
-    const int lm = v.lm_of[(size_t)c_t * WAVE + lane];
-    const int sg = v.seg[(size_t)c_t * WAVE + lane];
-    const double4 h4 = v.lml[(size_t)c_t * WAVE + lane], s4 = v.lsc[(size_t)c_t * WAVE + lane];
-    const double hx = h4.x, hy = h4.y, hz = h4.z;
-    double red[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (int j = 0; j < c_k; ++j) {
-      const LplRow cur = rows.next(T, v);
-      if (cur.cw == -1) continue;
-      double P[12];
-      if (cur.cw >= 0) prep_read_rec(hot + lpl_cw_slot(cur.cw) * PREP_STRIDE, P);
-      else prep_read_rec(rec_img + (size_t)(-2 - cur.cw) * (HOT_REC_STRIDE / 2) + 6, P);
-      PrepObs o;
-      o.set(d, P, cur.uv, ROBUST ? cur.w : 1.0, hx, hy, hz, s4.x, s4.y, s4.z);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        red[0] += o.jl[3 * r] * o.jl[3 * r];
-        red[1] += o.jl[3 * r] * o.jl[3 * r + 1];
-        red[2] += o.jl[3 * r] * o.jl[3 * r + 2];
-        red[3] += o.jl[3 * r + 1] * o.jl[3 * r + 1];
-        red[4] += o.jl[3 * r + 1] * o.jl[3 * r + 2];
-        red[5] += o.jl[3 * r + 2] * o.jl[3 * r + 2];
-        red[6] += o.jl[3 * r] * o.r[r];
-        red[7] += o.jl[3 * r + 1] * o.r[r];
-        red[8] += o.jl[3 * r + 2] * o.r[r];
-      }
-    }
-    if (c_fl & 1) seg_reduce_steps<9>(red, lane, sg & 255, (sg >> 8) & 255, 4);
-    double Hi[9], w3[3] = {0, 0, 0};
-    if (lm >= 0) {
-      double H[9];
-      sym3(red, H);
-      H[0] += d.lambda_lm;
-      H[4] += d.lambda_lm;
-      H[8] += d.lambda_lm;
-      inv3(H, Hi);
-      w3[0] = Hi[0] * red[6] + Hi[1] * red[7] + Hi[2] * red[8];
-      w3[1] = Hi[3] * red[6] + Hi[4] * red[7] + Hi[5] * red[8];
-      w3[2] = Hi[6] * red[6] + Hi[7] * red[7] + Hi[8] * red[8];
-      // per-term record of this lane (e0_lpl); Hll^-1 and the row-major record of the other kernels once per landmark
-      double* r2 = v.lmrec + ((size_t)c_t * 9) * WAVE + lane;
-      r2[0] = hx; r2[WAVE] = hy; r2[2 * WAVE] = hz;
-      r2[3 * WAVE] = s4.x * Hi[0] * s4.x; r2[4 * WAVE] = s4.x * Hi[1] * s4.y; r2[5 * WAVE] = s4.x * Hi[2] * s4.z;
-      r2[6 * WAVE] = s4.y * Hi[4] * s4.y; r2[7 * WAVE] = s4.y * Hi[5] * s4.z; r2[8 * WAVE] = s4.z * Hi[8] * s4.z;
-      if (lane == (sg & 255) && !d.prep_lpl_only) {
-#pragma unroll
-        for (int m = 0; m < 9; ++m) d.hll_inv[9 * (size_t)lm + m] = Hi[m];
-        double4* rec = reinterpret_cast<double4*>(d.lmrec) + 3 * (size_t)lm;
-        rec[0] = make_double4(hx, hy, hz, s4.x);
-        rec[1] = make_double4(s4.y, s4.z, Hi[0], Hi[1]);
-        rec[2] = make_double4(Hi[2], Hi[4], Hi[5], Hi[8]);
-      }
-    }
-    for (int jj = 0; jj < c_k; ++jj) {
-      const int j = c_k - 1 - jj;
-      const LplRow cur = rows.next(T, v);
-      if (cur.cw == -1) continue;
-      double P[12];
-      if (cur.cw >= 0) prep_read_rec(hot + lpl_cw_slot(cur.cw) * PREP_STRIDE, P);
-      else prep_read_rec(rec_img + (size_t)(-2 - cur.cw) * (HOT_REC_STRIDE / 2) + 6, P);
-      PrepObs o;
-      const double w = ROBUST ? cur.w : 1.0;
-      o.set(d, P, cur.uv, w, hx, hy, hz, s4.x, s4.y, s4.z);
-      double e[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) e[r] = o.r[r] - (o.jl[3 * r] * w3[0] + o.jl[3 * r + 1] * w3[1] + o.jl[3 * r + 2] * w3[2]);
-      const double4 q = pose_q(d, cur.uv.x, cur.uv.y, sqrt(w), e);
-      if (cur.cw >= 0) {
-        double* a = acc + lpl_acc_slot(cur.cw, hubs);
-        const double val[12] = {hx * q.x, hy * q.x, hz * q.x, q.x, hx * q.y, hy * q.y,
-                                hz * q.y, q.y, hx * q.z, hy * q.z, hz * q.z, q.z};
-#pragma unroll
-        for (int m = 0; m < 12; ++m)
-          __hip_atomic_fetch_add(a + m * n_slots, val[m], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      } else {
-        d.q4c[d.q_rows ? lpl_cold_q(c_fl, c_nh, j, lane) : v.cpos[((size_t)c_row0 + j) * WAVE + lane]] = make_double4(q.x, q.y, q.z, 0);
-      }
-    }
-    c_t = rows.nx_t;
-    if (c_t < t_end) {
-      T.info(c_t, c_row0, c_k, c_nh, c_fl);
-      rows.ahead(T.grab());
-    }
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < n_hot * 6; i += E0C_BLOCK)
-    reinterpret_cast<double2*>(hot_out + (size_t)v.wg_slot_rec[cam0 + i / 6] * 12)[i % 6] = lpl_acc_sum(acc, n_slots, hubs, i / 6, i % 6);
-}
-
-// ------------------------------------------------------------------------------------------
-// K12 on the lane-per-landmark layout: back_substitute_pOSE (landmark_block.hpp:670-707), POWER_VARPROJ -- the
-// arithmetic of OpBackVarproj on prepare_lpl's row stream.  Camera records in LDS: the UPDATED camera, its increment
-// and the camera of the linearisation point (36 doubles); no accumulators.  First pass: H = Jl^T Jl and Jl^T res of
-// the fresh, unweighted, unscaled tile; the lane solves for delta; second pass: the reference's model cost change
-// (stored Jl and residual rebuilt from the linearisation point) summed per workgroup into part[blockIdx.x].
-// Replaces lm_regular<OpBackVarproj> (204 us on venice-1778) for the LDSACC mode.
-// ------------------------------------------------------------------------------------------
+// backsub_lpl: the UPDATED camera, its increment and the camera of the linearisation point; lpl_pass: the camera matrix
 constexpr int BACK_REC = 18;  // double2 per camera record: P_new (12), inc (12), P_lin (12)
 constexpr int BACK_STRIDE = BACK_REC | 1;
-__host__ __device__ inline size_t back_lds_bytes(int n_hot) { return (size_t)n_hot * BACK_STRIDE * sizeof(double2) + 16; }
-
-template <bool ROBUST>
-__global__ __launch_bounds__(E0C_BLOCK) void backsub_lpl(Dp d, double* part) {
-  extern __shared__ double2 hot[];  // [n_hot][BACK_REC] records, then the tile counter
-  __shared__ double sh[E0C_BLOCK / 64];
-  const V2& v = d.v2;
-  const int cam0 = v.wg_cam_off[blockIdx.x];
-  const int n_hot = v.wg_cam_off[blockIdx.x + 1] - cam0;
-  int* grab_ctr = reinterpret_cast<int*>(hot + n_hot * BACK_STRIDE);
-  if (threadIdx.x == 0) *grab_ctr = 0;
-  // record piece j of a camera: 0-5 cams4, 6-11 inc, 12-17 cams_lin4 (each 12 doubles)
-  auto piece = [&](int cam, int j) -> double2 {
-    const double* src = j < 6 ? reinterpret_cast<const double*>(d.cams4) : j < 12 ? d.inc : reinterpret_cast<const double*>(d.cams_lin4);
-    return reinterpret_cast<const double2*>(src + 12 * (size_t)cam)[j % 6];
-  };
-  for (int i = threadIdx.x; i < n_hot * BACK_REC; i += E0C_BLOCK) {
-    const int r = i / BACK_REC, j = i - r * BACK_REC;
-    hot[r * BACK_STRIDE + j] = piece(d.hot_cams[v.wg_cams[cam0 + r]], j);
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & 63;
-  const LplTiles T(v, grab_ctr, lane);
-  const int t_end = T.t_end;
-  int c_t = T.grab(), c_row0 = 0, c_k = 0, c_nh = 0, c_fl = 0;
-  if (c_t < t_end) T.info(c_t, c_row0, c_k, c_nh, c_fl);
-  LplStream2<ROBUST> rows;
-  rows.start(T, v, c_t, c_row0, c_k, c_t < t_end ? T.grab() : t_end);
-  // which: 0 P_new, 1 inc, 2 P_lin, from the record (LDS) or from the camera-indexed global arrays (cold camera)
-  auto read_part = [&](int cw, int which, double4 (&o)[3]) {
-    if (cw >= 0) {
-      lpl_read12(hot + lpl_cw_slot(cw) * BACK_STRIDE + 6 * which, o);
-    } else {
-      const int cam = d.hot_cams[-2 - cw];
-      const double* src = which == 0 ? reinterpret_cast<const double*>(d.cams4)
-                                     : which == 1 ? d.inc : reinterpret_cast<const double*>(d.cams_lin4);
-      lpl_read12(reinterpret_cast<const double2*>(src + 12 * (size_t)cam), o);
-    }
-  };
-  double sc = 0;
-  while (c_t < t_end) {
-    const int lm = v.lm_of[(size_t)c_t * WAVE + lane];
-    const int sg = v.seg[(size_t)c_t * WAVE + lane];
-    const size_t li = (size_t)c_t * WAVE + lane;
-    const double4 h = v.lmx[li], hl = v.lml[li], s4 = v.lsc[li];
-    double red[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (int j = 0; j < c_k; ++j) {
-      const LplRow cur = rows.next(T, v);
-      if (cur.cw == -1) continue;
-      double4 pp[3];
-      read_part(cur.cw, 0, pp);
-      const Cam P = {pp[0], pp[1], pp[2]};
-      double res[4], jl[12];
-      pose_residual(d, P, h, cur.uv.x, cur.uv.y, res);
-      pose_jl(d, P, cur.uv.x, cur.uv.y, 1.0, make_double4(1, 1, 1, 1), jl);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        red[0] += jl[3 * r] * jl[3 * r];
-        red[1] += jl[3 * r] * jl[3 * r + 1];
-        red[2] += jl[3 * r] * jl[3 * r + 2];
-        red[3] += jl[3 * r + 1] * jl[3 * r + 1];
-        red[4] += jl[3 * r + 1] * jl[3 * r + 2];
-        red[5] += jl[3 * r + 2] * jl[3 * r + 2];
-        red[6] += jl[3 * r] * res[r];
-        red[7] += jl[3 * r + 1] * res[r];
-        red[8] += jl[3 * r + 2] * res[r];
-      }
-    }
-    if (c_fl & 1) seg_reduce_steps<9>(red, lane, sg & 255, (sg >> 8) & 255, 4);
-    double dl[3] = {0, 0, 0};
-    if (lm >= 0) {
-      double H[9], Hi[9];
-      sym3(red, H);
-      inv3(H, Hi);
-      dl[0] = -(Hi[0] * red[6] + Hi[1] * red[7] + Hi[2] * red[8]);
-      dl[1] = -(Hi[3] * red[6] + Hi[4] * red[7] + Hi[5] * red[8]);
-      dl[2] = -(Hi[6] * red[6] + Hi[7] * red[7] + Hi[8] * red[8]);
-      const double4 hn = make_double4(h.x + dl[0], h.y + dl[1], h.z + dl[2], h.w);
-      v.lmx[li] = hn;  // the mirror stays current: no rebuild after an accepted step
-      if (lane == (sg & 255)) d.lms4[lm] = hn;
-    }
-    for (int jj = 0; jj < c_k; ++jj) {
-      const LplRow cur = rows.next(T, v);
-      if (cur.cw == -1) continue;
-      double4 zz[3], pl[3];
-      read_part(cur.cw, 1, zz);
-      read_part(cur.cw, 2, pl);
-      const Cam Pl = {pl[0], pl[1], pl[2]};
-      const double sw = ROBUST ? sqrt(cur.w) : 1.0;
-      double jinc[4], jls[12], rr[4];
-      pose_jp_x(d, h, cur.uv.x, cur.uv.y, 1.0, zz, jinc);
-      pose_jl(d, Pl, cur.uv.x, cur.uv.y, sw, s4, jls);
-      pose_residual(d, Pl, hl, cur.uv.x, cur.uv.y, rr);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const double ji = jinc[r] + (jls[3 * r] * dl[0] + jls[3 * r + 1] * dl[1] + jls[3 * r + 2] * dl[2]);
-        sc -= ji * (0.5 * ji + sw * rr[r]);
-      }
-    }
-    c_t = rows.nx_t;
-    if (c_t < t_end) {
-      T.info(c_t, c_row0, c_k, c_nh, c_fl);
-      rows.ahead(T.grab());
-    }
-  }
-  double sv[1] = {sc};
-  block_sum<1, E0C_BLOCK>(sv, sh);
-  if (threadIdx.x == 0) part[blockIdx.x] = sv[0];
-}
-
-// ------------------------------------------------------------------------------------------
-// K2 / K3 + K5 on the lane-per-landmark layout: one forward walk over the rows, camera matrices in LDS (96 B per slot),
-// no accumulators.
-//   MODE 0  linearize_landmark_pOSE + scale_Jl_cols_pOSE (landmark_block.hpp:135-178, 284-295) at (cams_lin4, lms_lin4):
-//           robust weight per observation (V2::w), Jl column scale per landmark, finiteness flag.  The per-slot
-//           sqrt(w) / weighted residual arrays of the lane-per-observation kernels are NOT written: the lane-per-landmark
-//           kernels rebuild both from (P, x, u, v, w); povar_lm.hip fills them when a legacy kernel asks (ensure_legacy).
-//   MODE 1  compute_error_pOSE (bal_bundle_adjustment_helper.cpp:117-154) at (cams4, lms4): (error, |r|, count) summed per
-//           workgroup into part[3 * blockIdx.x ..].
-// ------------------------------------------------------------------------------------------
+__host__ __device__ constexpr size_t back_lds_bytes(int n_hot) { return (size_t)n_hot * BACK_STRIDE * sizeof(double2) + 16; }
 constexpr int PASS_REC = 6;  // double2 per camera record: P row-major
 constexpr int PASS_STRIDE = PASS_REC | 1;
-__host__ __device__ inline size_t pass_lds_bytes(int n_hot) { return (size_t)n_hot * PASS_STRIDE * sizeof(double2) + 16; }
-
-template <int MODE>
-__global__ __launch_bounds__(E0C_BLOCK) void lpl_pass(Dp d, double* part) {
-  extern __shared__ double2 hot[];  // [n_hot][PASS_REC] records, then the tile counter
-  __shared__ double sh[3 * (E0C_BLOCK / 64)];
-  const V2& v = d.v2;
-  const double4* cams = MODE == 0 ? d.cams_lin4 : d.cams4;
-  const int cam0 = v.wg_cam_off[blockIdx.x];
-  const int n_hot = v.wg_cam_off[blockIdx.x + 1] - cam0;
-  int* grab_ctr = reinterpret_cast<int*>(hot + n_hot * PASS_STRIDE);
-  if (threadIdx.x == 0) *grab_ctr = 0;
-  for (int i = threadIdx.x; i < n_hot * PASS_REC; i += E0C_BLOCK) {
-    const int r = i / PASS_REC, j = i - r * PASS_REC;
-    hot[r * PASS_STRIDE + j] = reinterpret_cast<const double2*>(cams + 3 * (size_t)d.hot_cams[v.wg_cams[cam0 + r]])[j];
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & 63;
-  const LplTiles T(v, grab_ctr, lane);
-  const int t_end = T.t_end;
-  int c_t = T.grab();
-  LplStream1 rows;
-  rows.start(T, v, c_t);
-  double sc[3] = {0, 0, 0};
-  int bad = 0;
-  while (c_t < t_end) {
-    int c_row0, c_k, c_nh, c_fl;
-    T.info(c_t, c_row0, c_k, c_nh, c_fl);
-    const double4 h = v.lmx[(size_t)c_t * WAVE + lane];
-    if (MODE == 0) v.lml[(size_t)c_t * WAVE + lane] = h;  // the linearisation point, lane-ordered, is left behind
-    double red[3] = {0, 0, 0};
-    for (int j = 0; j < c_k; ++j) {
-      const LplRow cur = rows.next(T, v);
-      if (cur.cw == -1) continue;
-      // (a select of an LDS and a global pointer: six flat_loads.  Measured against ds_read / global_load in two branches
-      // -- profiles/r02_ablations.txt item 16 --: the branches join with a wait on both counters, which drains the row
-      // prefetch every step: 50 instead of 44 us here; the two-pass kernels with their longer steps gain from the split)
-      const double2* hp = cur.cw >= 0 ? hot + lpl_cw_slot(cur.cw) * PASS_STRIDE
-                                      : reinterpret_cast<const double2*>(cams + 3 * (size_t)d.hot_cams[-2 - cur.cw]);
-      Cam P;
-      lpl_read_cam(hp, P);
-      double res[4];
-      pose_residual(d, P, h, cur.uv.x, cur.uv.y, res);
-      const double r2 = res[0] * res[0] + res[1] * res[1] + res[2] * res[2] + res[3] * res[3];
-      double e, w;
-      error_weight(d, r2, e, w);
-      if (MODE == 0) {
-        const double sw = sqrt(w);
-        bad |= !isfinite(r2) || !isfinite(sw);
-        if (d.robust && v.w) v.w[((size_t)c_row0 + j) * WAVE + lane] = w;
-        double jl[12];
-        pose_jl(d, P, cur.uv.x, cur.uv.y, sw, make_double4(1, 1, 1, 1), jl);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          red[0] += jl[3 * r] * jl[3 * r];
-          red[1] += jl[3 * r + 1] * jl[3 * r + 1];
-          red[2] += jl[3 * r + 2] * jl[3 * r + 2];
-        }
-      } else {
-        bad |= !isfinite(r2);
-        sc[0] += e;
-        sc[1] += sqrt(r2);
-        sc[2] += 1.0;
-      }
-    }
-    if (MODE == 0) {
-      const int sg = v.seg[(size_t)c_t * WAVE + lane];
-      if (c_fl & 1) seg_reduce_steps<3>(red, lane, sg & 255, (sg >> 8) & 255, 4);
-      const double4 sc4 = d.scale_jl ? make_double4(1.0 / (d.eps + sqrt(red[0])), 1.0 / (d.eps + sqrt(red[1])),
-                                                    1.0 / (d.eps + sqrt(red[2])), 0.0)
-                                     : make_double4(1.0, 1.0, 1.0, 0.0);
-      // every lane of the landmark holds the segment total.  The landmark-order copy (Dp::jl_scale4) is not written
-      // here: lanes_to_lm fills it when a lane-per-observation kernel or an export asks (povar_lm.hip: ensure_legacy)
-      v.lsc[(size_t)c_t * WAVE + lane] = sc4;
-    }
-    c_t = rows.advance(T);
-  }
-  if (bad) atomicOr(&d.flags[0], 1);
-  if (MODE == 1) {
-    block_sum<3, E0C_BLOCK>(sc, sh);
-    if (threadIdx.x == 0) {
-      part[3 * (size_t)blockIdx.x] = sc[0];
-      part[3 * (size_t)blockIdx.x + 1] = sc[1];
-      part[3 * (size_t)blockIdx.x + 2] = sc[2];
-    }
-  }
-}
+__host__ __device__ constexpr size_t pass_lds_bytes(int n_hot) { return (size_t)n_hot * PASS_STRIDE * sizeof(double2) + 16; }
 
 // K10 (stored tiles): right_mul_e0_pOSE on the tiles kept in HBM, blocked layout
 // tiles[bin][pair][lane] (double2): pairs 0-23 Jp (row-major 4x12), 24-29 Jl (4x3), 30-31 r.

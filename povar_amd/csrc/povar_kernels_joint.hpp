@@ -624,10 +624,9 @@ __device__ inline double nc_z_entry(int lane, double s, const double* w13, const
   return nc_z_entry(lane, s, lane < 11 ? w13[lane + 1] : 0.0, w13[l], w13[12], sig[l]);
 }
 
-// K10' on the lane-per-landmark layout (right_mul_e0_joint, linearization_power_varproj.hpp:408-453): e0_lpl's
-// structure (povar_kernels.hpp) with the 2-row tiles of step 2.  Records are 192 bytes (z = sigma * N_c x_c, then the
-// full P_c), the landmark lane carries X, the Jl column scale and Hll^-1 (the column scale cannot be folded into
-// Hll^-1 here: the tangent basis N_l sits between them).
+// The lane-per-landmark kernels of step 2 (e0_lpl_h, prepare_lpl_h, lpl_pass_h, backsub_lpl_h: povar_kernels_lpl.hpp, one body
+// per kernel with step 1).  Records are 192 bytes (z = sigma * N_c x_c, then the full P_c), the landmark lane carries X, the
+// Jl column scale and Hll^-1 (the column scale cannot be folded into Hll^-1 here: the tangent basis N_l sits between them).
 constexpr int LPL_REC_H = 14;  // doubles per landmark lane in V2::lmrec (step 2)
 // LDS stride of a camera record in the lane-per-landmark kernels of step 2, in double2: the record has 12 (192 B), but
 // a 12-quad stride puts every record on one of FOUR bank-quad classes (12 s mod 16) -- four-way ds_read_b128 conflicts
@@ -637,298 +636,10 @@ constexpr int LPL_REC_H = 14;  // doubles per landmark lane in V2::lmrec (step 2
 #define POVAR_LPL_CAMREC_H 13
 #endif
 constexpr int LPL_CAMREC_H = POVAR_LPL_CAMREC_H;
-__host__ __device__ inline size_t lpl_lds_bytes_h(int n_hot) {
+__host__ __device__ constexpr size_t lpl_lds_bytes_h(int n_hot) {
   return (size_t)n_hot * LPL_CAMREC_H * sizeof(double2) + (size_t)(n_hot + 3 * lpl_hubs(n_hot)) * 96 + 16;
 }
-template <bool ROBUST>
-__global__ __launch_bounds__(E0C_BLOCK) void e0_lpl_h(Dp d, double* hot_out) {
-  const int done = d.flags[1];  // requested first, tested after the LDS staging (no global side effects before)
-  extern __shared__ double2 hot[];  // [n_hot][HOT_REC_H] records, then acc[12][n_slots], then the tile counter
-  const V2& v = d.v2;
-  // this workgroup's camera slots: the records of the cameras it keeps in LDS (lpl_layout.hpp) and their accumulators
-  const int cam0 = v.wg_cam_off[blockIdx.x];
-  const int n_hot = v.wg_cam_off[blockIdx.x + 1] - cam0;
-  const int hubs = v.hubs, n_slots = n_hot + 3 * hubs;
-  double* acc = reinterpret_cast<double*>(hot + n_hot * LPL_CAMREC_H);
-  int* grab_ctr = reinterpret_cast<int*>(acc + n_slots * 12);
-  for (int i = threadIdx.x; i < n_slots * 12; i += E0C_BLOCK) acc[i] = 0;
-  if (threadIdx.x == 0) *grab_ctr = 0;
-  const double2* rec_img = reinterpret_cast<const double2*>(d.hot_rec);
-  {
-    // staging: slot -> camera rank -> record, two dependent L2 round trips; every thread first requests all its
-    // ranks, then all its record pieces, then writes LDS (a plain loop pays the two latencies once per pass)
-    constexpr int PASSES = (HOT_ACC_MAX * HOT_REC_H + E0C_BLOCK - 1) / E0C_BLOCK;
-    int rk[PASSES];
-    double2 piece[PASSES];
-#pragma unroll
-    for (int u = 0; u < PASSES; ++u) {
-      const int i = threadIdx.x + u * E0C_BLOCK;
-      rk[u] = i < n_hot * HOT_REC_H ? v.wg_cams[cam0 + i / HOT_REC_H] : 0;
-    }
-#pragma unroll
-    for (int u = 0; u < PASSES; ++u) {
-      const int i = threadIdx.x + u * E0C_BLOCK;
-      piece[u] = rec_img[(size_t)rk[u] * (HOT_REC_STRIDE / 2) + i % HOT_REC_H];
-    }
-#pragma unroll
-    for (int u = 0; u < PASSES; ++u) {
-      const int i = threadIdx.x + u * E0C_BLOCK;
-      if (i < n_hot * HOT_REC_H) hot[(i / HOT_REC_H) * LPL_CAMREC_H + i % HOT_REC_H] = piece[u];
-    }
-  }
-  __syncthreads();
-  if (done) return;
-  const int lane = threadIdx.x & 63;
-  const LplTiles T(v, grab_ctr, lane);
-  const int t_end = T.t_end;
-  int c_t = T.grab(), c_row0 = 0, c_k = 0, c_nh = 0, c_fl = 0;
-  if (c_t < t_end) T.info(c_t, c_row0, c_k, c_nh, c_fl);
-  LplStream2<ROBUST> rows;
-  rows.start(T, v, c_t, c_row0, c_k, c_t < t_end ? T.grab() : t_end);
-  // landmark record of the lane (step 2): X (4), Jl column scale s (4), Hll^-1 (6) = 14 entries of lmrec[tile][14][64];
-  // the Householder vector of X (tangent basis N_l, landmark_block.hpp:227-269) is rebuilt once per tile
-  auto load_rec = [&](int t, double4& X, double4& s4, double (&Hi)[6]) {
-    const double* rp = v.lmrec + ((size_t)t * LPL_REC_H) * WAVE + lane;
-    X = make_double4(rp[0], rp[WAVE], rp[2 * WAVE], rp[3 * WAVE]);
-    s4 = make_double4(rp[4 * WAVE], rp[5 * WAVE], rp[6 * WAVE], rp[7 * WAVE]);
-#pragma unroll
-    for (int m = 0; m < 6; ++m) Hi[m] = rp[(8 + m) * WAVE];
-  };
-  // a camera record: z (entries 0..11), then P row-major (12..23)
-  double4 X = make_double4(0, 0, 0, 1), s4 = make_double4(1, 1, 1, 1);
-  double Hi[6] = {0, 0, 0, 0, 0, 0};
-  if (c_t < t_end) load_rec(c_t, X, s4, Hi);
-  while (c_t < t_end) {
-    double hw[4], hbeta;
-    house4(X, hw, hbeta);
-    double red[3] = {0, 0, 0};
-    for (int j = 0; j < c_k; ++j) {
-      const LplRow cur = rows.next(T, v);
-      // LDS pointer or global pointer, never a select of the two (lpl_read12).  Rows [0, c_nh) have an LDS-resident
-      // camera in every lane: wave-uniform branch, LDS reads only.
-      auto fwd = [&](const Cam& P, const double4 (&zz)[3]) {
-        const double sw = ROBUST ? sqrt(cur.w) : 1.0;
-        const Hom h = hom_project(P, X, cur.uv.x, cur.uv.y);
-        double jl4[8], jl3[6], t[2];
-        hom_jl4(P, h, sw, s4, jl4);
-        jl3_of_jl4(jl4, hw, hbeta, jl3);
-        hom_jp_x(h, X, sw, zz, t);
-#pragma unroll
-        for (int m = 0; m < 3; ++m) red[m] += jl3[m] * t[0] + jl3[3 + m] * t[1];
-      };
-      Cam P;
-      double4 zz[3];
-      if (j < c_nh) {
-        const double2* hp = hot + lpl_cw_slot(cur.cw) * LPL_CAMREC_H;
-        lpl_read12(hp, zz);
-        lpl_read_cam(hp + 6, P);
-        fwd(P, zz);
-      } else if (cur.cw != -1) {
-        if (cur.cw >= 0) {
-          const double2* hp = hot + lpl_cw_slot(cur.cw) * LPL_CAMREC_H;
-          lpl_read12(hp, zz);
-          lpl_read_cam(hp + 6, P);
-        } else {
-          const double2* hp = rec_img + (size_t)(-2 - cur.cw) * (HOT_REC_STRIDE / 2);
-          lpl_read12(hp, zz);
-          lpl_read_cam(hp + 6, P);
-        }
-        fwd(P, zz);
-      }
-    }
-    if (c_fl & 1) {  // landmarks dealt over several lanes: sum their partial u = Jl^T t (segmented wavefront scan)
-      const int sg = v.seg[(size_t)c_t * WAVE + lane];
-      seg_reduce_steps<3>(red, lane, sg & 255, (sg >> 8) & 255, 4);
-    }
-    const double g[3] = {Hi[0] * red[0] + Hi[1] * red[1] + Hi[2] * red[2], Hi[1] * red[0] + Hi[3] * red[1] + Hi[4] * red[2],
-                         Hi[2] * red[0] + Hi[4] * red[1] + Hi[5] * red[2]};
-    // the next tile's record (Hll^-1 is dead by now; X and s are still needed: second set)
-    const int n_t = rows.nx_t;
-    double4 nX = make_double4(0, 0, 0, 1), ns4 = make_double4(1, 1, 1, 1);
-    double nHi[6] = {0, 0, 0, 0, 0, 0};
-    if (n_t < t_end) load_rec(n_t, nX, ns4, nHi);
-    for (int jj = 0; jj < c_k; ++jj) {
-      const int j = c_k - 1 - jj;
-      const LplRow cur = rows.next(T, v);
-      auto bwd = [&](const Cam& P) -> double4 {
-        const double sw = ROBUST ? sqrt(cur.w) : 1.0;
-        const Hom h = hom_project(P, X, cur.uv.x, cur.uv.y);
-        double jl4[8], jl3[6];
-        hom_jl4(P, h, sw, s4, jl4);
-        jl3_of_jl4(jl4, hw, hbeta, jl3);
-        const double s0 = jl3[0] * g[0] + jl3[1] * g[1] + jl3[2] * g[2];
-        const double s1 = jl3[3] * g[0] + jl3[4] * g[1] + jl3[5] * g[2];
-        return hom_q(h, sw, s0, s1);
-      };
-      auto scatter = [&](const double4& q) {
-        double* a = acc + lpl_acc_slot(cur.cw, hubs);  // acc[m][slot]: consecutive slots on consecutive banks
-        const double val[12] = {X.x * q.x, X.y * q.x, X.z * q.x, X.w * q.x, X.x * q.y, X.y * q.y,
-                                X.z * q.y, X.w * q.y, X.x * q.z, X.y * q.z, X.z * q.z, X.w * q.z};
-#pragma unroll
-        for (int m = 0; m < 12; ++m)
-          __hip_atomic_fetch_add(a + m * n_slots, val[m], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      };
-      Cam P;
-      if (j < c_nh) {  // wave-uniform: LDS only
-        lpl_read_cam(hot + lpl_cw_slot(cur.cw) * LPL_CAMREC_H + 6, P);
-        scatter(bwd(P));
-      } else if (cur.cw >= 0) {
-        lpl_read_cam(hot + lpl_cw_slot(cur.cw) * LPL_CAMREC_H + 6, P);
-        scatter(bwd(P));
-      } else if (cur.cw < -1) {
-        // where q goes: row-major next to the other lanes' (graphs with many cold observations: the per-camera kernel
-        // gathers, Dp::q_rows) or straight to its place in the camera-major cold view (few: one 32-byte store per lane)
-        const int cold_at = d.q_rows ? lpl_cold_q(c_fl, c_nh, j, lane) : v.cpos[((size_t)c_row0 + j) * WAVE + lane];
-        lpl_read_cam(rec_img + (size_t)(-2 - cur.cw) * (HOT_REC_STRIDE / 2) + 6, P);
-        d.q4c[cold_at] = bwd(P);
-      }
-    }
-    c_t = n_t;
-    if (c_t < t_end) {
-      T.info(c_t, c_row0, c_k, c_nh, c_fl);
-      rows.ahead(T.grab());
-    }
-    X = nX;
-    s4 = ns4;
-#pragma unroll
-    for (int m = 0; m < 6; ++m) Hi[m] = nHi[m];
-  }
-  __syncthreads();
-  // accumulators -> this workgroup's partial records (camera-major in hot_out: the per-camera kernel reads one run);
-  // 16-byte stores, all record indices requested first (one L2 round trip, not one per pass)
-  {
-    constexpr int PASSES = (HOT_ACC_MAX * 6 + E0C_BLOCK - 1) / E0C_BLOCK;
-    int rec[PASSES];
-#pragma unroll
-    for (int u = 0; u < PASSES; ++u) {
-      const int i = threadIdx.x + u * E0C_BLOCK;
-      rec[u] = i < n_hot * 6 ? v.wg_slot_rec[cam0 + i / 6] : 0;
-    }
-#pragma unroll
-    for (int u = 0; u < PASSES; ++u) {
-      const int i = threadIdx.x + u * E0C_BLOCK;
-      if (i < n_hot * 6)
-        reinterpret_cast<double2*>(hot_out + (size_t)rec[u] * 12)[i % 6] = lpl_acc_sum(acc, n_slots, hubs, i / 6, i % 6);
-    }
-  }
-  if (d.p2p_epoch && blockIdx.x == 0 && threadIdx.x == 0) *d.p2p_epoch += 1;  // one tick per term, read by the next kernels
-}
-
-
-// K7' on the lane-per-landmark layout: get_Hll_inv_add_Hpp_b_joint (landmark_block.hpp:474-507), the landmark half
-// of prepare_Hb_joint -- prepare_lpl (povar_kernels.hpp) with the homogeneous tile.  Forward pass: Hll = Jl3^T Jl3
-// and Jl3^T r in registers; the lane inverts Hll + lambda I, stores Hll^-1 and the landmark records of the per-term
-// kernels; backward pass: Jp^T (r - Jl3 w) into the camera accumulators (12 ambient values per observation; the
-// tangent projection N_c^T is applied per camera afterwards, cam_nt_project).  Replaces lm_regular<OpPrepareH> +
-// cm_scatter + cam_sum_items_h (495 + 124 + 6 us on venice-1778) for the LDSACC mode.
-template <bool ROBUST>
-__global__ __launch_bounds__(E0C_BLOCK) void prepare_lpl_h(Dp d, double* hot_out) {
-  extern __shared__ double2 hot[];  // [n_hot][PREP_REC] records (P_c row-major), then acc[12][n_slots], then the tile counter
-  const V2& v = d.v2;
-  const int cam0 = v.wg_cam_off[blockIdx.x];
-  const int n_hot = v.wg_cam_off[blockIdx.x + 1] - cam0;
-  const int hubs = v.hubs, n_slots = n_hot + 3 * hubs;
-  double* acc = reinterpret_cast<double*>(hot + n_hot * PREP_STRIDE);
-  int* grab_ctr = reinterpret_cast<int*>(acc + n_slots * 12);
-  for (int i = threadIdx.x; i < n_slots * 12; i += E0C_BLOCK) acc[i] = 0;
-  if (threadIdx.x == 0) *grab_ctr = 0;
-  const double2* rec_img = reinterpret_cast<const double2*>(d.hot_rec);
-  for (int i = threadIdx.x; i < n_hot * PREP_REC; i += E0C_BLOCK) {
-    const int r = i / PREP_REC, j = i - r * PREP_REC;
-    hot[r * PREP_STRIDE + j] = rec_img[(size_t)v.wg_cams[cam0 + r] * (HOT_REC_STRIDE / 2) + 6 + j];  // entries 12..23 of the image
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & 63;
-  const LplTiles T(v, grab_ctr, lane);
-  const int t_end = T.t_end;
-  int c_t = T.grab(), c_row0 = 0, c_k = 0, c_nh = 0, c_fl = 0;
-  if (c_t < t_end) T.info(c_t, c_row0, c_k, c_nh, c_fl);
-  LplStream2<ROBUST> rows;
-  rows.start(T, v, c_t, c_row0, c_k, c_t < t_end ? T.grab() : t_end);
-  while (c_t < t_end) {
-    const int lm = v.lm_of[(size_t)c_t * WAVE + lane];
-    const int sg = v.seg[(size_t)c_t * WAVE + lane];
-    const double4 X = v.lml[(size_t)c_t * WAVE + lane], s4 = v.lsc[(size_t)c_t * WAVE + lane];  // lane-ordered mirrors (V2)
-    double hw[4], hbeta;
-    house4(X, hw, hbeta);
-    double red[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (int j = 0; j < c_k; ++j) {
-      const LplRow cur = rows.next(T, v);
-      if (cur.cw == -1) continue;
-      Cam P;
-      // LDS pointer or global pointer, never a select of the two (lpl_read12)
-      if (cur.cw >= 0) lpl_read_cam(hot + lpl_cw_slot(cur.cw) * PREP_STRIDE, P);
-      else lpl_read_cam(rec_img + (size_t)(-2 - cur.cw) * (HOT_REC_STRIDE / 2) + 6, P);
-      const double sw = ROBUST ? sqrt(cur.w) : 1.0;
-      const Hom h = hom_project(P, X, cur.uv.x, cur.uv.y);
-      double jl4[8], jl3[6];
-      hom_jl4(P, h, sw, s4, jl4);
-      jl3_of_jl4(jl4, hw, hbeta, jl3);
-      const double r0 = sw * h.r0, r1 = sw * h.r1;
-      acc_h6(red, jl3);
-#pragma unroll
-      for (int m = 0; m < 3; ++m) red[6 + m] += jl3[m] * r0 + jl3[3 + m] * r1;
-    }
-    if (c_fl & 1) seg_reduce_steps<9>(red, lane, sg & 255, (sg >> 8) & 255, 4);
-    double w3[3] = {0, 0, 0};
-    if (lm >= 0) {
-      double Hi[9];
-      hinv_damped(red, d.lambda_lm, Hi);
-      w3[0] = Hi[0] * red[6] + Hi[1] * red[7] + Hi[2] * red[8];
-      w3[1] = Hi[3] * red[6] + Hi[4] * red[7] + Hi[5] * red[8];
-      w3[2] = Hi[6] * red[6] + Hi[7] * red[7] + Hi[8] * red[8];
-      // per-term record of this lane (e0_lpl_h); Hll^-1 and the row-major record of the other kernels once per landmark
-      double* r2 = v.lmrec + ((size_t)c_t * LPL_REC_H) * WAVE + lane;
-      const double rv[LPL_REC_H] = {X.x, X.y, X.z, X.w, s4.x, s4.y, s4.z, s4.w, Hi[0], Hi[1], Hi[2], Hi[4], Hi[5], Hi[8]};
-#pragma unroll
-      for (int m = 0; m < LPL_REC_H; ++m) r2[m * WAVE] = rv[m];
-      if (lane == (sg & 255) && !d.prep_lpl_only) {
-#pragma unroll
-        for (int m = 0; m < 9; ++m) d.hll_inv[9 * (size_t)lm + m] = Hi[m];
-        double4* rec = reinterpret_cast<double4*>(d.lmrec) + 4 * (size_t)lm;
-        rec[0] = X;
-        rec[1] = s4;
-        rec[2] = make_double4(Hi[0], Hi[1], Hi[2], Hi[4]);
-        rec[3] = make_double4(Hi[5], Hi[8], 0, 0);
-      }
-    }
-    for (int jj = 0; jj < c_k; ++jj) {
-      const int j = c_k - 1 - jj;
-      const LplRow cur = rows.next(T, v);
-      if (cur.cw == -1) continue;
-      Cam P;
-      // LDS pointer or global pointer, never a select of the two (lpl_read12)
-      if (cur.cw >= 0) lpl_read_cam(hot + lpl_cw_slot(cur.cw) * PREP_STRIDE, P);
-      else lpl_read_cam(rec_img + (size_t)(-2 - cur.cw) * (HOT_REC_STRIDE / 2) + 6, P);
-      const double sw = ROBUST ? sqrt(cur.w) : 1.0;
-      const Hom h = hom_project(P, X, cur.uv.x, cur.uv.y);
-      double jl4[8], jl3[6];
-      hom_jl4(P, h, sw, s4, jl4);
-      jl3_of_jl4(jl4, hw, hbeta, jl3);
-      const double e0 = sw * h.r0 - (jl3[0] * w3[0] + jl3[1] * w3[1] + jl3[2] * w3[2]);
-      const double e1 = sw * h.r1 - (jl3[3] * w3[0] + jl3[4] * w3[1] + jl3[5] * w3[2]);
-      const double4 q = hom_q(h, sw, e0, e1);
-      if (cur.cw >= 0) {
-        double* a = acc + lpl_acc_slot(cur.cw, hubs);
-        const double val[12] = {X.x * q.x, X.y * q.x, X.z * q.x, X.w * q.x, X.x * q.y, X.y * q.y,
-                                X.z * q.y, X.w * q.y, X.x * q.z, X.y * q.z, X.z * q.z, X.w * q.z};
-#pragma unroll
-        for (int m = 0; m < 12; ++m)
-          __hip_atomic_fetch_add(a + m * n_slots, val[m], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      } else {
-        d.q4c[d.q_rows ? lpl_cold_q(c_fl, c_nh, j, lane) : v.cpos[((size_t)c_row0 + j) * WAVE + lane]] = q;
-      }
-    }
-    c_t = rows.nx_t;
-    if (c_t < t_end) {
-      T.info(c_t, c_row0, c_k, c_nh, c_fl);
-      rows.ahead(T.grab());
-    }
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < n_hot * 6; i += E0C_BLOCK)
-    reinterpret_cast<double2*>(hot_out + (size_t)v.wg_slot_rec[cam0 + i / 6] * 12)[i % 6] = lpl_acc_sum(acc, n_slots, hubs, i / 6, i % 6);
-}
+__host__ __device__ constexpr size_t back_lds_bytes_h(int n_hot) { return (size_t)n_hot * LPL_CAMREC_H * sizeof(double2) + 16; }
 
 // b11_c = N_c^T y12_c for the per-camera sums of prepare_lpl_h (cam_cold_sum has applied sigma); y12 is scratch
 // and left zeroed, as the dense-y term loop expects it
@@ -944,185 +655,6 @@ POVAR_KERNEL __launch_bounds__(256) void cam_nt_project(Dp d, double* y12, doubl
   nt_apply(ncw + 13 * (size_t)c, ncw[13 * (size_t)c + 12], y, o);
 #pragma unroll
   for (int j = 0; j < 11; ++j) out11[11 * (size_t)c + j] = o[j];
-}
-
-
-
-// K2' / K3' + K5' on the lane-per-landmark layout (the step-2 twins of lpl_pass, povar_kernels.hpp):
-//   MODE 0  linearize_landmark_projective_space_homogeneous + scale_Jl_cols_homogeneous (landmark_block.hpp:180-225,
-//           298-309) at (cams_lin4, lms_lin4): robust weight per observation (V2::w), the four Jl column scales per
-//           landmark, finiteness flag; the per-slot arrays of the lane-per-observation kernels follow lazily.
-//   MODE 1  compute_error_projective_space_homogeneous (helper.cpp:157-196) at (cams4, lms4): the six sums of OpErrorH
-//           per workgroup into part[6 * blockIdx.x ..].
-template <int MODE>
-__global__ __launch_bounds__(E0C_BLOCK) void lpl_pass_h(Dp d, double* part) {
-  extern __shared__ double2 hot[];  // [n_hot][PASS_REC] records (P_c row-major), then the tile counter
-  __shared__ double sh[6 * (E0C_BLOCK / 64)];
-  const V2& v = d.v2;
-  const double4* cams = MODE == 0 ? d.cams_lin4 : d.cams4;
-  const int cam0 = v.wg_cam_off[blockIdx.x];
-  const int n_hot = v.wg_cam_off[blockIdx.x + 1] - cam0;
-  int* grab_ctr = reinterpret_cast<int*>(hot + n_hot * PASS_STRIDE);
-  if (threadIdx.x == 0) *grab_ctr = 0;
-  for (int i = threadIdx.x; i < n_hot * PASS_REC; i += E0C_BLOCK) {
-    const int r = i / PASS_REC, j = i - r * PASS_REC;
-    hot[r * PASS_STRIDE + j] = reinterpret_cast<const double2*>(cams + 3 * (size_t)d.hot_cams[v.wg_cams[cam0 + r]])[j];
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & 63;
-  const LplTiles T(v, grab_ctr, lane);
-  const int t_end = T.t_end;
-  int c_t = T.grab();
-  LplStream1 rows;
-  rows.start(T, v, c_t);
-  double sc[6] = {0, 0, 0, 0, 0, 0};
-  int bad = 0;
-  while (c_t < t_end) {
-    int c_row0, c_k, c_nh, c_fl;
-    T.info(c_t, c_row0, c_k, c_nh, c_fl);
-    const double4 X = v.lmx[(size_t)c_t * WAVE + lane];
-    if (MODE == 0) v.lml[(size_t)c_t * WAVE + lane] = X;  // the linearisation point, lane-ordered, is left behind
-    double red[4] = {0, 0, 0, 0};
-    for (int j = 0; j < c_k; ++j) {
-      const LplRow cur = rows.next(T, v);
-      if (cur.cw == -1) continue;
-      // (a select of an LDS and a global pointer: six flat_loads.  Measured against ds_read / global_load in two branches
-      // -- profiles/r02_ablations.txt item 16 --: the branches join with a wait on both counters, which drains the row
-      // prefetch every step: 50 instead of 44 us here; the two-pass kernels with their longer steps gain from the split)
-      const double2* hp = cur.cw >= 0 ? hot + lpl_cw_slot(cur.cw) * PASS_STRIDE
-                                      : reinterpret_cast<const double2*>(cams + 3 * (size_t)d.hot_cams[-2 - cur.cw]);
-      Cam P;
-      lpl_read_cam(hp, P);
-      const Hom h = hom_project(P, X, cur.uv.x, cur.uv.y);
-      const double r2 = h.r0 * h.r0 + h.r1 * h.r1;
-      double e, w;
-      error_weight(d, r2, e, w);
-      if (MODE == 0) {
-        const double sw = sqrt(w);
-        bad |= !isfinite(r2) || !isfinite(sw) || !isfinite(h.D02) || !isfinite(h.D12);
-        if (d.robust && v.w) v.w[((size_t)c_row0 + j) * WAVE + lane] = w;
-        double jl[8];
-        hom_jl4(P, h, sw, make_double4(1, 1, 1, 1), jl);
-#pragma unroll
-        for (int m = 0; m < 4; ++m) red[m] += jl[m] * jl[m] + jl[4 + m] * jl[4 + m];
-      } else {
-        bad |= !isfinite(r2);
-        sc[0] += e; sc[1] += sqrt(r2); sc[2] += 1.0;
-        if (h.valid) { sc[3] += e; sc[4] += sqrt(r2); sc[5] += 1.0; }
-      }
-    }
-    if (MODE == 0) {
-      const int sg = v.seg[(size_t)c_t * WAVE + lane];
-      if (c_fl & 1) seg_reduce_steps<4>(red, lane, sg & 255, (sg >> 8) & 255, 4);
-      // lane-ordered; the landmark-order copy (Dp::jl_scale4) is filled on demand (povar_lm.hip: ensure_legacy)
-      v.lsc[(size_t)c_t * WAVE + lane] = make_double4(1.0 / (d.eps + sqrt(red[0])), 1.0 / (d.eps + sqrt(red[1])),
-                                                      1.0 / (d.eps + sqrt(red[2])), 1.0 / (d.eps + sqrt(red[3])));
-    }
-    c_t = rows.advance(T);
-  }
-  if (bad) atomicOr(&d.flags[0], 1);
-  if (MODE == 1) {
-    block_sum<6, E0C_BLOCK>(sc, sh);
-    if (threadIdx.x == 0) {
-#pragma unroll
-      for (int k = 0; k < 6; ++k) part[6 * (size_t)blockIdx.x + k] = sc[k];
-    }
-  }
-}
-
-__host__ __device__ inline size_t back_lds_bytes_h(int n_hot) { return (size_t)n_hot * LPL_CAMREC_H * sizeof(double2) + 16; }
-
-// K12' on the lane-per-landmark layout: back_substitute_joint (landmark_block.hpp:574-623) -- OpBackJoint's arithmetic
-// on e0_lpl_h's records (z = sigma * N_c inc, left in the record image by cam_apply_inc_h, and P of the linearisation
-// point).  First pass: H = Jl3^T Jl3 and Jl3^T (r + Jp inc); the lane solves for the damped increment and lifts it with
-// the landmark's tangent basis; second pass: the model cost change, summed per workgroup into part[blockIdx.x].
-template <bool ROBUST>
-__global__ __launch_bounds__(E0C_BLOCK) void backsub_lpl_h(Dp d, double* part) {
-  extern __shared__ double2 hot[];  // [n_hot][HOT_REC_H] records, then the tile counter
-  __shared__ double sh[E0C_BLOCK / 64];
-  const V2& v = d.v2;
-  const int cam0 = v.wg_cam_off[blockIdx.x];
-  const int n_hot = v.wg_cam_off[blockIdx.x + 1] - cam0;
-  int* grab_ctr = reinterpret_cast<int*>(hot + n_hot * LPL_CAMREC_H);
-  if (threadIdx.x == 0) *grab_ctr = 0;
-  const double2* rec_img = reinterpret_cast<const double2*>(d.hot_rec);
-  for (int i = threadIdx.x; i < n_hot * HOT_REC_H; i += E0C_BLOCK)
-    hot[(i / HOT_REC_H) * LPL_CAMREC_H + i % HOT_REC_H] =
-        rec_img[(size_t)v.wg_cams[cam0 + i / HOT_REC_H] * (HOT_REC_STRIDE / 2) + i % HOT_REC_H];
-  __syncthreads();
-  const int lane = threadIdx.x & 63;
-  const LplTiles T(v, grab_ctr, lane);
-  const int t_end = T.t_end;
-  int c_t = T.grab(), c_row0 = 0, c_k = 0, c_nh = 0, c_fl = 0;
-  if (c_t < t_end) T.info(c_t, c_row0, c_k, c_nh, c_fl);
-  LplStream2<ROBUST> rows;
-  rows.start(T, v, c_t, c_row0, c_k, c_t < t_end ? T.grab() : t_end);
-  // an observation's tile at the linearisation point and Jp * inc (z part of the record)
-  auto obs = [&](const LplRow& cur, const double4& X, const double4& s4, const double (&hw)[4], double hbeta, Hom& h,
-                 double (&jl4)[8], double (&jl3)[6], double& sw, double (&jpi)[2]) {
-    // (select of an LDS and a global pointer: flat_loads; the split form spills here, see lpl_pass)
-    const double2* hp = cur.cw >= 0 ? hot + lpl_cw_slot(cur.cw) * LPL_CAMREC_H
-                                    : rec_img + (size_t)(-2 - cur.cw) * (HOT_REC_STRIDE / 2);
-    double4 zz[3];
-    Cam P;
-    lpl_read12(hp, zz);
-    lpl_read_cam(hp + 6, P);
-    sw = ROBUST ? sqrt(cur.w) : 1.0;
-    h = hom_project(P, X, cur.uv.x, cur.uv.y);
-    hom_jl4(P, h, sw, s4, jl4);
-    jl3_of_jl4(jl4, hw, hbeta, jl3);
-    hom_jp_x(h, X, sw, zz, jpi);
-  };
-  double sc = 0;
-  while (c_t < t_end) {
-    const int lm = v.lm_of[(size_t)c_t * WAVE + lane];
-    const int sg = v.seg[(size_t)c_t * WAVE + lane];
-    const double4 X = v.lml[(size_t)c_t * WAVE + lane], s4 = v.lsc[(size_t)c_t * WAVE + lane];  // lane-ordered mirrors (V2)
-    double hw[4], hbeta;
-    house4(X, hw, hbeta);
-    double red[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (int j = 0; j < c_k; ++j) {
-      const LplRow cur = rows.next(T, v);
-      if (cur.cw == -1) continue;
-      Hom h;
-      double jl4[8], jl3[6], sw, jpi[2];
-      obs(cur, X, s4, hw, hbeta, h, jl4, jl3, sw, jpi);
-      acc_h6(red, jl3);
-      const double a0 = sw * h.r0 + jpi[0], a1 = sw * h.r1 + jpi[1];
-#pragma unroll
-      for (int m = 0; m < 3; ++m) red[6 + m] += jl3[m] * a0 + jl3[3 + m] * a1;
-    }
-    if (c_fl & 1) seg_reduce_steps<9>(red, lane, sg & 255, (sg >> 8) & 255, 4);
-    double dp[4] = {0, 0, 0, 0};
-    if (lm >= 0) {
-      OpBackJoint::delta4(d, X, red, dp);
-      double4 Xc = v.lmx[(size_t)c_t * WAVE + lane];
-      Xc.x += dp[0] * s4.x; Xc.y += dp[1] * s4.y; Xc.z += dp[2] * s4.z; Xc.w += dp[3] * s4.w;
-      v.lmx[(size_t)c_t * WAVE + lane] = Xc;  // the mirror stays current
-      if (lane == (sg & 255)) d.lms4[lm] = Xc;
-    }
-    for (int jj = 0; jj < c_k; ++jj) {
-      const LplRow cur = rows.next(T, v);
-      if (cur.cw == -1) continue;
-      Hom h;
-      double jl4[8], jl3[6], sw, jpi[2];
-      obs(cur, X, s4, hw, hbeta, h, jl4, jl3, sw, jpi);
-      const double rr[2] = {sw * h.r0, sw * h.r1};
-#pragma unroll
-      for (int r = 0; r < 2; ++r) {
-        const double ji = jpi[r] + (jl4[4 * r] * dp[0] + jl4[4 * r + 1] * dp[1] + jl4[4 * r + 2] * dp[2] + jl4[4 * r + 3] * dp[3]);
-        sc -= ji * (0.5 * ji + rr[r]);
-      }
-    }
-    c_t = rows.nx_t;
-    if (c_t < t_end) {
-      T.info(c_t, c_row0, c_k, c_nh, c_fl);
-      rows.ahead(T.grab());
-    }
-  }
-  double sv[1] = {sc};
-  block_sum<1, E0C_BLOCK>(sv, sh);
-  if (threadIdx.x == 0) part[blockIdx.x] = sv[0];
 }
 
 // K13' (linearizor_power_varproj.cpp:283-305) and the z = sigma * (N_c inc_c) needed by K12'.

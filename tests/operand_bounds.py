@@ -29,13 +29,13 @@ Step 1 (pOSE).  Per observation i of camera c and landmark l: h = [X_l; 1], (u, 
            any tree gamma_{n_c}.  bound = gamma_{n_c + 12} diag2 + sum_i 2 rho_i summand_i.  No observations: exactly 0.
   SIGMA    1 / (eps + sqrt(diag2)) (:2536): half of diag2's relative error, the root, the sum of two non-negative numbers,
            the division: E(diag2) / (2 diag2) + gamma_3.  diag2 = 0: 1 / eps to gamma_3.
-  JL SCALE OpLinearize (:769-803) and lpl_pass<0> (:1992-2019) square the entries of pose_jl (:279-294) with s = 1:
+  JL SCALE OpLinearize (:769-803) and lpl_pass<0> (povar_kernels_lpl.hpp:519-528) square the entries of pose_jl (:279-294) with s = 1:
            jl = (sb sw) (P0j - u P2j) 1: the entry a = P0j - u P2j is computed and may cancel, err(a) <= gamma_2 am,
            am = |P0j| + |u| |P2j|; cb = sb sw (dsb + rho + 1), cb a (1): err(jl) <= sb sw (gamma_7 + rho) am =: ejl (rows 2, 3:
            am = |P0j|, fewer roundings).  tot = sum of 4 n_l squares, any order (registers, a segmented scan, wave_sum of
            lm_long): E(tot) = sum 2 |jl| ejl + gamma_{4 n_l + 1} tot; s = 1 / (eps + sqrt(tot)): E(s) = s (E(tot) / (2 tot) +
            gamma_3).  set_jl_col_scaling(False): exactly 1.0.
-  HLL_INV  OpPrepare (:808-881) / prepare_lpl (:1535-1714): H = sum of the 4 n_l rows jl_a jl_b with the STORED scale in
+  HLL_INV  OpPrepare (:808-881) / prepare_lpl (povar_kernels_lpl.hpp:647-743): H = sum of the 4 n_l rows jl_a jl_b with the STORED scale in
            the entry, jl = cb a s_a: err(jl) <= sb sw s_a (gamma_8 + rho + E(s_a) / s_a) am =: ejl (the reference uses its
            own s).  E(H)_ab = sum (|jl_a| ejl_b + |jl_b| ejl_a) + gamma_{4 n_l + 1} sum |jl_a| |jl_b| (+ u (|H_aa| + lambda) for
            POWER_SCHUR_COMPLEMENT's lambda on the diagonal).  inv3 (:209-224) is cofactors over determinant; on absolute
@@ -715,7 +715,7 @@ def emulate_pose(p, form):
 def emulate_joint(p):
     """Every step-2 operand in fp64 in the kernels' operation order.  One form: OpLinearizeH / OpPrepareH and lpl_pass_h<0> /
     prepare_lpl_h share hom_project, hom_jl4, house4, jl3_of_jl4 and hom_q, and sqrt(w) of the stored weight
-    (prepare_lpl_h :1065, cm_gram_h :473-477) is the per-observation kernels' stored sqrt(w) bit for bit; only the order
+    (prepare_lpl_h povar_kernels_lpl.hpp:780, cm_gram_h :473-477) is the per-observation kernels' stored sqrt(w) bit for bit; only the order
     of the sums differs, which the bounds leave free.  Sums in row order."""
     c, lm = p.cam_idx, p.lm
     n = len(c)

@@ -17,9 +17,9 @@ COST (both steps).  e = error_weight(r2) (povar_kernels.hpp:235-247) per observa
   r, step 1   pose_residual (povar_kernels.hpp:264-277): m = sb (P0j - P2j u) (the product, the difference, sb: 3), dot4 with
               h (4): seven roundings, and sb = sqrt(1 - alpha), sa = sqrt(alpha) in fp64 (set_alpha, povar_lm.hip:200-203:
               gamma_2): err(r_k) <= gamma_9 rm_k, rm_k = sb (|P0| + |u| |P2|) . |h| (rows 2, 3: sa (|P0| . |h| + |u|), fewer
-              roundings).  OpError :745-765 and lpl_pass<1> :1734-1754 share it.
+              roundings).  OpError :745-765 and lpl_pass<1> (povar_kernels_lpl.hpp:477-556) share it.
   r, step 2   hom_project (povar_kernels_joint.hpp:25-35): r0 = x / z - u with rounding_bounds.weights_joint's err(x / z):
-              err(r0) <= gamma_4 xm / |z| + |x / z| (gamma_4 zm / |z| + 2 u) + u |u|.  OpErrorH :86-101, lpl_pass_h<1> :996-1011.
+              err(r0) <= gamma_4 xm / |z| + |x / z| (gamma_4 zm / |z| + 2 u) + u |u|.  OpErrorH :86-101, lpl_pass_h<1> (povar_kernels_lpl.hpp:565-634).
   r2          a sum of four (two) squares: E(r2) = 2 sum |r_k| err(r_k) + gamma_4 r2 (gamma_3 in step 2).
   NONE        e = 0.5 r2: exact scaling.
   HUBER       w = r2 < t^2 ? 1 : t / sqrt(r2), e = 0.5 (2 - w) w r2 = t sqrt(r2) - t^2 / 2 on the outlier branch: continuous
@@ -37,8 +37,8 @@ COST (both steps).  e = error_weight(r2) (povar_kernels.hpp:235-247) per observa
   valid_*     the observations with |z| >= 1e-5 (hom_project :33).  err(z) = gamma_4 zm; the helper asserts that no
               observation has ||z| - 1e-5| <= err(z), so the classification follows from the inputs.
 
-APPLIED STEP, step 1, POWER_VARPROJ (OpBackVarproj povar_kernels.hpp:1952-2014, backsub_lpl :1573-1678, cam_apply_inc mode 0
-:2421-2435).
+APPLIED STEP, step 1, POWER_VARPROJ (OpBackVarproj povar_kernels.hpp:1462-1524, backsub_lpl = backsub_lpl_body
+povar_kernels_lpl.hpp:853-901 with LplPose :324-388, cam_apply_inc mode 0 povar_kernels.hpp:1931-1945).
   cameras     s = inc sigma (1), P_new = P + s (1): E(P_new) = |inc| E(sigma) + u |inc sigma| + u |P_new|.
   inc'        (inc sigma) (1 / sigma): inc itself in exact arithmetic whatever sigma is; three roundings: gamma_3 |inc|.
   rows        pose_jl with scale 1 and s = 1 at P_new (:280-295): a = P0j - u P2j carries E(P_new) through
@@ -72,7 +72,8 @@ sqrt(w): (gamma_7 + rho) on sb sw (|d0| + |u| |d2|).  a = r + jpi (1), g = sum j
 operand_bounds), delta = -inv3 g, x_new = x + s delta: E = s E(delta) + |delta| E(s) + u |s delta| + u |x_new|.  Cameras:
 P + z, two roundings.  l_diff with ji = jpi + jl delta, r the stored weighted residual.
 
-APPLIED STEP, step 2 (OpBackJoint povar_kernels_joint.hpp:231-279, backsub_lpl_h :1040-1126, cam_apply_inc_h :1130-1145).
+APPLIED STEP, step 2 (OpBackJoint povar_kernels_joint.hpp:231-279, backsub_lpl_h = backsub_lpl_body
+povar_kernels_lpl.hpp:853-901 with LplJoint :390-453, cam_apply_inc_h povar_kernels_joint.hpp:662-677).
   z           p = N_c inc = [0; inc] - beta w (w[1:] . inc): an 11-term dot, two products, the difference: gamma_14, and the
               device's reflector against the reference's long-double one, dNc = gamma_45 (operand_bounds): E(p) =
               (gamma_14 + dNc) |N_c| |inc|; z = p sigma: E(z) = sigma E(p) + |p| E(sigma) + u |z|.  P_new = P + z: u |P_new|.
