@@ -73,6 +73,13 @@ Counts, from the kernel sources (u = the arithmetic's unit roundoff; an FMA roun
              rho_i    = err(r2) / (2 r2) + gamma_4      (w = t rsq(r2): rsq about 1 ulp, then Newton steps; t rounded once)
            i.e. rho ~ u (|P||h| + |t| + |uv||p2|) / |r|, not a few ulps, wherever |r| is small against its terms.  The same
            rho enters the forward and the backward C (both recompute w).
+           stored: series_res does not recompute the weight, it reads the one the linearisation left
+           (povar_kernels_res.hpp:442-447: V2::w, or the stored sqrt squared).  That one comes from pose_residual
+           (povar_kernels.hpp:264-277) and error_weight (:235-239): the entries sb (P0j - P2j u) of the merged row round three
+           times before the 4-term dot, so err(p_k) carries gamma_7 instead of gamma_4 (kp = 7); sa u rounds before it is
+           subtracted (k1 = 2: err(c) <= err(p0) + (duv + 2 u)(|p0| + |u|)); w = t / sqrt(r2) is er2 / 2 + 2 u, its stored sqrt
+           er2 / 4 + 2 u, the square of that er2 / 2 + 5 u (kw = 5 instead of 4).  Model "fp64_stored_w"; every other count
+           of the resident body is e0_ck's (ck_obs_forward, ck_obs_backward unchanged; tests/series_bounds.py cites the lines).
   floor    an absolute 2^-149 per fp32 operation (underflow to subnormals) added at each stage (2^-1074 for fp64).
   det      e0_ck_det sums u_l in 64-bit fixed point on the grid 2^(E + L - 61), 2^E > the largest |contribution| of the
            landmark (first walk), L = ceil(log2 n_l) (povar_kernels_ck_det.hpp:13): each of the n_l contributions rounds by
@@ -189,8 +196,9 @@ class Model:
     """The rounding model of one kernel family (module docstring)."""
 
     def __init__(self, name, u, form="C", u_lm=None, kf=12, kg=3, kb=8, dz=U64, dh=0.0, dp=0.0, dg=2 * U64, duv=0.0,
-                 dsb2=None, chunk32=False, det=False, eta=2.0 ** -1074):
+                 dsb2=None, chunk32=False, det=False, eta=2.0 ** -1074, kp=4, k1=1, kw=4):
         self.name, self.u, self.form = name, u, form
+        self.kp, self.k1, self.kw = kp, k1, kw  # (rho_i: the counts of the weight's residual -- module docstring)
         self.u_lm = u if u_lm is None else u_lm
         self.kf, self.kg, self.kb = kf, kg, kb
         self.dz, self.dh, self.dp, self.dg, self.duv = dz, dh, dp, dg, duv
@@ -202,6 +210,8 @@ class Model:
 MODELS = {
     # e0_lpl, e0_ck, E0Core (lane-per-observation implicit kernels): fp64 C-form
     "fp64": Model("fp64", U64),
+    # series_res (povar_kernels_res.hpp): the fp64 C-form with the STORED weight of the linearisation (rho_i: "stored")
+    "fp64_stored_w": Model("fp64_stored_w", U64, kp=7, k1=2, kw=5),
     # e0_ck_det: fp64 C-form, u_l in fixed point
     "det": Model("det", U64, det=True),
     # e0_ck_f32 (include/povar_hip.h: the fp32 contract)
@@ -255,18 +265,18 @@ def huber_rho(P, t, hx, uv, sb2, sa2, model):
     u, v = uv[:, 0], uv[:, 1]
     a, b, c, e = p[0] - u * p[2], p[1] - v * p[2], p[0] - u, p[1] - v
     r2 = sb2 * (a * a + b * b) + sa2 * (c * c + e * e)
-    kp = float(gam(4, model.u)) + model.dp + model.dh
+    kp = float(gam(model.kp, model.u)) + model.dp + model.dh
     ep = [kp * m for m in Pm]
     d2 = model.duv + float(gam(2, model.u))
     ea = ep[0] + np.abs(u) * ep[2] + d2 * (ab(p[0]) + np.abs(u) * ab(p[2]))
     eb = ep[1] + np.abs(v) * ep[2] + d2 * (ab(p[1]) + np.abs(v) * ab(p[2]))
-    d1 = model.duv + model.u
+    d1 = model.duv + model.k1 * model.u
     ec = ep[0] + d1 * (ab(p[0]) + np.abs(u))
     ee = ep[1] + d1 * (ab(p[1]) + np.abs(v))
     fs, fa = float(sb2), float(sa2)
     r2f = np.maximum(r2.astype(f), 1e-300)
     er2 = 2 * (fs * (ab(a) * ea + ab(b) * eb) + fa * (ab(c) * ec + ab(e) * ee)) + (float(gam(4, model.u)) + model.dsb2) * r2f
-    rho = er2 / (2 * r2f) + float(gam(4, model.u))
+    rho = er2 / (2 * r2f) + float(gam(model.kw, model.u))
     return rho, r2, er2 / r2f
 
 
