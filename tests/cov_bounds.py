@@ -1,5 +1,5 @@
 """Componentwise, condition-free bounds for the covariance path (povar_sc.hip: cov_inverse, cov_camera_blocks,
-landmark_covariance; povar_kernels_cov.hpp), stage by stage on the device's own intermediates (helper module of
+landmark_covariance, observation_covariance; povar_kernels_cov.hpp), stage by stage on the device's own intermediates (helper module of
 tests/test_cov_bounds.py and tests/test_gpu_cov_bounds.py; not a test module).  Conventions of sc_bounds.py: LD, g(k) rounded
 up, first order, a final factor 1 + 1e-6, `worst` / `flagged` for reporting.  The device's buffers: R = POVAR_BUF_COV_FACTOR
 (upper triangle), W = the upper triangle of POVAR_BUF_COV_INVERSE, C = its strictly lower 64 x 64 blocks and POVAR_BUF_COV_PANEL
@@ -71,6 +71,39 @@ LANDMARK  lm_cov (:372-539) with C_dev through cov_at, Q_dev and the staged oper
           (:522-534): first N_l Sigma N_l^T with the long-double house4 of the caller's X_l, its entries to g(25) (operand_bounds:
           dn) on |N_l|, the two three-term products (3 + 3), then the same scaling with the four s of the landmark.
           Given C this is condition-free.  Every block is symmetric bit for bit.
+OBSERVATION  obs_cov (:559-715) with C_dev through cov_at, the staged U_i, G_j of pieces_pose / pieces_joint (U, Um, EU; G, Gm, EG)
+          and Sigma_l = lm_cov's output with nq = 0 in solver coordinates: its long-double value from the same C and its bound
+          E(Sigma_l) are LANDMARK's (landmark_reference with Q = None).  Row of observation i of landmark l (k observations):
+              Syy_i = K_ii - R_i L_i^T - L_i R_i^T + L_i Sigma_l L_i^T,  K_ij = U_i C[c_i, c_j] U_j^T,  R_i = sum_j K_ij G_j,
+              h_i = sum_e (M_i)_e (Syy_i)_e,    [[c_uu, c_uv], [c_uv, c_vv]] = J Syy_i J^T,  J = [[iz, 0, j0], [0, iz, j1]].
+          K_ij (:619-630): lane gl sums its t_K = ceil(DIM^2 / 16) terms `K += u * cv * v`: two products and t_K additions, and for
+          DIM = 12 the products sigma h of lm_cov_u (:362) on either side (2): k_K = t_K + 2 (+ 2).  R_i (:634): the three-term dot
+          with G_j (3), `R +=` once per observation of the track, in every chunk (k), the four butterfly additions (:642-647: 4);
+          K_ii is copied (:635-638) and passes the butterfly only:
+              E(K_ii) = EU_i |C_ii| Um_i^T + Um_i |C_ii| EU_i^T + g(k_K + 4) Um_i |C_ii| Um_i^T,
+              E(R_i)  = sum_j ((EU_i |C_ij| Um_j^T + Um_i |C_ij| EU_j^T) Gm_j + Km_ij EG_j) + g(k_K + 7 + k) sum_j Km_ij Gm_j,
+          Km_ij = Um_i |C_ij| Um_j^T.  Lane 0's operands (:649-683), from the caller's cameras, points and image points and the
+          reference chain of operand_bounds, as sc_bounds' pieces take theirs:
+            y    four-term dots (:660): E(y) = g(4) |P| |h|.
+            L_i  DIM = 12 (:663): P3 diag(s): one product and E(s) / s.  DIM = 11 (:665-668): q4 = p4 s4 (1 and E(s) / s), the
+                 four-term `aw` (4), two products and the difference (3), house4 of the device against the long-double one to
+                 g(25) (operand_bounds: dn) on |N_l|^T |q4|:  EL = |N_l|^T (|q4| (u + E(s) / s)) + (g(8) + g(25)) |N_l|^T |q4|.
+            M_i  DIM = 12 (:672-676): sb sb (g(4) + 1, operand_bounds: dsb), cuv = sb2 (u u + v v) (+ 3: the longest entry), w = sw sw
+                 (1 and 2 rho), the product (1): EM = (g(10) + 2 rho) |M|.  DIM = 11 (:678-682): hom_project's D00, D02, D12 with the
+                 chain's magnitudes A and errors E (as pieces_joint), D02 D02 + D12 D12 (3), w = sw sw (1, 2 rho), the product (1):
+                 EM = w E(m9) + (g(5) + 2 rho) Mm,  E(m9) by the product rule on A, E.
+            J    iz = 1 / y2 (:704): r_z = E(y2) / |y2| + u;  j = -y iz iz (:705): E(j) = |j| (2 r_z + 2 u) + E(y) iz^2.
+          The final expression (:689-697): `SL` and `lsl` three-term dots (3 + 3), `rl`, `lr` (3 each), the three additions of `v`:
+              E(Syy) = E(K_ii) + (E(R) |L|^T + |R| EL^T + g(3) |R| |L|^T) + (.)^T
+                       + EL |Sigma| |L|^T + |L| |Sigma| EL^T + |L| E(Sigma) |L|^T + g(6) |L| |Sigma| |L|^T + g(3) Smag,
+              Smag   = |K_ii| + |R| |L|^T + |L| |R|^T + |L| |Sigma| |L|^T:
+          the four magnitudes stay apart, so what cancels between them in the free gauge is charged.  With Sa = |Syy| + E(Syy):
+              E(h)   = sum_e (Mm E(Syy) + EM Sa)_e + g(9) sum_e (Mm Sa)_e                                  (:703: nine terms)
+              E(A)   = |J| E(Syy) + EJ Sa + g(2) |J| Sa,    A = J Syy                                          (:706-707)
+              E(c)   = E(A) |J|^T + (|J| Sa) EJ^T + g(2) |J| Sa |J|^T                                          (:710-712).
+          Given C this is condition-free: the inputs are the caller's data, the chain's operand bounds and the device's C.
+          Exact: every entry is finite; a landmark requested twice returns the same bits.  Step 2's h and w (c_uu + c_vv) are
+          different expressions (M_i has D02^2 + D12^2 in one entry; c_* goes through J twice): nothing is asserted between them.
 
 Emulations (fp64 NumPy, the kernels' operation order, two summation orders) and the mutation list: at the end.
 """
@@ -403,6 +436,172 @@ def landmark_check(sy, Cs, Q, blocks, ids=None, coords=1):
     return {"landmark": (_ab(blocks.astype(LD) - ref), e * ONE), "exact": bad}
 
 
+# ======== OBSERVATION
+class ObsOperands:
+    """Per observation, long double with magnitudes and operand errors: y [n, 3], L, M [n, 3, 3], J [n, 2, 3]."""
+
+
+def observation_operands(sy):
+    """What lane 0 of obs_cov forms at :649-683 and :704-705, from the caller's inputs and the reference chain -- module
+    docstring: OBSERVATION.  Computed once per system."""
+    if hasattr(sy, "_obs_operands"):
+        return sy._obs_operands
+    import rounding_bounds as RB
+    p, u, ch = sy.p, sy.u, sy.R.aux["chain"]
+    c, lm = p.cam_idx, p.lm
+    n = len(c)
+    o = ObsOperands()
+    P = p.cams[c].reshape(n, 3, 4)
+    Pl, Pa = P.astype(LD), np.abs(P)
+    h, ha = sy.q.h, _ab(sy.q.h)
+    o.y = np.einsum("nxk,nk->nx", Pl, h)
+    o.Ey = g(4, u) * np.einsum("nxk,nk->nx", Pa, ha)
+    rho = ch["rho"]
+    if sy.dim == 12:
+        s, ds = ch["s"][lm], (ch["Es"] / _f(ch["s"]))[lm]
+        o.L = Pl[:, :, :3] * s[:, None, :]
+        o.La = _ab(o.L)
+        o.EL = o.La * (u + ds[:, None, :])
+        w, sb2 = ch["w"], ch["sb2"]
+        uv = p.obs.astype(LD)
+        C9 = np.zeros((n, 3, 3), dtype=LD)
+        C9[:, 0, 0] = C9[:, 1, 1] = 1
+        C9[:, 0, 2] = C9[:, 2, 0] = -sb2 * uv[:, 0]
+        C9[:, 1, 2] = C9[:, 2, 1] = -sb2 * uv[:, 1]
+        C9[:, 2, 2] = sb2 * (uv[:, 0] * uv[:, 0] + uv[:, 1] * uv[:, 1])
+        o.M = w[:, None, None] * C9
+        o.Mm = _ab(o.M)
+        o.EM = o.Mm * (g(10, u) + 2 * rho)[:, None, None]
+    else:
+        s = sy.R.ref["JL_COL_SCALE_H"].reshape(-1, 4)[lm]
+        ds = (sy.R.bound["JL_COL_SCALE_H"].reshape(-1, 4) / _f(sy.R.ref["JL_COL_SCALE_H"].reshape(-1, 4)))[lm]
+        q4 = Pl * s[:, None, :]
+        q4a = _ab(q4)
+        Eq4 = q4a * (u + ds[:, None, :])
+        lw, lb = RB.house4(p.lms.astype(LD))
+        lwo, lbo, lwa, lba = lw[lm], lb[lm], _ab(lw)[lm], _f(lb)[lm]
+        o.L = np.stack([RB._nt(lwo, lbo, q4[:, x]) for x in range(3)], 1)
+        o.La = _ab(o.L)
+        Lm = np.stack([RB._nt(lwa, lba, q4a[:, x], +1) for x in range(3)], 1)
+        o.EL = np.stack([RB._nt(lwa, lba, Eq4[:, x], +1) for x in range(3)], 1) + (g(8, u) + g(25, u)) * Lm
+        sw, D, A, E = ch["sw"], ch["D"], ch["A"], ch["E"]
+        w, wa = sw * sw, _f(sw) * _f(sw)
+        m9, mm, em = np.zeros((n, 3, 3), dtype=LD), np.zeros((n, 3, 3)), np.zeros((n, 3, 3))
+        m9[:, 0, 0] = m9[:, 1, 1] = D[0] * D[0]
+        mm[:, 0, 0] = mm[:, 1, 1] = A[0] * A[0]
+        em[:, 0, 0] = em[:, 1, 1] = 2 * A[0] * E[0]
+        for k in range(2):
+            m9[:, k, 2] = m9[:, 2, k] = D[0] * D[k + 1]
+            mm[:, k, 2] = mm[:, 2, k] = A[0] * A[k + 1]
+            em[:, k, 2] = em[:, 2, k] = A[0] * E[k + 1] + A[k + 1] * E[0]
+        m9[:, 2, 2] = D[1] * D[1] + D[2] * D[2]
+        mm[:, 2, 2] = A[1] * A[1] + A[2] * A[2]
+        em[:, 2, 2] = 2 * (A[1] * E[1] + A[2] * E[2])
+        o.M = w[:, None, None] * m9
+        o.Mm = wa[:, None, None] * mm
+        o.EM = wa[:, None, None] * em + (g(5, u) + 2 * rho)[:, None, None] * o.Mm
+    iz = 1 / o.y[:, 2]
+    iza = _ab(iz)
+    rz = o.Ey[:, 2] * iza + u
+    o.J, o.Ja, o.EJ = np.zeros((n, 2, 3), dtype=LD), np.zeros((n, 2, 3)), np.zeros((n, 2, 3))
+    for k in range(2):
+        jk = -o.y[:, k] * iz * iz
+        o.J[:, k, k], o.J[:, k, 2] = iz, jk
+        o.EJ[:, k, k], o.EJ[:, k, 2] = iza * rz, _ab(jk) * (2 * rz + 2 * u) + o.Ey[:, k] * iza * iza
+    o.Ja = _ab(o.J)
+    sy._obs_operands = o
+    return o
+
+
+def observation_reference(sy, Cs, ids=None, mutate=None):
+    """(rows [sum of the tracks of ids, 4] long double: h, c_uu, c_uv, c_vv per observation in the order of the call, their
+    bound) -- module docstring: OBSERVATION.  Cs: the symmetric [n, n] C of cov_at's reads (c_symmetric).  mutate:
+    reference-side defects: {"Q": the gauge basis} takes Sigma_l with the gauge correction, {"no_cross": True} drops R_i."""
+    mutate = mutate or {}
+    p, q, dim, u = sy.p, sy.q, sy.dim, sy.u
+    ids = np.arange(p.n_lms) if ids is None else np.asarray(ids)
+    o = observation_operands(sy)
+    Sig, ESig = landmark_reference(sy, Cs, mutate.get("Q"), ids)
+    tK = -(-dim * dim // 16)
+    kK = tK + 2 + (2 if dim == 12 else 0)
+    Cl, Ca = np.asarray(Cs, dtype=F).astype(LD), np.abs(np.asarray(Cs, dtype=F))
+    n_rows = int(p.n_l[ids].sum())
+    out, bound = np.zeros((n_rows, 4), dtype=LD), np.zeros((n_rows, 4))
+    r0 = 0
+    T = lambda A: A.transpose(0, 2, 1)
+    mm = lambda A, B: np.einsum("ixz,izy->ixy", A, B)
+    for t, l in enumerate(ids):
+        a, b, rows, _ = SB._lm_index(p, int(l), dim)
+        k = b - a
+        ix = np.ix_(rows, rows)
+        X, Xa = Cl[ix].reshape(k, dim, k * dim), Ca[ix].reshape(k, dim, k * dim)
+        U, Um, EU = q.U[a:b], q.Um[a:b], q.EU[a:b]
+        G, Gm, EG = q.G[a:b], q.Gm[a:b], q.EG[a:b]
+        # K[i, j] = U_i C_ij U_j^T and its magnitude / operand error, [k, k, 3, 3]
+        right = lambda Y, V: np.einsum("iajc,jbc->ijab", Y.reshape(k, 3, k, dim), V)
+        K = right(U @ X, U)
+        UmX = Um @ Xa
+        Km = right(UmX, Um)
+        EK = right(EU @ Xa, Um) + right(UmX, EU)
+        R = np.einsum("ijab,jbm->iam", K, G)
+        Rm = np.einsum("ijab,jbm->iam", Km, Gm)
+        ER = np.einsum("ijab,jbm->iam", EK, Gm) + np.einsum("ijab,jbm->iam", Km, EG) + g(kK + 7 + k, u) * Rm
+        if mutate.get("no_cross"):
+            R = np.zeros_like(R)
+        d = np.arange(k)
+        Kii, Kiim = K[d, d], Km[d, d]
+        EKii = EK[d, d] + g(kK + 4, u) * Kiim
+        L, La, EL = o.L[a:b], o.La[a:b], o.EL[a:b]
+        S, Sa_, ES = Sig[t][None], _ab(Sig[t])[None], ESig[t][None]
+        Ra = _ab(R)
+        RL, RLa = mm(R, T(L)), mm(Ra, T(La))
+        ERL = mm(ER, T(La)) + mm(Ra, T(EL)) + g(3, u) * RLa
+        LSL, LSLa = mm(mm(L, S), T(L)), mm(mm(La, Sa_), T(La))
+        ELSL = mm(mm(EL, Sa_), T(La)) + mm(mm(La, Sa_), T(EL)) + mm(mm(La, ES), T(La)) + g(6, u) * LSLa
+        Syy = Kii - RL - T(RL) + LSL
+        Smag = _ab(Kii) + RLa + T(RLa) + LSLa
+        ESyy = EKii + ERL + T(ERL) + ELSL + g(3, u) * Smag
+        # the long-double reference's own rounding: k dim-term dots on the same magnitudes
+        RmL = mm(Rm, T(La))
+        ESyy = ESyy + (k * (dim + 3) + 20) * ULD * (Kiim + RmL + T(RmL) + LSLa)
+        Sa = _ab(Syy) + ESyy
+        M, Mm, EM = o.M[a:b], o.Mm[a:b], o.EM[a:b]
+        lev = (M * Syy).sum((1, 2))
+        Elev = (Mm * ESyy + EM * Sa).sum((1, 2)) + (g(9, u) + 20 * ULD) * (Mm * Sa).sum((1, 2))
+        J, Ja, EJ = o.J[a:b], o.Ja[a:b], o.EJ[a:b]
+        A = mm(J, Syy)
+        Am = mm(Ja, Sa)
+        EA = mm(Ja, ESyy) + mm(EJ, Sa) + g(2, u) * Am
+        O = mm(A, T(J))
+        Om = mm(Am, T(Ja))
+        EO = mm(EA, T(Ja)) + mm(Am, T(EJ)) + (g(2, u) + 20 * ULD) * Om
+        out[r0:r0 + k] = np.stack([lev, O[:, 0, 0], O[:, 0, 1], O[:, 1, 1]], 1)
+        bound[r0:r0 + k] = np.stack([Elev, EO[:, 0, 0], EO[:, 0, 1], EO[:, 1, 1]], 1) * ONE
+        r0 += k
+    return out, bound
+
+
+def observation_check(sy, Cs, rows, ids=None, ref=None):
+    """{'observation_h': (err, bound) [rows], 'observation_c': (err, bound) [rows, 3], 'exact': messages} for the rows of one
+    call; ref: observation_reference's result for the same Cs and ids, when it is at hand."""
+    want, e = observation_reference(sy, Cs, ids) if ref is None else ref
+    rows = np.asarray(rows, dtype=F)
+    assert rows.shape == want.shape, (rows.shape, want.shape)
+    bad = []
+    if not np.all(np.isfinite(rows)):
+        bad.append("non-finite entries in the observation rows")
+    ids_ = np.arange(sy.p.n_lms) if ids is None else np.asarray(ids)
+    start = np.r_[0, np.cumsum(sy.p.n_l[ids_])]
+    first = {}
+    for t, l in enumerate(ids_.tolist()):
+        if l in first and not np.array_equal(rows[start[t]:start[t + 1]], rows[start[first[l]]:start[first[l] + 1]]):
+            bad.append(f"landmark {l} requested twice returns different bits")
+        first.setdefault(l, t)
+    err = _ab(rows.astype(LD) - want)
+    err = np.where(np.isfinite(rows), err, np.inf)
+    return {"observation_h": (err[:, 0], e[:, 0]), "observation_c": (err[:, 1:], e[:, 1:]), "exact": bad}
+
+
 # ======== fp64 emulations in the kernels' operation order (order 0: ascending sums, order 1: descending)
 def _dot(A, B, order):
     """A B with the inner index summed ascending (0) or descending (1)."""
@@ -619,6 +818,138 @@ def emulate_landmarks(p, q, inv, panel, Q, dim, order, ids=None, mutate=None):
     return out
 
 
+def _dot3(A, B, order):
+    """A B for 3 x 3 operands (leading axes broadcast) as the kernel's three-term dots: a0 b0 + a1 b1 + a2 b2 (order 1: from
+    the last term)."""
+    t = [A[..., :, z, None] * B[..., None, z, :] for z in (range(3) if order == 0 else range(2, -1, -1))]
+    return (t[0] + t[1]) + t[2]
+
+
+def emulate_observations(p, q, inv, panel, sig, dim, order, ids=None, mutate=None):
+    """obs_cov (:559-715) in fp64 from the staged operands q and `sig` = emulate_landmarks(.., Q=None) of the same ids: lane gl's
+    share e = gl, gl + 16, ... of every K_ij, the j walk over all chunks, the butterfly as a tree, lane 0's expressions.
+    Returns the rows [sum of the tracks, 4].  mutate -- one defect each (mutations_obs):
+      c_tile: (I, J)      the reads of that 64 x 64 tile of C scaled by 1 + 1e-10
+      sw_f32, iz_f32, r_f32: True   that quantity rounded to single precision
+      kii_any_chunk: l    K_ii copied at j == i of every chunk (the last one stays)
+      skip_last_j: l      the last j of a full chunk left out
+      unmasked: l         the groups with i >= ni of the last pass of 16 write the rows behind the track
+      stale_oj: l         oj not staged again at jc = 0 when ic advances"""
+    mutate = mutate or {}
+    ids = np.arange(p.n_lms) if ids is None else np.asarray(ids)
+    chunk = 64 if dim == 12 else 32
+    dd = dim * dim
+    trips = -(-dd // 16)
+    f32 = lambda x: np.asarray(x, dtype=np.float32).astype(F)
+    P = p.cams.reshape(-1, 3, 4)
+    sw = f32(q.sw) if mutate.get("sw_f32") else q.sw
+    if dim == 12:
+        s_all = q.em["JL_COL_SCALE"].reshape(-1, 3)
+        sb2 = q.sb * q.sb
+    else:
+        import rounding_bounds as RB
+        s_all = q.em["JL_COL_SCALE_H"].reshape(-1, 4)
+        lw, lb = RB.house4(p.lms)
+    inv_, panel_ = np.asarray(inv), np.asarray(panel)
+    n_rows = int(p.n_l[ids].sum())
+    out = np.zeros((n_rows, 4))
+    stray = []  # (row, values) written by an unmasked group: after everything else
+    seq = (lambda n: range(n)) if order == 0 else (lambda n: range(n - 1, -1, -1))
+    row0 = 0
+    for t, l in enumerate(ids.tolist()):
+        a, b = int(p.lm_off[l]), int(p.lm_off[l + 1])
+        k = b - a
+        cams = p.cam_idx[a:b]
+        oj = np.zeros(chunk, dtype=np.int64)  # the observation each entry of oj holds
+        staged = -1
+        for ic in range(0, k, chunk):
+            ni = min(chunk, k - ic)
+            for i0 in range(0, ni, 16):
+                last_pass = i0 + 16 >= ni
+                groups = range(i0, i0 + 16) if (mutate.get("unmasked") == l and last_pass and ic + chunk >= k) else range(i0, min(i0 + 16, ni))
+                partial = {}
+                for jc in range(0, k, chunk):
+                    nj = min(chunk, k - jc)
+                    if staged != jc:
+                        if not (mutate.get("stale_oj") == l and ic > 0 and jc == 0 and i0 == 0):
+                            oj[:nj] = jc + np.arange(nj)
+                        staged = jc
+                    nj_walk = nj - 1 if (mutate.get("skip_last_j") == l and nj == chunk) else nj
+                    js = oj[:nj_walk]
+                    for i in groups:
+                        oi = ic + (i if i < ni else i % ni)  # (an unmasked group reads what the entry held: modelled as i mod ni)
+                        r = dim * cams[oi] + np.arange(dim)
+                        cc = (dim * cams[js][:, None] + np.arange(dim)[None, :])  # [nj, dim]
+                        Cb = cov_at(inv_, panel_, r[None, :, None], cc[:, None, :])  # [nj, dim, dim]
+                        if "c_tile" in mutate:
+                            I, J = mutate["c_tile"]
+                            rr, c2 = np.maximum(r[None, :, None], cc[:, None, :]), np.minimum(r[None, :, None], cc[:, None, :])
+                            Cb = np.where(((rr >> 6) == I) & ((c2 >> 6) == J), Cb * (1 + 1e-10), Cb)
+                        Ui, Uj = q.U[a + oi], q.U[a + js]  # [3, dim], [nj, 3, dim]
+                        terms = (Ui[None, :, None, :, None] * Cb[:, None, None, :, :]) * Uj[:, None, :, None, :]  # [nj, x, y, r, c]
+                        x = np.zeros((len(js), 3, 3, trips * 16))
+                        x[..., :dd] = terms.reshape(len(js), 3, 3, dd)
+                        x = x.reshape(len(js), 3, 3, trips, 16)
+                        Kl = np.zeros((len(js), 3, 3, 16))
+                        for tr in seq(trips):
+                            Kl = Kl + x[:, :, :, tr, :]
+                        Kl = np.moveaxis(Kl, -1, 1)  # [nj, lane, 3, 3]
+                        KG = _dot3(Kl, q.G[a + js][:, None], order)
+                        Rl, Kii = partial.get(i, (np.zeros((16, 3, 3)), np.zeros((16, 3, 3))))
+                        for jj in seq(len(js)):
+                            Rl = Rl + KG[jj]
+                            if jj == (i if i < ni else -1) and (jc == ic or mutate.get("kii_any_chunk") == l):
+                                Kii = Kl[jj]
+                        partial[i] = (Rl, Kii)
+                for i in groups:
+                    Rl, Kii = partial[i]
+                    R = _tree(np.moveaxis(Rl, 0, -1), order)
+                    Kii = _tree(np.moveaxis(Kii, 0, -1), order)
+                    if mutate.get("r_f32"):
+                        R = f32(R)
+                    oi = ic + (i if i < ni else i % ni)
+                    o = a + oi
+                    Pc = P[cams[oi]]
+                    h = q.h[o]
+                    w = sw[o] * sw[o]
+                    yv = ((Pc[:, 0] * h[0] + Pc[:, 1] * h[1]) + Pc[:, 2] * h[2]) + Pc[:, 3] * h[3]
+                    if dim == 12:
+                        L = Pc[:, :3] * s_all[l][None, :]
+                        u_, v_ = p.obs[o]
+                        cu, cv, cuv = sb2 * u_, sb2 * v_, sb2 * (u_ * u_ + v_ * v_)
+                        Mi = w * np.array([[1, 0, -cu], [0, 1, -cv], [-cu, -cv, cuv]])
+                    else:
+                        q4 = Pc * s_all[l][None, :]
+                        aw = ((q4[:, 0] * lw[l, 0] + q4[:, 1] * lw[l, 1]) + q4[:, 2] * lw[l, 2]) + q4[:, 3] * lw[l, 3]
+                        L = q4[:, 1:] - (lb[l] * aw)[:, None] * lw[l, None, 1:]
+                        D00, D02, D12 = (x_[o] for x_ in q.D)
+                        Mi = w * np.array([[D00 * D00, 0, D00 * D02], [0, D00 * D00, D00 * D12],
+                                           [D00 * D02, D00 * D12, D02 * D02 + D12 * D12]])
+                    Sg = sig[t]
+                    SL = _dot3(Sg, L.T, order)
+                    rl, lr, lsl = _dot3(R, L.T, order), _dot3(L, R.T, order), _dot3(L, SL, order)
+                    Syy = Kii - rl - lr + lsl
+                    Syy = np.triu(Syy) + np.triu(Syy, 1).T
+                    lev = 0.0
+                    for e in seq(9):
+                        lev = lev + Mi.reshape(-1)[e] * Syy.reshape(-1)[e]
+                    iz = 1.0 / yv[2]
+                    if mutate.get("iz_f32"):
+                        iz = float(f32(iz))
+                    j0, j1 = -yv[0] * iz * iz, -yv[1] * iz * iz
+                    a0 = iz * Syy[0] + j0 * Syy[2]
+                    a1 = iz * Syy[1] + j1 * Syy[2]
+                    row = [lev, a0[0] * iz + a0[2] * j0, a0[1] * iz + a0[2] * j1, a1[1] * iz + a1[2] * j1]
+                    if i < ni:
+                        out[row0 + ic + i] = row
+                    elif row0 + ic + i < n_rows:
+                        stray.append((row0 + ic + i, row))
+        row0 += k
+    for r, row in stray:
+        out[r] = row
+    return out
+
+
 # ======== the cases of tests/test_cov_bounds.py and tests/test_gpu_cov_bounds.py
 def case_problem(name, step, robust="NONE", lam=0.0):
     """The operand_bounds problem of one covariance case: the state of tests/landmark_covariance_reference.py (step 1 with the
@@ -637,6 +968,11 @@ CASES = ([("small", s, "NONE", lam) for s in (1, 2) for lam in (0.0, 1e-4)] + [(
          [("long", s, "NONE", 0.0) for s in (1, 2)] + [("small", s, "HUBER", 0.0) for s in (1, 2)])
 
 
+# the cases of the OBSERVATION stage: the smallest shapes that reach every loop edge of obs_cov (`tracks`:
+# landmark_covariance_reference.TRACK_EDGES), the robust weight, the damped system
+OBS_CASES = ([("small", s, "NONE", lam) for s in (1, 2) for lam in (0.0, 1e-4)] + [("small", s, "HUBER", 0.0) for s in (1, 2)] +
+             [("medium", s, "NONE", lam) for s in (1, 2) for lam in (1e-4, 1.0)] + [("tracks", s, "NONE", 0.0) for s in (1, 2)])
+
 _SYS, _EMU = {}, {}
 
 
@@ -650,10 +986,10 @@ def system(name, step, robust, lam):
 
 
 def emulated(name, step, robust, lam, order):
-    """emulate_case of one case and summation order, computed once and left unchanged."""
+    """emulate_case of one case and summation order (the observation rows: on OBS_CASES), computed once and left unchanged."""
     key = (name, step, robust, lam, order)
     if key not in _EMU:
-        _EMU[key] = emulate_case(system(name, step, robust, lam).p, step == 2, order)
+        _EMU[key] = emulate_case(system(name, step, robust, lam).p, step == 2, order, obs=(name, step, robust, lam) in OBS_CASES)
     return _EMU[key]
 
 
@@ -675,9 +1011,10 @@ def pair_tile_counts(p, dim):
     return seen
 
 
-def emulate_case(p, joint, order, mutate=None):
+def emulate_case(p, joint, order, mutate=None, obs=True):
     """The whole chain in fp64: assembly (sc_bounds.emulate_assembly), Q Q^T, factor, inverse, camera blocks, C, landmark
-    blocks.  Returns a dict of what the device hands out: R, Q, inv, panel, cam, lm (solver coordinates) and the operands q."""
+    blocks, observation rows (obs; sig0: the Sigma_l without the gauge correction that obs_cov reads).  Returns a dict of what
+    the device hands out: R, Q, inv, panel, cam, lm (solver coordinates), obs and the operands q."""
     mutate = mutate or {}
     M, _, q = SB.emulate_assembly(p, joint, order)
     dim = q.dim
@@ -695,16 +1032,28 @@ def emulate_case(p, joint, order, mutate=None):
     cam = emulate_camera(W, Q, n, dim, order, mutate)
     inv, panel = emulate_lauum(W, order, mutate)
     lm = emulate_landmarks(p, q, inv, panel, Q, dim, order, mutate=mutate)
-    return dict(R=R, Q=Q, inv=inv, panel=panel, cam=cam, lm=lm, q=q, n=n, N=N, dim=dim)
+    d = dict(R=R, Q=Q, inv=inv, panel=panel, cam=cam, lm=lm, q=q, n=n, N=N, dim=dim)
+    if obs:  # obs_cov reads lm_cov's output with nq = 0 (povar_sc.hip:529), whatever the gauge
+        d["sig0"] = lm if Q is None else emulate_landmarks(p, q, inv, panel, None, dim, order)
+        d["obs"] = emulate_observations(p, q, inv, panel, d["sig0"], dim, order)
+    return d
 
 
 def check_all(sy, d, coords=1, ids=None):
     """Every check of the module docstring on one set of buffers (the device's, or emulate_case's): {check: (err, bound)} and
-    the list of exact facts that do not hold."""
+    the list of exact facts that do not hold.  The camera, landmark and observation checks run on what d holds of `cam`,
+    `lm` (both in `coords`) and `obs`: an observation call returns rows only."""
     out, bad = {}, []
-    for res in (assembly_check(sy, d["R"], d["Q"]), inverse_check(d["R"], d["inv"], sy.n),
-                camera_check(d["inv"], d["Q"], d["cam"], sy.n, sy.dim, coords, sy), lauum_check(d["inv"], d["panel"]),
-                landmark_check(sy, c_symmetric(d["inv"], d["panel"])[:sy.n, :sy.n], d["Q"], d["lm"], ids, coords)):
+    Cs = c_symmetric(d["inv"], d["panel"])[:sy.n, :sy.n]
+    stages = [assembly_check(sy, d["R"], d["Q"]), inverse_check(d["R"], d["inv"], sy.n)]
+    if "cam" in d:
+        stages.append(camera_check(d["inv"], d["Q"], d["cam"], sy.n, sy.dim, coords, sy))
+    stages.append(lauum_check(d["inv"], d["panel"]))
+    if "lm" in d:
+        stages.append(landmark_check(sy, Cs, d["Q"], d["lm"], ids, coords))
+    if "obs" in d:  # (the rows have no coordinates: gauge- and scaling-invariant)
+        stages.append(observation_check(sy, Cs, d["obs"], ids))
+    for res in stages:
         bad += res.pop("exact", [])
         out.update(res)
     if d["Q"] is not None:
@@ -744,3 +1093,65 @@ def mutations(d, p):
                 ("qqt_none", {"qqt": ("qqt_none", 2)}, "camera", cam_blk(2)),
                 ("t_group_skipped", {"t_group": l3}, "landmark", {9 * l3 + e for e in range(9)})]
     return out
+
+
+def obs_chunk(dim):
+    """SCD_CHUNK / SCDH_CHUNK (povar_kernels_sc.hpp): the staging chunk of obs_cov."""
+    return 64 if dim == 12 else 32
+
+
+def mutations_obs(sy, d):
+    """Plausible defects of obs_cov alone, applied to the emulated rows (emulate_observations' mutate; "corrected": Sigma_l
+    taken with the gauge correction, i.e. d["lm"] for d["sig0"]): (name, mutate, the checks that must report it, the rows of
+    an all-landmark call it touches).  Every buffer the other checks read stays as it is.  A mutation is listed where the
+    shape has what it needs (tests/test_cov_bounds.py asserts which shapes do)."""
+    p, dim, q = sy.p, sy.dim, d["q"]
+    chunk = obs_chunk(dim)
+    both, every = ("observation_h", "observation_c"), set(range(len(p.cam_idx)))
+    track = lambda l: set(range(int(p.lm_off[l]), int(p.lm_off[l + 1])))
+    blk = lambda c: {(dim * int(c)) // NB, (dim * int(c) + dim - 1) // NB}
+    out = [("iz_f32", {"iz_f32": True}, ("observation_c",), every), ("r_f32", {"r_f32": True}, both, every)]
+    # a tile of C off the diagonal that the pair (a camera across a 64-edge, a camera of an earlier block row) of some landmark reads
+    tile = None
+    for l in range(p.n_lms):
+        cams = p.cam_idx[p.lm_off[l]:p.lm_off[l + 1]]
+        for ca in cams:
+            lo = [cb for cb in cams if len(blk(ca)) == 2 and max(blk(cb)) < min(blk(ca))]
+            if lo and tile is None:
+                tile = (max(blk(ca)), max(blk(lo[0])))
+    if tile is not None:
+        rows = set()
+        for l in range(p.n_lms):
+            a, b = int(p.lm_off[l]), int(p.lm_off[l + 1])
+            in_i = np.array([tile[0] in blk(c) for c in p.cam_idx[a:b]])
+            in_j = np.array([tile[1] in blk(c) for c in p.cam_idx[a:b]])
+            if in_i.any() and in_j.any():
+                rows |= {a + int(i) for i in np.flatnonzero(in_i | in_j)}
+        out.append(("c_tile_1e-10", {"c_tile": tile}, both, rows))
+    if p.robust == "HUBER" and np.any(q.sw < 1):
+        out.append(("sw_f32", {"sw_f32": True}, ("observation_h",), set(np.flatnonzero(q.sw < 1).tolist())))
+    if d["Q"] is not None:
+        out.append(("corrected", {"corrected": True}, both, every))
+    k = p.n_l
+    two = np.flatnonzero((k > chunk) & (k <= 2 * chunk))
+    if len(two):  # (the rows i < k - chunk of the first chunk meet their own index again in the second one)
+        l = int(two[0])
+        out.append(("kii_any_chunk", {"kii_any_chunk": l}, both, {int(p.lm_off[l]) + i for i in range(int(k[l]) - chunk)}))
+    full = np.flatnonzero(k == chunk)
+    if len(full):
+        out.append(("skip_last_j", {"skip_last_j": int(full[0])}, both, track(int(full[0]))))
+    l17 = np.flatnonzero(k == 17)
+    if len(l17) and int(p.lm_off[l17[0] + 1]) < len(p.cam_idx):
+        l = int(l17[0])
+        out.append(("unmasked", {"unmasked": l}, both, {r for r in range(int(p.lm_off[l]) + 17, int(p.lm_off[l]) + 32) if r < len(p.cam_idx)}))
+    if k.max() > chunk:  # (the first pass of sixteen of every later chunk walks the chunk staged last)
+        l = int(np.argmax(k))
+        out.append(("stale_oj", {"stale_oj": l}, both,
+                    {int(p.lm_off[l]) + i for ic in range(chunk, int(k[l]), chunk) for i in range(ic, min(ic + 16, int(k[l])))}))
+    return out
+
+
+def emulate_obs_mutation(sy, d, order, mutate):
+    """The rows of an all-landmark call with one defect of mutations_obs, from the clean buffers of d (emulate_case)."""
+    sig = d["lm"] if mutate.get("corrected") else d["sig0"]
+    return emulate_observations(sy.p, d["q"], d["inv"], d["panel"], sig, sy.dim, order, mutate=mutate)

@@ -26,7 +26,37 @@ EPS = 1e-5
 LONG = (66, 300, 3000, 5)  # two landmarks of >= 65 observations, three of 33..64: both chunk loops of both stagings repeat
 
 
+# `tracks`: 66 cameras, every track length at which obs_cov's loops turn (povar_kernels_cov.hpp:597-648): the generator's
+# shortest track (2), the pass of 16 lanes groups (15, 16, 17), step 2's staging chunk of 32 (31, 32, 33), step 1's of 64
+# (63, 64, 65; 65 is also three chunks of step 2).  The track of 17 is followed by another landmark (the rows after it
+# exist).  The rest: eighty short tracks, so that every camera has the six observations its eleven step-2 parameters need.
+TRACK_EDGES = (2, 17, 15, 16, 31, 32, 33, 63, 64, 65)
+TRACKS = (66, 7)
+
+
+def _tracks_problem():
+    """A subgraph of the complete 66-camera graph of the generator with the prescribed track lengths (a seeded choice of the
+    cameras of every landmark, ascending), so the image points are the generator's own projections."""
+    from povar_amd import synth
+    n_c, seed = TRACKS
+    lengths = np.array(list(TRACK_EDGES) + [3 + i % 8 for i in range(80)])
+    full = synth.make_problem(n_c, len(lengths), n_c * len(lengths), seed=seed, popularity="uniform")
+    assert np.all(np.diff(full.lm_off) == n_c)
+    rng = np.random.default_rng(seed)
+    keep = np.concatenate([n_c * l + np.sort(rng.choice(n_c, size=k, replace=False)) for l, k in enumerate(lengths)])
+    lm_off = np.zeros(len(lengths) + 1, dtype=np.int32)
+    np.cumsum(lengths, out=lm_off[1:])
+    # the generator's cameras have the third row (0, 0, 0, 1): y2 = 1 and 1 / y2 would be exact in every precision in step 1
+    cams = full.cams.copy()
+    cams[:, 8:11] = np.round(0.02 * rng.normal(size=(n_c, 3)), 6)
+    cams[:, 11] = np.round(1 + 0.1 * rng.normal(size=n_c), 6)
+    return synth.Problem(n_c, len(lengths), lm_off, np.ascontiguousarray(full.cam_idx[keep]), np.ascontiguousarray(full.obs[keep]),
+                         cams, full.lms)
+
+
 def problem(name):
+    if name == "tracks":
+        return _tracks_problem()
     if name == "long":
         from povar_amd import synth
         n_c, n_l, n_o, seed = LONG

@@ -458,6 +458,7 @@ def _emu_pieces_pose(p):
     m = np.stack([w, w * U, w * V, w * (U * U + V * V)], 1)
     Gm = OB._add_at(p.n_cams, c, m[:, :, None, None] * (h[:, :, None] * h[:, None, :])[:, None])
     q.h, q.em, q.sig, q.hpp = h, em, sig, OB._hpp_pose(Gm, sb2)
+    q.sw, q.sb = sw, sb  # (what obs_cov's lane 0 reads again: cov_bounds.emulate_observations)
     return q
 
 
@@ -496,6 +497,7 @@ def _emu_pieces_joint(p):
     ww = sw * sw
     m = np.stack([ww * D00 * D00, ww * D00 * D02, ww * D00 * D12, ww * (D02 * D02 + D12 * D12)], 1)
     q.h, q.em, q.sig, q.ncw = X, em, sig, ncw
+    q.sw, q.D = sw, (D00, D02, D12)  # (what obs_cov's lane 0 reads again: cov_bounds.emulate_observations)
     q.hpp = _hpp_joint(OB._add_at(p.n_cams, c, m[:, :, None, None] * (X[:, :, None] * X[:, None, :])[:, None]))
     return q
 

@@ -17,6 +17,20 @@
   a tile of C perturbed by 1e-10 relative (0.11 of the landmark bound) while LAUUM rejects it at 1.4e4 times its bound.  No
   structural mutation passes the normwise bounds on that case (small, step 1, free gauge), and the perturbed tile of W misses
   the camera bound by a factor 2.4; the stage checks reject every one of them by 1e3 .. 1e14.
+* OBSERVATION (obs_cov's rows; cov_bounds.OBS_CASES: small free / damped / HUBER, medium damped, tracks): both emulated orders
+  stay inside the bound on every entry of every row, all-landmark call and id list (reversed, one landmark twice); worst
+  err / bound h 0.0072, c_* 0.013 (medium, step 1, lambda 1).  In the free gauge |sum h_i - rank J| <= 6.8e-13 against a summed
+  bound of 2.5e-7 .. 6.6e-6.  The new bound over the normwise one of tests/observation_covariance_reference.py on the same
+  entries, median (largest), information only -- step 1: small 7.4e-4 (1.6), lambda 1e-4 6.1e-7 (2.2e-3), HUBER 7.4e-4 (1.9),
+  medium 1e-4 1.3e-7 (6.3), 1 1.6e-6 (35), tracks 5.5e-5 (0.049); step 2: small 0.043 (235), lambda 1e-4 9.3e-4 (5.2), HUBER 0.039
+  (213), medium 1e-4 1.6e-5 (2.1e3), 1 0.14 (7.5), tracks 1.4e-4 (6.1).  Where it is the wider one a small y2 or the charged
+  cancellation of the free gauge dominates the entry.
+* The nine mutations of cov_bounds.mutations_obs are reported on the rows and in the columns they touch and nowhere else.
+  Seen (both steps unless said): tracks: c_tile_1e-10, iz_f32, r_f32, corrected, kii_any_chunk, skip_last_j, unmasked, stale_oj;
+  small HUBER: sw_f32, r_f32, corrected, iz_f32 (step 2); small lambda 1e-4: r_f32, iz_f32 (step 2).  iz_f32 changes nothing on
+  small in step 1 (the generator's cameras have y2 = 1: 1 / y2 is exact), which is why tracks' cameras have another third
+  row.  err / bound on the touched rows, new | normwise: c_tile_1e-10 3.1 .. 3.8 | 2.8e-4 .. 3.2e-4; iz_f32 1.4e2 .. 7.4e5 | 0.018 ..
+  4.0e2; r_f32 5.5e3 .. 1.4e5 | 0.056 .. 4.0e2; sw_f32 3.5e3 .. 4.7e4 | 12 .. 122; the structural ones 4e9 .. 2e12 | 2e5 .. 4e8.
 """
 from fractions import Fraction
 
@@ -144,6 +158,7 @@ def test_both_emulation_orders_stay_inside_every_bound(name, step, robust, lam):
         # the maps to the parameters' own coordinates (cov_finish, lm_cov) on the same blocks
         q = d["q"]
         d0 = dict(d, cam=CB.emulate_camera_coords(d["cam"], q.sig, getattr(q, "ncw", None), sy.dim), lm=CB.emulate_landmark_coords(d["lm"], q, sy.p))
+        d0.pop("obs", None)  # (the rows have no coordinates: checked once, above)
         out0, bad0 = CB.check_all(sy, d0, coords=0)
         _report(f"{name} step {step} order {order} own coordinates", {k: out0[k] for k in ("camera", "landmark")}, bad0)
 
@@ -158,7 +173,7 @@ def test_every_mutation_is_reported_on_the_entries_it_touches(name, step, robust
     muts = CB.mutations(clean, sy.p)
     assert len(muts) >= 10
     for mname, mutate, check, expected in muts:
-        d = CB.emulate_case(sy.p, step == 2, 0, mutate)
+        d = CB.emulate_case(sy.p, step == 2, 0, mutate, obs=False)  # (obs_cov's own mutations: at the end of this module)
         out, bad = CB.check_all(sy, d)
         assert not bad, (mname, bad)
         for k, (err, bound) in out.items():
@@ -196,7 +211,7 @@ def test_the_normwise_bounds_accept_what_the_stage_checks_reject():
     assert normwise_accepts(clean)[0]
     accepted = []
     for mname, mutate, check, expected in CB.mutations(clean, sy.p):
-        d = CB.emulate_case(sy.p, False, 0, mutate)
+        d = CB.emulate_case(sy.p, False, 0, mutate, obs=False)
         ok, rl, rc = normwise_accepts(d)
         out, _ = CB.check_all(sy, d)
         rejected = bool(CB.flagged(*out[check]))
@@ -210,3 +225,138 @@ def test_the_normwise_bounds_accept_what_the_stage_checks_reject():
     # each of them moves some block by far more than n u cond |A^-1|.  The perturbation case is the demonstration kept.
     # (when this was written they accepted nothing else: GAP lines above)
     assert "c_tile_1e-10" in accepted, accepted
+
+
+# ======== OBSERVATION: obs_cov's rows (module docstring, last item)
+def _obs_id(c):
+    return f"{c[0]}-{c[1]}-{c[2]}-{c[3]:g}"
+
+
+def _old_reference(name, step, robust, lam):
+    """The long-double Schur-route rows and the normwise bound tests/test_gpu_observation_covariance.py holds the rows to."""
+    import observation_covariance_reference as OC
+    return OC.reference(name, step, robust, lam, lam == 0.0)
+
+
+def _id_list(p):
+    """Reversed order, one landmark twice: row0 and ids index differently from the workgroup's number."""
+    k = p.n_l
+    pick = sorted({int(np.argmax(k)), int(np.argmin(k)), p.n_lms - 1, 0, int(np.flatnonzero(k >= 3)[0])})
+    return np.array(pick[::-1] + [pick[-1]], dtype=np.int32)
+
+
+def _assert_shape_reaches_the_loop_edges(name, step, sy):
+    """What each shape is there for, asserted on the shape itself (obs_cov :597-648)."""
+    import landmark_covariance_reference as L
+    p, dim = sy.p, sy.dim
+    chunk = CB.obs_chunk(dim)
+    k = set(p.n_l.tolist())
+    assert {1, 2, 4} <= CB.pair_tile_counts(p, dim)
+    # a camera across a 64-edge in a track with another camera: all k^2 pairs are walked, so it is the i and the j of pairs
+    # whose blocks lie on two tiles, and its own block on four
+    strad = {c for c in range(p.n_cams) if (dim * c) // 64 != (dim * c + dim - 1) // 64}
+    assert any(len(set(p.cam_idx[a:b].tolist()) & strad) and b - a >= 2 for a, b in zip(p.lm_off[:-1], p.lm_off[1:]))
+    if name in ("small", "tracks"):
+        assert min(k) == 2  # the shortest track the generator makes (synth._degrees)
+    if name == "tracks":
+        assert set(L.TRACK_EDGES) <= k and {15, 16, 17} <= k  # the pass of 16 groups (`live`)
+        assert {chunk - 1, chunk, chunk + 1} <= k  # 63, 64, 65 (step 1) or 31, 32, 33 (step 2)
+        assert sy.N <= 832
+        assert np.any(CB.observation_operands(sy).y[:, 2] != 1)  # (1 / y2 is not exact: the rounding of iz can show in step 1 too)
+        if step == 2:
+            assert max(k) > 2 * chunk  # three chunks: oj is staged again in every pass, `staged` carries over from one ic to the next
+    if sy.p.robust == "HUBER":
+        assert np.any(CB.emulated(name, step, "HUBER", 0.0, 0)["q"].sw < 1)
+
+
+@pytest.mark.parametrize("name,step,robust,lam", CB.OBS_CASES, ids=[_obs_id(c) for c in CB.OBS_CASES])
+def test_observation_rows_of_both_emulation_orders_stay_inside_the_bound(name, step, robust, lam):
+    """Every entry of every row, both summation orders, an id list with a duplicate; in the free gauge sum h_i = rank J inside
+    the summed bound; the gain over the normwise bound of the end-to-end test (printed: information, not a threshold)."""
+    sy = system(name, step, robust, lam)
+    p = sy.p
+    _assert_shape_reaches_the_loop_edges(name, step, sy)
+    n_obs = len(p.cam_idx)
+    ids = _id_list(p)
+    old = _old_reference(name, step, robust, lam)
+    for order in (0, 1):
+        d = emulated(name, step, robust, lam, order)
+        tag = f"{name} step {step} {robust} lambda {lam:g} order {order}"
+        if (name, step, robust, lam) in CB.CASES:  # (every other stage of these: test_both_emulation_orders_stay_inside_every_bound)
+            res = CB.observation_check(sy, CB.c_symmetric(d["inv"], d["panel"])[:sy.n, :sy.n], d["obs"])
+            bad = res.pop("exact")
+            out = res
+        else:
+            out, bad = CB.check_all(sy, d)
+        assert out["observation_h"][0].shape == (n_obs,) and out["observation_c"][0].shape == (n_obs, 3)  # no entry skipped
+        _report(tag, out, bad)
+        if lam == 0.0:
+            rank = sy.n + 3 * p.n_lms - d["Q"].shape[1]
+            assert rank == old.rank
+            gap, room = abs(float(d["obs"][:, 0].sum()) - rank), float(out["observation_h"][1].sum())
+            print(f"OBSRANK {tag}: |sum h - {rank}| = {gap:.3g}, summed bound {room:.3g}")
+            assert gap <= room
+        # the id list: reversed, one landmark twice, each row against its own landmark
+        sig = CB.emulate_landmarks(p, d["q"], d["inv"], d["panel"], None, sy.dim, order, ids=ids)
+        rows = CB.emulate_observations(p, d["q"], d["inv"], d["panel"], sig, sy.dim, order, ids=ids)
+        res = CB.observation_check(sy, CB.c_symmetric(d["inv"], d["panel"])[:sy.n, :sy.n], rows, ids)
+        _report(tag + " id list", {k: v for k, v in res.items() if k != "exact"}, res["exact"])
+        start = np.r_[0, np.cumsum(p.n_l[ids])]
+        for t, l in enumerate(ids):  # (and the same bits as the all-landmark call: a row depends on its landmark alone)
+            assert np.array_equal(rows[start[t]:start[t + 1]], d["obs"][p.lm_off[l]:p.lm_off[l + 1]])
+    new = np.concatenate([out["observation_h"][1][:, None], out["observation_c"][1]], 1)
+    ratio = new / old.bound
+    print(f"OBSGAIN {name} step {step} {robust} lambda {lam:g}: new bound / normwise bound median {np.median(ratio):.3g}, largest {ratio.max():.3g}")
+
+
+def test_a_reference_side_defect_is_reported_on_clean_rows():
+    """The long-double formula of observation_reference itself: with Sigma_l taken with the gauge correction, or the cross
+    term dropped, the clean emulated rows leave the bound (small, step 1, free gauge)."""
+    case = ("small", 1, "NONE", 0.0)
+    sy, d = system(*case), emulated(*case, 0)
+    Cs = CB.c_symmetric(d["inv"], d["panel"])[:sy.n, :sy.n]
+    for mutate in ({"Q": d["Q"]}, {"no_cross": True}):
+        res = CB.observation_check(sy, Cs, d["obs"], ref=CB.observation_reference(sy, Cs, mutate=mutate))
+        assert CB.flagged(*res["observation_h"]) and CB.flagged(*res["observation_c"]), mutate.keys()
+
+
+@pytest.mark.parametrize("step", [1, 2])
+def test_every_observation_mutation_is_reported_on_the_rows_it_touches(step):
+    """cov_bounds.mutations_obs on `tracks` (the loop edges, a camera across a 64-edge, the free gauge), `small` with HUBER (a
+    weight below 1) and `small` damped.  Each defect lives in obs_cov alone: the buffers every other check of check_all reads
+    are those of the clean chain, which the test above holds inside every bound.  Reported: on the rows it touches and no
+    other, in the columns it touches and no other.  Printed per case: err / bound under the new bound and under the normwise
+    bound of tests/observation_covariance_reference.py (against the long-double Schur route) on the touched rows: the second
+    column says what the suite could see before."""
+    cases = [("tracks", step, "NONE", 0.0), ("small", step, "HUBER", 0.0), ("small", step, "NONE", 1e-4)]
+    seen, unseen = {}, {}
+    for name, step, robust, lam in cases:
+        sy, d = system(name, step, robust, lam), emulated(name, step, robust, lam, 0)
+        Cs = CB.c_symmetric(d["inv"], d["panel"])[:sy.n, :sy.n]
+        ref = CB.observation_reference(sy, Cs)
+        clean = CB.observation_check(sy, Cs, d["obs"], ref=ref)
+        assert not clean["exact"] and not CB.flagged(*clean["observation_h"]) and not CB.flagged(*clean["observation_c"])
+        old = _old_reference(name, step, robust, lam)
+        for mname, mutate, checks, touched in CB.mutations_obs(sy, d):
+            assert touched, mname
+            rows = CB.emulate_obs_mutation(sy, d, 0, mutate)
+            res = CB.observation_check(sy, Cs, rows, ref=ref)
+            hit = {"observation_h": CB.flagged(*res["observation_h"]), "observation_c": {i // 3 for i in CB.flagged(*res["observation_c"])}}
+            for check in hit:
+                if check not in checks:
+                    assert not hit[check], f"{name} step {step} {mname}: {check} reports rows {sorted(hit[check])[:5]}"
+                assert hit[check] <= touched, f"{name} step {step} {mname}: {check} reports rows it does not touch: {sorted(hit[check] - touched)[:5]}"
+            t = sorted(touched)
+            cols = [0] if checks == ("observation_h",) else [1, 2, 3] if checks == ("observation_c",) else [0, 1, 2, 3]
+            e_new = np.concatenate([res["observation_h"][0][:, None], res["observation_c"][0]], 1)[np.ix_(t, cols)]
+            b_new = np.concatenate([res["observation_h"][1][:, None], res["observation_c"][1]], 1)[np.ix_(t, cols)]
+            e_old = np.abs((rows.astype(np.longdouble) - old.rows).astype(F))[np.ix_(t, cols)]
+            ok = all(hit[c] for c in checks)
+            print(f"OBSMUTATION {name} step {step} {robust} lambda {lam:g} {mname}: err / bound new {CB.worst(e_new, b_new)[0]:.3g}, "
+                  f"normwise {CB.worst(e_old, old.bound[np.ix_(t, cols)])[0]:.3g}; reported on {len(hit['observation_h'])} h rows, "
+                  f"{len(hit['observation_c'])} c rows of {len(touched)} touched{'' if ok else ' -- NOT SEEN on this case'}")
+            (seen if ok else unseen).setdefault(mname, []).append(name + " " + robust)
+    want = {"c_tile_1e-10", "sw_f32", "iz_f32", "r_f32", "corrected", "kii_any_chunk", "skip_last_j", "unmasked", "stale_oj"}
+    assert want <= set(seen) | set(unseen), "a mutation of the list found no shape"
+    print(f"OBSMUTATION step {step}: seen {seen}; not seen {unseen}")
+    assert want <= set(seen), f"not seen on any case of step {step}: {sorted(want - set(seen))}"

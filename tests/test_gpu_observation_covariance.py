@@ -10,6 +10,8 @@ bound is not tightened to it.  In the free gauge every case also checks sum_i h_
 
 Two calls on one context do not invert the same bits (the assembly of S adds with atomics), so rows of different calls are
 compared inside the bound; rows of one call are compared bit for bit.
+The kernel itself (obs_cov) is held entry by entry to a condition-free bound on the C of its own call by the OBSERVATION stage
+of tests/cov_bounds.py (tests/test_gpu_cov_bounds.py); this module stays the end-to-end check against an independent route.
 """
 import ctypes as C
 import os
