@@ -523,3 +523,18 @@ void p2p_dp(povar_ctx* c, Dp& dt);  // povar_comm.hip
 int ensure_sc(povar_ctx* c);  // povar_sc.hip
 int e0_dense(povar_ctx* c);  // povar_sc.hip
 int run_cholesky(povar_ctx* c, int dim, int32_t* num_iterations, int32_t* termination);  // povar_sc.hip (dim: 12 step 1, 11 step 2)
+
+// Geometry of the augmented dense matrix of CHOLESKY / RICHOLESKY and the covariance calls (povar_kernels_chol.hpp): n = dim *
+// n_cams rows, N = n rounded up to the 64-row panel, row stride ld, and the doubles of the allocation (slack rows / columns for
+// the 128 x 128 update tiles)
+struct DenseDims {
+  int n, N;
+  int64_t ld;
+  size_t count;
+};
+inline DenseDims dense_dims(int dim, int n_cams) {
+  const int n = dim * n_cams;
+  const int N = (n + CH_NB - 1) / CH_NB * CH_NB;
+  const int64_t ld = (int64_t)N + CH_T;
+  return {n, N, ld, (size_t)(N + CH_NB) * (size_t)ld};
+}

@@ -85,12 +85,71 @@ POVAR_KERNEL __launch_bounds__(128) void chol_trsm(double* M, int64_t ld, int k0
   for (int i = 0; i < CH_NB; ++i) col[(int64_t)i * ld] = s[i];
 }
 
+// One 64 x 64 fp64 product tile, C = sum_k A_k B_k over 64 x 64 operand blocks staged in LDS: what chol_syrk, cov_trmm and
+// cov_lauum (povar_kernels_cov.hpp) share.  4 wavefronts per workgroup of 256, each a 32 x 32 quadrant = 2 x 2 MFMA tiles
+// (v_mfma_f64_16x16x4_f64); fragments: A (16x4): lane l holds A[i + (l & 15)][kk + (l >> 4)], B (4x16): B[kk + (l >> 4)][j + (l & 15)],
+// D: col = l & 15, row = (l >> 4) + 4 reg.  The LDS arrays, their strides and the global fetch stay in the kernels.
+struct Mma64 {
+  static constexpr int NLD = CH_NB * CH_NB / 2 / 256;  // double2 per thread and operand
+  int wi, wj, lr, lc;  // the wavefront's quadrant, the lane's place in a fragment
+  ch_d4 acc[2][2];
+  __device__ __forceinline__ Mma64() {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    wi = (w >> 1) * 32, wj = (w & 1) * 32;
+    lr = lane >> 4, lc = lane & 15;
+#pragma unroll
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+      for (int y = 0; y < 2; ++y) acc[x][y] = ch_d4{0, 0, 0, 0};
+  }
+  // element u of a thread's share of a 64 x 64 block: row p, columns q and q + 1
+  __device__ static __forceinline__ void share(int u, int& p, int& q) {
+    const int e = threadIdx.x + 256 * u;
+    p = e >> 5, q = (e & 31) * 2;
+  }
+  // registers to LDS, both operands as they lie in memory: As[p][q] = row p, column q of the fetched block
+  template <int SA, int SB>
+  __device__ static __forceinline__ void stage(double (&As)[CH_NB][SA], double (&Bs)[CH_NB][SB], const double2 (&ra)[NLD],
+                                               const double2 (&rb)[NLD]) {
+#pragma unroll
+    for (int u = 0; u < NLD; ++u) {
+      int p, q;
+      share(u, p, q);
+      As[p][q] = ra[u].x; As[p][q + 1] = ra[u].y;
+      Bs[p][q] = rb[u].x; Bs[p][q + 1] = rb[u].y;
+    }
+  }
+  // acc += A B over the 64 staged K.  *_ALONG_ROWS: K runs along the rows of that LDS array (As[k][i]), else along its columns
+  template <bool A_ALONG_ROWS, bool B_ALONG_ROWS, int SA, int SB>
+  __device__ __forceinline__ void mma(const double (&As)[CH_NB][SA], const double (&Bs)[CH_NB][SB]) {
+#pragma unroll 4
+    for (int kk = 0; kk < CH_NB; kk += 4) {
+      const double a0 = A_ALONG_ROWS ? As[kk + lr][wi + lc] : As[wi + lc][kk + lr];
+      const double a1 = A_ALONG_ROWS ? As[kk + lr][wi + 16 + lc] : As[wi + 16 + lc][kk + lr];
+      const double b0 = B_ALONG_ROWS ? Bs[kk + lr][wj + lc] : Bs[wj + lc][kk + lr];
+      const double b1 = B_ALONG_ROWS ? Bs[kk + lr][wj + 16 + lc] : Bs[wj + 16 + lc][kk + lr];
+      acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
+      acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
+      acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
+      acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
+    }
+  }
+  // fn(row, col, value) for the lane's sixteen entries of the tile
+  template <class F>
+  __device__ __forceinline__ void store(F fn) const {
+#pragma unroll
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+      for (int y = 0; y < 2; ++y)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) fn(wi + 16 * x + lr + 4 * r, wj + 16 * y + lc, acc[x][y][r]);
+  }
+};
+
 // Rows of the current 256-block below the panel at k0: C -= R12^T R12 on the upper block triangle
 // (including the rhs tile).  grid = (n_jt, n_it) with n_it limited to the block's remaining panels;
-// tile (it, jt) with jt >= it covers rows k1 + 64 it, columns k1 + 64 jt.
-// 4 wavefronts per workgroup, each a 32 x 32 quadrant = 2 x 2 MFMA tiles; fragments:
-// A (16x4): lane l holds panel[kk + (l >> 4)][i + (l & 15)], B likewise with j, D: col = l & 15,
-// row = (l >> 4) + 4 reg.
+// tile (it, jt) with jt >= it covers rows k1 + 64 it, columns k1 + 64 jt.  Both operands are columns of the row panel:
+// K along the rows of both LDS tiles.
 POVAR_KERNEL __launch_bounds__(256) void chol_syrk(double* M, int64_t ld, int k0) {
   const int it = blockIdx.y, jt = blockIdx.x;
   if (jt < it) return;
@@ -99,6 +158,7 @@ POVAR_KERNEL __launch_bounds__(256) void chol_syrk(double* M, int64_t ld, int k0
   const int k1 = k0 + CH_NB;
   const int64_t i0 = (int64_t)k1 + (int64_t)it * CH_NB, j0 = (int64_t)k1 + (int64_t)jt * CH_NB;
   const double* pan = M + (int64_t)k0 * ld;
+  // (global to LDS in one rolled loop, no register stage: there is one K step and nothing to overlap the loads with)
   for (int e = threadIdx.x; e < CH_NB * CH_NB / 2; e += 256) {
     const int p = e >> 5, q = (e & 31) * 2;
     const double2 a = *reinterpret_cast<const double2*>(pan + (int64_t)p * ld + i0 + q);
@@ -107,32 +167,9 @@ POVAR_KERNEL __launch_bounds__(256) void chol_syrk(double* M, int64_t ld, int k0
     Bs[p][q] = b.x; Bs[p][q + 1] = b.y;
   }
   __syncthreads();
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int wi = (w >> 1) * 32, wj = (w & 1) * 32;
-  const int lr = lane >> 4, lc = lane & 15;
-  ch_d4 acc[2][2];
-#pragma unroll
-  for (int x = 0; x < 2; ++x)
-#pragma unroll
-    for (int y = 0; y < 2; ++y) acc[x][y] = ch_d4{0, 0, 0, 0};
-#pragma unroll 4
-  for (int kk = 0; kk < CH_NB; kk += 4) {
-    const double a0 = As[kk + lr][wi + lc], a1 = As[kk + lr][wi + 16 + lc];
-    const double b0 = Bs[kk + lr][wj + lc], b1 = Bs[kk + lr][wj + 16 + lc];
-    acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-    acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-    acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-    acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-  }
-#pragma unroll
-  for (int x = 0; x < 2; ++x)
-#pragma unroll
-    for (int y = 0; y < 2; ++y)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        double* cp = M + (i0 + wi + 16 * x + lr + 4 * r) * ld + j0 + wj + 16 * y + lc;
-        *cp -= acc[x][y][r];
-      }
+  Mma64 t;
+  t.mma<true, true>(As, Bs);
+  t.store([&](int r, int c, double v) { M[(i0 + r) * ld + j0 + c] -= v; });
 }
 
 // Rows below a finished block of `kdepth` rows (P = M[K0 : K0 + kdepth, :]):  C -= P^T P on the upper

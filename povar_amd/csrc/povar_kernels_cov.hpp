@@ -92,8 +92,7 @@ POVAR_KERNEL __launch_bounds__(64) void cov_diag_inv(double* M, int64_t ld, int 
 //   W[0:j, j] = -W[0:j, 0:j] T    A = M (tri), B = the scratch panel, C = M + 64 j
 // The second product never reads what another workgroup writes: it reads columns < 64 j of M and the scratch panel
 // and writes column block j only -- the N x 64 scratch panel is what keeps R[0:j, j] readable until every row is done.
-// 4 wavefronts, each a 32 x 32 quadrant = 2 x 2 MFMA tiles; fragments as chol_syrk, with A held row-major in LDS:
-// A (16x4): lane l holds A[i + (l & 15)][kk + (l >> 4)], B (4x16): B[kk + (l >> 4)][j + (l & 15)].
+// The product is Mma64's (povar_kernels_chol.hpp) with A held row-major in LDS (K along its columns) and B as chol_syrk's.
 // 73 KiB of static LDS (As 64 x 66, Bs 64 x 80 doubles: chol_syrk's B stride, the only one under 96 that keeps the two
 // rows of a 32-lane half on different banks): within gfx950's 160 KiB per workgroup, two workgroups per CU, as chol_syrk's 80.
 POVAR_KERNEL __launch_bounds__(256) void cov_trmm(const double* A, int64_t lda, const double* B, int64_t ldb, double* C,
@@ -101,23 +100,15 @@ POVAR_KERNEL __launch_bounds__(256) void cov_trmm(const double* A, int64_t lda, 
   __shared__ double As[CH_NB][CV_ALDS];
   __shared__ double Bs[CH_NB][CH_LDS];
   const int i = blockIdx.x;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int wi = (w >> 1) * 32, wj = (w & 1) * 32;
-  const int lr = lane >> 4, lc = lane & 15;
-  ch_d4 acc[2][2];
-#pragma unroll
-  for (int x = 0; x < 2; ++x)
-#pragma unroll
-    for (int y = 0; y < 2; ++y) acc[x][y] = ch_d4{0, 0, 0, 0};
+  Mma64 t;
   const double* arow = A + (int64_t)i * CH_NB * lda;
   // software pipeline, as chol_syrk_outer: the global loads of block kb + 1 are in flight while the MFMAs of block kb run
-  constexpr int NLD = CH_NB * CH_NB / 2 / 256;  // double2 per thread and operand
-  double2 ra[NLD], rb[NLD];
+  double2 ra[Mma64::NLD], rb[Mma64::NLD];
   auto fetch = [&](int kb) {
 #pragma unroll
-    for (int u = 0; u < NLD; ++u) {
-      const int e = threadIdx.x + 256 * u;
-      const int p = e >> 5, q = (e & 31) * 2;
+    for (int u = 0; u < Mma64::NLD; ++u) {
+      int p, q;
+      Mma64::share(u, p, q);
       ra[u] = *reinterpret_cast<const double2*>(arow + (int64_t)p * lda + (int64_t)kb * CH_NB + q);
       rb[u] = *reinterpret_cast<const double2*>(B + ((int64_t)kb * CH_NB + p) * ldb + q);
     }
@@ -126,33 +117,13 @@ POVAR_KERNEL __launch_bounds__(256) void cov_trmm(const double* A, int64_t lda, 
   fetch(k_first);
   for (int kb = k_first; kb < k_end; ++kb) {
     __syncthreads();
-#pragma unroll
-    for (int u = 0; u < NLD; ++u) {
-      const int e = threadIdx.x + 256 * u;
-      const int p = e >> 5, q = (e & 31) * 2;
-      As[p][q] = ra[u].x; As[p][q + 1] = ra[u].y;
-      Bs[p][q] = rb[u].x; Bs[p][q + 1] = rb[u].y;
-    }
+    Mma64::stage(As, Bs, ra, rb);
     __syncthreads();
     if (kb + 1 < k_end) fetch(kb + 1);
-#pragma unroll 4
-    for (int kk = 0; kk < CH_NB; kk += 4) {
-      const double a0 = As[wi + lc][kk + lr], a1 = As[wi + 16 + lc][kk + lr];
-      const double b0 = Bs[kk + lr][wj + lc], b1 = Bs[kk + lr][wj + 16 + lc];
-      acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-    }
+    t.mma<false, true>(As, Bs);
   }
   double* crow = C + (int64_t)i * CH_NB * ldc;
-#pragma unroll
-  for (int x = 0; x < 2; ++x)
-#pragma unroll
-    for (int y = 0; y < 2; ++y)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        crow[(int64_t)(wi + 16 * x + lr + 4 * r) * ldc + wj + 16 * y + lc] = alpha * acc[x][y][r];
+  t.store([&](int r, int c, double v) { crow[(int64_t)r * ldc + c] = alpha * v; });
 }
 
 // Solver-coordinate block of camera c: T[a][b] = sum_k W[J_a][k] W[J_b][k], J_a = DIM c + a, over the columns
@@ -256,7 +227,7 @@ __global__ __launch_bounds__(256) void cov_finish(double* blk, const double* Q, 
 // lower one and the panel: no workgroup reads what another workgroup of the launch writes, and W itself stays in place.
 // The K = I block of W[I][.] (and of W[J][.] when J = I) is masked below its diagonal, as cov_gram masks.
 // Both operands are row-major along K (an A B^T product), so both sit in LDS as cov_trmm's A tile (stride CV_ALDS) and
-// both fragments read A[i + (l & 15)][kk + (l >> 4)]; 4 wavefronts, each a 32 x 32 quadrant = 2 x 2 MFMA tiles; the global
+// both fragments read A[i + (l & 15)][kk + (l >> 4)] (Mma64 with K along the columns of both tiles); the global
 // loads of block K + 1 are in flight under the MFMAs of block K.  A tile of block row I takes N / 64 - I K steps: the
 // linear blockIdx walks the rows I upwards (tile t = I (I + 1) / 2 + J), so the long tiles start first.
 // grid = nb (nb + 1) / 2 with nb = N / 64.  66 KiB of static LDS: two workgroups per CU.
@@ -268,23 +239,15 @@ POVAR_KERNEL __launch_bounds__(256) void cov_lauum(double* M, int64_t ld, double
   while ((I + 1) * (I + 2) / 2 <= t) ++I;
   while (I * (I + 1) / 2 > t) --I;
   const int J = t - I * (I + 1) / 2;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int wi = (w >> 1) * 32, wj = (w & 1) * 32;
-  const int lr = lane >> 4, lc = lane & 15;
-  ch_d4 acc[2][2];
-#pragma unroll
-  for (int x = 0; x < 2; ++x)
-#pragma unroll
-    for (int y = 0; y < 2; ++y) acc[x][y] = ch_d4{0, 0, 0, 0};
+  Mma64 tile;
   const double* arow = M + (int64_t)I * CH_NB * ld;
   const double* brow = M + (int64_t)J * CH_NB * ld;
-  constexpr int NLD = CH_NB * CH_NB / 2 / 256;  // double2 per thread and operand
-  double2 ra[NLD], rb[NLD];
+  double2 ra[Mma64::NLD], rb[Mma64::NLD];
   auto fetch = [&](int kb) {
 #pragma unroll
-    for (int u = 0; u < NLD; ++u) {
-      const int e = threadIdx.x + 256 * u;
-      const int p = e >> 5, q = (e & 31) * 2;
+    for (int u = 0; u < Mma64::NLD; ++u) {
+      int p, q;
+      Mma64::share(u, p, q);
       ra[u] = *reinterpret_cast<const double2*>(arow + (int64_t)p * ld + (int64_t)kb * CH_NB + q);
       rb[u] = *reinterpret_cast<const double2*>(brow + (int64_t)p * ld + (int64_t)kb * CH_NB + q);
       if (kb == I) {  // the diagonal block of W: upper triangular
@@ -300,33 +263,14 @@ POVAR_KERNEL __launch_bounds__(256) void cov_lauum(double* M, int64_t ld, double
   fetch(I);
   for (int kb = I; kb < nb; ++kb) {
     __syncthreads();
-#pragma unroll
-    for (int u = 0; u < NLD; ++u) {
-      const int e = threadIdx.x + 256 * u;
-      const int p = e >> 5, q = (e & 31) * 2;
-      As[p][q] = ra[u].x; As[p][q + 1] = ra[u].y;
-      Bs[p][q] = rb[u].x; Bs[p][q + 1] = rb[u].y;
-    }
+    Mma64::stage(As, Bs, ra, rb);
     __syncthreads();
     if (kb + 1 < nb) fetch(kb + 1);
-#pragma unroll 4
-    for (int kk = 0; kk < CH_NB; kk += 4) {
-      const double a0 = As[wi + lc][kk + lr], a1 = As[wi + 16 + lc][kk + lr];
-      const double b0 = Bs[wj + lc][kk + lr], b1 = Bs[wj + 16 + lc][kk + lr];
-      acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-    }
+    tile.mma<false, false>(As, Bs);
   }
   double* crow = I == J ? panel + (int64_t)I * CH_NB * CH_NB : M + (int64_t)I * CH_NB * ld + (int64_t)J * CH_NB;
   const int64_t ldc = I == J ? (int64_t)CH_NB : ld;
-#pragma unroll
-  for (int x = 0; x < 2; ++x)
-#pragma unroll
-    for (int y = 0; y < 2; ++y)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) crow[(int64_t)(wi + 16 * x + lr + 4 * r) * ldc + wj + 16 * y + lc] = acc[x][y][r];
+  tile.store([&](int r, int c, double v) { crow[(int64_t)r * ldc + c] = v; });
 }
 
 // Entry (r, c) of the symmetric C = W W^T as cov_lauum leaves it: the one place that knows the layout (a camera block of
@@ -340,7 +284,7 @@ __device__ inline double cov_at(const double* M, int64_t ld, const double* panel
 // Per-landmark contraction.  With C the camera covariance (S(lambda)^-1, or S0^+ = (S0 + Q Q^T)^-1 - Q Q^T), E_i the
 // DIM x 3 block of Hpl of observation i and G_i = F_i Hll^-1 (scd_stage / scdh_stage):
 //   Sigma_l = Hll^-1 + sum_{i,j in obs(l)} (E_i Hll^-1)^T C[c_i, c_j] (E_j Hll^-1),    E_i Hll^-1 = sum_a u_a G_i[a][:],
-//   u_a = sigma_ci o (e_a (x) h) (DIM = 12) or N_ci^T (sigma_ci o (e_a (x) X)) (DIM = 11: the staged U),
+//   u_a = sigma_ci o (e_a (x) h) (ScdPose) or N_ci^T (sigma_ci o (e_a (x) X)) (ScdJoint: the staged U)   -- Step::u,
 // so a camera pair costs the 3 x 3 bilinear form K_ij[a][b] = u_a^T C[c_i, c_j] v_b (DIM^2 entries of C through cov_at, a
 // 16-lane group per pair) and G_i^T K_ij G_j, plus its transpose for i != j (pairs i <= j only).  C here is (S0 + Q Q^T)^-1
 // in the free gauge; the - Q Q^T part is T_l^T T_l with T_l = sum_i Q[rows of c_i, :]^T (E_i Hll^-1) (nq x 3), gathered per
@@ -350,64 +294,27 @@ __device__ inline double cov_at(const double* M, int64_t ld, const double* panel
 // so the block is reproducible given C.  Then + Hll^-1 and the coords map:
 //   coords = 1 (solver):    Sigma (3 x 3) in the first 9 of the stride, the rest zero;
 //   coords = 0 (landmark):  the block carried through the map back-substitution applies to a landmark increment:
-//                           DIM = 12: D Sigma D, D = diag(s_l) (stride 9); DIM = 11: the 4 x 4 D4 N_l Sigma N_l^T D4 with
+//                           step 1: D Sigma D, D = diag(s_l) (stride 9); step 2: the 4 x 4 D4 N_l Sigma N_l^T D4 with
 //                           N_l = (I - beta w w^T)[:, 1:] from house4(X_l) (stride 16; rank 3, null vector X_l / s_l).
 // The upper triangle is written mirrored: every block is symmetric bit for bit.
-template <int DIM> struct LmCovObs;
-template <> struct LmCovObs<12> { typedef ScdObs T; static constexpr int CHUNK = SCD_CHUNK; };
-template <> struct LmCovObs<11> { typedef ScdObsH T; static constexpr int CHUNK = SCDH_CHUNK; };
-
-// u[a] = entry r of u_a of a staged observation
-__device__ inline void lm_cov_u(const ScdObs& o, const double* sigma, const double (&h)[4], int r, double (&u)[3]) {
-  const double v = sigma[12 * (size_t)o.cam + r] * h[r & 3];
-  u[0] = (r >> 2) == 0 ? v : 0.0;
-  u[1] = (r >> 2) == 1 ? v : 0.0;
-  u[2] = (r >> 2) == 2 ? v : 0.0;
-}
-__device__ inline void lm_cov_u(const ScdObsH& o, const double*, const double (&)[4], int r, double (&u)[3]) {
-  u[0] = o.U[r];
-  u[1] = o.U[11 + r];
-  u[2] = o.U[22 + r];
-}
-
-template <int DIM>
+// Step = ScdPose / ScdJoint (povar_kernels_sc.hpp) supplies the landmark head, the staging and u_a.  What this kernel and obs_cov
+// keep as their own text, because the compiler's output moved when it was shared (profiles/dense_parts_isa.txt): the bilinear
+// form's loop over the DIM^2 entries, K G_j, and the two arms of the map to landmark coordinates below.
+template <class Step>
 __global__ __launch_bounds__(256) void lm_cov(Dp d, const double* ncw, const int* lm_slot0, const int* lm_cnt, const int* ids,
                                               const double* M, int64_t ld, const double* panel, const double* Q, int nq,
                                               int coords, double* out) {
-  typedef typename LmCovObs<DIM>::T Obs;
-  constexpr int CHUNK = LmCovObs<DIM>::CHUNK;
-  constexpr int STRIDE = DIM == 12 ? 9 : 16;
+  typedef typename Step::Obs Obs;
+  constexpr int DIM = Step::DIM, CHUNK = Step::CHUNK, STRIDE = Step::LM_STRIDE;
   __shared__ Obs oi[CHUNK], oj[CHUNK];
   __shared__ double sh[4 * 9];
   __shared__ double shT[4][16][3];
   const int lm = ids ? ids[blockIdx.x] : (int)blockIdx.x;
   const int s0 = lm_slot0[lm], k = lm_cnt[lm];
-  double h[4], s4[4], Hi[9], hw[4] = {0, 0, 0, 0}, hbeta = 0;
-  double4 X = make_double4(0, 0, 0, 0), s = make_double4(0, 0, 0, 0);
-  if constexpr (DIM == 12) {
-    const double4* rec = reinterpret_cast<const double4*>(d.lmrec) + 3 * (size_t)lm;
-    const double4 r0 = rec[0], r1 = rec[1], r2 = rec[2];
-    h[0] = r0.x; h[1] = r0.y; h[2] = r0.z; h[3] = 1.0;
-    s4[0] = r0.w; s4[1] = r1.x; s4[2] = r1.y; s4[3] = 0.0;
-    const double t9[9] = {r1.z, r1.w, r2.x, r1.w, r2.y, r2.z, r2.x, r2.z, r2.w};
-#pragma unroll
-    for (int e = 0; e < 9; ++e) Hi[e] = t9[e];
-  } else {
-    const double4* rec = reinterpret_cast<const double4*>(d.lmrec) + 4 * (size_t)lm;
-    X = rec[0];
-    s = rec[1];
-    const double4 r2 = rec[2], r3 = rec[3];
-    h[0] = X.x; h[1] = X.y; h[2] = X.z; h[3] = X.w;
-    s4[0] = s.x; s4[1] = s.y; s4[2] = s.z; s4[3] = s.w;
-    const double t9[9] = {r2.x, r2.y, r2.z, r2.y, r2.w, r3.x, r2.z, r3.x, r3.y};
-#pragma unroll
-    for (int e = 0; e < 9; ++e) Hi[e] = t9[e];
-    house4(X, hw, hbeta);
-  }
-  auto stage = [&](int slot, Obs& o) {
-    if constexpr (DIM == 12) scd_stage(d, slot, s4, Hi, o);
-    else scdh_stage(d, ncw, slot, X, s, Hi, hw, hbeta, o);
-  };
+  const typename Step::Head hd = Step::load(d, lm);
+  const double h[4] = {hd.h[0], hd.h[1], hd.h[2], hd.h[3]};  // (Step::u indexes it at run time: not left inside the Head)
+  // (a closure: called directly, the staging compiles to other code -- the same values; profiles/dense_parts_isa.txt)
+  auto stage = [&](int slot, Obs& o) { Step::stage(d, ncw, slot, hd, o); };
   const int grp = threadIdx.x >> 4, gl = threadIdx.x & 15;
   double acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   double tacc[3] = {0, 0, 0};  // threads < 64: T_l[k = t & 15][:] over the observations t >> 4, + 4, ...
@@ -427,7 +334,7 @@ __global__ __launch_bounds__(256) void lm_cov(Dp d, const double* ncw, const int
           double ta[3] = {0, 0, 0};
           for (int r = 0; r < DIM; ++r) {
             double u[3];
-            lm_cov_u(a, d.sigma, h, r, u);
+            Step::u(a, d.sigma, h, r, u);
             const double qv = qrow[(size_t)r * nq];
             ta[0] += qv * u[0];
             ta[1] += qv * u[1];
@@ -450,8 +357,8 @@ __global__ __launch_bounds__(256) void lm_cov(Dp d, const double* ncw, const int
             const int r = e / DIM, c = e - DIM * r;
             const double cv = cov_at(M, ld, panel, DIM * a.cam + r, DIM * b.cam + c);
             double u[3], v[3];
-            lm_cov_u(a, d.sigma, h, r, u);
-            lm_cov_u(b, d.sigma, h, c, v);
+            Step::u(a, d.sigma, h, r, u);
+            Step::u(b, d.sigma, h, c, v);
 #pragma unroll
             for (int x = 0; x < 3; ++x)
 #pragma unroll
@@ -501,7 +408,7 @@ __global__ __launch_bounds__(256) void lm_cov(Dp d, const double* ncw, const int
         const double ty = ((shT[0][q][y] + shT[1][q][y]) + shT[2][q][y]) + shT[3][q][y];
         tt += tx * ty;
       }
-      const double v = Hi[3 * x + y] + acc[3 * x + y] - tt;
+      const double v = hd.Hi[3 * x + y] + acc[3 * x + y] - tt;
       Sg[3 * x + y] = v;
       Sg[3 * y + x] = v;
     }
@@ -511,12 +418,12 @@ __global__ __launch_bounds__(256) void lm_cov(Dp d, const double* ncw, const int
     for (int e = 0; e < STRIDE; ++e) o[e] = e < 9 ? Sg[e] : 0.0;
     return;
   }
-  if constexpr (DIM == 12) {
+  if constexpr (!Step::HOM) {
 #pragma unroll
     for (int x = 0; x < 3; ++x)
 #pragma unroll
       for (int y = x; y < 3; ++y) {
-        const double v = s4[x] * Sg[3 * x + y] * s4[y];
+        const double v = hd.s4[x] * Sg[3 * x + y] * hd.s4[y];
         o[3 * x + y] = v;
         o[3 * y + x] = v;
       }
@@ -525,7 +432,7 @@ __global__ __launch_bounds__(256) void lm_cov(Dp d, const double* ncw, const int
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int p = 0; p < 3; ++p) Nl[i][p] = (i == p + 1 ? 1.0 : 0.0) - hbeta * hw[i] * hw[p + 1];
+      for (int p = 0; p < 3; ++p) Nl[i][p] = (i == p + 1 ? 1.0 : 0.0) - hd.hbeta * hd.hw[i] * hd.hw[p + 1];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -533,7 +440,7 @@ __global__ __launch_bounds__(256) void lm_cov(Dp d, const double* ncw, const int
         double v = 0;
 #pragma unroll
         for (int p = 0; p < 3; ++p) v += Nl[i][p] * (Sg[3 * p] * Nl[j][0] + Sg[3 * p + 1] * Nl[j][1] + Sg[3 * p + 2] * Nl[j][2]);
-        v = s4[i] * v * s4[j];
+        v = hd.s4[i] * v * hd.s4[j];
         o[4 * i + j] = v;
         o[4 * j + i] = v;
       }
@@ -541,8 +448,8 @@ __global__ __launch_bounds__(256) void lm_cov(Dp d, const double* ncw, const int
 }
 
 // Per-observation block of the hat matrix J H^+ J^T (povar_observation_covariance_pose / _joint).  With y = P_c X_l the
-// projected homogeneous point of observation i of landmark l, dy = U_i^T dp_c + L_i dl (U_i the three vectors lm_cov_u
-// reads; L_i = P3 diag(s) (DIM = 12) or P diag(s4) N_l (DIM = 11)) and M_i the 3 x 3 Gram matrix of the weighted residual
+// projected homogeneous point of observation i of landmark l, dy = U_i^T dp_c + L_i dl (U_i the three vectors Step::u
+// reads; L_i = P3 diag(s) (step 1) or P diag(s4) N_l (step 2): Step::l_row) and M_i (Step::gram_m) the 3 x 3 Gram matrix of the weighted residual
 // Jacobian with respect to y (w C, or w Dm^T Dm: F_i = M_i L_i), the covariance of y is
 //   Syy_i = K_ii - R_i L_i^T - L_i R_i^T + L_i Sigma_l L_i^T,   K_ij = U_i^T C[c_i, c_j] U_j,   R_i = sum_{j in obs(l)} K_ij G_j
 // (- C F_l is the camera-landmark cross covariance), and the row is
@@ -555,43 +462,19 @@ __global__ __launch_bounds__(256) void lm_cov(Dp d, const double* ncw, const int
 // R_i is linear in K_ij, so the lanes' partial R_i and K_ii stay in registers and meet in one butterfly after the walk --
 // no atomics, a fixed order, the row reproducible given C.  Lane 0 of the group then forms the row at
 // out + 4 (row0[blockIdx.x] + i): the rows of a landmark in the order of its observations.  y2 = 0 leaves c_* non-finite
-// by IEEE rules (DIM = 12: h_i does not depend on J).
-template <int DIM>
+// by IEEE rules (step 1: h_i does not depend on J).
+template <class Step>
 __global__ __launch_bounds__(256) void obs_cov(Dp d, const double* ncw, const int* lm_slot0, const int* lm_cnt, const int* ids,
                                                const int* row0, const double* M, int64_t ld, const double* panel,
                                                const double* sig, double* out) {
-  typedef typename LmCovObs<DIM>::T Obs;
-  constexpr int CHUNK = LmCovObs<DIM>::CHUNK;
-  constexpr int STRIDE = DIM == 12 ? 9 : 16;
+  typedef typename Step::Obs Obs;
+  constexpr int DIM = Step::DIM, CHUNK = Step::CHUNK, STRIDE = Step::LM_STRIDE;
   __shared__ Obs oi[CHUNK], oj[CHUNK];
   const int lm = ids ? ids[blockIdx.x] : (int)blockIdx.x;
   const int s0 = lm_slot0[lm], k = lm_cnt[lm];
-  double h[4], s4[4], Hi[9], hw[4] = {0, 0, 0, 0}, hbeta = 0;
-  double4 X = make_double4(0, 0, 0, 0), s = make_double4(0, 0, 0, 0);
-  if constexpr (DIM == 12) {
-    const double4* rec = reinterpret_cast<const double4*>(d.lmrec) + 3 * (size_t)lm;
-    const double4 r0 = rec[0], r1 = rec[1], r2 = rec[2];
-    h[0] = r0.x; h[1] = r0.y; h[2] = r0.z; h[3] = 1.0;
-    s4[0] = r0.w; s4[1] = r1.x; s4[2] = r1.y; s4[3] = 0.0;
-    const double t9[9] = {r1.z, r1.w, r2.x, r1.w, r2.y, r2.z, r2.x, r2.z, r2.w};
-#pragma unroll
-    for (int e = 0; e < 9; ++e) Hi[e] = t9[e];
-  } else {
-    const double4* rec = reinterpret_cast<const double4*>(d.lmrec) + 4 * (size_t)lm;
-    X = rec[0];
-    s = rec[1];
-    const double4 r2 = rec[2], r3 = rec[3];
-    h[0] = X.x; h[1] = X.y; h[2] = X.z; h[3] = X.w;
-    s4[0] = s.x; s4[1] = s.y; s4[2] = s.z; s4[3] = s.w;
-    const double t9[9] = {r2.x, r2.y, r2.z, r2.y, r2.w, r3.x, r2.z, r3.x, r3.y};
-#pragma unroll
-    for (int e = 0; e < 9; ++e) Hi[e] = t9[e];
-    house4(X, hw, hbeta);
-  }
-  auto stage = [&](int slot, Obs& o) {
-    if constexpr (DIM == 12) scd_stage(d, slot, s4, Hi, o);
-    else scdh_stage(d, ncw, slot, X, s, Hi, hw, hbeta, o);
-  };
+  const typename Step::Head hd = Step::load(d, lm);
+  const double h[4] = {hd.h[0], hd.h[1], hd.h[2], hd.h[3]};  // (Step::u indexes it at run time: not left inside the Head)
+  auto stage = [&](int slot, Obs& o) { Step::stage(d, ncw, slot, hd, o); };  // (a closure: see lm_cov)
   const int grp = threadIdx.x >> 4, gl = threadIdx.x & 15;
   int staged = -1;  // the chunk oj holds: a track of one chunk stages it once
   for (int ic = 0; ic < k; ic += CHUNK) {
@@ -621,8 +504,8 @@ __global__ __launch_bounds__(256) void obs_cov(Dp d, const double* ncw, const in
             const int r = e / DIM, c = e - DIM * r;
             const double cv = cov_at(M, ld, panel, DIM * a.cam + r, DIM * b.cam + c);
             double u[3], v[3];
-            lm_cov_u(a, d.sigma, h, r, u);
-            lm_cov_u(b, d.sigma, h, c, v);
+            Step::u(a, d.sigma, h, r, u);
+            Step::u(b, d.sigma, h, c, v);
 #pragma unroll
             for (int x = 0; x < 3; ++x)
 #pragma unroll
@@ -658,29 +541,9 @@ __global__ __launch_bounds__(256) void obs_cov(Dp d, const double* ncw, const in
       for (int x = 0; x < 3; ++x) {
         const double p4[4] = {pr[x].x, pr[x].y, pr[x].z, pr[x].w};
         yv[x] = p4[0] * h[0] + p4[1] * h[1] + p4[2] * h[2] + p4[3] * h[3];
-        if constexpr (DIM == 12) {
-#pragma unroll
-          for (int y = 0; y < 3; ++y) L[3 * x + y] = p4[y] * s4[y];
-        } else {  // a row of P diag(s4) N_l, N_l = (I - beta w w^T)[:, 1:]
-          const double q4[4] = {p4[0] * s4[0], p4[1] * s4[1], p4[2] * s4[2], p4[3] * s4[3]};
-          const double aw = q4[0] * hw[0] + q4[1] * hw[1] + q4[2] * hw[2] + q4[3] * hw[3];
-#pragma unroll
-          for (int y = 0; y < 3; ++y) L[3 * x + y] = q4[y + 1] - hbeta * aw * hw[y + 1];
-        }
+        Step::l_row(hd, p4, L + 3 * x);
       }
-      if constexpr (DIM == 12) {
-        const double sb2 = d.sb * d.sb;
-        const double cu = sb2 * uv.x, cv = sb2 * uv.y, cuv = sb2 * (uv.x * uv.x + uv.y * uv.y);
-        const double C9[9] = {1, 0, -cu, 0, 1, -cv, -cu, -cv, cuv};
-#pragma unroll
-        for (int e = 0; e < 9; ++e) Mi[e] = w * C9[e];
-      } else {
-        const Hom hp = hom_project(P, X, uv.x, uv.y);
-        const double m9[9] = {hp.D00 * hp.D00, 0, hp.D00 * hp.D02, 0, hp.D00 * hp.D00, hp.D00 * hp.D12,
-                              hp.D00 * hp.D02, hp.D00 * hp.D12, hp.D02 * hp.D02 + hp.D12 * hp.D12};
-#pragma unroll
-        for (int e = 0; e < 9; ++e) Mi[e] = w * m9[e];
-      }
+      Step::gram_m(d, P, hd, uv, w, Mi);
       const double* Sg = sig + (size_t)STRIDE * blockIdx.x;
       double SL[9], Syy[9];  // Sigma_l L_i^T, then the upper triangle of Syy_i, mirrored
 #pragma unroll

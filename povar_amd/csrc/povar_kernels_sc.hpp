@@ -548,24 +548,61 @@ __device__ inline void scd_stage(const Dp& d, int slot, const double* s3, const 
   o.cam = cam;
 }
 
+// ---- the two steps of the per-landmark dense kernels (sc_dense_offdiag[_h], and lm_cov / obs_cov of povar_kernels_cov.hpp):
+// what a workgroup holds of its landmark (Head, by value: see LplWg), the one decode of the landmark record, the staging of
+// an observation, the vectors u_a of an observation, the row of L_i and M_i of obs_cov.  Pieces, not a walker: the kernels keep
+// their chunk loops, barriers, shuffles and pair arithmetic.  HOM and DIM also serve the host's dispatch (with_step, povar_sc.hip).
+struct ScdPose {
+  static constexpr int DIM = 12, CHUNK = SCD_CHUNK;
+  static constexpr bool HOM = false;
+  static constexpr int LM_STRIDE = 9;  // doubles per landmark block of lm_cov
+  typedef ScdObs Obs;
+  struct Head { double h[4], s4[4], Hi[9]; };  // (x, y, z, 1), the column scaling (s, 0), Hll^-1
+  __device__ static __forceinline__ Head load(const Dp& d, int lm) {
+    const double4* rec = reinterpret_cast<const double4*>(d.lmrec) + 3 * (size_t)lm;
+    const double4 r0 = rec[0], r1 = rec[1], r2 = rec[2];
+    return Head{{r0.x, r0.y, r0.z, 1.0}, {r0.w, r1.x, r1.y, 0.0}, {r1.z, r1.w, r2.x, r1.w, r2.y, r2.z, r2.x, r2.z, r2.w}};
+  }
+  __device__ static __forceinline__ void stage(const Dp& d, const double*, int slot, Head hd, Obs& o) {
+    scd_stage(d, slot, hd.s4, hd.Hi, o);
+  }
+  // u[a] = entry r of u_a = sigma_c o (e_a (x) h).  h: the kernel's copy of Head::h (indexed at run time: not left in the Head)
+  __device__ static inline void u(const Obs& o, const double* sigma, const double (&h)[4], int r, double (&u)[3]) {
+    const double v = sigma[12 * (size_t)o.cam + r] * h[r & 3];
+    u[0] = (r >> 2) == 0 ? v : 0.0;
+    u[1] = (r >> 2) == 1 ? v : 0.0;
+    u[2] = (r >> 2) == 2 ? v : 0.0;
+  }
+  // a row of L_i = P3 diag(s) from the row p4 of P_c
+  __device__ static __forceinline__ void l_row(Head hd, const double (&p4)[4], double* L) {
+#pragma unroll
+    for (int y = 0; y < 3; ++y) L[y] = p4[y] * hd.s4[y];
+  }
+  // M_i = w C_i
+  __device__ static __forceinline__ void gram_m(const Dp& d, const Cam&, Head, double2 uv, double w, double (&Mi)[9]) {
+    const double sb2 = d.sb * d.sb;
+    const double cu = sb2 * uv.x, cv = sb2 * uv.y, cuv = sb2 * (uv.x * uv.x + uv.y * uv.y);
+    const double C9[9] = {1, 0, -cu, 0, 1, -cv, -cu, -cv, cuv};
+#pragma unroll
+    for (int e = 0; e < 9; ++e) Mi[e] = w * C9[e];
+  }
+};
+
 POVAR_KERNEL __launch_bounds__(256) void sc_dense_offdiag(Dp d, const int* lm_slot0, const int* lm_cnt, double* S, int64_t ld) {
   __shared__ ScdObs oi[SCD_CHUNK], oj[SCD_CHUNK];
   const int lm = blockIdx.x;
   const int s0 = lm_slot0[lm], k = lm_cnt[lm];
-  const double4* rec = reinterpret_cast<const double4*>(d.lmrec) + 3 * (size_t)lm;
-  const double4 r0 = rec[0], r1 = rec[1], r2 = rec[2];
-  const double h[4] = {r0.x, r0.y, r0.z, 1.0};
-  const double s3[3] = {r0.w, r1.x, r1.y};
-  const double Hi[9] = {r1.z, r1.w, r2.x, r1.w, r2.y, r2.z, r2.x, r2.z, r2.w};
+  const ScdPose::Head hd = ScdPose::load(d, lm);
+  const double h[4] = {hd.h[0], hd.h[1], hd.h[2], hd.h[3]};  // (indexed at run time: not left inside the Head)
   const int grp = threadIdx.x >> 4, gl = threadIdx.x & 15;
   for (int ic = 0; ic < k; ic += SCD_CHUNK) {
     const int ni = min(SCD_CHUNK, k - ic);
     __syncthreads();
-    if ((int)threadIdx.x < ni) scd_stage(d, s0 + ic + threadIdx.x, s3, Hi, oi[threadIdx.x]);
+    if ((int)threadIdx.x < ni) ScdPose::stage(d, nullptr, s0 + ic + threadIdx.x, hd, oi[threadIdx.x]);
     for (int jc = ic; jc < k; jc += SCD_CHUNK) {
       const int nj = min(SCD_CHUNK, k - jc);
       __syncthreads();
-      if ((int)threadIdx.x < nj) scd_stage(d, s0 + jc + threadIdx.x, s3, Hi, oj[threadIdx.x]);
+      if ((int)threadIdx.x < nj) ScdPose::stage(d, nullptr, s0 + jc + threadIdx.x, hd, oj[threadIdx.x]);
       __syncthreads();
       for (int pp = grp; pp < ni * nj; pp += 16) {
         const int i = pp / nj, j = pp - i * nj;
@@ -663,26 +700,65 @@ __device__ inline void scdh_stage(const Dp& d, const double* ncw, int slot, cons
   o.cam = cam;
 }
 
+struct ScdJoint {
+  static constexpr int DIM = 11, CHUNK = SCDH_CHUNK;
+  static constexpr bool HOM = true;
+  static constexpr int LM_STRIDE = 16;
+  typedef ScdObsH Obs;
+  // X and s as the record holds them and as arrays, the damped tangent Hll^-1, the reflector of N_l (house4)
+  struct Head {
+    double h[4], s4[4], Hi[9], hw[4], hbeta;
+    double4 X, s;
+  };
+  // (the landmark record povar_prepare_joint(lambda) leaves: X, s, damped tangent Hll^-1 -- as cm_gram_sc<true> reads it)
+  __device__ static __forceinline__ Head load(const Dp& d, int lm) {
+    const double4* rec = reinterpret_cast<const double4*>(d.lmrec) + 4 * (size_t)lm;
+    const double4 X = rec[0], s = rec[1], r2 = rec[2], r3 = rec[3];
+    Head hd{{X.x, X.y, X.z, X.w}, {s.x, s.y, s.z, s.w}, {r2.x, r2.y, r2.z, r2.y, r2.w, r3.x, r2.z, r3.x, r3.y}, {0, 0, 0, 0}, 0, X, s};
+    house4(X, hd.hw, hd.hbeta);
+    return hd;
+  }
+  __device__ static __forceinline__ void stage(const Dp& d, const double* ncw, int slot, Head hd, Obs& o) {
+    scdh_stage(d, ncw, slot, hd.X, hd.s, hd.Hi, hd.hw, hd.hbeta, o);
+  }
+  // u[a] = entry r of u_a = N_c^T (sigma_c o (e_a (x) X)): the staged U
+  __device__ static inline void u(const Obs& o, const double*, const double (&)[4], int r, double (&u)[3]) {
+    u[0] = o.U[r];
+    u[1] = o.U[11 + r];
+    u[2] = o.U[22 + r];
+  }
+  // a row of L_i = P diag(s4) N_l, N_l = (I - beta w w^T)[:, 1:]
+  __device__ static __forceinline__ void l_row(Head hd, const double (&p4)[4], double* L) {
+    const double q4[4] = {p4[0] * hd.s4[0], p4[1] * hd.s4[1], p4[2] * hd.s4[2], p4[3] * hd.s4[3]};
+    const double aw = q4[0] * hd.hw[0] + q4[1] * hd.hw[1] + q4[2] * hd.hw[2] + q4[3] * hd.hw[3];
+#pragma unroll
+    for (int y = 0; y < 3; ++y) L[y] = q4[y + 1] - hd.hbeta * aw * hd.hw[y + 1];
+  }
+  // M_i = w Dm^T Dm
+  __device__ static __forceinline__ void gram_m(const Dp&, const Cam& P, Head hd, double2 uv, double w, double (&Mi)[9]) {
+    const Hom hp = hom_project(P, hd.X, uv.x, uv.y);
+    const double m9[9] = {hp.D00 * hp.D00, 0, hp.D00 * hp.D02, 0, hp.D00 * hp.D00, hp.D00 * hp.D12,
+                          hp.D00 * hp.D02, hp.D00 * hp.D12, hp.D02 * hp.D02 + hp.D12 * hp.D12};
+#pragma unroll
+    for (int e = 0; e < 9; ++e) Mi[e] = w * m9[e];
+  }
+};
+
 POVAR_KERNEL __launch_bounds__(256) void sc_dense_offdiag_h(Dp d, const double* ncw, const int* lm_slot0, const int* lm_cnt,
                                                             double* S, int64_t ld) {
   __shared__ ScdObsH oi[SCDH_CHUNK], oj[SCDH_CHUNK];
   const int lm = blockIdx.x;
   const int s0 = lm_slot0[lm], k = lm_cnt[lm];
-  // (the landmark record povar_prepare_joint(lambda) leaves: X, s, damped tangent Hll^-1 -- as cm_gram_sc<true> reads it)
-  const double4* rec = reinterpret_cast<const double4*>(d.lmrec) + 4 * (size_t)lm;
-  const double4 X = rec[0], s = rec[1], r2 = rec[2], r3 = rec[3];
-  const double Hi[9] = {r2.x, r2.y, r2.z, r2.y, r2.w, r3.x, r2.z, r3.x, r3.y};
-  double hw[4], hbeta;
-  house4(X, hw, hbeta);
+  const ScdJoint::Head hd = ScdJoint::load(d, lm);
   const int grp = threadIdx.x >> 4, gl = threadIdx.x & 15;
   for (int ic = 0; ic < k; ic += SCDH_CHUNK) {
     const int ni = min(SCDH_CHUNK, k - ic);
     __syncthreads();
-    if ((int)threadIdx.x < ni) scdh_stage(d, ncw, s0 + ic + threadIdx.x, X, s, Hi, hw, hbeta, oi[threadIdx.x]);
+    if ((int)threadIdx.x < ni) ScdJoint::stage(d, ncw, s0 + ic + threadIdx.x, hd, oi[threadIdx.x]);
     for (int jc = ic; jc < k; jc += SCDH_CHUNK) {
       const int nj = min(SCDH_CHUNK, k - jc);
       __syncthreads();
-      if ((int)threadIdx.x < nj) scdh_stage(d, ncw, s0 + jc + threadIdx.x, X, s, Hi, hw, hbeta, oj[threadIdx.x]);
+      if ((int)threadIdx.x < nj) ScdJoint::stage(d, ncw, s0 + jc + threadIdx.x, hd, oj[threadIdx.x]);
       __syncthreads();
       for (int pp = grp; pp < ni * nj; pp += 16) {
         const int i = pp / nj, j = pp - i * nj;

@@ -603,9 +603,9 @@ int povar_get_buffer(povar_ctx* c, int32_t which, double* out, int64_t n) {
       if (c->sc_factor_dim == 0 || !c->sc_dense.p || !c->sc_xpad.p)
         return fail(-1, "povar_get_buffer: POVAR_BUF_SC_FACTOR: no factor in place (the last call that wrote the dense matrix "
                         "must be a CHOLESKY / RICHOLESKY solve that found it positive definite)");
-      const size_t N = ((size_t)c->sc_factor_n + CH_NB - 1) / CH_NB * CH_NB;
+      const DenseDims g = dense_dims(c->sc_factor_dim, c->n_cams);
+      const size_t N = g.N, ld = g.ld;
       if ((size_t)n != N * (N + 2)) return fail(-1, "povar_get_buffer: wrong size");
-      const size_t ld = N + CH_T;  // row stride of the augmented matrix (chol_factor, povar_sc.hip)
       std::vector<double> xh(N);
       HIP_TRY(hipMemcpy2DAsync(out, (N + 2) * sizeof(double), c->sc_dense.p, ld * sizeof(double), (N + 1) * sizeof(double), N,
                                hipMemcpyDeviceToHost, c->stream));
@@ -621,8 +621,8 @@ int povar_get_buffer(povar_ctx* c, int32_t which, double* out, int64_t n) {
       if (c->sc_cov_kind == 0 || !c->sc_dense.p)
         return fail(-1, "povar_get_buffer: POVAR_BUF_COV_*: no covariance in place (the last call that wrote the dense matrix "
                         "must be a povar_*_covariance_* call that returned 0)");
-      const size_t N = ((size_t)c->sc_cov_n + CH_NB - 1) / CH_NB * CH_NB;
-      const size_t ld = N + CH_T;  // row stride of the augmented matrix (chol_factor, povar_sc.hip)
+      const DenseDims g = dense_dims(c->sc_cov_n / c->n_cams, c->n_cams);  // (sc_cov_n = dim * n_cams, n_cams > 0)
+      const size_t N = g.N, ld = g.ld;
       if (which == POVAR_BUF_COV_GAUGE) {
         if (c->sc_cov_nq == 0 || !c->sc_cov_q.p) return fail(-1, "povar_get_buffer: POVAR_BUF_COV_GAUGE: the last covariance call was damped");
         return copy(c->sc_cov_q.p, (size_t)c->sc_cov_n * (size_t)c->sc_cov_nq);

@@ -55,29 +55,73 @@ int e0_dense(povar_ctx* c) {
   return 0;
 }
 
+namespace {
+// The run-time block dimension (12: step 1, 11: step 2) to the step type of the dense kernels: fn(ScdPose()) or fn(ScdJoint()),
+// so every launch templated on the step is written once
+template <class F>
+auto with_step(int dim, F fn) {
+  return dim == 12 ? fn(ScdPose()) : fn(ScdJoint());
+}
+
+// A device buffer the context keeps (counted in povar_device_bytes), grown to `count` elements once the stream has drained.
+// `headroom` > 0: the device must have that many bytes free beside the new buffer, else hipErrorOutOfMemory without trying.
+// On an error the buffer is empty.
+template <typename T>
+hipError_t grow_buffer(povar_ctx* c, DevBuf<T>& buf, size_t count, size_t headroom = 0) {
+  if (buf.p && buf.n >= count) return hipSuccess;
+  if (buf.p) {
+    if (hipError_t e = hipStreamSynchronize(c->stream)) return e;
+    c->bytes -= buf.n * sizeof(T);
+    buf.release();
+  }
+  buf.n = 0;
+  size_t free_b = 0, total_b = 0;
+  if (headroom > 0) {
+    if (hipError_t e = hipMemGetInfo(&free_b, &total_b)) return e;
+    if (count * sizeof(T) + headroom > free_b) return hipErrorOutOfMemory;
+  }
+  const hipError_t e = buf.alloc(count, &c->bytes);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    buf.p = nullptr;
+    buf.n = 0;
+  }
+  return e;
+}
+
+int no_memory(int dim, int n_cams, const char* what, size_t bytes) {
+  return fail(-1, std::string(dim == 11 ? "RICHOLESKY" : "CHOLESKY") + ": not enough device memory for the " + what + " of " +
+                      std::to_string(dim * n_cams) + " rows (" + std::to_string(bytes >> 20) + " MiB)");
+}
+}  // namespace
+
+// The system as the direct and PCG solvers prepare it (an argument error without the step's linearisation): B_c and the
+// Schur-Jacobi preconditioner on top of povar_prepare_pose (LinearizorSC::solve, linearizor_sc.cpp:85-160: no landmark damping
+// on this path) or povar_prepare_joint (solve_joint, linearizor_sc.cpp:224-303; landmark damping is part of the prepared system)
+static int prepare_sc(povar_ctx* c, int dim, double lambda) {
+  if (int rc = dim == 12 ? povar_prepare_pose(c, lambda, POVAR_POWER_VARPROJ) : povar_prepare_joint(c, lambda)) return rc;
+  // cm_gram_sc reads the per-slot sqrt(w) and the landmark-order records: after a lane-per-landmark linearisation /
+  // prepare they are rebuilt here (missing until round 3: RIPCG with a robust norm took stale weights on every problem
+  // large enough for the lane-per-landmark kernels -- the parity tests' "lane-per-landmark" halves were not running
+  // those kernels, tests/conftest.py)
+  ensure_legacy(c);
+  if (int rc = ensure_sc(c)) return rc;
+  return with_step(dim, [&](auto step) { return build_schur_jacobi<decltype(step)::HOM>(c, lambda); });
+}
+
 // First half, shared with the covariance calls below: assembly of the augmented matrix and its factorisation, R left in
 // sc_dense.  Q (device, n x nq row-major; null for the solvers) is the free-gauge term: A = S + Q Q^T, added on rank 0 before
 // the all-reduce; `stat` (device, 2 doubles; null for the solvers) then receives max_k A_kk and min_k R_kk^2.
 static int chol_factor(povar_ctx* c, int dim, const double* Q, int nq, double* stat) {
   c->sc_factor_dim = c->sc_factor_n = 0;  // (run_cholesky sets it again once the factorisation has succeeded)
   c->sc_cov_kind = c->sc_cov_n = 0;  // (a covariance call sets it again once it has returned its blocks)
-  const int n = dim * c->n_cams;
-  const int N = (n + CH_NB - 1) / CH_NB * CH_NB;
-  const int64_t ld = (int64_t)N + CH_T;
-  const size_t count = (size_t)(N + CH_NB) * (size_t)ld;  // slack rows / columns for the 128 x 128 update tiles
-  if (c->sc_dense.n < count) {
-    if (c->sc_dense.p) {
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      c->bytes -= c->sc_dense.n * sizeof(double);
-      c->sc_dense.release();
-      c->sc_dense.n = 0;
-    }
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    if (count * sizeof(double) + (1u << 30) > free_b)
-      return fail(-1, std::string(dim == 11 ? "RICHOLESKY" : "CHOLESKY") + ": not enough device memory for the dense reduced camera matrix of " +
-                          std::to_string(n) + " rows (" + std::to_string(count * sizeof(double) >> 20) + " MiB)");
-    HIP_TRY(c->sc_dense.alloc(count, &c->bytes));
+  const DenseDims g = dense_dims(dim, c->n_cams);
+  const int n = g.n, N = g.N;
+  const int64_t ld = g.ld;
+  const size_t count = g.count;
+  if (const hipError_t e = grow_buffer(c, c->sc_dense, count, (size_t)1 << 30)) {
+    if (e == hipErrorOutOfMemory) return no_memory(dim, c->n_cams, "dense reduced camera matrix", count * sizeof(double));
+    HIP_TRY(e);
   }
   if (!c->sc_info.p) {
     HIP_TRY(c->sc_info.alloc(1, &c->bytes));
@@ -94,10 +138,9 @@ static int chol_factor(povar_ctx* c, int dim, const double* Q, int nq, double* s
   HIP_TRY(hipMemsetAsync(c->sc_info.p, 0, sizeof(int), c->stream));
   // replicated parts (B_c, -b, padding identity) once over the ranks; the landmark part is sharded
   if (c->rank == 0) {
-    if (dim == 11)
-      hipLaunchKernelGGL(sc_dense_diag<11>, dim3(c->n_cams), dim3(256), 0, c->stream, c->d, (const double*)c->sc.bmat, M, ld, N);
-    else
-      hipLaunchKernelGGL(sc_dense_diag<12>, dim3(c->n_cams), dim3(256), 0, c->stream, c->d, (const double*)c->sc.bmat, M, ld, N);
+    with_step(dim, [&](auto step) {
+      hipLaunchKernelGGL(sc_dense_diag<decltype(step)::DIM>, dim3(c->n_cams), dim3(256), 0, c->stream, c->d, (const double*)c->sc.bmat, M, ld, N);
+    });
     if (N > n) hipLaunchKernelGGL(chol_pad, dim3(1), dim3(64), 0, c->stream, M, ld, n, N);
     if (Q) hipLaunchKernelGGL(cov_add_qqt, dim3(N / CH_NB, N / CH_NB), dim3(256), 0, c->stream, M, ld, n, Q, nq);
   }
@@ -136,18 +179,11 @@ static int chol_factor(povar_ctx* c, int dim, const double* Q, int nq, double* s
 // step 2 (RICHOLESKY; not in the reference).  A context that solves both keeps one dense buffer, sized for the larger.
 int run_cholesky(povar_ctx* c, int dim, int32_t* num_iterations, int32_t* termination) {
   if (int rc = chol_factor(c, dim, nullptr, 0, nullptr)) return rc;
-  const int n = dim * c->n_cams;
-  const int N = (n + CH_NB - 1) / CH_NB * CH_NB;
-  const int64_t ld = (int64_t)N + CH_T;
+  const DenseDims g = dense_dims(dim, c->n_cams);
+  const int n = g.n, N = g.N;
+  const int64_t ld = g.ld;
   double* M = c->sc_dense.p;
-  if (c->sc_xpad.n < (size_t)N) {
-    if (c->sc_xpad.p) {
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      c->bytes -= c->sc_xpad.n * sizeof(double);
-      c->sc_xpad.release();
-    }
-    HIP_TRY(c->sc_xpad.alloc((size_t)N, &c->bytes));
-  }
+  HIP_TRY(grow_buffer(c, c->sc_xpad, (size_t)N));
   double* x = c->sc_xpad.p;  // N entries, the first n are the solution
   hipLaunchKernelGGL(chol_copy_rhs, dim3(grid_for(N, 256)), dim3(256), 0, c->stream, (const double*)M, ld, N, x);
   for (int k0 = N - CH_NB; k0 >= 0; k0 -= CH_NB) {
@@ -222,19 +258,9 @@ namespace {
 // the error of CHOLESKY / RICHOLESKY
 template <typename T>
 int cov_buffer(povar_ctx* c, DevBuf<T>& buf, size_t count, int dim) {
-  if (buf.p && buf.n >= count) return 0;
-  if (buf.p) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    c->bytes -= buf.n * sizeof(T);
-    buf.release();
-  }
-  if (buf.alloc(count, &c->bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    buf.p = nullptr;
-    buf.n = 0;
-    return fail(-1, std::string(dim == 11 ? "RICHOLESKY" : "CHOLESKY") + ": not enough device memory for the covariance scratch of " +
-                        std::to_string(dim * c->n_cams) + " rows (" + std::to_string(count * sizeof(T) >> 20) + " MiB)");
-  }
+  const hipError_t e = grow_buffer(c, buf, count);
+  if (e == hipErrorOutOfMemory) return no_memory(dim, c->n_cams, "covariance scratch", count * sizeof(T));
+  HIP_TRY(e);
   return 0;
 }
 
@@ -305,9 +331,7 @@ bool gauge_basis(int n_cams, int dim, const std::vector<double>& P, const std::v
 
 // What the covariance calls share: the argument checks, the prepared system, the gauge basis, the factorisation of
 // CHOLESKY / RICHOLESKY (A = S(lambda), or S0 + Q Q^T in the free gauge), the pivot rule and W = R^-1 in place.
-struct CovInverse {
-  int n = 0, N = 0;           // dim * n_cams and its multiple of 64
-  int64_t ld = 0;
+struct CovInverse : DenseDims {
   const double* q = nullptr;  // device: the gauge basis (free gauge), n x nq row-major
   int nq = 0;
 };
@@ -322,15 +346,9 @@ static int cov_inverse(povar_ctx* c, int dim, const char* who, bool have_out, do
   if (coords != POVAR_COV_CAMERA_COORDS && coords != POVAR_COV_SOLVER_COORDS) return fail(-1, std::string(who) + ": unknown coords");
   if (gauge == POVAR_COV_FREE_GAUGE && lambda != 0.0) return fail(-1, std::string(who) + ": POVAR_COV_FREE_GAUGE takes lambda = 0");
   if (gauge == POVAR_COV_DAMPED && !(lambda > 0.0)) return fail(-1, std::string(who) + ": POVAR_COV_DAMPED takes lambda > 0");
-  // the system as the direct solvers prepare it (an argument error without the step's linearisation)
-  if (int rc = dim == 12 ? povar_prepare_pose(c, lambda, POVAR_POWER_VARPROJ) : povar_prepare_joint(c, lambda)) return rc;
-  ensure_legacy(c);
-  if (int rc = ensure_sc(c)) return rc;
-  if (int rc = dim == 12 ? build_schur_jacobi<false>(c, lambda) : build_schur_jacobi<true>(c, lambda)) return rc;
+  if (int rc = prepare_sc(c, dim, lambda)) return rc;
   const size_t nc = c->n_cams;
-  f.n = dim * c->n_cams;
-  f.N = (f.n + CH_NB - 1) / CH_NB * CH_NB;
-  f.ld = (int64_t)f.N + CH_T;
+  static_cast<DenseDims&>(f) = dense_dims(dim, c->n_cams);
   ts.emplace(c, 2);
   c->sc_cov_kind = 0;  // (from here on Q, the dense matrix and the panel are rewritten: POVAR_BUF_COV_* wait for cov_done)
   const bool free_gauge = gauge == POVAR_COV_FREE_GAUGE;
@@ -395,15 +413,12 @@ static int cov_camera_blocks(povar_ctx* c, int dim, const CovInverse& f, int32_t
   const double* M = c->sc_dense.p;
   double* blocks = c->sc_cov_blocks.p;
   HIP_TRY(hipMemsetAsync(blocks, 0, out_count * sizeof(double), c->stream));
-  if (dim == 12) {
-    hipLaunchKernelGGL(cov_gram<12>, dim3(c->n_cams), dim3(256), 0, c->stream, M, f.ld, f.n, blocks);
-    hipLaunchKernelGGL(cov_finish<12>, dim3(c->n_cams), dim3(256), 0, c->stream, blocks, f.q, f.nq,
+  with_step(dim, [&](auto step) {
+    constexpr int DIM = decltype(step)::DIM;
+    hipLaunchKernelGGL(cov_gram<DIM>, dim3(c->n_cams), dim3(256), 0, c->stream, M, f.ld, f.n, blocks);
+    hipLaunchKernelGGL(cov_finish<DIM>, dim3(c->n_cams), dim3(256), 0, c->stream, blocks, f.q, f.nq,
                        (const double*)c->sigma.p, (const double*)c->ncw.p, coords);
-  } else {
-    hipLaunchKernelGGL(cov_gram<11>, dim3(c->n_cams), dim3(256), 0, c->stream, M, f.ld, f.n, blocks);
-    hipLaunchKernelGGL(cov_finish<11>, dim3(c->n_cams), dim3(256), 0, c->stream, blocks, f.q, f.nq,
-                       (const double*)c->sigma.p, (const double*)c->ncw.p, coords);
-  }
+  });
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(cov, blocks, out_count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -423,7 +438,7 @@ static void cov_done(povar_ctx* c, const CovInverse& f, int kind) {
 // (POVAR_COV_FREE_GAUGE), through the factorisation of CHOLESKY / RICHOLESKY: A = R^T R, W = R^-1 in place, blocks of W W^T.
 static int camera_covariance(povar_ctx* c, int dim, double lambda, int32_t gauge, int32_t coords, double* cov) {
   const char* who = dim == 12 ? "povar_camera_covariance_pose" : "povar_camera_covariance_joint";
-  CovInverse f;
+  CovInverse f{};
   std::optional<TimeScope> ts;
   int rc = cov_inverse(c, dim, who, cov != nullptr, lambda, gauge, coords, f, ts);
   if (rc == 0) rc = cov_camera_blocks(c, dim, f, coords, cov);
@@ -437,51 +452,93 @@ static void cov_lm_launch(povar_ctx* c, int dim, const CovInverse& f, const int*
   double* M = c->sc_dense.p;
   const int nb = f.N / CH_NB;
   hipLaunchKernelGGL(cov_lauum, dim3((unsigned)(nb * (nb + 1) / 2)), dim3(256), 0, c->stream, M, f.ld, c->sc_cov_panel.p, nb);
-  if (dim == 12)
-    hipLaunchKernelGGL(lm_cov<12>, dim3(n_out), dim3(256), 0, c->stream, c->d, (const double*)c->ncw.p, (const int*)c->sc_lm_slot0.p,
-                       (const int*)c->sc_lm_cnt.p, ids, (const double*)M, f.ld, (const double*)c->sc_cov_panel.p, q, nq, coords,
-                       c->sc_cov_lm.p);
-  else
-    hipLaunchKernelGGL(lm_cov<11>, dim3(n_out), dim3(256), 0, c->stream, c->d, (const double*)c->ncw.p, (const int*)c->sc_lm_slot0.p,
-                       (const int*)c->sc_lm_cnt.p, ids, (const double*)M, f.ld, (const double*)c->sc_cov_panel.p, q, nq, coords,
-                       c->sc_cov_lm.p);
+  with_step(dim, [&](auto step) {
+    hipLaunchKernelGGL(lm_cov<decltype(step)>, dim3(n_out), dim3(256), 0, c->stream, c->d, (const double*)c->ncw.p,
+                       (const int*)c->sc_lm_slot0.p, (const int*)c->sc_lm_cnt.p, ids, (const double*)M, f.ld,
+                       (const double*)c->sc_cov_panel.p, q, nq, coords, c->sc_cov_lm.p);
+  });
 }
+
+static int lm_stride(int dim) {
+  return with_step(dim, [](auto step) { return decltype(step)::LM_STRIDE; });
+}
+
+// A request of the landmark and observation calls: which landmarks (lm_ids null: all of them), where the results go, and what
+// the two calls do alike on both sides of cov_inverse
+struct CovRequest {
+  const char* who = "";
+  const int32_t* lm_ids = nullptr;
+  int n_out = 0;
+  std::vector<int> row0;     // observation call: the first row of every requested landmark, and the number of rows
+  int64_t rows = 0;
+  double* out = nullptr;     // the call's outputs (cam: the landmark call's camera blocks, on request): NaN on a numeric failure
+  double* cam = nullptr;
+  size_t count = 0, cam_count = 0;
+  const int* ids = nullptr;  // device copy of lm_ids
+
+  // n_out and the id check; with_rows: row0 and rows in the same walk
+  int check(povar_ctx* c, const int32_t* lm_ids_, int32_t n_ids, bool with_rows) {
+    if (int rc = check_ctx(c)) return rc;
+    lm_ids = lm_ids_;
+    n_out = lm_ids ? n_ids : c->n_lms;
+    if (n_out < 0) return fail(-1, std::string(who) + ": negative n_ids");
+    if (with_rows) row0.resize((size_t)n_out);
+    for (int i = 0; (lm_ids || with_rows) && i < n_out; ++i) {
+      const int l = lm_ids ? lm_ids[i] : i;
+      if (l < 0 || l >= c->n_lms) return fail(-1, std::string(who) + ": landmark id out of range");
+      if (!with_rows) continue;
+      if (rows > INT32_MAX) return fail(-1, std::string(who) + ": more than 2^31 rows requested");
+      row0[i] = (int)rows;
+      rows += c->lm_off[l + 1] - c->lm_off[l];
+    }
+    return 0;
+  }
+  int all_nan() const {
+    std::fill(out, out + count, std::nan(""));
+    if (cam) std::fill(cam, cam + cam_count, std::nan(""));
+    return POVAR_NUMERIC_FAILURE;
+  }
+  // After cov_inverse (and the camera blocks).  true: the call ends here with rc -- an error, a numeric failure (NaN), or
+  // nothing requested: W alone is in place (kind 1; cov_lauum does not run)
+  bool over(povar_ctx* c, const CovInverse& f, bool empty, int& rc) const {
+    if (rc == POVAR_NUMERIC_FAILURE) rc = all_nan();
+    else if (rc == 0 && empty) cov_done(c, f, 1);
+    return rc != 0 || empty;
+  }
+  // (lm_ids is the caller's memory: the call synchronises the stream before it returns)
+  int upload_ids(povar_ctx* c, int dim) {
+    if (!lm_ids) return 0;
+    if (int rc = cov_buffer(c, c->sc_cov_ids, (size_t)n_out, dim)) return rc;
+    HIP_TRY(hipMemcpyAsync(c->sc_cov_ids.p, lm_ids, (size_t)n_out * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    ids = c->sc_cov_ids.p;
+    return 0;
+  }
+};
 
 // Landmark blocks Sigma_l = Hll^-1 + F_l^T C F_l of the requested landmarks (and, on request, the camera blocks of the
 // same C): the camera call's W, then C = W W^T off the diagonal too (cov_lauum) and the per-landmark contraction (lm_cov).
 static int landmark_covariance(povar_ctx* c, int dim, double lambda, int32_t gauge, int32_t coords, const int32_t* lm_ids,
                                int32_t n_ids, double* lm_cov_out, double* cam_cov) {
-  const char* who = dim == 12 ? "povar_landmark_covariance_pose" : "povar_landmark_covariance_joint";
-  if (int rc = check_ctx(c)) return rc;
-  const int n_out = lm_ids ? n_ids : c->n_lms;
-  if (n_out < 0) return fail(-1, std::string(who) + ": negative n_ids");
-  for (int i = 0; lm_ids && i < n_out; ++i)
-    if (lm_ids[i] < 0 || lm_ids[i] >= c->n_lms) return fail(-1, std::string(who) + ": landmark id out of range");
-  const int stride = dim == 12 ? 9 : 16;
-  const size_t lm_count = (size_t)stride * (size_t)n_out, cam_count = 144 * (size_t)c->n_cams;
-  CovInverse f;
+  CovRequest q;
+  q.who = dim == 12 ? "povar_landmark_covariance_pose" : "povar_landmark_covariance_joint";
+  if (int rc = q.check(c, lm_ids, n_ids, false)) return rc;
+  q.out = lm_cov_out;
+  q.count = (size_t)lm_stride(dim) * (size_t)q.n_out;
+  q.cam = cam_cov;
+  q.cam_count = 144 * (size_t)c->n_cams;
+  CovInverse f{};
   std::optional<TimeScope> ts;
-  int rc = cov_inverse(c, dim, who, lm_cov_out != nullptr || n_out == 0, lambda, gauge, coords, f, ts);
-  auto all_nan = [&]() {
-    std::fill(lm_cov_out, lm_cov_out + lm_count, std::nan(""));
-    if (cam_cov) std::fill(cam_cov, cam_cov + cam_count, std::nan(""));
-    return POVAR_NUMERIC_FAILURE;
-  };
+  int rc = cov_inverse(c, dim, q.who, lm_cov_out != nullptr || q.n_out == 0, lambda, gauge, coords, f, ts);
   if (rc == 0 && cam_cov) rc = cov_camera_blocks(c, dim, f, coords, cam_cov);
-  if (rc == POVAR_NUMERIC_FAILURE) return all_nan();
-  if (rc == 0 && n_out == 0) cov_done(c, f, 1);  // (no landmark: cov_lauum does not run)
-  if (rc != 0 || n_out == 0) return rc;
-  if (int rc2 = cov_buffer(c, c->sc_cov_lm, lm_count, dim)) return rc2;
-  if (lm_ids) {
-    if (int rc2 = cov_buffer(c, c->sc_cov_ids, (size_t)n_out, dim)) return rc2;
-    HIP_TRY(hipMemcpyAsync(c->sc_cov_ids.p, lm_ids, (size_t)n_out * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  }
-  cov_lm_launch(c, dim, f, lm_ids ? c->sc_cov_ids.p : nullptr, n_out, f.q, f.nq, coords);
+  if (q.over(c, f, q.n_out == 0, rc)) return rc;
+  if (int rc2 = cov_buffer(c, c->sc_cov_lm, q.count, dim)) return rc2;
+  if (int rc2 = q.upload_ids(c, dim)) return rc2;
+  cov_lm_launch(c, dim, f, q.ids, q.n_out, f.q, f.nq, coords);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(lm_cov_out, c->sc_cov_lm.p, lm_count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));  // (also: lm_ids is the caller's memory)
-  for (size_t i = 0; i < lm_count; ++i)
-    if (!std::isfinite(lm_cov_out[i])) return all_nan();
+  HIP_TRY(hipMemcpyAsync(lm_cov_out, c->sc_cov_lm.p, q.count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (size_t i = 0; i < q.count; ++i)
+    if (!std::isfinite(lm_cov_out[i])) return q.all_nan();
   cov_done(c, f, 2);
   return 0;
 }
@@ -491,57 +548,58 @@ static int landmark_covariance(povar_ctx* c, int dim, double lambda, int32_t gau
 // contraction obs_cov, which reads no Q: the gauge part of C cancels in J C J^T only if no term carries the correction.
 static int observation_covariance(povar_ctx* c, int dim, double lambda, int32_t gauge, const int32_t* lm_ids, int32_t n_ids,
                                   double* obs_cov_out, int64_t n_rows) {
-  const char* who = dim == 12 ? "povar_observation_covariance_pose" : "povar_observation_covariance_joint";
-  if (int rc = check_ctx(c)) return rc;
-  const int n_out = lm_ids ? n_ids : c->n_lms;
-  if (n_out < 0) return fail(-1, std::string(who) + ": negative n_ids");
-  std::vector<int> row0((size_t)n_out);
-  int64_t rows = 0;
-  for (int i = 0; i < n_out; ++i) {
-    const int l = lm_ids ? lm_ids[i] : i;
-    if (l < 0 || l >= c->n_lms) return fail(-1, std::string(who) + ": landmark id out of range");
-    if (rows > INT32_MAX) return fail(-1, std::string(who) + ": more than 2^31 rows requested");
-    row0[i] = (int)rows;
-    rows += c->lm_off[l + 1] - c->lm_off[l];
-  }
-  if (n_rows != rows) return fail(-1, std::string(who) + ": n_rows is " + std::to_string(n_rows) + ", the request produces " + std::to_string(rows));
-  const size_t count = 4 * (size_t)rows;
-  CovInverse f;
+  CovRequest q;
+  q.who = dim == 12 ? "povar_observation_covariance_pose" : "povar_observation_covariance_joint";
+  if (int rc = q.check(c, lm_ids, n_ids, true)) return rc;
+  if (n_rows != q.rows)
+    return fail(-1, std::string(q.who) + ": n_rows is " + std::to_string(n_rows) + ", the request produces " + std::to_string(q.rows));
+  q.out = obs_cov_out;
+  q.count = 4 * (size_t)q.rows;
+  CovInverse f{};
   std::optional<TimeScope> ts;
-  int rc = cov_inverse(c, dim, who, obs_cov_out != nullptr || rows == 0, lambda, gauge, POVAR_COV_SOLVER_COORDS, f, ts);
-  auto all_nan = [&]() {
-    std::fill(obs_cov_out, obs_cov_out + count, std::nan(""));
-    return POVAR_NUMERIC_FAILURE;
-  };
-  if (rc == POVAR_NUMERIC_FAILURE) return all_nan();
-  if (rc == 0 && rows == 0) cov_done(c, f, 1);  // (no observation: cov_lauum does not run)
-  if (rc != 0 || rows == 0) return rc;
-  if (int rc2 = cov_buffer(c, c->sc_cov_lm, (size_t)(dim == 12 ? 9 : 16) * (size_t)n_out, dim)) return rc2;
-  if (int rc2 = cov_buffer(c, c->sc_cov_row0, (size_t)n_out, dim)) return rc2;
-  if (int rc2 = cov_buffer(c, c->sc_cov_obs, count, dim)) return rc2;
-  if (lm_ids) {
-    if (int rc2 = cov_buffer(c, c->sc_cov_ids, (size_t)n_out, dim)) return rc2;
-    HIP_TRY(hipMemcpyAsync(c->sc_cov_ids.p, lm_ids, (size_t)n_out * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  }
-  HIP_TRY(hipMemcpyAsync(c->sc_cov_row0.p, row0.data(), (size_t)n_out * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  int rc = cov_inverse(c, dim, q.who, obs_cov_out != nullptr || q.rows == 0, lambda, gauge, POVAR_COV_SOLVER_COORDS, f, ts);
+  if (q.over(c, f, q.rows == 0, rc)) return rc;
+  if (int rc2 = cov_buffer(c, c->sc_cov_lm, (size_t)lm_stride(dim) * (size_t)q.n_out, dim)) return rc2;
+  if (int rc2 = cov_buffer(c, c->sc_cov_row0, (size_t)q.n_out, dim)) return rc2;
+  if (int rc2 = cov_buffer(c, c->sc_cov_obs, q.count, dim)) return rc2;
+  if (int rc2 = q.upload_ids(c, dim)) return rc2;
+  HIP_TRY(hipMemcpyAsync(c->sc_cov_row0.p, q.row0.data(), (size_t)q.n_out * sizeof(int), hipMemcpyHostToDevice, c->stream));
   // (rows of a landmark without observations do not exist; every other entry is written)
-  const int* ids = lm_ids ? c->sc_cov_ids.p : nullptr;
-  cov_lm_launch(c, dim, f, ids, n_out, nullptr, 0, POVAR_COV_SOLVER_COORDS);
-  if (dim == 12)
-    hipLaunchKernelGGL(obs_cov<12>, dim3(n_out), dim3(256), 0, c->stream, c->d, (const double*)c->ncw.p, (const int*)c->sc_lm_slot0.p,
-                       (const int*)c->sc_lm_cnt.p, ids, (const int*)c->sc_cov_row0.p, (const double*)c->sc_dense.p, f.ld,
-                       (const double*)c->sc_cov_panel.p, (const double*)c->sc_cov_lm.p, c->sc_cov_obs.p);
-  else
-    hipLaunchKernelGGL(obs_cov<11>, dim3(n_out), dim3(256), 0, c->stream, c->d, (const double*)c->ncw.p, (const int*)c->sc_lm_slot0.p,
-                       (const int*)c->sc_lm_cnt.p, ids, (const int*)c->sc_cov_row0.p, (const double*)c->sc_dense.p, f.ld,
-                       (const double*)c->sc_cov_panel.p, (const double*)c->sc_cov_lm.p, c->sc_cov_obs.p);
+  cov_lm_launch(c, dim, f, q.ids, q.n_out, nullptr, 0, POVAR_COV_SOLVER_COORDS);
+  with_step(dim, [&](auto step) {
+    hipLaunchKernelGGL(obs_cov<decltype(step)>, dim3(q.n_out), dim3(256), 0, c->stream, c->d, (const double*)c->ncw.p,
+                       (const int*)c->sc_lm_slot0.p, (const int*)c->sc_lm_cnt.p, q.ids, (const int*)c->sc_cov_row0.p,
+                       (const double*)c->sc_dense.p, f.ld, (const double*)c->sc_cov_panel.p, (const double*)c->sc_cov_lm.p,
+                       c->sc_cov_obs.p);
+  });
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(obs_cov_out, c->sc_cov_obs.p, count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));  // (also: lm_ids and row0 are host memory that goes out of scope)
+  HIP_TRY(hipMemcpyAsync(obs_cov_out, c->sc_cov_obs.p, q.count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));  // (also: row0 is host memory that goes out of scope)
   // the status judges the factorisation: a leverage that is not finite means C is not; c_* may be non-finite at y2 = 0
-  for (size_t i = 0; i < count; i += 4)
-    if (!std::isfinite(obs_cov_out[i])) return all_nan();
+  for (size_t i = 0; i < q.count; i += 4)
+    if (!std::isfinite(obs_cov_out[i])) return q.all_nan();
   cov_done(c, f, 2);
+  return 0;
+}
+
+// LinearizorSC::solve / solve_joint behind povar_solve_pose_sc and povar_solve_joint_sc_method: PCG / RIPCG or the direct solve
+// of the step's reduced camera system, the increment to the host, POVAR_NUMERIC_FAILURE when it is not finite
+// (bal_bundle_adjustment.cpp:362)
+static int solve_sc(povar_ctx* c, int dim, const char* who, double lambda, int32_t method, int32_t min_iterations,
+                    int32_t max_iterations, double eta, double* inc, int32_t* num_iterations, int32_t* termination) {
+  if (method != POVAR_SC_PCG && method != POVAR_SC_CHOLESKY) return fail(-1, std::string(who) + ": unknown method");
+  if (int rc = prepare_sc(c, dim, lambda)) return rc;
+  {
+    TimeScope ts(c, 2);
+    const int rc = method == POVAR_SC_CHOLESKY ? run_cholesky(c, dim, num_iterations, termination) : with_step(dim, [&](auto step) {
+      typedef decltype(step) S;
+      return run_pcg<S::DIM, S::HOM>(c, min_iterations, max_iterations, eta, num_iterations, termination);
+    });
+    if (rc) return rc;
+  }
+  if (int rc = povar_get_increment(c, inc)) return rc;
+  for (size_t i = 0; i < (size_t)dim * (size_t)c->n_cams; ++i)
+    if (!std::isfinite(inc[i])) return POVAR_NUMERIC_FAILURE;
   return 0;
 }
 
@@ -589,50 +647,13 @@ int povar_set_jl_col_scaling(povar_ctx* c, int32_t enable) {
 
 int povar_solve_pose_sc(povar_ctx* c, double lambda, int32_t method, int32_t min_iterations, int32_t max_iterations,
                         double eta, double* inc, int32_t* num_iterations, int32_t* termination) {
-  if (method != POVAR_SC_PCG && method != POVAR_SC_CHOLESKY) return fail(-1, "povar_solve_pose_sc: unknown method");
-  // LinearizorSC::solve (linearizor_sc.cpp:85-160): no landmark damping on this path
-  if (int rc = povar_prepare_pose(c, lambda, POVAR_POWER_VARPROJ)) return rc;
-  ensure_legacy(c);
-  if (int rc = ensure_sc(c)) return rc;
-  if (int rc = build_schur_jacobi<false>(c, lambda)) return rc;
-  {
-    TimeScope ts(c, 2);
-    if (method == POVAR_SC_CHOLESKY) {
-      if (int rc = run_cholesky(c, 12, num_iterations, termination)) return rc;
-    } else {
-      if (int rc = run_pcg<12, false>(c, min_iterations, max_iterations, eta, num_iterations, termination)) return rc;
-    }
-  }
-  if (int rc = povar_get_increment(c, inc)) return rc;
-  for (size_t i = 0; i < 12 * (size_t)c->n_cams; ++i)
-    if (!std::isfinite(inc[i])) return POVAR_NUMERIC_FAILURE;  // bal_bundle_adjustment.cpp:362
-  return 0;
+  return solve_sc(c, 12, "povar_solve_pose_sc", lambda, method, min_iterations, max_iterations, eta, inc, num_iterations, termination);
 }
 
 int povar_solve_joint_sc_method(povar_ctx* c, double lambda, int32_t method, int32_t min_iterations, int32_t max_iterations,
                                 double eta, double* inc, int32_t* num_iterations, int32_t* termination) {
-  if (method != POVAR_SC_PCG && method != POVAR_SC_CHOLESKY) return fail(-1, "povar_solve_joint_sc_method: unknown method");
-  // LinearizorSC::solve_joint (linearizor_sc.cpp:224-303); landmark damping is part of the prepared system
-  if (int rc = povar_prepare_joint(c, lambda)) return rc;
-  // cm_gram_sc reads the per-slot sqrt(w) and the landmark-order records: after a lane-per-landmark linearisation /
-  // prepare they are rebuilt here (missing until round 3: RIPCG with a robust norm took stale weights on every problem
-  // large enough for the lane-per-landmark kernels -- the parity tests' "lane-per-landmark" halves were not running
-  // those kernels, tests/conftest.py)
-  ensure_legacy(c);
-  if (int rc = ensure_sc(c)) return rc;
-  if (int rc = build_schur_jacobi<true>(c, lambda)) return rc;
-  {
-    TimeScope ts(c, 2);
-    if (method == POVAR_SC_CHOLESKY) {
-      if (int rc = run_cholesky(c, 11, num_iterations, termination)) return rc;
-    } else {
-      if (int rc = run_pcg<11, true>(c, min_iterations, max_iterations, eta, num_iterations, termination)) return rc;
-    }
-  }
-  if (int rc = povar_get_increment(c, inc)) return rc;
-  for (size_t i = 0; i < 11 * (size_t)c->n_cams; ++i)
-    if (!std::isfinite(inc[i])) return POVAR_NUMERIC_FAILURE;
-  return 0;
+  return solve_sc(c, 11, "povar_solve_joint_sc_method", lambda, method, min_iterations, max_iterations, eta, inc, num_iterations,
+                  termination);
 }
 
 int povar_solve_joint_sc(povar_ctx* c, double lambda, int32_t min_iterations, int32_t max_iterations, double eta,
