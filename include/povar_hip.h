@@ -65,7 +65,9 @@ typedef struct {
 enum {
   /* run-to-run BIT-reproducible results for a given device count (fixed reduction order inside a GPU): the gather
    * mode for linearisation / preparation / cost, the fixed-point, ticket-ordered camera-chunk kernels for the terms (1.26 x the
-   * default term on venice-1778), no row placement on a host thread, no timing decides a kernel.  [POVAR_DETERMINISTIC=1] */
+   * default term on venice-1778), the ordered assembly of the dense reduced camera matrix (povar_set_sc_assembly: CHOLESKY,
+   * RICHOLESKY and the covariance calls are covered like PCG / RIPCG and the power series), no row placement on a host thread,
+   * no timing decides a kernel.  [POVAR_DETERMINISTIC=1] */
   POVAR_FLAG_DETERMINISTIC = 1u << 0,
   /* with POVAR_FLAG_DETERMINISTIC: the terms in the gather form too (3.7 x the default term).  [POVAR_DET_CK=0] */
   POVAR_FLAG_DET_GATHER_TERMS = 1u << 1,
@@ -119,7 +121,8 @@ typedef struct {
 
 /* per-kernel-class device time measured with HIP events on the context's stream */
 typedef struct {
-  double e0_ms;      /* sum over launches of the E0 (SpMV) kernels of one term */
+  double e0_ms;      /* sum over launches of the E0 (SpMV) kernels of one term; a dense call (CHOLESKY, RICHOLESKY, covariance)
+                        adds one interval: the launches that assemble its matrix */
   int64_t e0_launches;
   double binv_ms;    /* B^-1 / AXPY kernel */
   int64_t binv_launches;
@@ -245,8 +248,9 @@ int povar_solve_joint_sc(povar_ctx* ctx, double lambda, int32_t min_iterations, 
  * N_c^T sigma E0 sigma N_c of the 11 n_cams tangent coordinates is assembled on the device (landmark damping
  * included, as povar_prepare_joint leaves it) and factored by the kernels of CHOLESKY (needs 8 * (11 n_cams)^2 bytes
  * of HBM; num_iterations = 0; min / max_iterations and eta are not read).  The reference has no direct step-2
- * solver: this is `bal --solver-type-step-2 RICHOLESKY`, the limit RIPOBA and RIPCG approach.  The assembly adds
- * with fp64 atomics, so it is not bit-reproducible (as step 1's).  A system that is not positive definite gives a
+ * solver: this is `bal --solver-type-step-2 RICHOLESKY`, the limit RIPOBA and RIPCG approach.  The default assembly
+ * adds with fp64 atomics, so it is not bit-reproducible (as step 1's); the ordered assembly is (povar_set_sc_assembly; what a
+ * POVAR_FLAG_DETERMINISTIC context runs), and everything after the assembly is fixed-order in both.  A system that is not positive definite gives a
  * non-finite increment and POVAR_NUMERIC_FAILURE; an unknown method is an argument error. */
 int povar_solve_joint_sc_method(povar_ctx* ctx, double lambda, int32_t method, int32_t min_iterations,
                                 int32_t max_iterations, double eta, double* inc /*11 n_cams*/,
@@ -298,7 +302,8 @@ int povar_camera_covariance_joint(povar_ctx* ctx, double lambda, int32_t gauge, 
  *       Sigma_l = Hll_l^-1 + F_l^T C F_l.
  * From the same factor: W = R^-1 as above, then C = W W^T off the diagonal too (a third n^3 / 3 pass on the fp64 matrix
  * cores, in place: no further n^2 buffer) and one workgroup per requested landmark that contracts the blocks C[c_i, c_j] of
- * its camera pairs.  Given C a block is reproducible: the contraction uses no atomics (the assembly of S does).
+ * its camera pairs.  Given C a block is reproducible: the contraction uses no atomics (the default assembly
+ * of S does; with the ordered assembly -- povar_set_sc_assembly, POVAR_FLAG_DETERMINISTIC -- C and the blocks are bit-reproducible).
  *   gauge  POVAR_COV_DAMPED: C = S(lambda)^-1 and Sigma_l is exactly the (l, l) block of H^-1.
  *          POVAR_COV_FREE_GAUGE (lambda = 0): C = S(0)^+.  This is the covariance with the gauge fixed on the cameras: minimum
  *          norm over the camera parameters, i.e. under the constraint Q^T x_cameras = 0 -- the gauge the camera call fixes,
@@ -340,7 +345,7 @@ int povar_landmark_covariance_joint(povar_ctx* ctx, double lambda, int32_t gauge
  * and no caveat about where the gauge is fixed.  In the free gauge, over all observations of an unsharded context,
  *       sum_i h_i = rank J = DIM n_cams + 3 n_lms - nq     (DIM = 12, nq = 12 in step 1; DIM = 11, nq = 15 in step 2).
  * From the same factor as the landmark calls: C = W W^T, Sigma_l (without the gauge correction, which cancels in J C J^T) and
- * one more workgroup per landmark; given C a row is reproducible (no atomics).
+ * one more workgroup per landmark; given C a row is reproducible (no atomics; with the ordered assembly, as above, bit for bit).
  *   gauge, lambda   the camera calls' rules.  POVAR_COV_DAMPED: h = tr(J_i H(lambda)^-1 J_i^T).
  *   lm_ids, n_ids   as the landmark calls'.
  *   obs_cov, n_rows 4 n_rows doubles.  The rows are the observations of the requested landmarks in the caller's CSR order:
@@ -544,6 +549,17 @@ int povar_set_e0_kernel(povar_ctx* ctx, int32_t kernel);
  * (povar_layout_info.res_auto[_h], tune_terms[_h]_us, tune_res[_h]_us).  The switch covers both steps; a series of either
  * step that gives up (res_failed) leaves both on the per-term kernels.  Environment: POVAR_RES=0|1. */
 int povar_set_series_kernel(povar_ctx* ctx, int32_t mode);
+/* Assembly of the dense reduced camera matrix that CHOLESKY, RICHOLESKY and the covariance calls factor (one switch: they share
+ * the assembly).  mode 1: fp64 atomics, a workgroup per landmark (sc_dense_offdiag[_h]; the last bits depend on the arrival
+ * order); mode 2: the ordered kernel (sc_dense_ordered, povar_kernels_sc.hpp): the same terms, no floating-point atomic, added
+ * in an order that is a function of the context's layout alone -- with it a direct solve and a covariance are bit-reproducible
+ * run to run (sharded: for a given device count and an all-reduce that sums in a fixed order, as the host hook does);
+ * mode -1 (default): the library's choice, ordered on a POVAR_FLAG_DETERMINISTIC context and atomics otherwise.  On a
+ * deterministic context the choice is pinned: the call returns 0 and changes nothing.  An unknown mode is an argument error. */
+int povar_set_sc_assembly(povar_ctx* ctx, int32_t mode);
+/* the assembly the context's last dense call ran: 0 = none yet, 1 = atomics, 2 = ordered (PCG / RIPCG and the power series
+ * assemble nothing and leave the value alone); < 0 on error */
+int povar_sc_assembly(povar_ctx* ctx);
 /* Diagnostic builds only (tools/variants/build_variant.sh ck_stamps -- a patched copy of the sources --, tools/ck_stamps.py):
  * in-kernel s_memtime stamps of e0_ck's phases, [workgroups][16 wavefronts][40]; the first call arms the collection.  The
  * shipped library executes no stamp and returns an error. */

@@ -484,6 +484,15 @@ class Context:
         """-1: timed choice, 0: per-term kernels in a hipGraph, 1: the resident power series (include/povar_hip.h)."""
         self._chk(self.L.povar_set_series_kernel(self.h, C.c_int32(int(mode))))
 
+    def set_sc_assembly(self, mode):
+        """Assembly of the dense matrix of CHOLESKY / RICHOLESKY / the covariance calls: -1 the library's choice (ordered on a
+        deterministic context, atomics otherwise), 1 atomics, 2 the ordered, bit-reproducible kernel (include/povar_hip.h)."""
+        self._chk(self.L.povar_set_sc_assembly(self.h, C.c_int32(int(mode))))
+
+    def sc_assembly(self):
+        """The assembly the last dense call ran: 0 none yet, 1 atomics, 2 ordered."""
+        return self._chk(self.L.povar_sc_assembly(self.h), allow_numeric=True)
+
     def comm_ranks(self):
         n = self.L.povar_comm_ranks(self.h)
         if n < 0:

@@ -260,6 +260,10 @@ struct povar_ctx {
   DevBuf<double> sc_dense, sc_xpad;      // CHOLESKY / RICHOLESKY: augmented S (povar_kernels_chol.hpp) and the padded solution,
                                          // grown to the larger of the two systems a context solves (run_cholesky)
   DevBuf<int> sc_lm_slot0, sc_lm_cnt, sc_info;
+  // assembly of the dense matrix (povar_set_sc_assembly / povar_sc_assembly): the caller's choice (-1: the library's -- ordered on
+  // a deterministic context, atomics otherwise; 1: atomics, sc_dense_diag + sc_dense_offdiag[_h]; 2: ordered, sc_dense_ordered)
+  // and what the last chol_factor ran (0: none yet)
+  int sc_assembly = -1, sc_assembly_last = 0;
   int sc_factor_dim = 0;                 // POVAR_BUF_SC_FACTOR: the system whose R, y (sc_dense) and x (sc_xpad) are in place:
   int sc_factor_n = 0;                   // 12 (step 1) or 11 (step 2) and dim * n_cams; 0: none (chol_factor, the covariance calls)
   // camera covariance (povar_camera_covariance_*), grown on demand and kept: the gauge basis Q, (max A_kk, min R_kk^2), the

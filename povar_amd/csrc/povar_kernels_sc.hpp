@@ -520,6 +520,8 @@ POVAR_KERNEL __launch_bounds__(256) void pcg_finish(const double* x, double* acc
 // One workgroup per landmark, observations staged 64 at a time in LDS, 16-lane groups take one
 // camera pair each and add its 144 entries with fp64 atomics (hub cameras' blocks are shared by many
 // landmarks).  S is the augmented row-major matrix of povar_kernels_chol.hpp (row stride ld).
+// The atomics land in arrival order, so this assembly is reproducible to rounding only; sc_dense_ordered below adds the same
+// terms (ScdPose::term) in an order the layout fixes and is what a POVAR_FLAG_DETERMINISTIC context runs (povar_set_sc_assembly).
 // ------------------------------------------------------------------------------------------
 constexpr int SCD_CHUNK = 64;
 struct ScdObs {
@@ -566,6 +568,18 @@ struct ScdPose {
   __device__ static __forceinline__ void stage(const Dp& d, const double*, int slot, Head hd, Obs& o) {
     scd_stage(d, slot, hd.s4, hd.Hi, o);
   }
+  // The term a pair of observations (a, b) of one landmark adds to entry (r, c) of the block (a.cam, b.cam) of S -- the one
+  // expression of the atomic and the ordered assembly (sc_dense_offdiag, sc_dense_ordered) --, and what the entries of a pair
+  // share (Pair).  h: the landmark's Head::h.
+  struct Pair { const double *sgi, *sgj; };
+  __device__ static __forceinline__ Pair pair(const Dp& d, const Obs& a, const Obs& b) {
+    return Pair{d.sigma + 12 * (size_t)a.cam, d.sigma + 12 * (size_t)b.cam};
+  }
+  __device__ static __forceinline__ double term(const Pair& p, const Obs& oa, const Obs& ob, const double (&h)[4], int r, int c) {
+    const int a = r >> 2, ii = r & 3, b = c >> 2, jj = c & 3;
+    const double t = oa.G[3 * a] * ob.F[3 * b] + oa.G[3 * a + 1] * ob.F[3 * b + 1] + oa.G[3 * a + 2] * ob.F[3 * b + 2];
+    return -t * h[ii] * h[jj] * p.sgi[r] * p.sgj[c];
+  }
   // u[a] = entry r of u_a = sigma_c o (e_a (x) h).  h: the kernel's copy of Head::h (indexed at run time: not left in the Head)
   __device__ static inline void u(const Obs& o, const double* sigma, const double (&h)[4], int r, double (&u)[3]) {
     const double v = sigma[12 * (size_t)o.cam + r] * h[r & 3];
@@ -608,15 +622,10 @@ POVAR_KERNEL __launch_bounds__(256) void sc_dense_offdiag(Dp d, const int* lm_sl
         const int i = pp / nj, j = pp - i * nj;
         if (ic == jc && i > j) continue;  // cameras ascend inside a landmark: keep camera_i <= camera_j
         const int ci = oi[i].cam, cj = oj[j].cam;
-        const double* sgi = d.sigma + 12 * (size_t)ci;
-        const double* sgj = d.sigma + 12 * (size_t)cj;
+        const ScdPose::Pair pr = ScdPose::pair(d, oi[i], oj[j]);
         for (int e = gl; e < 144; e += 16) {
           const int r = e / 12, c = e - 12 * r;
-          const int a = r >> 2, ii = r & 3, b = c >> 2, jj = c & 3;
-          const double t = oi[i].G[3 * a] * oj[j].F[3 * b] + oi[i].G[3 * a + 1] * oj[j].F[3 * b + 1] +
-                           oi[i].G[3 * a + 2] * oj[j].F[3 * b + 2];
-          const double v = -t * h[ii] * h[jj] * sgi[r] * sgj[c];
-          atomicAdd(S + (12 * (int64_t)ci + r) * ld + 12 * (int64_t)cj + c, v);
+          atomicAdd(S + (12 * (int64_t)ci + r) * ld + 12 * (int64_t)cj + c, ScdPose::term(pr, oi[i], oj[j], h, r, c));
         }
       }
     }
@@ -626,10 +635,11 @@ POVAR_KERNEL __launch_bounds__(256) void sc_dense_offdiag(Dp d, const int* lm_sl
 // S_cc += B_c = Hpp_c + lambda I (landmark_block.hpp:381-384 + linearization_sc.hpp:477-481; step 2: its tangent
 // projection, cam_build_sc<true>'s out_mat) and the right-hand side -b into column N of the augmented matrix
 // (povar_kernels_chol.hpp).  DIM = 12 (step 1) or 11 (step 2): B_c is DIM x DIM row-major at stride 144.
-template <int DIM>
+// WITH_B = false: the right-hand side alone (the ordered assembly adds B_c itself, without an atomic).
+template <int DIM, bool WITH_B = true>
 __global__ __launch_bounds__(256) void sc_dense_diag(Dp d, const double* bmat, double* S, int64_t ld, int N) {
   const int c = blockIdx.x, e = threadIdx.x;
-  if (e < DIM * DIM) {
+  if (WITH_B && e < DIM * DIM) {
     const int r = e / DIM, cc = e - DIM * r;
     atomicAdd(S + (DIM * (int64_t)c + r) * ld + DIM * (int64_t)c + cc, bmat[144 * (size_t)c + e]);
   }
@@ -648,7 +658,8 @@ __global__ __launch_bounds__(256) void sc_dense_diag(Dp d, const double* bmat, d
 // bilinear form; the reflector stays out of the pair loop.  The i == j terms are the E0 part of the diagonal block
 // (what cm_gram_sc<true> + cam_build_sc<true> subtract for the preconditioner); B_c comes from sc_dense_diag<11>.
 // Workgroup per landmark, chunks of 32 staged observations (two arrays: 26 KB of LDS), a 16-lane group per camera
-// pair, camera_i <= camera_j only, fp64 atomics as in step 1 (so the assembly is not bit-reproducible either).
+// pair, camera_i <= camera_j only, fp64 atomics as in step 1 (so this assembly is not bit-reproducible either; the ordered one,
+// sc_dense_ordered<ScdJoint>, adds the same ScdJoint::term in a fixed order).
 // ------------------------------------------------------------------------------------------
 constexpr int SCDH_CHUNK = 32;
 struct ScdObsH {
@@ -721,6 +732,23 @@ struct ScdJoint {
   __device__ static __forceinline__ void stage(const Dp& d, const double* ncw, int slot, Head hd, Obs& o) {
     scdh_stage(d, ncw, slot, hd.X, hd.s, hd.Hi, hd.hw, hd.hbeta, o);
   }
+  // as ScdPose::pair / term: T = F_a Hll^-1 F_b^T is what the 121 entries share; entry (r, c) is -sum_pq U_a[p][r] T_pq U_b[q][c]
+  struct Pair { double T[9]; };
+  __device__ static __forceinline__ Pair pair(const Dp&, const Obs& a, const Obs& b) {
+    Pair p;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int q = 0; q < 3; ++q) p.T[3 * i + q] = a.G[3 * i] * b.F[3 * q] + a.G[3 * i + 1] * b.F[3 * q + 1] + a.G[3 * i + 2] * b.F[3 * q + 2];
+    return p;
+  }
+  __device__ static __forceinline__ double term(const Pair& p, const Obs& a, const Obs& b, const double (&)[4], int r, int c) {
+    const double* T = p.T;
+    const double v0 = b.U[c], v1 = b.U[11 + c], v2 = b.U[22 + c];
+    const double t = a.U[r] * (T[0] * v0 + T[1] * v1 + T[2] * v2) + a.U[11 + r] * (T[3] * v0 + T[4] * v1 + T[5] * v2) +
+                     a.U[22 + r] * (T[6] * v0 + T[7] * v1 + T[8] * v2);
+    return -t;
+  }
   // u[a] = entry r of u_a = N_c^T (sigma_c o (e_a (x) X)): the staged U
   __device__ static inline void u(const Obs& o, const double*, const double (&)[4], int r, double (&u)[3]) {
     u[0] = o.U[r];
@@ -765,20 +793,140 @@ POVAR_KERNEL __launch_bounds__(256) void sc_dense_offdiag_h(Dp d, const double* 
         if (ic == jc && i > j) continue;  // cameras ascend inside a landmark: keep camera_i <= camera_j
         const ScdObsH& a = oi[i];
         const ScdObsH& b = oj[j];
-        double T[9];  // F_i Hll^-1 F_j^T
-#pragma unroll
-        for (int p = 0; p < 3; ++p)
-#pragma unroll
-          for (int q = 0; q < 3; ++q) T[3 * p + q] = a.G[3 * p] * b.F[3 * q] + a.G[3 * p + 1] * b.F[3 * q + 1] + a.G[3 * p + 2] * b.F[3 * q + 2];
+        const ScdJoint::Pair pr = ScdJoint::pair(d, a, b);  // F_i Hll^-1 F_j^T
         double* blk = S + 11 * (int64_t)a.cam * ld + 11 * (int64_t)b.cam;
         for (int e = gl; e < 121; e += 16) {
           const int r = e / 11, c = e - 11 * r;
-          const double v0 = b.U[c], v1 = b.U[11 + c], v2 = b.U[22 + c];
-          const double t = a.U[r] * (T[0] * v0 + T[1] * v1 + T[2] * v2) + a.U[11 + r] * (T[3] * v0 + T[4] * v1 + T[5] * v2) +
-                           a.U[22 + r] * (T[6] * v0 + T[7] * v1 + T[8] * v2);
-          atomicAdd(blk + r * ld + c, -t);
+          atomicAdd(blk + r * ld + c, ScdJoint::term(pr, a, b, hd.h, r, c));
         }
       }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// Ordered dense assembly (povar_set_sc_assembly; the assembly of a POVAR_FLAG_DETERMINISTIC context): the same terms as
+// sc_dense_offdiag[_h] (Step::stage, Step::pair, Step::term) and B_c, added without a floating-point atomic in an order that is a
+// function of the context's layout alone, into the same block triangle camera_i <= camera_j; no buffer beside S.
+//   ownership  a workgroup owns the blocks (ci, cj) of one row camera ci and SCO_T consecutive column cameras cj >= ci, as
+//              accumulators in LDS.  A wavefront owns the columns with col % SCO_WAVES == its number, a lane the entries
+//              e % 64 == its number of each: every entry has one thread from the first add to the store.
+//   walk       ci's observations in the context's camera-major order (cam_item_off -> item_off -> cm_slot / cm_lm), SCO_WALK
+//              at a time, one per thread: the partners of an observation are the slots of its landmark from its own on
+//              (cameras ascend inside a landmark: two searches in Dp::cam give those inside the tile; its own slot is the
+//              i == j term of the diagonal block).  An exclusive prefix sum over the counts -- integers: exact in any order --
+//              numbers the pairs: by observation in camera-major order, then by column.
+//   windows    SCO_PAIRS pairs at a time are staged (one wavefront the own observations, one the partners; every staging
+//              thread decodes its landmark's record itself) and, after a barrier, every wavefront goes through the window in
+//              order and adds the pairs of its columns.  The order of the terms of an entry is therefore the camera-major order
+//              of ci's observations, whatever the timing, the number of CUs or the order of the workgroups.
+//   write-out  B_c once per entry of the diagonal block (bmat: rank 0 only), then S += accumulator with plain loads and stores
+//              (S holds zeros, or Q Q^T of the free gauge); columns no term touched are left alone.
+// grid = n_cams * ceil(n_cams / SCO_T); the row cameras in popularity order (Dp::hot_cams: the long walks first); a workgroup
+// whose tile lies left of the diagonal returns at once.  On a sharded context the camera-major arrays hold the shard's
+// observations: every rank adds its part in its order and the all-reduce sums the parts.
+// ------------------------------------------------------------------------------------------
+constexpr int SCO_T = 32, SCO_WALK = 256, SCO_WAVES = SCO_WALK / 64, SCO_PAIRS = 32;
+
+// the first index in [lo, hi) whose camera is >= v (hi: none); cameras ascend over the slots of a landmark
+__device__ inline int sco_lower(const int* cam, int lo, int hi, int v) {
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (cam[mid] < v) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+template <class Step>
+__global__ __launch_bounds__(SCO_WALK) void sc_dense_ordered(Dp d, const double* ncw, const double* bmat, double* S, int64_t ld) {
+  constexpr int DIM = Step::DIM, DD = DIM * DIM;
+  typedef typename Step::Obs Obs;
+  __shared__ double acc[SCO_T * DD];
+  __shared__ Obs oi[SCO_PAIRS], oj[SCO_PAIRS];
+  __shared__ double hh[SCO_PAIRS][4];  // Head::h of every staged pair's landmark
+  __shared__ int pre[SCO_WALK], own[SCO_WALK], first[SCO_WALK], wsum[SCO_WAVES];
+  static_assert(sizeof(double) * SCO_T * DD + 2 * SCO_PAIRS * sizeof(Obs) + sizeof(double) * 4 * SCO_PAIRS +
+                        sizeof(int) * (3 * SCO_WALK + SCO_WAVES) <= 64 * 1024, "sc_dense_ordered: static LDS");
+  static_assert(SCO_T <= 32 && 2 * 64 <= SCO_WALK && SCO_PAIRS <= 64, "sc_dense_ordered: the touched mask, the two staging wavefronts");
+  const int n_tiles = (d.n_cams + SCO_T - 1) / SCO_T;
+  const int ci = d.hot_cams[blockIdx.x / n_tiles];
+  const int t0 = SCO_T * (int)(blockIdx.x % n_tiles);
+  if (t0 + SCO_T <= ci) return;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  for (int col = wave; col < SCO_T; col += SCO_WAVES)
+    for (int e = lane; e < DD; e += 64) acc[col * DD + e] = 0.0;
+  unsigned touched = 0;  // (the same in every lane of a wavefront)
+  const int pb = d.item_off[d.cam_item_off[ci]], pe = d.item_off[d.cam_item_off[ci + 1]];
+  for (int p0 = pb; p0 < pe; p0 += SCO_WALK) {
+    int s = 0, f = 0, n = 0;
+    if (p0 + tid < pe) {
+      s = d.cm_slot[p0 + tid];
+      const int lm = d.cm_lm[p0 + tid];
+      const int end = d.lm_slot0[lm] + d.lm_cnt[lm];
+      f = sco_lower(d.cam, s, end, t0);
+      n = sco_lower(d.cam, f, end, t0 + SCO_T) - f;
+    }
+    int inc = n;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int v = __shfl_up(inc, o, 64);
+      if (lane >= o) inc += v;
+    }
+    if (lane == 63) wsum[wave] = inc;
+    own[tid] = s;
+    first[tid] = f;
+    __syncthreads();
+    int base = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < SCO_WAVES; ++w) {
+      if (w < wave) base += wsum[w];
+      total += wsum[w];
+    }
+    pre[tid] = base + inc - n;
+    __syncthreads();
+    for (int g0 = 0; g0 < total; g0 += SCO_PAIRS) {
+      const int np = min(SCO_PAIRS, total - g0);
+      if (g0 > 0) __syncthreads();  // (the window before has been added)
+      if (wave < 2 && lane < np) {
+        const int g = g0 + lane;
+        int lo = 0, hi = SCO_WALK;  // the last observation whose first pair is <= g: the one pair g belongs to
+        while (hi - lo > 1) {
+          const int mid = (lo + hi) >> 1;
+          if (pre[mid] <= g) lo = mid;
+          else hi = mid;
+        }
+        const int slot = wave == 0 ? own[lo] : first[lo] + (g - pre[lo]);
+        const typename Step::Head hd = Step::load(d, d.lm[slot]);
+        Step::stage(d, ncw, slot, hd, wave == 0 ? oi[lane] : oj[lane]);
+        if (wave == 0) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) hh[lane][k] = hd.h[k];
+        }
+      }
+      __syncthreads();
+      for (int q = 0; q < np; ++q) {
+        const int col = oj[q].cam - t0;
+        if ((col & (SCO_WAVES - 1)) != wave) continue;
+        const typename Step::Pair pr = Step::pair(d, oi[q], oj[q]);
+        for (int e = lane; e < DD; e += 64) {
+          const int r = e / DIM, c = e - DIM * r;
+          acc[col * DD + e] += Step::term(pr, oi[q], oj[q], hh[q], r, c);
+        }
+        touched |= 1u << col;
+      }
+    }
+  }
+  if (bmat && ci >= t0 && ((ci - t0) & (SCO_WAVES - 1)) == wave) {  // the tile that holds the diagonal block (ci < t0 + SCO_T here)
+    for (int e = lane; e < DD; e += 64) acc[(ci - t0) * DD + e] += bmat[144 * (size_t)ci + e];
+    touched |= 1u << (ci - t0);
+  }
+  for (int col = wave; col < SCO_T; col += SCO_WAVES) {
+    if (!((touched >> col) & 1u)) continue;
+    double* blk = S + DIM * (int64_t)ci * ld + DIM * (int64_t)(t0 + col);
+    for (int e = lane; e < DD; e += 64) {
+      const int r = e / DIM, c = e - DIM * r;
+      blk[r * ld + c] += acc[col * DD + e];
     }
   }
 }

@@ -89,6 +89,10 @@ hipError_t grow_buffer(povar_ctx* c, DevBuf<T>& buf, size_t count, size_t headro
   return e;
 }
 
+// which assembly the next dense call runs (povar_set_sc_assembly): the ordered kernel where the caller asked for it and, unasked, on
+// a deterministic context (whose setter changes nothing)
+bool sc_assembly_ordered(const povar_ctx* c) { return c->sc_assembly == 2 || (c->sc_assembly < 0 && c->deterministic); }
+
 int no_memory(int dim, int n_cams, const char* what, size_t bytes) {
   return fail(-1, std::string(dim == 11 ? "RICHOLESKY" : "CHOLESKY") + ": not enough device memory for the " + what + " of " +
                       std::to_string(dim * n_cams) + " rows (" + std::to_string(bytes >> 20) + " MiB)");
@@ -137,14 +141,29 @@ static int chol_factor(povar_ctx* c, int dim, const double* Q, int nq, double* s
   HIP_TRY(hipMemsetAsync(M, 0, count * sizeof(double), c->stream));
   HIP_TRY(hipMemsetAsync(c->sc_info.p, 0, sizeof(int), c->stream));
   // replicated parts (B_c, -b, padding identity) once over the ranks; the landmark part is sharded
+  const bool ordered = sc_assembly_ordered(c);
+  c->sc_assembly_last = ordered ? 2 : 1;
+  prof_mark(c, 0);  // (povar_profile_info.e0_ms of a dense call: the assembly's launches)
   if (c->rank == 0) {
     with_step(dim, [&](auto step) {
-      hipLaunchKernelGGL(sc_dense_diag<decltype(step)::DIM>, dim3(c->n_cams), dim3(256), 0, c->stream, c->d, (const double*)c->sc.bmat, M, ld, N);
+      constexpr int DIM = decltype(step)::DIM;
+      if (ordered)  // (B_c is sc_dense_ordered's last addition: the right-hand side alone)
+        hipLaunchKernelGGL((sc_dense_diag<DIM, false>), dim3(c->n_cams), dim3(256), 0, c->stream, c->d, (const double*)c->sc.bmat, M, ld, N);
+      else
+        hipLaunchKernelGGL(sc_dense_diag<DIM>, dim3(c->n_cams), dim3(256), 0, c->stream, c->d, (const double*)c->sc.bmat, M, ld, N);
     });
     if (N > n) hipLaunchKernelGGL(chol_pad, dim3(1), dim3(64), 0, c->stream, M, ld, n, N);
     if (Q) hipLaunchKernelGGL(cov_add_qqt, dim3(N / CH_NB, N / CH_NB), dim3(256), 0, c->stream, M, ld, n, Q, nq);
   }
-  if (c->n_lms > 0) {
+  if (ordered) {
+    // (after cov_add_qqt in stream order: an entry is Q Q^T, then the workgroup's sum; every rank's cameras: rank 0 has B_c to add
+    // where no landmark is)
+    const unsigned n_tiles = (unsigned)((c->n_cams + SCO_T - 1) / SCO_T);
+    with_step(dim, [&](auto step) {
+      hipLaunchKernelGGL(sc_dense_ordered<decltype(step)>, dim3((unsigned)c->n_cams * n_tiles), dim3(SCO_WALK), 0, c->stream, c->d,
+                         (const double*)c->sc.ncw, c->rank == 0 ? (const double*)c->sc.bmat : (const double*)nullptr, M, ld);
+    });
+  } else if (c->n_lms > 0) {
     if (dim == 11)
       hipLaunchKernelGGL(sc_dense_offdiag_h, dim3(c->n_lms), dim3(256), 0, c->stream, c->d, c->sc.ncw, (const int*)c->sc_lm_slot0.p,
                          (const int*)c->sc_lm_cnt.p, M, ld);
@@ -152,6 +171,7 @@ static int chol_factor(povar_ctx* c, int dim, const double* Q, int nq, double* s
       hipLaunchKernelGGL(sc_dense_offdiag, dim3(c->n_lms), dim3(256), 0, c->stream, c->d, (const int*)c->sc_lm_slot0.p,
                          (const int*)c->sc_lm_cnt.p, M, ld);
   }
+  prof_mark(c, -1);
   HIP_TRY(hipGetLastError());
   if (int rc = allreduce(c, M, count)) return rc;
   if (stat) hipLaunchKernelGGL(cov_diag_scan, dim3(1), dim3(256), 0, c->stream, (const double*)M, ld, n, 0, stat);
@@ -637,6 +657,19 @@ int povar_set_cov_inspect(povar_ctx* c, int32_t enable) {
   if (int rc = check_ctx(c)) return rc;
   c->cov_inspect = enable ? 1 : 0;
   return 0;
+}
+
+int povar_set_sc_assembly(povar_ctx* c, int32_t mode) {
+  if (int rc = check_ctx(c)) return rc;
+  if (mode != -1 && mode != 1 && mode != 2) return fail(-1, "unknown dense assembly");
+  if (c->deterministic) return 0;  // pinned (POVAR_DETERMINISTIC)
+  c->sc_assembly = mode;
+  return 0;
+}
+
+int povar_sc_assembly(povar_ctx* c) {
+  if (int rc = check_ctx(c)) return rc;
+  return c->sc_assembly_last;
 }
 
 int povar_set_jl_col_scaling(povar_ctx* c, int32_t enable) {
