@@ -213,22 +213,11 @@ bool ck_upload(povar_ctx* c, povar_ctx::CkDev& D, const CkLayout& K, bool locked
   const bool usable = K.n_uv * sizeof(double2) < (1ull << 32) && c->n_cams <= ck_max_cams();
   D.ready = false;
   if (!usable) return true;
-  auto guarded = [&](auto&& fn) {
-    if (locked) {
-      std::lock_guard<std::mutex> lk(g_capture_mu);
-      fn();
-    } else {
-      fn();
-    }
-  };
-  auto up = [&](auto& buf, const auto& v) {
+  auto up = [&](auto& buf, const auto& v) { ok = ok && upload(buf, v, c, bytes, locked) == 0; };
+  auto room = [&](auto& buf, size_t count) {
     if (!ok) return;
-    guarded([&] { ok = buf.alloc(std::max<size_t>(v.size(), 1), bytes) == hipSuccess; });
-    const size_t piece = ((size_t)8 << 20) / sizeof(v[0]);  // 8 MB per copy: a capture waits a millisecond at most
-    for (size_t at = 0; ok && at < v.size() && !(locked && c->placer_cancel.load()); at += piece)
-      guarded([&] {
-        ok = hipMemcpy(buf.p + at, v.data() + at, std::min(piece, v.size() - at) * sizeof(v[0]), hipMemcpyHostToDevice) == hipSuccess;
-      });
+    const auto lk = capture_lock(locked);
+    ok = buf.alloc(count, bytes) == hipSuccess;
   };
   std::vector<int2> meta(K.lane_cam.size());
   for (size_t i = 0; i < meta.size(); ++i) {
@@ -249,9 +238,9 @@ bool ck_upload(povar_ctx* c, povar_ctx::CkDev& D, const CkLayout& K, bool locked
   }
   D.cold_q = K.cold_q;
   if (K.cold_q) up(D.cpos, K.cpos);
-  if (ok) guarded([&] { ok = D.part.alloc((size_t)std::max(K.n_part_rec, 1) * 12, bytes) == hipSuccess; });
-  if (ok && c->opt.robust_norm && !need_uv)  // (step 2's kernel reads the weights in chunk order; step 1's recomputes them)
-    guarded([&] { ok = D.w.alloc(std::max<size_t>(K.src.size(), 1), bytes) == hipSuccess; });  // (padded like the rows)
+  room(D.part, (size_t)std::max(K.n_part_rec, 1) * 12);
+  if (c->opt.robust_norm && !need_uv)  // (step 2's kernel reads the weights in chunk order; step 1's recomputes them)
+    room(D.w, std::max<size_t>(K.src.size(), 1));  // (padded like the rows)
   D.nb = K.nb; D.slots = K.slots; D.n_part_rec = K.n_part_rec; D.max_acc = K.max_acc; D.max_tiles_bt = K.max_tiles_bt;
   D.stride = K.stride; D.n_capped_obs = K.n_capped_obs;
   D.rows = K.rows; D.li_rows = K.li_rows; D.n_chunks = K.n_chunks; D.n_cold_chunks = K.n_cold_chunks;
@@ -313,21 +302,17 @@ int swap_in_placed_rows(povar_ctx* c, bool wait) {
   if (!wait && c->placer_state.load(std::memory_order_acquire) < 2) return 0;
   if (c->placer.joinable()) c->placer.join();
   if (c->placer_state.load(std::memory_order_acquire) != 2) {  // the build or an upload failed: stay on the natural order
-    c->pl_uv.release(); c->pl_cw.release(); c->pl_cpos.release(); c->pl_lm_pos.release(); c->pl_lm_of.release(); c->pl_of_slot.release();
-    c->pl_c3_src.release();
+    c->pl_rows = {};
     c->pl_ck.release(); c->pl_ckh.release();
     c->placement = 0;
     return 0;
   }
   HIP_TRY(hipStreamSynchronize(c->stream));  // nothing in flight reads the old rows
-  std::swap(c->v2_uv, c->pl_uv); std::swap(c->v2_cw, c->pl_cw); std::swap(c->v2_cpos, c->pl_cpos);
-  std::swap(c->v2_lm_pos, c->pl_lm_pos); std::swap(c->v2_lm_of, c->pl_lm_of); std::swap(c->v2_of_slot, c->pl_of_slot);
-  std::swap(c->c3_src, c->pl_c3_src);  // ldsacc_dp takes it from the context at every launch
-  c->pl_uv.release(); c->pl_cw.release(); c->pl_cpos.release(); c->pl_lm_pos.release(); c->pl_lm_of.release(); c->pl_of_slot.release();
-  c->pl_c3_src.release();
+  c->rows = std::move(c->pl_rows);  // (frees the natural rows, leaves pl_rows empty; ldsacc_dp takes cold_src from the context at every launch)
+  const povar_ctx::LplRows& r = c->rows;
   V2& v = c->d.v2;
-  v.uv = c->v2_uv.p; v.cw = c->v2_cw.p; v.cpos = c->v2_cpos.p; v.lm_pos = c->v2_lm_pos.p; v.lm_of = c->v2_lm_of.p;
-  v.of_slot = c->v2_of_slot.p;
+  v.uv = r.uv.p; v.cw = r.cw.p; v.cpos = r.cpos.p; v.lm_pos = r.lm_pos.p; v.lm_of = r.lm_of.p;
+  v.of_slot = r.of_slot.p;
   c->lmx_ver = 0;                          // lane-ordered landmark mirror: regather
   c->lml_lin_id = c->lsc_lin_id = -1;
   // the camera-chunk layout belongs to the row order it was derived from
@@ -340,6 +325,63 @@ int swap_in_placed_rows(povar_ctx* c, bool wait) {
   c->ck_tuned = c->ckh_tuned = false;  // (the choice between the E0 kernels is timed again on the new rows)
   c->placement = 3;
   return 1;
+}
+
+// The body of povar_ctx::placer: the builder of the lane-per-landmark layout again, with the placement, on copies of the
+// caller's arrays (they need not outlive povar_create), then the uploads into pl_rows and the chunk layouts cut from the
+// placed rows.  Every HIP call under g_capture_mu (upload / ck_upload: locked).
+// The job carries what povar_create alone knows.  n_cams, n_lms, n_slots, e0c_grid, n_hot_acc and opt.device the thread reads
+// from the context: povar_create writes each of them once, before it starts the thread, and nothing may write them afterwards.
+struct PlaceJob {
+  std::vector<int32_t> lm_off, cam_idx;
+  std::vector<double> obs;
+  std::vector<int> rank1, slot_of_obs, cam_of_rank;
+  int64_t rows = 0;     // of the natural order: the placed layout must have as many rows and tiles
+  size_t n_tiles = 0;
+  bool want_ck = false, ck_place = false, ck_pack = false;
+  int ck_nw = 0, ck_hmax = 0, ck_ng = 0;
+  CkShape ck_shape1, ck_shape2;
+};
+static void place_rows(povar_ctx* c, std::shared_ptr<PlaceJob> job) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const int n_cams = c->n_cams, grid = c->e0c_grid;
+  LplLayout P;
+  bool built = true;
+  try {  // an allocation failure of this thread must not terminate the caller's process: stay on the natural order
+    build_lpl(n_cams, c->n_lms, job->lm_off.data(), job->cam_idx.data(), job->obs.data(), job->rank1, job->slot_of_obs,
+              (size_t)c->n_slots, grid, c->n_hot_acc, P, true, &c->placer_cancel);
+  } catch (...) {
+    built = false;
+  }
+  bool ok = built && !c->placer_cancel.load() && P.rows == job->rows && P.tile.size() == job->n_tiles;
+  if (ok) {
+    std::lock_guard<std::mutex> lk(g_capture_mu);
+    ok = hipSetDevice(c->opt.device) == hipSuccess;
+  }
+  auto up = [&](auto& buf, const auto& v) { ok = ok && upload(buf, v, c, &c->pl_bytes, true) == 0; };
+  povar_ctx::LplRows& R = c->pl_rows;
+  up(R.uv, P.uv); up(R.cw, P.cw); up(R.cpos, P.cpos);
+  up(R.lm_pos, P.lm_pos); up(R.lm_of, P.lm_of); up(R.of_slot, P.of_slot);
+  up(R.cold_src, P.cold_src);
+  if (ok && job->want_ck) {  // the camera-chunk layout of the placed rows (a failure here only leaves e0_lpl in charge)
+    try {
+      const auto tk = std::chrono::steady_clock::now();
+      CkLayout K;
+      build_ck(P, n_cams, grid, job->cam_of_rank, job->ck_nw, K, job->ck_place, job->ck_hmax, job->ck_ng, job->ck_shape1, job->ck_pack);
+      c->pl_ck.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tk).count();
+      if (!c->placer_cancel.load()) ck_upload(c, c->pl_ck, K, true, &c->pl_bytes);
+      if (!c->placer_cancel.load()) {  // step 2's instance
+        CkLayout KH;
+        build_ck(P, n_cams, grid, job->cam_of_rank, 16, KH, job->ck_place, job->ck_hmax, 1, job->ck_shape2);
+        if (!c->placer_cancel.load()) ck_upload(c, c->pl_ckh, KH, true, &c->pl_bytes, false);
+      }
+    } catch (...) {
+      c->pl_ck.ready = false;
+      c->pl_ckh.ready = false;
+    }
+  }
+  c->placement_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  c->placer_state.store(ok ? 2 : 3, std::memory_order_release);
 }
 
 int check_ctx(povar_ctx* c) {
@@ -393,6 +435,22 @@ int read_cam_vector(povar_ctx* c, double* out, const double* src, size_t n) {
   return 0;
 }
 
+// Steps 1 to 4 of the teardown order (povar_ctx.hpp); the buffers and then the stream follow as the members are destroyed.
+povar_ctx::~povar_ctx() {
+  placer_cancel.store(true);  // do not finish a placement nobody will use
+  if (placer.joinable()) placer.join();
+  (void)hipSetDevice(opt.device);
+  if (stream) (void)hipStreamSynchronize(stream);
+  if (series_graph) (void)hipGraphExecDestroy(series_graph);
+  if (pin) (void)hipHostFree(pin);
+  if (comm) (void)ncclCommDestroy(comm);
+  for (double* peer : peer_host)
+    if (peer && peer != xbuf) (void)hipIpcCloseMemHandle(peer);
+  if (xbuf) (void)hipFree(xbuf);
+  for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+  for (hipEvent_t e : tev) (void)hipEventDestroy(e);
+}
+
 // ------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------
@@ -430,15 +488,6 @@ int povar_shard_range(int32_t n_lms, const int32_t* lm_offsets, int32_t world, i
   return 0;
 }
 
-// inside povar_create, once the context exists: a failing HIP call releases everything allocated so far
-#define HIP_TRY_C(expr)                                                                     \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if (e_ != hipSuccess) {                                                                 \
-      povar_destroy(c);                                                                     \
-      return fail(-(int)e_ - 1000, std::string(#expr) + ": " + hipGetErrorString(e_));      \
-    }                                                                                       \
-  } while (0)
 int povar_create(povar_ctx** out, int32_t n_cams, int32_t n_lms, int64_t n_obs,
                  const int32_t* lm_offsets, const int32_t* cam_idx, const double* obs,
                  const povar_options* options) {
@@ -469,7 +518,10 @@ int povar_create(povar_ctx** out, int32_t n_cams, int32_t n_lms, int64_t n_obs,
   if (n_dev <= 0) return fail(-2, "no HIP device: the MI355X path has no CPU fallback");
   HIP_TRY(hipSetDevice(options->device));
 
-  povar_ctx* c = new povar_ctx();
+  // every early return below destroys the context (declared before the Joiner of the second host thread: that thread is
+  // joined first); *out takes it over at the end
+  std::unique_ptr<povar_ctx, decltype(&povar_destroy)> owner(new povar_ctx(), &povar_destroy);
+  povar_ctx* const c = owner.get();
   c->opt = *options;
   c->n_cams = n_cams;
   c->n_lms = n_lms;
@@ -483,17 +535,15 @@ int povar_create(povar_ctx** out, int32_t n_cams, int32_t n_lms, int64_t n_obs,
   if (const char* g = std::getenv("POVAR_CU_MASK")) {
     int first = 0, last = -1;
     hipDeviceProp_t prop;
-    HIP_TRY_C(hipGetDeviceProperties(&prop, options->device));
-    if (std::sscanf(g, "%d-%d", &first, &last) != 2 || first < 0 || last < first || last >= prop.multiProcessorCount) {
-      povar_destroy(c);
+    HIP_TRY(hipGetDeviceProperties(&prop, options->device));
+    if (std::sscanf(g, "%d-%d", &first, &last) != 2 || first < 0 || last < first || last >= prop.multiProcessorCount)
       return fail(-1, "POVAR_CU_MASK: expected <first>-<last> inside the device's CU range");
-    }
     std::vector<uint32_t> mask((prop.multiProcessorCount + 31) / 32, 0u);
     for (int i = first; i <= last; ++i) mask[i / 32] |= 1u << (i % 32);
-    HIP_TRY_C(hipExtStreamCreateWithCUMask(&c->stream, (uint32_t)mask.size(), mask.data()));
+    HIP_TRY(hipExtStreamCreateWithCUMask(&c->stream.s, (uint32_t)mask.size(), mask.data()));
     c->cu_limit = last - first + 1;  // "one workgroup per CU" then means per CU of the range
   } else {
-    HIP_TRY_C(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    HIP_TRY(hipStreamCreateWithFlags(&c->stream.s, hipStreamNonBlocking));
   }
   // POVAR_DETERMINISTIC=1: run-to-run BIT-reproducible results for a given device count (SURVEY 8(e) "fixed reduction order
   // inside a GPU"), whatever E0 mode the caller asked for, and no run-time timing decides a kernel:
@@ -538,10 +588,7 @@ int povar_create(povar_ctx** out, int32_t n_cams, int32_t n_lms, int64_t n_obs,
                         : lpl_forced ? "POVAR_FLAG_E0_KERNEL(0): the fp32 terms are a camera-chunk kernel"
                         : options->e0_mode != POVAR_E0_IMPLICIT_LDSACC ? "an E0 mode other than POVAR_E0_IMPLICIT_LDSACC"
                         : nullptr;
-      if (why) {
-        povar_destroy(c);
-        return fail(-1, std::string("POVAR_FLAG_FP32_TERMS cannot be combined with ") + why);
-      }
+      if (why) return fail(-1, std::string("POVAR_FLAG_FP32_TERMS cannot be combined with ") + why);
       c->fp32_terms = true;
       c->res_mode = 0;
     }
@@ -576,15 +623,15 @@ int povar_create(povar_ctx** out, int32_t n_cams, int32_t n_lms, int64_t n_obs,
   {
     // one 1024-thread workgroup per CU for the LDS-cached E0 kernel
     hipDeviceProp_t prop;
-    HIP_TRY_C(hipGetDeviceProperties(&prop, options->device));
+    HIP_TRY(hipGetDeviceProperties(&prop, options->device));
     int cus = std::max(c->cu_limit > 0 ? c->cu_limit : prop.multiProcessorCount, 1);
     if (const char* e = std::getenv("POVAR_E0_WGS")) cus = std::max(std::atoi(e), 1);  // tuning knob: E0 workgroups
     c->e0c_bins_per_wg = std::max((c->n_bins + cus - 1) / cus, 1);
     c->e0c_grid = (c->n_bins + c->e0c_bins_per_wg - 1) / c->e0c_bins_per_wg;
     c->n_hot = std::min(n_cams, HOT_MAX);
     // (dynamic LDS of the kernels each unit launches, set on that unit's instantiations)
-    HIP_TRY_C(term_set_lds_all());
-    HIP_TRY_C(lm_set_lds_all());
+    HIP_TRY(term_set_lds_all());
+    HIP_TRY(lm_set_lds_all());
   }
   // per-term E0 kernel of step 1: e0_lpl (0) or an e0_ck instantiation (POVAR_E0_CK=<variant>, povar_set_e0_kernel)
   {
@@ -664,130 +711,77 @@ int povar_create(povar_ctx** out, int32_t n_cams, int32_t n_lms, int64_t n_obs,
     }
     if (place_mode == 2 && !V.tile.empty()) {
       // the same builder again, with the placement, on copies of the caller's arrays (they need not outlive this call)
-      struct Job {
-        std::vector<int32_t> lm_off, cam_idx;
-        std::vector<double> obs;
-        std::vector<int> rank1, slot_of_obs, cam_of_rank;
-      };
-      auto job = std::make_shared<Job>();
+      auto job = std::make_shared<PlaceJob>();
       job->lm_off.assign(lm_offsets, lm_offsets + n_lms + 1);
       job->cam_idx.assign(cam_idx, cam_idx + n_obs);
       job->obs.assign(obs, obs + 2 * n_obs);
       job->rank1 = L.cam_hot;
       job->slot_of_obs = L.slot_of_obs;
       job->cam_of_rank = L.hot_cams;
-      const int64_t rows = V.rows;
-      const size_t n_tiles = V.tile.size();
-      const int dev = options->device, grid = c->e0c_grid, n_acc = c->n_hot_acc;
-      const size_t n_slots = (size_t)c->n_slots;
+      job->rows = V.rows;
+      job->n_tiles = V.tile.size();
+      job->want_ck = want_ck;
+      job->ck_nw = ck_nw; job->ck_hmax = ck_hmax; job->ck_ng = ck_ng; job->ck_place = ck_place; job->ck_pack = ck_pack;
+      job->ck_shape1 = ck_shape1; job->ck_shape2 = ck_shape2;
       c->placer_state.store(1);
-      c->placer = std::thread([c, job, rows, n_tiles, dev, grid, n_acc, n_slots, n_cams, n_lms, want_ck, ck_nw, ck_hmax, ck_ng, ck_place, ck_pack, ck_shape1, ck_shape2]() {
-        const auto t0 = std::chrono::steady_clock::now();
-        LplLayout P;
-        bool built = true;
-        try {  // an allocation failure of this thread must not terminate the caller's process: stay on the natural order
-          build_lpl(n_cams, n_lms, job->lm_off.data(), job->cam_idx.data(), job->obs.data(), job->rank1, job->slot_of_obs,
-                    n_slots, grid, n_acc, P, true, &c->placer_cancel);
-        } catch (...) {
-          built = false;
-        }
-        bool ok = built && !c->placer_cancel.load() && P.rows == rows && P.tile.size() == n_tiles;
-        if (ok) {
-          std::lock_guard<std::mutex> lk(g_capture_mu);
-          ok = hipSetDevice(dev) == hipSuccess;
-        }
-        auto up = [&](auto& buf, const auto& v) {
-          if (!ok) return;
-          {
-            std::lock_guard<std::mutex> lk(g_capture_mu);
-            ok = buf.alloc(std::max<size_t>(v.size(), 1), &c->pl_bytes) == hipSuccess;
-          }
-          const size_t piece = ((size_t)8 << 20) / sizeof(v[0]);  // 8 MB per copy: a capture waits a millisecond at most
-          for (size_t at = 0; ok && at < v.size() && !c->placer_cancel.load(); at += piece) {
-            std::lock_guard<std::mutex> lk(g_capture_mu);
-            ok = hipMemcpy(buf.p + at, v.data() + at, std::min(piece, v.size() - at) * sizeof(v[0]), hipMemcpyHostToDevice) == hipSuccess;
-          }
-        };
-        up(c->pl_uv, P.uv); up(c->pl_cw, P.cw); up(c->pl_cpos, P.cpos);
-        up(c->pl_lm_pos, P.lm_pos); up(c->pl_lm_of, P.lm_of); up(c->pl_of_slot, P.of_slot);
-        up(c->pl_c3_src, P.cold_src);
-        if (ok && want_ck) {  // the camera-chunk layout of the placed rows (a failure here only leaves e0_lpl in charge)
-          try {
-            const auto tk = std::chrono::steady_clock::now();
-            CkLayout K;
-            build_ck(P, n_cams, grid, job->cam_of_rank, ck_nw, K, ck_place, ck_hmax, ck_ng, ck_shape1, ck_pack);
-            c->pl_ck.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tk).count();
-            if (!c->placer_cancel.load()) ck_upload(c, c->pl_ck, K, true, &c->pl_bytes);
-            if (!c->placer_cancel.load()) {  // step 2's instance
-              CkLayout KH;
-              build_ck(P, n_cams, grid, job->cam_of_rank, 16, KH, ck_place, ck_hmax, 1, ck_shape2);
-              if (!c->placer_cancel.load()) ck_upload(c, c->pl_ckh, KH, true, &c->pl_bytes, false);
-            }
-          } catch (...) {
-            c->pl_ck.ready = false;
-            c->pl_ckh.ready = false;
-          }
-        }
-        c->placement_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        c->placer_state.store(ok ? 2 : 3, std::memory_order_release);
-      });
+      c->placer = std::thread(place_rows, c, job);
       lap("row placement handed to a host thread");
     }
-    if (V.max_slots > c->n_hot_acc) { povar_destroy(c); return fail(-1, "lpl layout: workgroup camera set exceeds the LDS capacity"); }
+    if (V.max_slots > c->n_hot_acc) return fail(-1, "lpl layout: workgroup camera set exceeds the LDS capacity");
     c->v2_rows = V.rows;
     c->v2_max_slots = V.max_slots;
     c->v2_n_global = V.n_global;
     c->v2_strategy = V.strategy;
     c->v2_n_tail = V.n_tail;
     c->n_cold3 = (int64_t)V.cold_lm.size();
-    if (int rc = upload(c->v2_uv, V.uv, c)) { povar_destroy(c); return rc; }
-    if (int rc = upload(c->v2_cw, V.cw, c)) { povar_destroy(c); return rc; }
-    if (int rc = upload(c->v2_cpos, V.cpos, c)) { povar_destroy(c); return rc; }
-    if (int rc = upload(c->v2_lm_pos, V.lm_pos, c)) { povar_destroy(c); return rc; }
-    if (int rc = upload(c->v2_lm_of, V.lm_of, c)) { povar_destroy(c); return rc; }
-    if (int rc = upload(c->v2_of_slot, V.of_slot, c)) { povar_destroy(c); return rc; }
-    if (int rc = upload(c->v2_tile, V.tile, c)) { povar_destroy(c); return rc; }
-    if (int rc = upload(c->v2_seg, V.seg, c)) { povar_destroy(c); return rc; }
-    if (int rc = upload(c->v2_wg_tile_off, V.wg_tile_off, c)) { povar_destroy(c); return rc; }
-    if (int rc = upload(c->v2_wg_cam_off, V.wg_cam_off, c)) { povar_destroy(c); return rc; }
-    if (int rc = upload(c->v2_wg_cams, V.wg_cams, c)) { povar_destroy(c); return rc; }
-    if (int rc = upload(c->v2_wg_slot_rec, V.wg_slot_rec, c)) { povar_destroy(c); return rc; }
-    if (int rc = upload(c->v2_part_range, V.part_range, c)) { povar_destroy(c); return rc; }
-    if (int rc = upload(c->c3_lm, V.cold_lm, c)) { povar_destroy(c); return rc; }
-    if (int rc = upload(c->c3_range, V.cold_range, c)) { povar_destroy(c); return rc; }
-    if (int rc = upload(c->c3_src, V.cold_src, c)) { povar_destroy(c); return rc; }
+    if (int rc = upload(c->rows.uv, V.uv, c)) return rc;
+    if (int rc = upload(c->rows.cw, V.cw, c)) return rc;
+    if (int rc = upload(c->rows.cpos, V.cpos, c)) return rc;
+    if (int rc = upload(c->rows.lm_pos, V.lm_pos, c)) return rc;
+    if (int rc = upload(c->rows.lm_of, V.lm_of, c)) return rc;
+    if (int rc = upload(c->rows.of_slot, V.of_slot, c)) return rc;
+    if (int rc = upload(c->v2_tile, V.tile, c)) return rc;
+    if (int rc = upload(c->v2_seg, V.seg, c)) return rc;
+    if (int rc = upload(c->v2_wg_tile_off, V.wg_tile_off, c)) return rc;
+    if (int rc = upload(c->v2_wg_cam_off, V.wg_cam_off, c)) return rc;
+    if (int rc = upload(c->v2_wg_cams, V.wg_cams, c)) return rc;
+    if (int rc = upload(c->v2_wg_slot_rec, V.wg_slot_rec, c)) return rc;
+    if (int rc = upload(c->v2_part_range, V.part_range, c)) return rc;
+    if (int rc = upload(c->c3_lm, V.cold_lm, c)) return rc;
+    if (int rc = upload(c->c3_range, V.cold_range, c)) return rc;
+    if (int rc = upload(c->rows.cold_src, V.cold_src, c)) return rc;
     n_cold_q = (size_t)V.cold_rows * WAVE;
     c->q_rows = (double)V.cold_lm.size() >= 0.20 * (double)std::max<int64_t>(n_obs, 1);
     if (const char* e = std::getenv("POVAR_COLD_Q_ROWS")) c->q_rows = e[0] == '1';
     const int nt = (int)V.tile.size();
-    HIP_TRY_C(c->v2_lmrec.alloc((size_t)std::max(nt, 1) * LPL_REC_H * WAVE, &c->bytes));  // 9 entries used by step 1
-    HIP_TRY_C(c->v2_lmx.alloc((size_t)std::max(nt, 1) * WAVE, &c->bytes));
-    HIP_TRY_C(c->v2_lml.alloc((size_t)std::max(nt, 1) * WAVE, &c->bytes));
-    HIP_TRY_C(c->v2_lsc.alloc((size_t)std::max(nt, 1) * WAVE, &c->bytes));
-    HIP_TRY_C(c->v2_part.alloc((size_t)std::max(V.n_part_rec, 1) * 12, &c->bytes));
-    HIP_TRY_C(c->c3_h.alloc(4 * std::max<size_t>(V.cold_lm.size(), 1), &c->bytes));
-    if (options->robust_norm) HIP_TRY_C(c->v2_w.alloc((size_t)std::max<int64_t>(c->v2_rows, 1) * WAVE, &c->bytes));
+    HIP_TRY(c->v2_lmrec.alloc((size_t)std::max(nt, 1) * LPL_REC_H * WAVE, &c->bytes));  // 9 entries used by step 1
+    HIP_TRY(c->v2_lmx.alloc((size_t)std::max(nt, 1) * WAVE, &c->bytes));
+    HIP_TRY(c->v2_lml.alloc((size_t)std::max(nt, 1) * WAVE, &c->bytes));
+    HIP_TRY(c->v2_lsc.alloc((size_t)std::max(nt, 1) * WAVE, &c->bytes));
+    HIP_TRY(c->v2_part.alloc((size_t)std::max(V.n_part_rec, 1) * 12, &c->bytes));
+    HIP_TRY(c->c3_h.alloc(4 * std::max<size_t>(V.cold_lm.size(), 1), &c->bytes));
+    if (options->robust_norm) HIP_TRY(c->v2_w.alloc((size_t)std::max<int64_t>(c->v2_rows, 1) * WAVE, &c->bytes));
     n_cold_lpl = V.cold_lm.size();
     if (want_ck && !V.tile.empty()) {
-      if (int rc = upload(c->ck_zero_range, std::vector<int2>((size_t)n_cams, make_int2(0, 0)), c)) { povar_destroy(c); return rc; }
+      if (int rc = upload(c->ck_zero_range, std::vector<int2>((size_t)n_cams, make_int2(0, 0)), c)) return rc;
       if (place_mode == 2) {
-        if (!ck_upload(c, c->ck, *ck_nat, false, &c->bytes)) { povar_destroy(c); return fail(-1, "camera-chunk layout: upload failed"); }
-        if (ckh_nat && !ck_upload(c, c->ckh, *ckh_nat, false, &c->bytes, false)) { povar_destroy(c); return fail(-1, "camera-chunk layout (step 2): upload failed"); }
+        if (!ck_upload(c, c->ck, *ck_nat, false, &c->bytes)) return fail(-1, "camera-chunk layout: upload failed");
+        if (ckh_nat && !ck_upload(c, c->ckh, *ckh_nat, false, &c->bytes, false)) return fail(-1, "camera-chunk layout (step 2): upload failed");
         lap("camera-chunk layouts (natural rows): uploads");
       } else {  // (step 2's, and both of the placed rows, come from the host thread with place_mode 2)
         const auto tk = std::chrono::steady_clock::now();
         CkLayout K;
         build_ck(V, n_cams, c->e0c_grid, L.hot_cams, ck_nw, K, ck_place, ck_hmax, ck_ng, ck_shape1, ck_pack);
         c->ck.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tk).count();
-        if (!ck_upload(c, c->ck, K, false, &c->bytes)) { povar_destroy(c); return fail(-1, "camera-chunk layout: upload failed"); }
+        if (!ck_upload(c, c->ck, K, false, &c->bytes)) return fail(-1, "camera-chunk layout: upload failed");
         if (c->fp32_terms && c->ck.ready && !c->ck.packed) {  // fp32 image points where the rows do not pack (8 bytes per entry)
           std::vector<float2> u32(K.uv.size());
           for (size_t i = 0; i < u32.size(); ++i) u32[i] = make_float2((float)K.uv[i].x, (float)K.uv[i].y);
-          if (int rc = upload(c->ck32_uv, u32, c)) { povar_destroy(c); return rc; }
+          if (int rc = upload(c->ck32_uv, u32, c)) return rc;
         }
         CkLayout KH;  // step 2's instance: 64 bytes of LDS per landmark slot, no image coordinates
         build_ck(V, n_cams, c->e0c_grid, L.hot_cams, 16, KH, ck_place, ck_hmax, 1, ck_shape2);
-        if (!ck_upload(c, c->ckh, KH, false, &c->bytes, false)) { povar_destroy(c); return fail(-1, "camera-chunk layout (step 2): upload failed"); }
+        if (!ck_upload(c, c->ckh, KH, false, &c->bytes, false)) return fail(-1, "camera-chunk layout (step 2): upload failed");
         lap("camera-chunk layouts");
       }
     }
@@ -799,12 +793,12 @@ int povar_create(povar_ctx** out, int32_t n_cams, int32_t n_lms, int64_t n_obs,
                         : (uint64_t)c->ck.src.n * sizeof(float2) >= (1ull << 32) ? "the chunk rows exceed 2^32 bytes"
                         : ck32_lds_bytes(c->ck.slots, c->ck.max_acc) > (size_t)CK_LDS_BYTES ? "the landmark batches exceed the LDS"
                         : nullptr;
-      if (why) { povar_destroy(c); return fail(-1, std::string("POVAR_FLAG_FP32_TERMS: ") + why); }
-      HIP_TRY_C(c->ck32_lmrec.alloc((size_t)std::max(nt, 1) * 9 * WAVE, &c->bytes));
-      HIP_TRY_C(c->ck32_pimg.alloc((size_t)n_cams * 12, &c->bytes));
+      if (why) return fail(-1, std::string("POVAR_FLAG_FP32_TERMS: ") + why);
+      HIP_TRY(c->ck32_lmrec.alloc((size_t)std::max(nt, 1) * 9 * WAVE, &c->bytes));
+      HIP_TRY(c->ck32_pimg.alloc((size_t)n_cams * 12, &c->bytes));
     }
-    c->d.v2 = V2{c->v2_uv.p, c->v2_cw.p, c->v2_cpos.p, c->v2_w.p, c->v2_tile.p, c->v2_seg.p, c->v2_lmrec.p,
-                 c->v2_lm_of.p, c->v2_lmx.p, c->v2_lml.p, c->v2_lsc.p, c->v2_lm_pos.p, c->v2_of_slot.p, c->v2_wg_tile_off.p, c->v2_wg_cam_off.p, c->v2_wg_cams.p,
+    c->d.v2 = V2{c->rows.uv.p, c->rows.cw.p, c->rows.cpos.p, c->v2_w.p, c->v2_tile.p, c->v2_seg.p, c->v2_lmrec.p,
+                 c->rows.lm_of.p, c->v2_lmx.p, c->v2_lml.p, c->v2_lsc.p, c->rows.lm_pos.p, c->rows.of_slot.p, c->v2_wg_tile_off.p, c->v2_wg_cam_off.p, c->v2_wg_cams.p,
                  c->v2_wg_slot_rec.p, nt, V.hubs};
   }
   lap("uploads (lane/landmark)");
@@ -822,17 +816,17 @@ int povar_create(povar_ctx** out, int32_t n_cams, int32_t n_lms, int64_t n_obs,
     if (c->res_mode != 0 && n_obs <= max_obs) {
       const auto tr = std::chrono::steady_clock::now();
       hipDeviceProp_t prop;
-      HIP_TRY_C(hipGetDeviceProperties(&prop, options->device));
+      HIP_TRY(hipGetDeviceProperties(&prop, options->device));
       const int cus = std::min(std::max(c->cu_limit > 0 ? c->cu_limit : prop.multiProcessorCount, 1), RES_MAX_WG);
       int per_wg = 256;  // (ladybug-49: 32 workgroups 8.7, 63: 7.5, 125: 7.3 us per term -- the phases of a term are the workgroup's size)
       if (const char* e = std::getenv("POVAR_RES_OBS_PER_WG")) per_wg = std::max(64, std::atoi(e));
       int wgs = (int)std::min<int64_t>(cus, std::max<int64_t>(8, (n_obs + per_wg - 1) / per_wg));
       if (const char* e = std::getenv("POVAR_RES_WGS")) wgs = std::max(1, std::min(std::atoi(e), cus));
-      HIP_TRY_C(res_set_lds_all());
+      HIP_TRY(res_set_lds_all());
       ResLayout R;
       res_build_for(n_cams, n_lms, lm_offsets, cam_idx, obs, L.cam_hot, L.slot_of_obs, wgs, R);
       if (R.fits && res_variant_exists(R.NW, R.H, R.R, R.LS)) {
-        if (int rc = res_upload(c, c->res, R)) { povar_destroy(c); return rc; }
+        if (int rc = res_upload(c, c->res, R)) return rc;
         c->res.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr).count();
       }
       lap("resident-series layout");
@@ -846,7 +840,7 @@ int povar_create(povar_ctx** out, int32_t n_cams, int32_t n_lms, int64_t n_obs,
         ResLayout RH;
         res_build_for(n_cams, n_lms, lm_offsets, cam_idx, obs, L.cam_hot, L.slot_of_obs, wgs, RH, res_shape_step2());
         if (RH.fits && res_variant_exists(RH.NW, RH.H, RH.R, RH.LS, true)) {
-          if (int rc = res_upload(c, c->res_h, RH)) { povar_destroy(c); return rc; }
+          if (int rc = res_upload(c, c->res_h, RH)) return rc;
           c->res_h_lds = RH.lds_bytes;
         }
       }
@@ -855,7 +849,7 @@ int povar_create(povar_ctx** out, int32_t n_cams, int32_t n_lms, int64_t n_obs,
     }
   }
   part_b.join();
-  if (part_b_failed.load()) { povar_destroy(c); return fail(-4, "out of host memory while building the lane-per-observation layout"); }
+  if (part_b_failed.load()) return fail(-4, "out of host memory while building the lane-per-observation layout");
   lap("wait for the lane/obs arrays");
   int rc = 0;
   if ((rc = upload(c->uv, L.uv, c)) || (rc = upload(c->cam, L.cam, c)) || (rc = upload(c->lm, L.lm, c)) ||
@@ -865,43 +859,34 @@ int povar_create(povar_ctx** out, int32_t n_cams, int32_t n_lms, int64_t n_obs,
       (rc = upload(c->long_first, L.long_first, c)) || (rc = upload(c->long_cnt, L.long_cnt, c)) ||
       (rc = upload(c->cm_slot, L.cm_slot, c)) || (rc = upload(c->cm_lm, L.cm_lm, c)) ||
       (rc = upload(c->cm_uv, L.cm_uv, c)) || (rc = upload(c->item_off, L.item_off, c)) ||
-      (rc = upload(c->item_cam, L.item_cam, c)) || (rc = upload(c->cam_item_off, L.cam_item_off, c))) {
-    povar_destroy(c);
+      (rc = upload(c->item_cam, L.item_cam, c)) || (rc = upload(c->cam_item_off, L.cam_item_off, c)))
     return rc;
-  }
   lap("uploads (lane/obs)");
   const size_t nc = n_cams, nl = n_lms, ns = c->n_slots, ni = std::max(c->n_items, 1);
   const size_t n_part = (size_t)(c->n_reg_blocks + c->n_long) * 4;
-#define ALLOC(buf, count)                                  \
-  do {                                                     \
-    hipError_t e_ = c->buf.alloc((count), &c->bytes);      \
-    if (e_ != hipSuccess) {                                \
-      povar_destroy(c);                                    \
-      return fail(-(int)e_ - 1000, "hipMalloc " #buf);     \
-    }                                                      \
-  } while (0)
-  ALLOC(cams4, 3 * nc); ALLOC(cams_lin4, 3 * nc); ALLOC(cams_bak4, 3 * nc);
-  ALLOC(lms4, nl); ALLOC(lms_lin4, nl); ALLOC(lms_bak4, nl); ALLOC(jl_scale4, nl);
-  ALLOC(hll_inv, 9 * nl); ALLOC(lmrec, 16 * nl);
-  ALLOC(sw, ns); ALLOC(rres, ns); ALLOC(q4, ns);
-  ALLOC(sigma, 12 * nc); ALLOC(diag2, 12 * nc); ALLOC(G, 40 * nc); ALLOC(binv, 144 * nc);
-  ALLOC(b, 12 * nc); ALLOC(tmp, 12 * nc); ALLOC(accum, 12 * nc); ALLOC(z, 12 * nc); ALLOC(y, 12 * nc);
-  ALLOC(inc, 12 * nc);
-  ALLOC(item_part, 12 * ni); ALLOC(item_partG, 40 * ni); ALLOC(cm_h, 4 * (size_t)n_obs); ALLOC(ncw, 13 * nc);
+  auto room = [&](auto& buf, size_t count) { return buf.alloc(count, &c->bytes); };  // (state and scratch: allocated, not uploaded)
+  HIP_TRY(room(c->cams4, 3 * nc)); HIP_TRY(room(c->cams_lin4, 3 * nc)); HIP_TRY(room(c->cams_bak4, 3 * nc));
+  HIP_TRY(room(c->lms4, nl)); HIP_TRY(room(c->lms_lin4, nl)); HIP_TRY(room(c->lms_bak4, nl)); HIP_TRY(room(c->jl_scale4, nl));
+  HIP_TRY(room(c->hll_inv, 9 * nl)); HIP_TRY(room(c->lmrec, 16 * nl));
+  HIP_TRY(room(c->sw, ns)); HIP_TRY(room(c->rres, ns)); HIP_TRY(room(c->q4, ns));
+  HIP_TRY(room(c->sigma, 12 * nc)); HIP_TRY(room(c->diag2, 12 * nc)); HIP_TRY(room(c->G, 40 * nc)); HIP_TRY(room(c->binv, 144 * nc));
+  HIP_TRY(room(c->b, 12 * nc)); HIP_TRY(room(c->tmp, 12 * nc)); HIP_TRY(room(c->accum, 12 * nc)); HIP_TRY(room(c->z, 12 * nc)); HIP_TRY(room(c->y, 12 * nc));
+  HIP_TRY(room(c->inc, 12 * nc));
+  HIP_TRY(room(c->item_part, 12 * ni)); HIP_TRY(room(c->item_partG, 40 * ni)); HIP_TRY(room(c->cm_h, 4 * (size_t)n_obs)); HIP_TRY(room(c->ncw, 13 * nc));
   c->n_cold = (int64_t)L.cc_slot.size();
   c->n_cold_items = (int)L.cc_item_off.size() - 1;
   {
     std::vector<int2> range(n_cams);
     for (int k = 0; k < n_cams; ++k)
       range[k] = make_int2(L.cc_item_off[L.cc_cam_item_off[k]], L.cc_item_off[L.cc_cam_item_off[k + 1]]);
-    if (int rc = upload(c->cc_cam_range, range, c)) { povar_destroy(c); return rc; }
-    if (int rc = upload(c->cold_pos, L.cold_pos, c)) { povar_destroy(c); return rc; }
+    if (int rc = upload(c->cc_cam_range, range, c)) return rc;
+    if (int rc = upload(c->cold_pos, L.cold_pos, c)) return rc;
     if (!L.long_lm.empty()) {
       c->n_cold2 = (int64_t)L.c2_lm.size();
-      if (int rc = upload(c->c2_lm, L.c2_lm, c)) { povar_destroy(c); return rc; }
-      if (int rc = upload(c->c2_pos, L.c2_pos, c)) { povar_destroy(c); return rc; }
-      if (int rc = upload(c->c2_range, L.c2_range, c)) { povar_destroy(c); return rc; }
-      HIP_TRY_C(c->c2_h.alloc(4 * std::max<size_t>(L.c2_lm.size(), 1), &c->bytes));
+      if (int rc = upload(c->c2_lm, L.c2_lm, c)) return rc;
+      if (int rc = upload(c->c2_pos, L.c2_pos, c)) return rc;
+      if (int rc = upload(c->c2_range, L.c2_range, c)) return rc;
+      HIP_TRY(c->c2_h.alloc(4 * std::max<size_t>(L.c2_lm.size(), 1), &c->bytes));
       // knob POVAR_LONG_SEPARATE: keep the lm_long kernel (old lane-per-observation kernels only; e0_lpl has no
       // long/short distinction and always uses this cold view)
       c->long_in_kernel = c->use_lpl || std::getenv("POVAR_LONG_SEPARATE") == nullptr;
@@ -913,32 +898,31 @@ int povar_create(povar_ctx** out, int32_t n_cams, int32_t n_lms, int64_t n_obs,
       cnt[l] = lm_offsets[l + 1] - lm_offsets[l];
       s0[l] = cnt[l] > 0 ? L.slot_of_obs[lm_offsets[l]] : 0;
     }
-    if (int rc = upload(c->lm_slot0, s0, c)) { povar_destroy(c); return rc; }
-    if (int rc = upload(c->lm_cnt_dev, cnt, c)) { povar_destroy(c); return rc; }
+    if (int rc = upload(c->lm_slot0, s0, c)) return rc;
+    if (int rc = upload(c->lm_cnt_dev, cnt, c)) return rc;
     c->d.lm_slot0 = c->lm_slot0.p;
     c->d.lm_cnt = c->lm_cnt_dev.p;
   }
   lap("uploads, allocations (lane/obs)");
   // scatter scalars of the cold observations: one buffer, sized for the largest of the cold views
-  HIP_TRY_C(c->q4c.alloc(std::max<size_t>(std::max(std::max(std::max(L.cc_slot.size(), L.c2_lm.size()), n_cold_lpl), n_cold_q), 1), &c->bytes));
-  ALLOC(cc_h, 4 * std::max<size_t>(L.cc_slot.size(), 1)); ALLOC(cc_part, 12 * (size_t)std::max(c->n_cold_items, 1));
-  ALLOC(hot_part, (size_t)c->e0c_grid * c->n_hot_acc * 12);
-  ALLOC(hot_rec, (size_t)std::max(n_cams, HOT_MAX) * HOT_REC_STRIDE);  // every camera, in popularity order
-  ALLOC(zimg, (size_t)n_cams * 12);  // z alone, by rank: what e0_ck gathers Z from (Dp::zimg)
-  ALLOC(norm_part, 2 * (size_t)std::max(c->n_cam_blocks, n_cams)); ALLOC(norms, 4); ALLOC(flags, 4);
-  ALLOC(part, n_part * 2 + 8 * 1024); ALLOC(scal, 8);  // + one slot set per workgroup of the lane-per-landmark kernels
-  ALLOC(stage, std::max(3 * nl, 144 * nc));
-#undef ALLOC
-  HIP_TRY_C(hipMemsetAsync(c->flags.p, 0, sizeof(int) * 4, c->stream));
-  HIP_TRY_C(hipMemsetAsync(c->lms4.p, 0, sizeof(double4) * nl, c->stream));
-  HIP_TRY_C(hipMemsetAsync(c->cams4.p, 0, sizeof(double4) * 3 * nc, c->stream));
-  HIP_TRY_C(hipMemsetAsync(c->y.p, 0, sizeof(double) * 12 * nc, c->stream));
-  HIP_TRY_C(hipMemsetAsync(c->q4.p, 0, sizeof(double4) * ns, c->stream));
-  HIP_TRY_C(hipMemsetAsync(c->sw.p, 0, sizeof(double) * ns, c->stream));
-  HIP_TRY_C(hipMemsetAsync(c->rres.p, 0, sizeof(double4) * ns, c->stream));
+  HIP_TRY(c->q4c.alloc(std::max<size_t>(std::max(std::max(std::max(L.cc_slot.size(), L.c2_lm.size()), n_cold_lpl), n_cold_q), 1), &c->bytes));
+  HIP_TRY(room(c->cc_h, 4 * std::max<size_t>(L.cc_slot.size(), 1))); HIP_TRY(room(c->cc_part, 12 * (size_t)std::max(c->n_cold_items, 1)));
+  HIP_TRY(room(c->hot_part, (size_t)c->e0c_grid * c->n_hot_acc * 12));
+  HIP_TRY(room(c->hot_rec, (size_t)std::max(n_cams, HOT_MAX) * HOT_REC_STRIDE));  // every camera, in popularity order
+  HIP_TRY(room(c->zimg, (size_t)n_cams * 12));  // z alone, by rank: what e0_ck gathers Z from (Dp::zimg)
+  HIP_TRY(room(c->norm_part, 2 * (size_t)std::max(c->n_cam_blocks, n_cams))); HIP_TRY(room(c->norms, 4)); HIP_TRY(room(c->flags, 4));
+  HIP_TRY(room(c->part, n_part * 2 + 8 * 1024)); HIP_TRY(room(c->scal, 8));  // + one slot set per workgroup of the lane-per-landmark kernels
+  HIP_TRY(room(c->stage, std::max(3 * nl, 144 * nc)));
+  HIP_TRY(hipMemsetAsync(c->flags.p, 0, sizeof(int) * 4, c->stream));
+  HIP_TRY(hipMemsetAsync(c->lms4.p, 0, sizeof(double4) * nl, c->stream));
+  HIP_TRY(hipMemsetAsync(c->cams4.p, 0, sizeof(double4) * 3 * nc, c->stream));
+  HIP_TRY(hipMemsetAsync(c->y.p, 0, sizeof(double) * 12 * nc, c->stream));
+  HIP_TRY(hipMemsetAsync(c->q4.p, 0, sizeof(double4) * ns, c->stream));
+  HIP_TRY(hipMemsetAsync(c->sw.p, 0, sizeof(double) * ns, c->stream));
+  HIP_TRY(hipMemsetAsync(c->rres.p, 0, sizeof(double4) * ns, c->stream));
   // every initialisation above (uploads on the null stream, memsets on the context's non-blocking
   // stream) is complete before the context is handed out
-  HIP_TRY_C(hipDeviceSynchronize());
+  HIP_TRY(hipDeviceSynchronize());
 
   Dp& d = c->d;
   d.n_cams = n_cams; d.n_lms = n_lms; d.n_bins = c->n_bins; d.n_items = c->n_items;
@@ -966,55 +950,12 @@ int povar_create(povar_ctx** out, int32_t n_cams, int32_t n_lms, int64_t n_obs,
   lap("allocations, memsets, sync");
   c->create_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_create).count();
   if (timing) std::fprintf(stderr, "[povar_create] total %.1f ms\n", c->create_ms);
-  *out = c;
+  *out = owner.release();
   return 0;
 }
 
-#undef HIP_TRY_C
 void povar_destroy(povar_ctx* c) {
-  if (!c) return;
-  c->placer_cancel.store(true);
-  if (c->placer.joinable()) c->placer.join();
-  (void)hipSetDevice(c->opt.device);
-  c->pl_uv.release(); c->pl_cw.release(); c->pl_cpos.release(); c->pl_lm_pos.release(); c->pl_lm_of.release(); c->pl_of_slot.release();
-  c->pl_c3_src.release(); c->c3_src.release();
-  c->ck32_uv.release(); c->ck32_lmrec.release(); c->ck32_pimg.release();
-  c->ck.release(); c->pl_ck.release(); c->ckh.release(); c->pl_ckh.release(); c->ck_zero_range.release();
-  c->res.release();
-  c->res_h.release();
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
-  if (c->series_graph) (void)hipGraphExecDestroy(c->series_graph);
-  if (c->pin) (void)hipHostFree(c->pin);
-  if (c->comm) (void)ncclCommDestroy(c->comm);
-  for (size_t p = 0; p < c->peer_host.size(); ++p)
-    if (c->peer_host[p] && c->peer_host[p] != c->xbuf) (void)hipIpcCloseMemHandle(c->peer_host[p]);
-  if (c->xbuf) (void)hipFree(c->xbuf);
-  c->peer_dev.release(); c->p2p_epoch.release();
-  for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->tev) (void)hipEventDestroy(e);
-  c->lm_slot0.release(); c->lm_cnt_dev.release();
-  c->uv.release(); c->cm_uv.release(); c->tiles.release();
-  c->cam.release(); c->lm.release(); c->meta.release(); c->long_lm.release(); c->long_first.release();
-  c->long_cnt.release(); c->cm_slot.release(); c->cm_lm.release(); c->item_off.release();
-  c->item_cam.release(); c->cam_item_off.release(); c->flags.release();
-  c->cams4.release(); c->cams_lin4.release(); c->cams_bak4.release(); c->lms4.release();
-  c->lms_lin4.release(); c->lms_bak4.release(); c->jl_scale4.release(); c->rres.release(); c->q4.release();
-  c->hll_inv.release(); c->sw.release(); c->sigma.release(); c->diag2.release(); c->G.release();
-  c->binv.release(); c->b.release(); c->tmp.release(); c->accum.release(); c->z.release(); c->y.release();
-  c->inc.release(); c->item_part.release(); c->item_partG.release(); c->norm_part.release();
-  c->norms.release(); c->part.release(); c->scal.release(); c->stage.release(); c->cm_h.release(); c->lmrec.release(); c->ncw.release(); c->cc_h.release(); c->cc_part.release(); c->hot_part.release(); c->hot_rec.release(); c->zimg.release();
-  c->sc_dense.release(); c->sc_xpad.release(); c->sc_lm_slot0.release(); c->sc_lm_cnt.release(); c->sc_info.release();
-  c->sc_cov_q.release(); c->sc_cov_stat.release(); c->sc_cov_panel.release(); c->sc_cov_blocks.release(); c->sc_cov_lm.release(); c->sc_cov_ids.release(); c->sc_cov_r.release(); c->sc_cov_obs.release(); c->sc_cov_row0.release();
-  c->sc_dm_part.release(); c->sc_dm.release(); c->sc_bmat.release(); c->sc_minv.release(); c->sc_x.release();
-  c->sc_r.release(); c->sc_p.release(); c->sc_q.release(); c->sc_zv.release(); c->sc_part.release(); c->sc_s.release();
-  c->cc_cam_range.release(); c->cold_pos.release(); c->q4c.release();
-  c->v2_uv.release(); c->v2_cw.release(); c->v2_cpos.release(); c->v2_lm_pos.release(); c->v2_of_slot.release();
-  c->v2_lm_of.release(); c->v2_seg.release(); c->v2_tile.release(); c->v2_wg_tile_off.release(); c->v2_wg_cam_off.release(); c->v2_wg_cams.release();
-  c->v2_wg_slot_rec.release(); c->c3_lm.release(); c->v2_part_range.release(); c->c3_range.release(); c->c3_h.release(); c->v2_part.release(); c->v2_w.release(); c->v2_lmrec.release(); c->v2_lmx.release(); c->v2_lml.release(); c->v2_lsc.release();
-  c->c2_lm.release(); c->c2_pos.release(); c->c2_range.release(); c->c2_h.release();
-  c->cam_hot.release(); c->cc_slot.release(); c->cc_lm.release(); c->cc_item_off.release(); c->cc_cam_item_off.release(); c->hot_cams.release();
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
+  if (c) delete c;
 }
 
 int64_t povar_device_bytes(povar_ctx* c) { return c ? (int64_t)c->bytes : 0; }

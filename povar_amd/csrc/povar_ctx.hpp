@@ -6,9 +6,11 @@
 //   povar_series.hip   the term loop: E0 / B^-1 launchers, kernel choice by timing, hipGraph, the series entry points
 //   povar_comm.hip     exchange steps: RCCL / host-hook all-reduce, the peer-to-peer term exchange
 //   povar_sc.hip       explicit-Schur-complement solvers (PCG / CHOLESKY / RIPCG / RICHOLESKY)
+//   dev_buf.hpp        DevBuf<T>, the self-freeing device allocation every buffer of the context is
 // Device code: povar_kernels*.hpp (kernels that are not templates have internal linkage: every unit compiles what it launches).
 #pragma once
 #include "../../include/povar_hip.h"
+#include "dev_buf.hpp"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -65,26 +67,30 @@ inline int fail(int code, const std::string& msg) {
       return fail(-(int)e_ - 2000, std::string(#expr) + ": " + ncclGetErrorString(e_));     \
   } while (0)
 
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  hipError_t alloc(size_t count, size_t* total) {
-    n = count;
-    if (count == 0) return hipSuccess;
-    hipError_t e = hipMalloc((void**)&p, count * sizeof(T));
-    if (e == hipSuccess && total) *total += count * sizeof(T);
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-  }
-};
-
 extern std::mutex g_capture_mu;  // see povar_ctx::placer_cancel (defined in povar_create.hip)
+// the row-placement thread (locked) makes every HIP call under g_capture_mu; the caller's thread takes no lock
+inline std::unique_lock<std::mutex> capture_lock(bool locked) {
+  return locked ? std::unique_lock<std::mutex>(g_capture_mu) : std::unique_lock<std::mutex>();
+}
 
+// Ownership: every device buffer of a context is a DevBuf member (dev_buf.hpp) and frees itself; povar_destroy is `delete`.
+// Teardown order (~povar_ctx, povar_create.hip):
+//   1. cancel and join the placement thread   2. hipSetDevice(opt.device)   3. synchronise the stream
+//   4. destroy the graph exec, the pinned block, the communicator, the opened IPC mappings, xbuf and both event vectors
+//      (1 to 4: the destructor's body, which runs before any member is destroyed)
+//   5. every DevBuf member frees its memory   6. the stream is destroyed (OwnedStream, below)
 struct povar_ctx {
+  povar_ctx() = default;
+  povar_ctx(const povar_ctx&) = delete;
+  ~povar_ctx();
+  // destroyed after every buffer: members die in reverse order, so `stream` must stay declared BEFORE the first DevBuf member
+  struct OwnedStream {
+    hipStream_t s = nullptr;
+    OwnedStream() = default;
+    OwnedStream(const OwnedStream&) = delete;
+    operator hipStream_t() const { return s; }
+    ~OwnedStream() { if (s) (void)hipStreamDestroy(s); }
+  };
   int n_cams = 0, n_lms = 0;
   int64_t n_obs = 0;
   int n_bins = 0, n_slots = 0, n_items = 0, n_long = 0;
@@ -94,7 +100,7 @@ struct povar_ctx {
   int64_t n_cold = 0;
   int n_cold_items = 0;
   povar_options opt{};
-  hipStream_t stream = nullptr;
+  OwnedStream stream;
   size_t bytes = 0;
   char* pin = nullptr;  // pinned host block of the small read-backs (read_scal_flags)
   size_t pin_bytes = 0;
@@ -113,11 +119,14 @@ struct povar_ctx {
   int64_t n_cold2 = 0;
   bool long_in_kernel = false;
   // lane-per-landmark layout of e0_lpl (struct V2)
-  DevBuf<double2> v2_uv;
-  DevBuf<int> v2_lm_of;
-  DevBuf<int> v2_cw, v2_cpos, v2_lm_pos, v2_of_slot, v2_seg, v2_wg_tile_off, v2_wg_cam_off, v2_wg_cams, v2_wg_slot_rec, c3_lm;
+  // the arrays that belong to a row order: the ones in use and the placed ones a host thread uploads (swap_in_placed_rows)
+  struct LplRows {
+    DevBuf<double2> uv;
+    DevBuf<int> cw, cpos, lm_pos, lm_of, of_slot;
+    DevBuf<int> cold_src;  // CmView::src of the lane-per-landmark cold view (row-major q: lpl_cold_q)
+  } rows, pl_rows;
+  DevBuf<int> v2_seg, v2_wg_tile_off, v2_wg_cam_off, v2_wg_cams, v2_wg_slot_rec, c3_lm;
   DevBuf<int2> v2_part_range, c3_range;
-  DevBuf<int> c3_src, pl_c3_src;  // CmView::src of the lane-per-landmark cold view (row-major q: lpl_cold_q)
   // Cold observations of the lane-per-landmark kernels leave q row-major, side by side with the other lanes of their
   // row, and the per-camera kernels gather it -- instead of one scattered 32-byte store per lane into the camera-major
   // view (a third of the term on final-13682 with 24 % cold observations).  The gather costs the per-camera kernel a
@@ -141,9 +150,7 @@ struct povar_ctx {
   // invalidates the capture ("operation failed due to a previous error during capture", also in thread-local capture
   // mode): the thread makes its HIP calls in short pieces under g_capture_mu (one for the process: the check is not
   // per stream), the capture holds it from begin to end.
-  DevBuf<double2> pl_uv;
-  DevBuf<int> pl_cw, pl_cpos, pl_lm_pos, pl_lm_of, pl_of_slot;
-  size_t pl_bytes = 0;
+  size_t pl_bytes = 0;        // what the thread allocated (pl_rows, pl_ck, pl_ckh)
   int placement = 0;          // povar_layout_info::placement: 0 natural order, 1 placed in povar_create, 2 pending, 3 swapped in
   double placement_ms = 0;    // host wall time of the background build (valid from state 2 on)
   bool use_lpl = true;        // POVAR_E0_V1=1: keep e0_lm_cached<true> (lane per observation) for A/B runs
@@ -151,12 +158,10 @@ struct povar_ctx {
   bool use_lpl_prepare = true;  // POVAR_PREPARE_V1=1: keep lm_regular<OpPrepare> + cm_scatter
   // camera-chunk layout of e0_ck (ck_layout.hpp): derived from the lane-per-landmark rows in use, so it is rebuilt
   // with them (pl_ck: built by the placement thread from the placed rows, swapped in together with them)
-  struct CkDev {
+  struct CkBufs {                // (the buffers apart from the counts: CkDev::release frees them by assigning an empty CkBufs)
     DevBuf<double2> uv;
     DevBuf<int2> uvp;            // packed image points (CkLayout::uvp) instead of uv
-    bool packed = false;
     DevBuf<int> cpos;            // cold-view positions of the entries of chunks without an accumulator slot (CkLayout::cpos)
-    bool cold_q = false;         // ... which leave q there instead of partial records of their own
     DevBuf<uint32_t> li;
     DevBuf<int> src, bt_off, slot_rec;
     DevBuf<int2> lane_meta;
@@ -167,6 +172,10 @@ struct povar_ctx {
     DevBuf<double> part, w;
     DevBuf<uint8_t> lcnt;        // e0_ck_det: ceil(log2(observations)) per landmark lane
     DevBuf<uint16_t> tick;       // e0_ck_det: ticket of every run total
+  };
+  struct CkDev : CkBufs {
+    bool packed = false;         // uvp instead of uv
+    bool cold_q = false;         // the chunks behind cpos leave q in the cold view instead of partial records of their own
     int nb = 0, slots = 0, n_part_rec = 0, max_acc = 0, max_tiles_bt = 0;
     int stride = 0;              // step 2: CKH_STRIDE or CKH_STRIDE_WIDE, whichever the layout was cut for (CkLayout::stride)
     int64_t n_capped_obs = 0;
@@ -174,32 +183,27 @@ struct povar_ctx {
     double build_ms = 0;
     int64_t w_lin_id = -1;       // linearisation whose robust weights w holds
     bool ready = false;
-    void release() {
-      cpos.release(); cold_q = false;
-      uv.release(); uvp.release(); li.release(); src.release(); lane_meta.release(); bt_off.release(); first_meta.release(); first_hdr.release();
-      slot_rec.release(); tile.release(); part_range.release(); part.release(); w.release();
-      packed = false;
-      lcnt.release(); tick.release();
-      ready = false;
+    void release() {             // the counts stay: povar_get_layout_info reports them whatever `ready` says
+      static_cast<CkBufs&>(*this) = CkBufs();
+      packed = cold_q = ready = false;
     }
   } ck, pl_ck,       // step 1 (e0_ck): the layout in use / the one the placement thread built for the placed rows
     ckh, pl_ckh;     // step 2 (e0_ck_h): a second instance (64 bytes of LDS per landmark slot: more batches, other chunks)
   // resident power series (series_res, povar_kernels_res.hpp): the layout of res_layout.hpp on the device
-  struct ResDev {
+  struct ResBufs {
     DevBuf<int> lane_cam, lane_seg, lslot, oslot, wave_h, lm_off, lm_id, cam_off, cam_id, cam_zi, own_off, own_cam, own_zi, oq_off, oq_rec;
     DevBuf<double2> uv;
     DevBuf<int2> own_q;
     DevBuf<uint4> part, zbuf, nrm;   // granule pairs (povar_kernels_res.hpp)
     DevBuf<unsigned> launch;         // launch counter: the high bits of the granule tags
+  };
+  struct ResDev : ResBufs {
     int W = 0, NW = 0, H = 0, R = 1, LS = 1, n_rec = 0, max_lm = 0, max_cam = 0, max_oq = 0, max_own = 0, max_chunks = 0, order = 0;
     size_t lds_bytes = 0;
     double build_ms = 0;
     bool ready = false;
-    void release() {
-      lane_cam.release(); lane_seg.release(); lslot.release(); oslot.release(); wave_h.release();
-      lm_off.release(); lm_id.release(); cam_off.release(); cam_id.release(); cam_zi.release(); own_off.release(); own_cam.release();
-      own_zi.release(); oq_off.release(); oq_rec.release();
-      uv.release(); own_q.release(); part.release(); zbuf.release(); nrm.release(); launch.release();
+    void release() {                 // (as CkDev::release)
+      static_cast<ResBufs&>(*this) = ResBufs();
       ready = false;
     }
   } res,
@@ -362,10 +366,25 @@ inline CkVariant ck_variant_info(int variant) {
 }
 
 
+// A host vector to a device buffer of its size (one element for an empty one), counted into *bytes (default: the context's).
+// locked: the caller is the row-placement thread -- its HIP calls go in short pieces under g_capture_mu, and a cancelled
+// placement (povar_ctx::placer_cancel) stops copying (nobody will read the buffer).
 template <class T>
-int upload(DevBuf<T>& buf, const std::vector<T>& v, povar_ctx* c) {
-  HIP_TRY(buf.alloc(std::max<size_t>(v.size(), 1), &c->bytes));
-  if (!v.empty()) HIP_TRY(hipMemcpy(buf.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+int upload(DevBuf<T>& buf, const std::vector<T>& v, povar_ctx* c, size_t* bytes = nullptr, bool locked = false) {
+  if (!bytes) bytes = &c->bytes;
+  {
+    const auto lk = capture_lock(locked);
+    HIP_TRY(buf.alloc(std::max<size_t>(v.size(), 1), bytes));
+  }
+  if (!locked) {
+    if (!v.empty()) HIP_TRY(hipMemcpy(buf.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return 0;
+  }
+  const size_t piece = ((size_t)8 << 20) / sizeof(T);  // 8 MB per copy: a capture waits a millisecond at most
+  for (size_t at = 0; at < v.size() && !c->placer_cancel.load(); at += piece) {
+    const auto lk = capture_lock(true);
+    HIP_TRY(hipMemcpy(buf.p + at, v.data() + at, std::min(piece, v.size() - at) * sizeof(T), hipMemcpyHostToDevice));
+  }
   return 0;
 }
 

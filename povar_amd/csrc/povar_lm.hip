@@ -666,18 +666,18 @@ int povar_get_buffer(povar_ctx* c, int32_t which, double* out, int64_t n) {
       if (!c->linearized) return fail(-1, "not linearized");
       set_alpha(c, c->alpha_lin);
       const size_t cnt = (size_t)c->n_bins * TILE_PAIRS * WAVE;
-      double2* tmp_tiles = nullptr;
+      DevBuf<double2> tmp_tiles;  // (not the context's: uncounted, freed on every return)
       Dp d = c->d;
       if (!c->tiles.p) {
-        HIP_TRY(hipMalloc((void**)&tmp_tiles, cnt * sizeof(double2)));
-        d.tiles = tmp_tiles;
+        HIP_TRY(tmp_tiles.alloc(cnt, nullptr));
+        d.tiles = tmp_tiles.p;
       }
       hipLaunchKernelGGL(materialize_tiles, dim3(grid_for(c->n_slots, LM_BLOCK)), dim3(LM_BLOCK), 0, c->stream, d);
       std::vector<double2> h(cnt);
       HIP_TRY(hipMemcpyAsync(h.data(), d.tiles, cnt * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
       HIP_TRY(hipStreamSynchronize(c->stream));
-      if (tmp_tiles) (void)hipFree(tmp_tiles);
-      else c->tiles_valid = true;
+      if (!tmp_tiles.p) c->tiles_valid = true;
+      tmp_tiles.release();
       // blocked [bin][pair][lane] -> reference rows [4*obs + r][16] = [Jp(12) | Jl(3) | r]
       for (int64_t i = 0; i < c->n_obs; ++i) {
         const int s = c->slot_of_obs[i];

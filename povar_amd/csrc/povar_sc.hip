@@ -74,18 +74,13 @@ hipError_t grow_buffer(povar_ctx* c, DevBuf<T>& buf, size_t count, size_t headro
     c->bytes -= buf.n * sizeof(T);
     buf.release();
   }
-  buf.n = 0;
   size_t free_b = 0, total_b = 0;
   if (headroom > 0) {
     if (hipError_t e = hipMemGetInfo(&free_b, &total_b)) return e;
     if (count * sizeof(T) + headroom > free_b) return hipErrorOutOfMemory;
   }
   const hipError_t e = buf.alloc(count, &c->bytes);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    buf.p = nullptr;
-    buf.n = 0;
-  }
+  if (e != hipSuccess) (void)hipGetLastError();
   return e;
 }
 

@@ -232,7 +232,7 @@ Dp ldsacc_dp(povar_ctx* c, bool long_in_kernel) {
     dt.cmv.h = c->c3_h.p;
     dt.cmv.n = c->n_cold3;
     dt.cmv.cam_range = c->c3_range.p;
-    dt.cmv.src = c->q_rows ? c->c3_src.p : nullptr;
+    dt.cmv.src = c->q_rows ? c->rows.cold_src.p : nullptr;
     dt.q_rows = c->q_rows ? 1 : 0;
     dt.hot_part = c->v2_part.p;
     dt.part_range = c->v2_part_range.p;

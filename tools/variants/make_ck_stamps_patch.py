@@ -25,16 +25,12 @@ def main():
         shutil.copytree(os.path.join(ROOT, "include"), os.path.join(top, ab, "include"))
     b = os.path.join(top, "b", "povar_amd", "csrc")
 
-    # ---- the stamp buffer (povar_ctx.hpp), its release (povar_create.hip), the kernel argument and povar_debug_ck_stamps (povar_series.hip)
+    # ---- the stamp buffer (povar_ctx.hpp: a DevBuf member frees itself), the kernel argument and povar_debug_ck_stamps (povar_series.hip)
     p = os.path.join(b, "povar_ctx.hpp")
     s = open(p).read()
     s = sub(s, "    ckh, pl_ckh;     // step 2 (e0_ck_h): a second instance (64 bytes of LDS per landmark slot: more batches, other chunks)\n",
             "    ckh, pl_ckh;     // step 2 (e0_ck_h): a second instance (64 bytes of LDS per landmark slot: more batches, other chunks)\n"
             "  DevBuf<unsigned long long> ck_stamps;  // diagnostic build: CkP::stamps\n")
-    open(p, "w").write(s)
-    p = os.path.join(b, "povar_create.hip")
-    s = open(p).read()
-    s = sub(s, "c->ckh.release(); c->pl_ckh.release(); c->ck_zero_range.release();", "c->ckh.release(); c->pl_ckh.release(); c->ck_zero_range.release(); c->ck_stamps.release();")
     open(p, "w").write(s)
     p = os.path.join(b, "povar_series.hip")
     s = open(p).read()
