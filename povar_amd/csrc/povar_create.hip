@@ -6,13 +6,6 @@ std::mutex g_capture_mu;  // see povar_ctx::placer_cancel
 // ------------------------------------------------------------------------------------------
 // layout construction (host)
 // ------------------------------------------------------------------------------------------
-// number of cameras whose Jp^T s is accumulated in LDS (POVAR_HOT_ACC=<n> lowers it: tuning knob)
-int hot_acc_cap(int n_cams) {
-  int cap = HOT_ACC_MAX;
-  if (const char* e = std::getenv("POVAR_HOT_ACC")) cap = std::max(1, std::min(HOT_ACC_MAX, std::atoi(e)));
-  return std::min(n_cams, cap);
-}
-
 struct Layout {
   std::vector<double2> uv, cm_uv;
   std::vector<int> cam, lm, meta, hot_cams, cam_hot, cc_slot, cc_lm, cc_item_off, cc_cam_item_off, long_lm, long_first, long_cnt, cm_slot, cm_lm, item_off,
@@ -96,8 +89,8 @@ void build_layout_a(int n_cams, int n_lms, const int32_t* lm_off, const int32_t*
 }
 
 // Part B: the arrays of the lane-per-observation kernels (wave-bin slots, camera-major inverse index, cold views).
-// Independent of the lane-per-landmark layout: povar_create builds the two side by side.
-void build_layout_b(int n_cams, int n_lms, const int32_t* lm_off, const int32_t* cam_idx, const double* obs, Layout& L,
+// Independent of the lane-per-landmark layout: povar_create builds the two side by side.  n_acc: CreatePlan::n_hot_acc
+void build_layout_b(int n_cams, int n_lms, const int32_t* lm_off, const int32_t* cam_idx, const double* obs, int n_acc, Layout& L,
                     const LayoutTmp& T) {
   const int64_t n_obs = lm_off[n_lms];
   const std::vector<int>&seg_first = T.seg_first, &seg_last = T.seg_last, &rank = T.rank;
@@ -158,7 +151,6 @@ void build_layout_b(int n_cams, int n_lms, const int32_t* lm_off, const int32_t*
     // "cold" camera-major structure for POVAR_E0_IMPLICIT_LDSACC: only the observations whose
     // Jp^T s is NOT accumulated in LDS (camera outside the HOT_ACC_MAX hottest, or a long landmark,
     // which the lm_long driver handles through q4)
-    const int n_acc = hot_acc_cap(n_cams);
     L.cc_cam_item_off.assign(n_cams + 1, 0);
     for (int c = 0; c < n_cams; ++c) {
       L.cc_cam_item_off[c] = (int)L.cc_item_off.size();
@@ -199,25 +191,18 @@ void build_layout_b(int n_cams, int n_lms, const int32_t* lm_off, const int32_t*
 // camera-chunk layout of e0_ck: upload, kernel parameters, launch
 // ------------------------------------------------------------------------------------------
 // locked: called by the row-placement thread -- its HIP calls go in short pieces under g_capture_mu (povar_ctx::placer_cancel)
-// POVAR_CK_MAX_CAMS lowers the camera limit of the camera-chunk kernels (tests: the fall-back to e0_lpl without a 65536-camera problem)
-int ck_max_cams() {
-  if (const char* e = std::getenv("POVAR_CK_MAX_CAMS")) return std::max(0, std::atoi(e));
-  return 65535;
-}
-
 // Returns false only on a HIP failure (allocation, copy).  A layout this kernel family cannot run -- more than 65535 cameras
 // (the lane metadata keeps a popularity rank in 16 bits), a row array of 4 GiB or more (32-bit buffer offsets) -- is not
 // an error: D.ready stays false, what was uploaded is released and the term loop stays on e0_lpl / e0_lpl_h.
-bool ck_upload(povar_ctx* c, povar_ctx::CkDev& D, const CkLayout& K, bool locked, size_t* bytes, bool need_uv) {
-  bool ok = true;
-  const bool usable = K.n_uv * sizeof(double2) < (1ull << 32) && c->n_cams <= ck_max_cams();
+static bool ck_upload(povar_ctx* c, povar_ctx::CkDev& D, const CkLayout& K, bool locked, size_t* bytes, bool need_uv = true) {
+  const bool usable = K.n_uv * sizeof(double2) < (1ull << 32) && c->n_cams <= c->ck_max_cams;
   D.ready = false;
   if (!usable) return true;
-  auto up = [&](auto& buf, const auto& v) { ok = ok && upload(buf, v, c, bytes, locked) == 0; };
+  Uploader up{c, bytes, locked};
   auto room = [&](auto& buf, size_t count) {
-    if (!ok) return;
+    if (up.rc) return;
     const auto lk = capture_lock(locked);
-    ok = buf.alloc(count, bytes) == hipSuccess;
+    up.rc = buf.alloc(count, bytes) == hipSuccess ? 0 : -1;
   };
   std::vector<int2> meta(K.lane_cam.size());
   for (size_t i = 0; i < meta.size(); ++i) {
@@ -227,14 +212,13 @@ bool ck_upload(povar_ctx* c, povar_ctx::CkDev& D, const CkLayout& K, bool locked
   D.packed = need_uv && K.packed;
   if (D.packed) up(D.uvp, K.uvp);  // 8 bytes per observation where every image point is a six-decimal number (ck_pack_uv)
   else if (need_uv) up(D.uv, K.uv);  // (step 2's operator does not read the image coordinates)
-  up(D.li, K.li); up(D.src, K.src); up(D.tile, K.tile); up(D.lane_meta, meta);
-  up(D.bt_off, K.bt_off); up(D.slot_rec, K.slot_rec); up(D.part_range, K.part_range);
-  if (c->det_ck) { up(D.lcnt, K.lcnt_log2); up(D.tick, K.tick); }
+  up(D.li, K.li)(D.src, K.src)(D.tile, K.tile)(D.lane_meta, meta)(D.bt_off, K.bt_off)(D.slot_rec, K.slot_rec)(D.part_range, K.part_range);
+  if (c->det_ck) up(D.lcnt, K.lcnt_log2)(D.tick, K.tick);
   if (need_uv) {  // (step 1's e0_ck)
     std::vector<int2> fm;
     std::vector<int4> fh;
     ck_first_tables(K, K.nb > 0 ? (int)((K.bt_off.size() - 1) / K.nb) : 0, fm, fh);
-    up(D.first_meta, fm); up(D.first_hdr, fh);
+    up(D.first_meta, fm)(D.first_hdr, fh);
   }
   D.cold_q = K.cold_q;
   if (K.cold_q) up(D.cpos, K.cpos);
@@ -245,23 +229,21 @@ bool ck_upload(povar_ctx* c, povar_ctx::CkDev& D, const CkLayout& K, bool locked
   D.stride = K.stride; D.n_capped_obs = K.n_capped_obs;
   D.rows = K.rows; D.li_rows = K.li_rows; D.n_chunks = K.n_chunks; D.n_cold_chunks = K.n_cold_chunks;
   D.w_lin_id = -1;
-  D.ready = ok && !(locked && c->placer_cancel.load());
-  if (!ok) D.release();
-  return ok;
+  D.ready = !up.rc && !(locked && c->placer_cancel.load());
+  if (up.rc) D.release();
+  return !up.rc;
 }
 
 // ------------------------------------------------------------------------------------------
 // resident power series (series_res): upload, kernel parameters, launch
 // ------------------------------------------------------------------------------------------
-int res_upload(povar_ctx* c, povar_ctx::ResDev& D, const ResLayout& R) {
-  int rc = 0;
-  if ((rc = upload(D.lane_cam, R.lane_cam, c)) || (rc = upload(D.lane_seg, R.lane_seg, c)) ||
-      (!R.uv.empty() && (rc = upload(D.uv, R.uv, c))) /* (step 2's rows carry none) */ || (rc = upload(D.lslot, R.lslot, c)) || (rc = upload(D.oslot, R.oslot, c)) ||
-      (rc = upload(D.wave_h, R.wave_h, c)) || (rc = upload(D.lm_off, R.lm_off, c)) || (rc = upload(D.lm_id, R.lm_id, c)) ||
-      (rc = upload(D.cam_off, R.cam_off, c)) || (rc = upload(D.cam_id, R.cam_id, c)) || (rc = upload(D.cam_zi, R.cam_zi, c)) ||
-      (rc = upload(D.own_off, R.own_off, c)) || (rc = upload(D.own_cam, R.own_cam, c)) || (rc = upload(D.own_zi, R.own_zi, c)) ||
-      (rc = upload(D.own_q, R.own_q, c)) || (rc = upload(D.oq_off, R.oq_off, c)) || (rc = upload(D.oq_rec, R.oq_rec, c)))
-    return rc;
+static int res_upload(povar_ctx* c, povar_ctx::ResDev& D, const ResLayout& R) {
+  Uploader up{c};
+  up(D.lane_cam, R.lane_cam)(D.lane_seg, R.lane_seg);
+  if (!R.uv.empty()) up(D.uv, R.uv);  // (step 2's rows carry none)
+  up(D.lslot, R.lslot)(D.oslot, R.oslot)(D.wave_h, R.wave_h)(D.lm_off, R.lm_off)(D.lm_id, R.lm_id)(D.cam_off, R.cam_off)(D.cam_id, R.cam_id)
+    (D.cam_zi, R.cam_zi)(D.own_off, R.own_off)(D.own_cam, R.own_cam)(D.own_zi, R.own_zi)(D.own_q, R.own_q)(D.oq_off, R.oq_off)(D.oq_rec, R.oq_rec);
+  if (up.rc) return up.rc;
   // granule buffers: tag 0 everywhere (no launch has the number 0), the launch counter starts at 1
   const size_t n_part = (size_t)std::max(R.n_rec, 1) * 12, n_z = (size_t)c->n_cams * 12, n_nrm = (size_t)RES_MAX_WG * 2 * 2;  // (two halves: the norms are double-buffered by term parity)
   if (n_part * sizeof(uint4) >= (1ull << 32)) return fail(-1, "resident series: partial records exceed a buffer descriptor");
@@ -281,8 +263,8 @@ int res_upload(povar_ctx* c, povar_ctx::ResDev& D, const ResLayout& R) {
 }
 
 // the layout for a context: the lightest instantiation that holds it (fewest rows in registers first)
-void res_build_for(int n_cams, int n_lms, const int32_t* lm_off, const int32_t* cam_idx, const double* obs,
-                   const std::vector<int>& rank1, const std::vector<int>& slot_of_obs, int wgs, ResLayout& R, const ResShape& sh) {
+static void res_build_for(int n_cams, int n_lms, const int32_t* lm_off, const int32_t* cam_idx, const double* obs, const std::vector<int>& rank1,
+                          const std::vector<int>& slot_of_obs, int wgs, ResLayout& R, const ResShape& sh = ResShape()) {
   if (sh.has_uv) {  // (step 1; series_res_h has no 1024-thread instantiation: POVAR_RES_H_VARIANTS)
     build_res(n_cams, n_lms, lm_off, cam_idx, obs, rank1, slot_of_obs, wgs, 16, 1, 1, 2, 1, R, -1, sh);
     if (R.fits) return;
@@ -338,18 +320,40 @@ struct PlaceJob {
   std::vector<int> rank1, slot_of_obs, cam_of_rank;
   int64_t rows = 0;     // of the natural order: the placed layout must have as many rows and tiles
   size_t n_tiles = 0;
-  bool want_ck = false, ck_place = false, ck_pack = false;
-  int ck_nw = 0, ck_hmax = 0, ck_ng = 0;
-  CkShape ck_shape1, ck_shape2;
+  bool want_ck = false;
+  CkCut cut;
 };
+
+// The camera-chunk layouts of one row order V: step 1's, cut for the instantiation that will run it (CkCut) and uploaded into D1,
+// then step 2's (64 bytes of LDS per landmark slot, no image coordinates) into D2.  The one caller of build_ck.  H holds the host
+// layouts between the stages a call is asked for (`what`): the natural rows are cut before the placement thread starts and
+// uploaded after it, the fp32 image points go up between the two steps.  locked: the caller is the placement thread -- a
+// cancelled placement stops at the next stage, a failed upload there only leaves that step's layout not ready.
+// Returns 0, or the step (1, 2) whose upload failed.
+enum : unsigned { CK_CUT1 = 1, CK_UP1 = 2, CK_CUT2 = 4, CK_UP2 = 8, CK_STEP1 = CK_CUT1 | CK_UP1, CK_STEP2 = CK_CUT2 | CK_UP2, CK_BOTH = 15 };
+struct CkHost { CkLayout k1, k2; };
+static int ck_layouts(povar_ctx* c, const LplLayout& V, const std::vector<int>& cam_of_rank, const CkCut& cut, povar_ctx::CkDev& D1,
+                      povar_ctx::CkDev& D2, bool locked, CkHost& H, unsigned what = CK_BOTH) {
+  size_t* const bytes = locked ? &c->pl_bytes : &c->bytes;
+  const auto go = [&](unsigned stage) { return (what & stage) && !(locked && stage != CK_CUT1 && c->placer_cancel.load()); };
+  if (go(CK_CUT1)) {
+    const auto tk = std::chrono::steady_clock::now();
+    build_ck(V, c->n_cams, c->e0c_grid, cam_of_rank, cut.nw, H.k1, cut.place, cut.hmax, cut.ng, cut.shape1, cut.pack);
+    D1.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tk).count();
+  }
+  if (go(CK_UP1) && !ck_upload(c, D1, H.k1, locked, bytes) && !locked) return 1;
+  if (go(CK_CUT2)) build_ck(V, c->n_cams, c->e0c_grid, cam_of_rank, 16, H.k2, cut.place, cut.hmax, 1, cut.shape2);
+  if (go(CK_UP2) && !ck_upload(c, D2, H.k2, locked, bytes, false) && !locked) return 2;
+  return 0;
+}
+
 static void place_rows(povar_ctx* c, std::shared_ptr<PlaceJob> job) {
   const auto t0 = std::chrono::steady_clock::now();
-  const int n_cams = c->n_cams, grid = c->e0c_grid;
   LplLayout P;
   bool built = true;
   try {  // an allocation failure of this thread must not terminate the caller's process: stay on the natural order
-    build_lpl(n_cams, c->n_lms, job->lm_off.data(), job->cam_idx.data(), job->obs.data(), job->rank1, job->slot_of_obs,
-              (size_t)c->n_slots, grid, c->n_hot_acc, P, true, &c->placer_cancel);
+    build_lpl(c->n_cams, c->n_lms, job->lm_off.data(), job->cam_idx.data(), job->obs.data(), job->rank1, job->slot_of_obs,
+              (size_t)c->n_slots, c->e0c_grid, c->n_hot_acc, P, true, &c->placer_cancel);
   } catch (...) {
     built = false;
   }
@@ -358,23 +362,14 @@ static void place_rows(povar_ctx* c, std::shared_ptr<PlaceJob> job) {
     std::lock_guard<std::mutex> lk(g_capture_mu);
     ok = hipSetDevice(c->opt.device) == hipSuccess;
   }
-  auto up = [&](auto& buf, const auto& v) { ok = ok && upload(buf, v, c, &c->pl_bytes, true) == 0; };
   povar_ctx::LplRows& R = c->pl_rows;
-  up(R.uv, P.uv); up(R.cw, P.cw); up(R.cpos, P.cpos);
-  up(R.lm_pos, P.lm_pos); up(R.lm_of, P.lm_of); up(R.of_slot, P.of_slot);
-  up(R.cold_src, P.cold_src);
-  if (ok && job->want_ck) {  // the camera-chunk layout of the placed rows (a failure here only leaves e0_lpl in charge)
+  Uploader up{c, &c->pl_bytes, true, ok ? 0 : -1};
+  up(R.uv, P.uv)(R.cw, P.cw)(R.cpos, P.cpos)(R.lm_pos, P.lm_pos)(R.lm_of, P.lm_of)(R.of_slot, P.of_slot)(R.cold_src, P.cold_src);
+  ok = !up.rc;
+  if (ok && job->want_ck) {  // the camera-chunk layouts of the placed rows (a failure here only leaves e0_lpl in charge)
     try {
-      const auto tk = std::chrono::steady_clock::now();
-      CkLayout K;
-      build_ck(P, n_cams, grid, job->cam_of_rank, job->ck_nw, K, job->ck_place, job->ck_hmax, job->ck_ng, job->ck_shape1, job->ck_pack);
-      c->pl_ck.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tk).count();
-      if (!c->placer_cancel.load()) ck_upload(c, c->pl_ck, K, true, &c->pl_bytes);
-      if (!c->placer_cancel.load()) {  // step 2's instance
-        CkLayout KH;
-        build_ck(P, n_cams, grid, job->cam_of_rank, 16, KH, job->ck_place, job->ck_hmax, 1, job->ck_shape2);
-        if (!c->placer_cancel.load()) ck_upload(c, c->pl_ckh, KH, true, &c->pl_bytes, false);
-      }
+      CkHost H;
+      ck_layouts(c, P, job->cam_of_rank, job->cut, c->pl_ck, c->pl_ckh, true, H);
     } catch (...) {
       c->pl_ck.ready = false;
       c->pl_ckh.ready = false;
@@ -393,7 +388,7 @@ int check_ctx(povar_ctx* c) {
 // Small results come back through one pinned block: an asynchronous copy into pageable memory is staged by the
 // runtime (a synchronisation per copy), two of those per API call were most of its latency.
 // Layout of the block: [0, 16) the four flags, [64, 64 + 8 * 16) scalars, [256, ...) one 12 n_cams vector.
-int ensure_pin(povar_ctx* c) {
+static int ensure_pin(povar_ctx* c) {
   if (c->pin) return 0;
   c->pin_bytes = 256 + sizeof(double) * 12 * (size_t)std::max(c->n_cams, 1);
   HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->pin), c->pin_bytes, hipHostMallocDefault));
@@ -452,6 +447,309 @@ povar_ctx::~povar_ctx() {
 }
 
 // ------------------------------------------------------------------------------------------
+// povar_create: the phases (each reads the CreatePlan, none decides anything; create_plan.hpp)
+// ------------------------------------------------------------------------------------------
+// POVAR_LAYOUT_TIMING: the wall time of every phase on stderr (tools/create_time.py reads the lines)
+struct Laps {
+  using Clock = std::chrono::steady_clock;
+  bool on = false;
+  Clock::time_point t0 = Clock::now(), last = t0;
+  void operator()(const char* what, Clock::time_point now = Clock::now()) {
+    if (on) std::fprintf(stderr, "[povar_create] %-26s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(now - last).count());
+    last = now;
+  }
+};
+
+// what the phases hand to each other
+struct CreateJob {
+  int n_cams, n_lms;
+  int64_t n_obs;
+  const int32_t *lm_off, *cam_idx;
+  const double* obs;  // (the caller's problem)
+  Layout L;
+  LayoutTmp LT;
+  LplLayout V;      // lane-per-landmark layout of e0_lpl (lpl_layout.hpp): the natural rows, or the rows placed in the call
+  CkHost ck_nat;    // placement on a host thread: the chunk layouts cut from the natural rows before that thread starts
+  size_t n_cold_lpl = 0, n_cold_q = 0;
+  Laps lap;
+};
+
+static int check_arguments(povar_ctx** out, int32_t n_cams, int32_t n_lms, int64_t n_obs, const int32_t* lm_offsets,
+                           const int32_t* cam_idx, const double* obs, const povar_options* options) {
+  if (!out || !lm_offsets || !cam_idx || !obs || !options) return fail(-1, "null argument");
+  if (n_cams <= 0 || n_lms <= 0 || n_obs <= 0 || lm_offsets[0] != 0 || lm_offsets[n_lms] != n_obs)
+    return fail(-1, "invalid problem sizes");
+  for (int l = 0; l < n_lms; ++l) {
+    if (lm_offsets[l + 1] < lm_offsets[l]) return fail(-1, "lm_offsets not monotone");
+    for (int i = lm_offsets[l]; i < lm_offsets[l + 1]; ++i) {
+      if (cam_idx[i] < 0 || cam_idx[i] >= n_cams) return fail(-1, "camera index out of range");
+      // duplicate (camera, landmark) pairs abort the reference loader (bal_problem.cpp:227)
+      if (i > lm_offsets[l] && cam_idx[i] <= cam_idx[i - 1])
+        return fail(-1, "camera indices of a landmark must be strictly ascending");
+    }
+  }
+  return 0;
+}
+
+// there must be a device; the resolver wants its CU count (the one query of the device's properties)
+static int select_device(const povar_options* options, int* cus) {
+  int n_dev = 0;
+  HIP_TRY(hipGetDeviceCount(&n_dev));
+  if (n_dev <= 0) return fail(-2, "no HIP device: the MI355X path has no CPU fallback");
+  HIP_TRY(hipSetDevice(options->device));
+  hipDeviceProp_t prop;
+  HIP_TRY(hipGetDeviceProperties(&prop, options->device));
+  *cus = prop.multiProcessorCount;
+  return 0;
+}
+
+// the stream (on the plan's CU range, if any) and the dynamic LDS of the kernels
+static int open_device(povar_ctx* c, const CreatePlan& plan) {
+  if (plan.cu_limit > 0) {
+    std::vector<uint32_t> mask((plan.device_cus + 31) / 32, 0u);
+    for (int i = plan.cu_first; i <= plan.cu_last; ++i) mask[i / 32] |= 1u << (i % 32);
+    HIP_TRY(hipExtStreamCreateWithCUMask(&c->stream.s, (uint32_t)mask.size(), mask.data()));
+  } else {
+    HIP_TRY(hipStreamCreateWithFlags(&c->stream.s, hipStreamNonBlocking));
+  }
+  // (dynamic LDS of the kernels each unit launches, set on that unit's instantiations)
+  HIP_TRY(term_set_lds_all());
+  HIP_TRY(lm_set_lds_all());
+  return 0;
+}
+
+// part A of the layout and the counts that follow from it
+static void layout_part_a(povar_ctx* c, const CreatePlan& plan, CreateJob& J) {
+  build_layout_a(J.n_cams, J.n_lms, J.lm_off, J.cam_idx, J.L, J.LT);
+  J.lap("slots, camera ranks");
+  c->n_bins = J.L.n_bins; c->n_slots = J.L.n_bins * WAVE; c->n_items = (int)J.L.item_cam.size(); c->n_long = (int)J.L.long_lm.size();
+  c->n_reg_blocks = grid_for(c->n_slots, LM_BLOCK); c->n_cam_blocks = grid_for(J.n_cams, K9_CAMS);
+  c->slot_of_obs = J.L.slot_of_obs;
+  c->e0c_bins_per_wg = std::max((c->n_bins + plan.e0_wgs - 1) / plan.e0_wgs, 1);
+  c->e0c_grid = (c->n_bins + c->e0c_bins_per_wg - 1) / c->e0c_bins_per_wg;
+  c->n_hot = std::min(J.n_cams, HOT_MAX);
+}
+
+// The lane-per-landmark rows.  Placed on a host thread (place_mode 2), the chunk layouts of the placed rows arrive with them --
+// half a second later on venice-1778, i.e. after the first two hundred LM iterations.  e0_ck does not care which order the
+// lane-per-landmark rows are in (its own bank placement is what counts: 16.0 k terms/s on the natural rows, 15.9 k
+// without its placement on either; profiles/r05_experiments.txt), so step 1's layout is cut HERE from the natural
+// rows -- before the host thread starts: the two would share the CPUs -- for e0_ck from the first solve on (0.09 s of
+// povar_create; `bal` on venice: 96 -> 62 us per term).  POVAR_CKH_EARLY=1: step 2's instance likewise.
+static void build_rows(povar_ctx* c, const CreatePlan& plan, CreateJob& J) {
+  build_lpl(J.n_cams, J.n_lms, J.lm_off, J.cam_idx, J.obs, J.L.cam_hot, J.L.slot_of_obs, (size_t)c->n_slots, c->e0c_grid, c->n_hot_acc, J.V,
+            plan.place_mode == 1);
+  J.lap("build_lpl (lane/landmark)");
+  c->placement = plan.place_mode;
+  if (plan.place_mode != 2 || J.V.tile.empty()) return;
+  if (plan.want_ck) {
+    ck_layouts(c, J.V, J.L.hot_cams, plan.cut, c->ck, c->ckh, false, J.ck_nat, CK_CUT1 | (plan.ckh_early ? CK_CUT2 : 0u));
+    J.lap("camera-chunk layout(s) from the natural rows");
+  }
+  // the same builder again, with the placement, on copies of the caller's arrays (they need not outlive this call)
+  auto job = std::make_shared<PlaceJob>();
+  job->lm_off.assign(J.lm_off, J.lm_off + J.n_lms + 1);
+  job->cam_idx.assign(J.cam_idx, J.cam_idx + J.n_obs);
+  job->obs.assign(J.obs, J.obs + 2 * J.n_obs);
+  job->rank1 = J.L.cam_hot; job->slot_of_obs = J.L.slot_of_obs; job->cam_of_rank = J.L.hot_cams;
+  job->rows = J.V.rows; job->n_tiles = J.V.tile.size();
+  job->want_ck = plan.want_ck; job->cut = plan.cut;
+  c->placer_state.store(1);
+  c->placer = std::thread(place_rows, c, job);
+  J.lap("row placement handed to a host thread");
+}
+
+static int upload_rows(povar_ctx* c, const CreatePlan& plan, CreateJob& J) {
+  const LplLayout& V = J.V;
+  if (V.max_slots > c->n_hot_acc) return fail(-1, "lpl layout: workgroup camera set exceeds the LDS capacity");
+  c->v2_rows = V.rows; c->v2_max_slots = V.max_slots; c->v2_n_global = V.n_global; c->v2_strategy = V.strategy; c->v2_n_tail = V.n_tail;
+  c->n_cold3 = (int64_t)V.cold_lm.size();
+  Uploader up{c};
+  up(c->rows.uv, V.uv)(c->rows.cw, V.cw)(c->rows.cpos, V.cpos)(c->rows.lm_pos, V.lm_pos)(c->rows.lm_of, V.lm_of)(c->rows.of_slot, V.of_slot)
+    (c->v2_tile, V.tile)(c->v2_seg, V.seg)(c->v2_wg_tile_off, V.wg_tile_off)(c->v2_wg_cam_off, V.wg_cam_off)(c->v2_wg_cams, V.wg_cams)
+    (c->v2_wg_slot_rec, V.wg_slot_rec)(c->v2_part_range, V.part_range)(c->c3_lm, V.cold_lm)(c->c3_range, V.cold_range)(c->rows.cold_src, V.cold_src);
+  if (up.rc) return up.rc;
+  J.n_cold_q = (size_t)V.cold_rows * WAVE;
+  J.n_cold_lpl = V.cold_lm.size();
+  c->q_rows = plan.q_rows >= 0 ? plan.q_rows == 1 : (double)V.cold_lm.size() >= 0.20 * (double)std::max<int64_t>(J.n_obs, 1);
+  const int nt = (int)V.tile.size();
+  HIP_TRY(c->v2_lmrec.alloc((size_t)std::max(nt, 1) * LPL_REC_H * WAVE, &c->bytes));  // 9 entries used by step 1
+  HIP_TRY(c->v2_lmx.alloc((size_t)std::max(nt, 1) * WAVE, &c->bytes));
+  HIP_TRY(c->v2_lml.alloc((size_t)std::max(nt, 1) * WAVE, &c->bytes));
+  HIP_TRY(c->v2_lsc.alloc((size_t)std::max(nt, 1) * WAVE, &c->bytes));
+  HIP_TRY(c->v2_part.alloc((size_t)std::max(V.n_part_rec, 1) * 12, &c->bytes));
+  HIP_TRY(c->c3_h.alloc(4 * std::max<size_t>(V.cold_lm.size(), 1), &c->bytes));
+  if (c->opt.robust_norm) HIP_TRY(c->v2_w.alloc((size_t)std::max<int64_t>(c->v2_rows, 1) * WAVE, &c->bytes));
+  return 0;
+}
+
+// the camera-chunk layouts of the rows in use, and what the fp32 terms keep beside step 1's
+static int chunk_layouts(povar_ctx* c, const CreatePlan& plan, CreateJob& J) {
+  const LplLayout& V = J.V;
+  const int n_cams = J.n_cams, nt = (int)V.tile.size();
+  const bool want = plan.want_ck && !V.tile.empty();
+  static const char* const failed[] = {nullptr, "camera-chunk layout: upload failed", "camera-chunk layout (step 2): upload failed"};
+  if (want) {
+    if (int rc = upload(c->ck_zero_range, std::vector<int2>((size_t)n_cams, make_int2(0, 0)), c)) return rc;
+    if (plan.place_mode == 2) {  // (cut in build_rows; the layouts of the placed rows, and step 2's without POVAR_CKH_EARLY, come from the host thread)
+      if (int step = ck_layouts(c, V, J.L.hot_cams, plan.cut, c->ck, c->ckh, false, J.ck_nat, CK_UP1 | (plan.ckh_early ? CK_UP2 : 0u))) return fail(-1, failed[step]);
+      J.lap("camera-chunk layouts (natural rows): uploads");
+    } else {
+      CkHost H;
+      if (int step = ck_layouts(c, V, J.L.hot_cams, plan.cut, c->ck, c->ckh, false, H, CK_STEP1)) return fail(-1, failed[step]);
+      if (c->fp32_terms && c->ck.ready && !c->ck.packed) {  // fp32 image points where the rows do not pack (8 bytes per entry)
+        std::vector<float2> u32(H.k1.uv.size());
+        for (size_t i = 0; i < u32.size(); ++i) u32[i] = make_float2((float)H.k1.uv[i].x, (float)H.k1.uv[i].y);
+        if (int rc = upload(c->ck32_uv, u32, c)) return rc;
+      }
+      if (int step = ck_layouts(c, V, J.L.hot_cams, plan.cut, c->ck, c->ckh, false, H, CK_STEP2)) return fail(-1, failed[step]);
+      J.lap("camera-chunk layouts");
+    }
+  }
+  if (c->fp32_terms) {
+    // e0_ck_f32 addresses its partial records with 32-bit byte offsets (rec * 96) through a descriptor of their exact size:
+    // the layout must keep them under 2^31 bytes -- checked here, not assumed (e0_ck's descriptor spans 2^31 whatever the size)
+    const char* why = !want || !c->ck.ready ? "the camera-chunk layout could not be built for this problem"
+                      : (uint64_t)c->ck.part.n * sizeof(double) >= (1ull << 31) ? "the partial records exceed 2^31 bytes"
+                      : (uint64_t)c->ck.src.n * sizeof(float2) >= (1ull << 32) ? "the chunk rows exceed 2^32 bytes"
+                      : ck32_lds_bytes(c->ck.slots, c->ck.max_acc) > (size_t)CK_LDS_BYTES ? "the landmark batches exceed the LDS"
+                      : nullptr;
+    if (why) return fail(-1, std::string("POVAR_FLAG_FP32_TERMS: ") + why);
+    HIP_TRY(c->ck32_lmrec.alloc((size_t)std::max(nt, 1) * 9 * WAVE, &c->bytes));
+    HIP_TRY(c->ck32_pimg.alloc((size_t)n_cams * 12, &c->bytes));
+  }
+  c->d.v2 = V2{c->rows.uv.p, c->rows.cw.p, c->rows.cpos.p, c->v2_w.p, c->v2_tile.p, c->v2_seg.p, c->v2_lmrec.p,
+               c->rows.lm_of.p, c->v2_lmx.p, c->v2_lml.p, c->v2_lsc.p, c->rows.lm_pos.p, c->rows.of_slot.p, c->v2_wg_tile_off.p, c->v2_wg_cam_off.p, c->v2_wg_cams.p,
+               c->v2_wg_slot_rec.p, nt, V.hubs};
+  J.V = LplLayout();  // (the host copies of the rows and of their chunk layouts are done with)
+  J.ck_nat = CkHost();
+  return 0;
+}
+
+// resident power series (res_layout.hpp), both steps: the one caller of build_res (through res_build_for)
+static int resident_layouts(povar_ctx* c, const CreatePlan& plan, CreateJob& J) {
+  if (c->res_mode == 0 || J.n_obs > plan.res_max_obs) return 0;
+  const auto tr = std::chrono::steady_clock::now();
+  HIP_TRY(res_set_lds_all());
+  ResLayout R;
+  res_build_for(J.n_cams, J.n_lms, J.lm_off, J.cam_idx, J.obs, J.L.cam_hot, J.L.slot_of_obs, plan.res_wgs, R);
+  if (R.fits && res_variant_exists(R.NW, R.H, R.R, R.LS)) {
+    if (int rc = res_upload(c, c->res, R)) return rc;
+    c->res.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr).count();
+  }
+  J.lap("resident-series layout");
+  // step 2 (series_res_h): step 1's instance where its cut fits the step-2 LDS formula and series_res_h has the shape;
+  // else a cut of its own (64 bytes per landmark slot at the instantiation's slot capacity, no image points)
+  const auto th = std::chrono::steady_clock::now();
+  if (c->res.ready && res_shared_fits(R) && res_variant_exists(R.NW, R.H, R.R, R.LS, true)) {
+    c->res_h_shared = true;
+    c->res_h_lds = res_lds_bytes_of(R, res_shape_step2());
+  } else {
+    ResLayout RH;
+    res_build_for(J.n_cams, J.n_lms, J.lm_off, J.cam_idx, J.obs, J.L.cam_hot, J.L.slot_of_obs, plan.res_wgs, RH, res_shape_step2());
+    if (RH.fits && res_variant_exists(RH.NW, RH.H, RH.R, RH.LS, true)) {
+      if (int rc = res_upload(c, c->res_h, RH)) return rc;
+      c->res_h_lds = RH.lds_bytes;
+    }
+  }
+  c->res_h_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - th).count();
+  J.lap("resident-series layout (step 2)");
+  return 0;
+}
+
+// part B's arrays, then the state and scratch of the lane-per-observation kernels (allocated, not uploaded), zeroed where read first
+static int upload_lane_obs(povar_ctx* c, const CreatePlan& plan, CreateJob& J) {
+  const Layout& L = J.L;
+  const int n_cams = J.n_cams, n_lms = J.n_lms;
+  const int64_t n_obs = J.n_obs;
+  const size_t n_cold_lpl = J.n_cold_lpl, n_cold_q = J.n_cold_q;
+  Uploader up{c};
+  up(c->uv, L.uv)(c->cam, L.cam)(c->lm, L.lm)(c->meta, L.meta)(c->hot_cams, L.hot_cams)(c->cam_hot, L.cam_hot)(c->cc_slot, L.cc_slot)(c->cc_lm, L.cc_lm)
+    (c->cc_item_off, L.cc_item_off)(c->cc_cam_item_off, L.cc_cam_item_off)(c->long_lm, L.long_lm)(c->long_first, L.long_first)(c->long_cnt, L.long_cnt)
+    (c->cm_slot, L.cm_slot)(c->cm_lm, L.cm_lm)(c->cm_uv, L.cm_uv)(c->item_off, L.item_off)(c->item_cam, L.item_cam)(c->cam_item_off, L.cam_item_off);
+  if (up.rc) return up.rc;
+  J.lap("uploads (lane/obs)");
+  const size_t nc = n_cams, nl = n_lms, ns = c->n_slots, ni = std::max(c->n_items, 1);
+  const size_t n_part = (size_t)(c->n_reg_blocks + c->n_long) * 4;
+  auto room = [&](auto& buf, size_t count) { return buf.alloc(count, &c->bytes); };
+  HIP_TRY(room(c->cams4, 3 * nc)); HIP_TRY(room(c->cams_lin4, 3 * nc)); HIP_TRY(room(c->cams_bak4, 3 * nc));
+  HIP_TRY(room(c->lms4, nl)); HIP_TRY(room(c->lms_lin4, nl)); HIP_TRY(room(c->lms_bak4, nl)); HIP_TRY(room(c->jl_scale4, nl));
+  HIP_TRY(room(c->hll_inv, 9 * nl)); HIP_TRY(room(c->lmrec, 16 * nl));
+  HIP_TRY(room(c->sw, ns)); HIP_TRY(room(c->rres, ns)); HIP_TRY(room(c->q4, ns));
+  HIP_TRY(room(c->sigma, 12 * nc)); HIP_TRY(room(c->diag2, 12 * nc)); HIP_TRY(room(c->G, 40 * nc)); HIP_TRY(room(c->binv, 144 * nc));
+  HIP_TRY(room(c->b, 12 * nc)); HIP_TRY(room(c->tmp, 12 * nc)); HIP_TRY(room(c->accum, 12 * nc)); HIP_TRY(room(c->z, 12 * nc)); HIP_TRY(room(c->y, 12 * nc));
+  HIP_TRY(room(c->inc, 12 * nc));
+  HIP_TRY(room(c->item_part, 12 * ni)); HIP_TRY(room(c->item_partG, 40 * ni)); HIP_TRY(room(c->cm_h, 4 * (size_t)n_obs)); HIP_TRY(room(c->ncw, 13 * nc));
+  c->n_cold = (int64_t)L.cc_slot.size();
+  c->n_cold_items = (int)L.cc_item_off.size() - 1;
+  std::vector<int2> range(n_cams);
+  for (int k = 0; k < n_cams; ++k)
+    range[k] = make_int2(L.cc_item_off[L.cc_cam_item_off[k]], L.cc_item_off[L.cc_cam_item_off[k + 1]]);
+  if (up(c->cc_cam_range, range)(c->cold_pos, L.cold_pos).rc) return up.rc;
+  if (!L.long_lm.empty()) {
+    c->n_cold2 = (int64_t)L.c2_lm.size();
+    if (up(c->c2_lm, L.c2_lm)(c->c2_pos, L.c2_pos)(c->c2_range, L.c2_range).rc) return up.rc;
+    HIP_TRY(c->c2_h.alloc(4 * std::max<size_t>(L.c2_lm.size(), 1), &c->bytes));
+    // (e0_lpl has no long/short distinction and always uses this cold view)
+    c->long_in_kernel = c->use_lpl || !plan.long_separate;
+  }
+  std::vector<int> s0(n_lms, 0), cnt(n_lms, 0);
+  for (int l = 0; l < n_lms; ++l) {
+    cnt[l] = J.lm_off[l + 1] - J.lm_off[l];
+    s0[l] = cnt[l] > 0 ? L.slot_of_obs[J.lm_off[l]] : 0;
+  }
+  if (up(c->lm_slot0, s0)(c->lm_cnt_dev, cnt).rc) return up.rc;
+  J.lap("uploads, allocations (lane/obs)");
+  // scatter scalars of the cold observations: one buffer, sized for the largest of the cold views
+  HIP_TRY(c->q4c.alloc(std::max<size_t>(std::max(std::max(std::max(L.cc_slot.size(), L.c2_lm.size()), n_cold_lpl), n_cold_q), 1), &c->bytes));
+  HIP_TRY(room(c->cc_h, 4 * std::max<size_t>(L.cc_slot.size(), 1))); HIP_TRY(room(c->cc_part, 12 * (size_t)std::max(c->n_cold_items, 1)));
+  HIP_TRY(room(c->hot_part, (size_t)c->e0c_grid * c->n_hot_acc * 12));
+  HIP_TRY(room(c->hot_rec, (size_t)std::max(n_cams, HOT_MAX) * HOT_REC_STRIDE));  // every camera, in popularity order
+  HIP_TRY(room(c->zimg, (size_t)n_cams * 12));  // z alone, by rank: what e0_ck gathers Z from (Dp::zimg)
+  HIP_TRY(room(c->norm_part, 2 * (size_t)std::max(c->n_cam_blocks, n_cams))); HIP_TRY(room(c->norms, 4)); HIP_TRY(room(c->flags, 4));
+  HIP_TRY(room(c->part, n_part * 2 + 8 * 1024)); HIP_TRY(room(c->scal, 8));  // + one slot set per workgroup of the lane-per-landmark kernels
+  HIP_TRY(room(c->stage, std::max(3 * nl, 144 * nc)));
+  HIP_TRY(hipMemsetAsync(c->flags.p, 0, sizeof(int) * 4, c->stream));
+  HIP_TRY(hipMemsetAsync(c->lms4.p, 0, sizeof(double4) * nl, c->stream));
+  HIP_TRY(hipMemsetAsync(c->cams4.p, 0, sizeof(double4) * 3 * nc, c->stream));
+  HIP_TRY(hipMemsetAsync(c->y.p, 0, sizeof(double) * 12 * nc, c->stream));
+  HIP_TRY(hipMemsetAsync(c->q4.p, 0, sizeof(double4) * ns, c->stream));
+  HIP_TRY(hipMemsetAsync(c->sw.p, 0, sizeof(double) * ns, c->stream));
+  HIP_TRY(hipMemsetAsync(c->rres.p, 0, sizeof(double4) * ns, c->stream));
+  // every initialisation above (uploads on the null stream, memsets on the context's non-blocking
+  // stream) is complete before the context is handed out
+  HIP_TRY(hipDeviceSynchronize());
+  return 0;
+}
+
+static void fill_dp(povar_ctx* c) {
+  Dp& d = c->d;
+  d.n_cams = c->n_cams; d.n_lms = c->n_lms; d.n_bins = c->n_bins; d.n_items = c->n_items;
+  d.n_long = c->n_long; d.n_reg_blocks = c->n_reg_blocks;
+  d.uv = c->uv.p; d.cam = c->cam.p; d.lm = c->lm.p; d.meta = c->meta.p;
+  d.long_lm = c->long_lm.p; d.long_first = c->long_first.p; d.long_cnt = c->long_cnt.p;
+  d.cm_slot = c->cm_slot.p; d.cm_lm = c->cm_lm.p; d.cm_uv = c->cm_uv.p;
+  d.item_off = c->item_off.p; d.item_cam = c->item_cam.p; d.cam_item_off = c->cam_item_off.p;
+  d.cams4 = c->cams4.p; d.cams_lin4 = c->cams_lin4.p; d.lms4 = c->lms4.p; d.lms_lin4 = c->lms_lin4.p;
+  d.jl_scale4 = c->jl_scale4.p; d.hll_inv = c->hll_inv.p; d.lmrec = c->lmrec.p;
+  d.cmv = CmView{c->cm_slot.p, c->cm_h.p, c->n_obs, c->item_off.p, c->cam_item_off.p, c->item_part.p, c->n_items, nullptr};
+  d.hot_part = nullptr; d.cam_hot = c->cam_hot.p; d.n_hot_acc = c->n_hot_acc; d.n_hot_wg = c->e0c_grid;
+  d.hot_rec = c->hot_rec.p;
+  d.zimg = c->zimg.p;
+  d.hot_cams = c->hot_cams.p; d.n_hot = std::min(c->n_cams, HOT_MAX);
+  d.part_range = nullptr;
+  d.p2p_peer = nullptr; d.p2p_epoch = nullptr; d.p2p_world = 1; d.p2p_rank = 0;
+  d.sw = c->sw.p; d.rres = c->rres.p; d.q4 = c->q4.p; d.q4c = nullptr; d.cold_pos = nullptr; d.long_in_kernel = 0; d.tiles = nullptr;
+  d.sigma = c->sigma.p; d.diag2 = c->diag2.p; d.G = c->G.p; d.binv = c->binv.p; d.b = c->b.p;
+  d.tmp = c->tmp.p; d.accum = c->accum.p; d.z = c->z.p; d.y = c->y.p; d.inc = c->inc.p;
+  d.item_part = c->item_part.p; d.item_partG = c->item_partG.p; d.cm_h = c->cm_h.p; d.n_obs = c->n_obs;
+  d.flags = c->flags.p; d.norm_part = c->norm_part.p; d.norms = c->norms.p;
+  d.lm_slot0 = c->lm_slot0.p; d.lm_cnt = c->lm_cnt_dev.p;
+  d.sa = 0; d.sb = 1; d.eps = c->opt.jacobi_scaling_eps; d.huber = c->opt.huber_parameter;
+  d.lambda_lm = 0; d.robust = c->opt.robust_norm; d.scale_jl = 1;
+}
+
+// ------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------
 
@@ -491,180 +789,37 @@ int povar_shard_range(int32_t n_lms, const int32_t* lm_offsets, int32_t world, i
 int povar_create(povar_ctx** out, int32_t n_cams, int32_t n_lms, int64_t n_obs,
                  const int32_t* lm_offsets, const int32_t* cam_idx, const double* obs,
                  const povar_options* options) {
-  if (!out || !lm_offsets || !cam_idx || !obs || !options) return fail(-1, "null argument");
-  if (n_cams <= 0 || n_lms <= 0 || n_obs <= 0 || lm_offsets[0] != 0 || lm_offsets[n_lms] != n_obs)
-    return fail(-1, "invalid problem sizes");
-  const bool timing = std::getenv("POVAR_LAYOUT_TIMING") != nullptr;
-  const auto t_create = std::chrono::steady_clock::now();
-  auto t_last = t_create;
-  auto lap = [&](const char* what) {
-    if (!timing) return;
-    const auto now = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "[povar_create] %-26s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-    t_last = now;
-  };
-  for (int l = 0; l < n_lms; ++l) {
-    if (lm_offsets[l + 1] < lm_offsets[l]) return fail(-1, "lm_offsets not monotone");
-    for (int i = lm_offsets[l]; i < lm_offsets[l + 1]; ++i) {
-      if (cam_idx[i] < 0 || cam_idx[i] >= n_cams) return fail(-1, "camera index out of range");
-      // duplicate (camera, landmark) pairs abort the reference loader (bal_problem.cpp:227)
-      if (i > lm_offsets[l] && cam_idx[i] <= cam_idx[i - 1])
-        return fail(-1, "camera indices of a landmark must be strictly ascending");
-    }
-  }
-  lap("argument checks");
-  int n_dev = 0;
-  HIP_TRY(hipGetDeviceCount(&n_dev));
-  if (n_dev <= 0) return fail(-2, "no HIP device: the MI355X path has no CPU fallback");
-  HIP_TRY(hipSetDevice(options->device));
+  CreateJob J{n_cams, n_lms, n_obs, lm_offsets, cam_idx, obs};
+  if (int rc = check_arguments(out, n_cams, n_lms, n_obs, lm_offsets, cam_idx, obs, options)) return rc;
+  const auto t_checked = Laps::Clock::now();
+  int device_cus = 0;
+  if (int rc = select_device(options, &device_cus)) return rc;
+  CreatePlan plan;
+  std::string refusal;
+  if (int rc = resolve_create_plan(plan, *options, n_cams, n_obs, device_cus, &refusal)) return fail(rc, refusal);
+  J.lap.on = plan.timing;
+  J.lap("argument checks", t_checked);
 
   // every early return below destroys the context (declared before the Joiner of the second host thread: that thread is
   // joined first); *out takes it over at the end
   std::unique_ptr<povar_ctx, decltype(&povar_destroy)> owner(new povar_ctx(), &povar_destroy);
   povar_ctx* const c = owner.get();
   c->opt = *options;
-  c->n_cams = n_cams;
-  c->n_lms = n_lms;
-  c->n_obs = n_obs;
+  c->n_cams = n_cams; c->n_lms = n_lms; c->n_obs = n_obs;
   c->lm_off.assign(lm_offsets, lm_offsets + n_lms + 1);
   for (int l = 0; l < n_lms; ++l) c->has_empty_lm |= lm_offsets[l + 1] == lm_offsets[l];
-  // POVAR_CU_MASK=<first>-<last>: the context's stream runs on that range of CUs only.  For several contexts that share ONE
-  // device and wait for each other inside kernels (the peer-to-peer term exchange with two ranks on a one-GPU box): an
-  // E0 workgroup takes a CU's whole register file, so the bounded spin of one rank's reduce kernel on every CU kept the
-  // other rank's E0 kernel off the device until the spin timed out.  Disjoint CU ranges make the ranks two half devices.
-  if (const char* g = std::getenv("POVAR_CU_MASK")) {
-    int first = 0, last = -1;
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, options->device));
-    if (std::sscanf(g, "%d-%d", &first, &last) != 2 || first < 0 || last < first || last >= prop.multiProcessorCount)
-      return fail(-1, "POVAR_CU_MASK: expected <first>-<last> inside the device's CU range");
-    std::vector<uint32_t> mask((prop.multiProcessorCount + 31) / 32, 0u);
-    for (int i = first; i <= last; ++i) mask[i / 32] |= 1u << (i % 32);
-    HIP_TRY(hipExtStreamCreateWithCUMask(&c->stream.s, (uint32_t)mask.size(), mask.data()));
-    c->cu_limit = last - first + 1;  // "one workgroup per CU" then means per CU of the range
-  } else {
-    HIP_TRY(hipStreamCreateWithFlags(&c->stream.s, hipStreamNonBlocking));
-  }
-  // POVAR_DETERMINISTIC=1: run-to-run BIT-reproducible results for a given device count (SURVEY 8(e) "fixed reduction order
-  // inside a GPU"), whatever E0 mode the caller asked for, and no run-time timing decides a kernel:
-  //   * linearisation, preparation and cost of both steps run in the gather mode (POVAR_E0_IMPLICIT: per-landmark wavefront
-  //     scans, per-camera sums through the camera-major index -- no atomics anywhere);
-  //   * the terms of the power series -- the hot path -- run e0_ck_det (step 1) / e0_ck_h_det (step 2)
-  //     (povar_kernels_ck_det.hpp: the camera-chunk kernels with the landmark sums in 64-bit fixed point -- integer adds are
-  //     associative -- and the accumulator adds in ticket order) + cam_cold_sum_binv[_h] (a fixed-order sum), on the landmark
-  //     records and camera image the gather mode's kernels leave in lane order anyway.  POVAR_DET_CK=0: the gather form there
-  //     too (3.7 x slower than the default mode on venice-1778, profiles/r05_experiments.txt; also what runs when a chunk
-  //     layout does not fit);
-  //   * the rows are never placed on a host thread (when they arrive would decide the bits of every later solve).
-  // The default mode accumulates in LDS in arrival order and is reproducible to rounding (1e-15), like the reference's
-  // mutex order.
-  // The switches come from povar_options.flags (include/povar_hip.h: POVAR_FLAG_*); an environment variable that is set
-  // overrides its flag (diagnosis, the forced-mode suites).
-  const uint32_t fl = options->flags;
-  bool want_det = (fl & POVAR_FLAG_DETERMINISTIC) != 0, det_gather = (fl & POVAR_FLAG_DET_GATHER_TERMS) != 0;
-  if (const char* g = std::getenv("POVAR_DETERMINISTIC")) want_det = g[0] == '1';
-  if (const char* k = std::getenv("POVAR_DET_CK")) det_gather = k[0] == '0';
-  if (want_det) {
-    c->opt.e0_mode = POVAR_E0_IMPLICIT;
-    c->ck_auto = false;
-    c->ck_variant = c->ckh_variant = 0;
-    c->res_mode = 0;
-    c->deterministic = true;
-    c->det_ck = !det_gather;
-  }
-  // POVAR_FLAG_FP32_TERMS (POVAR_FP32_TERMS=1|0): step 1's power-series terms in single precision (povar_kernels_ck_f32.hpp).  The
-  // kernel is a camera-chunk kernel that adds in arrival order and runs per term: the switches that promise something else are
-  // refused, not overridden.
-  {
-    bool want_f32 = (fl & POVAR_FLAG_FP32_TERMS) != 0;
-    if (const char* g = std::getenv("POVAR_FP32_TERMS")) want_f32 = g[0] == '1';
-    if (want_f32) {
-      const char* ek = std::getenv("POVAR_E0_CK");
-      const char* rs = std::getenv("POVAR_RES");
-      const bool lpl_forced = ek ? std::atoi(ek) == 0 : ((fl & POVAR_FLAG_E0_KERNEL_MASK) >> POVAR_FLAG_E0_KERNEL_SHIFT) == 1;
-      const bool res_forced = rs ? rs[0] == '1' : ((fl & POVAR_FLAG_SERIES_KERNEL_MASK) >> POVAR_FLAG_SERIES_KERNEL_SHIFT) == 2;
-      const char* why = want_det ? "POVAR_FLAG_DETERMINISTIC: its adds land in arrival order"
-                        : res_forced ? "POVAR_FLAG_SERIES_KERNEL(1): the resident series has no fp32 form"
-                        : lpl_forced ? "POVAR_FLAG_E0_KERNEL(0): the fp32 terms are a camera-chunk kernel"
-                        : options->e0_mode != POVAR_E0_IMPLICIT_LDSACC ? "an E0 mode other than POVAR_E0_IMPLICIT_LDSACC"
-                        : nullptr;
-      if (why) return fail(-1, std::string("POVAR_FLAG_FP32_TERMS cannot be combined with ") + why);
-      c->fp32_terms = true;
-      c->res_mode = 0;
-    }
-  }
-  if (fl & POVAR_FLAG_NO_GRAPH) c->use_graph = false;
-  if (const char* g = std::getenv("POVAR_NO_GRAPH")) c->use_graph = !(g[0] == '1');
-  if (const char* g = std::getenv("POVAR_NO_ERR_MEMO")) c->no_err_memo = g[0] == '1';
-  if (const char* g = std::getenv("POVAR_GRAPH_COMM")) c->graph_with_comm = g[0] == '1';
-  if (const char* g = std::getenv("POVAR_NO_FUSE")) c->fuse_binv = !(g[0] == '1');
-  // A problem that gives the 256 x 16 wavefronts of the lane-per-landmark kernels less than a row each is bound by the
-  // launch of the 1024-thread workgroups: the lane-per-observation kernels of round 1 are faster there (ladybug-49,
-  // 31 843 observations: 127 k against 106 k terms/s; trafalgar-257, 225 911: 64.9 k against 67.0 k).
-  c->use_lpl = n_obs >= 65536;
-  if (const char* g = std::getenv("POVAR_E0_V1")) { c->use_lpl = !(g[0] == '1'); c->lpl_forced = true; }
-  if (const char* g = std::getenv("POVAR_K1_NORMAL_EQ")) c->k1_qr = !(g[0] == '1');
-  if (const char* g = std::getenv("POVAR_PREPARE_V1")) c->use_lpl_prepare = !(g[0] == '1');
-  if (c->fp32_terms) c->use_lpl = c->use_lpl_prepare = true;  // (the fp32 kernel runs on the chunk layout, whatever the size)
-
-  lap("device, stream");
-  Layout L;
-  LayoutTmp LT;
-  build_layout_a(n_cams, n_lms, lm_offsets, cam_idx, L, LT);
-  lap("slots, camera ranks");
-  c->n_bins = L.n_bins;
-  c->n_slots = L.n_bins * WAVE;
-  c->n_items = (int)L.item_cam.size();
-  c->n_long = (int)L.long_lm.size();
-  c->n_reg_blocks = grid_for(c->n_slots, LM_BLOCK);
-  c->n_cam_blocks = grid_for(n_cams, K9_CAMS);
-  c->slot_of_obs = L.slot_of_obs;
-  c->n_hot_acc = hot_acc_cap(n_cams);
-  {
-    // one 1024-thread workgroup per CU for the LDS-cached E0 kernel
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, options->device));
-    int cus = std::max(c->cu_limit > 0 ? c->cu_limit : prop.multiProcessorCount, 1);
-    if (const char* e = std::getenv("POVAR_E0_WGS")) cus = std::max(std::atoi(e), 1);  // tuning knob: E0 workgroups
-    c->e0c_bins_per_wg = std::max((c->n_bins + cus - 1) / cus, 1);
-    c->e0c_grid = (c->n_bins + c->e0c_bins_per_wg - 1) / c->e0c_bins_per_wg;
-    c->n_hot = std::min(n_cams, HOT_MAX);
-    // (dynamic LDS of the kernels each unit launches, set on that unit's instantiations)
-    HIP_TRY(term_set_lds_all());
-    HIP_TRY(lm_set_lds_all());
-  }
-  // per-term E0 kernel of step 1: e0_lpl (0) or an e0_ck instantiation (POVAR_E0_CK=<variant>, povar_set_e0_kernel)
-  {
-    int e0k = (int)((fl & POVAR_FLAG_E0_KERNEL_MASK) >> POVAR_FLAG_E0_KERNEL_SHIFT) - 1;  // -1: timed
-    if (const char* g = std::getenv("POVAR_E0_CK")) e0k = std::atoi(g);
-    if (e0k >= 0 && !c->deterministic) {
-      c->ck_variant = std::max(0, std::min(CK_VARIANTS, e0k));
-      c->ckh_variant = c->ck_variant > 0 ? 1 : 0;  // (step 2 has one camera-chunk instantiation)
-      c->ck_auto = false;
-    }
-    if (c->fp32_terms) c->ck_variant = 1;  // e0_ck_f32 runs the layout of variant 1 (16 wavefronts, one group)
-  }
-  const bool want_ck = c->use_lpl && std::getenv("POVAR_NO_CK") == nullptr;
-  // the camera-chunk layout is cut for the instantiation that will run it (its tiles are scheduled over its wavefronts)
-  const CkVariant ckv = ck_variant_info(c->ck_variant > 0 ? c->ck_variant : 1);
-  int ck_nw = ckv.nw / ckv.ng, ck_hmax = CK_HMAX;  // (wavefronts of one group)
-  const int ck_ng = ckv.ng;
-  const bool ck_place = std::getenv("POVAR_CK_NOPLACE") == nullptr;  // LDS bank placement of the chunk rows (ck_layout.hpp)
-  const bool ck_pack = !(fl & POVAR_FLAG_NO_PACKED_ROWS);            // packed image points where they pack (POVAR_CK_PACK=0 overrides inside build_ck)
-  if (const char* e = std::getenv("POVAR_CK_HMAX")) ck_hmax = std::min(CK_HMAX, std::max(1, std::atoi(e)));
-  // (step 1's layout: batches cut for the kernel that runs them; e0_ck leaves q of its cold observations in the parent's cold view)
-  // (not with the HUBER norm: e0_ck<..., ROBUST = true> has no cold loop -- povar_kernels_ck.hpp)
-  const CkShape ck_shape1 = c->det_ck ? ck_shape_det()
-                            : (std::getenv("POVAR_CK_COLD_RECORDS") || options->robust_norm == POVAR_NORM_HUBER) ? CkShape()
-                            : ck_shape_step1();
-  const CkShape ck_shape2 = c->det_ck ? ck_shape_step2_det() : ck_shape_step2();
+  static_cast<CtxSwitches&>(*c) = plan;  // the switches the other units read
+  c->opt.e0_mode = plan.e0_mode;
+  if (int rc = open_device(c, plan)) return rc;
+  J.lap("device, stream");
+  layout_part_a(c, plan, J);
 
   // The arrays of the lane-per-observation kernels (part B) are built on a second host thread while this one builds
   // and uploads the lane-per-landmark layout: the two only share the slot numbers and camera ranks of part A.
   std::atomic<bool> part_b_failed{false};
   std::thread part_b([&]() {
     try {
-      build_layout_b(n_cams, n_lms, lm_offsets, cam_idx, obs, L, LT);
+      build_layout_b(n_cams, n_lms, lm_offsets, cam_idx, obs, plan.n_hot_acc, J.L, J.LT);
     } catch (...) {  // (an allocation failure of this thread must not terminate the caller's process)
       part_b_failed.store(true);
     }
@@ -673,283 +828,19 @@ int povar_create(povar_ctx** out, int32_t n_cams, int32_t n_lms, int64_t n_obs,
     std::thread& t;
     ~Joiner() { if (t.joinable()) t.join(); }
   } joiner{part_b};
-  size_t n_cold_lpl = 0, n_cold_q = 0;
-  {
-    // lane-per-landmark layout of e0_lpl (lpl_layout.hpp)
-    LplLayout V;
-    int place_mode = n_obs >= (1 << 20) ? 2 : 1;  // 0 none, 1 in this call, 2 on a host thread
-    bool place_forced = false;
-    if (const uint32_t pf = (fl & POVAR_FLAG_PLACEMENT_MASK) >> POVAR_FLAG_PLACEMENT_SHIFT) { place_mode = pf == 3 ? 0 : (int)pf; place_forced = true; }
-    if (std::getenv("POVAR_LPL_NOPLACE")) place_mode = 0;
-    if (const char* e = std::getenv("POVAR_LPL_PLACE")) { place_mode = e[0] == 'n' ? 0 : e[0] == 's' ? 1 : e[0] == 'a' ? 2 : place_mode; place_forced = true; }
-    // POVAR_DETERMINISTIC: never on a host thread -- WHEN the placed rows (and the chunk layout cut from them: another, equally
-    // fixed summation order) arrive would depend on the host's timing, and with it the bits of every later solve.  None at
-    // all unless asked for: the gather-mode kernels do not read these rows, e0_ck_det does not care about their order.
-    if (c->deterministic) place_mode = place_mode == 1 && place_forced ? 1 : 0;
-    if (c->fp32_terms) place_mode = 1;  // the rows placed in this call: every solve, from the first, runs the fp32 terms
-    build_lpl(n_cams, n_lms, lm_offsets, cam_idx, obs, L.cam_hot, L.slot_of_obs, (size_t)c->n_slots, c->e0c_grid,
-              c->n_hot_acc, V, place_mode == 1);
-    lap("build_lpl (lane/landmark)");
-    c->placement = place_mode;
-    // The rows are placed on a host thread, and the chunk layouts of the placed rows arrive with them -- half a second later
-    // on venice-1778, i.e. after the first two hundred LM iterations.  e0_ck does not care which order the
-    // lane-per-landmark rows are in (its own bank placement is what counts: 16.0 k terms/s on the natural rows, 15.9 k
-    // without its placement on either; profiles/r05_experiments.txt), so step 1's layout is built HERE from the natural
-    // rows -- before the host thread starts: the two would share the CPUs -- for e0_ck from the first solve on (0.09 s of
-    // povar_create; `bal` on venice: 96 -> 62 us per term).  POVAR_CKH_EARLY=1: step 2's instance likewise.
-    std::unique_ptr<CkLayout> ck_nat, ckh_nat;
-    if (place_mode == 2 && want_ck && !V.tile.empty()) {
-      const auto tk = std::chrono::steady_clock::now();
-      ck_nat.reset(new CkLayout());
-      build_ck(V, n_cams, c->e0c_grid, L.hot_cams, ck_nw, *ck_nat, ck_place, ck_hmax, ck_ng, ck_shape1, ck_pack);
-      c->ck.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tk).count();
-      if (std::getenv("POVAR_CKH_EARLY") != nullptr) {
-        ckh_nat.reset(new CkLayout());
-        build_ck(V, n_cams, c->e0c_grid, L.hot_cams, 16, *ckh_nat, ck_place, ck_hmax, 1, ck_shape2);
-      }
-      lap("camera-chunk layout(s) from the natural rows");
-    }
-    if (place_mode == 2 && !V.tile.empty()) {
-      // the same builder again, with the placement, on copies of the caller's arrays (they need not outlive this call)
-      auto job = std::make_shared<PlaceJob>();
-      job->lm_off.assign(lm_offsets, lm_offsets + n_lms + 1);
-      job->cam_idx.assign(cam_idx, cam_idx + n_obs);
-      job->obs.assign(obs, obs + 2 * n_obs);
-      job->rank1 = L.cam_hot;
-      job->slot_of_obs = L.slot_of_obs;
-      job->cam_of_rank = L.hot_cams;
-      job->rows = V.rows;
-      job->n_tiles = V.tile.size();
-      job->want_ck = want_ck;
-      job->ck_nw = ck_nw; job->ck_hmax = ck_hmax; job->ck_ng = ck_ng; job->ck_place = ck_place; job->ck_pack = ck_pack;
-      job->ck_shape1 = ck_shape1; job->ck_shape2 = ck_shape2;
-      c->placer_state.store(1);
-      c->placer = std::thread(place_rows, c, job);
-      lap("row placement handed to a host thread");
-    }
-    if (V.max_slots > c->n_hot_acc) return fail(-1, "lpl layout: workgroup camera set exceeds the LDS capacity");
-    c->v2_rows = V.rows;
-    c->v2_max_slots = V.max_slots;
-    c->v2_n_global = V.n_global;
-    c->v2_strategy = V.strategy;
-    c->v2_n_tail = V.n_tail;
-    c->n_cold3 = (int64_t)V.cold_lm.size();
-    if (int rc = upload(c->rows.uv, V.uv, c)) return rc;
-    if (int rc = upload(c->rows.cw, V.cw, c)) return rc;
-    if (int rc = upload(c->rows.cpos, V.cpos, c)) return rc;
-    if (int rc = upload(c->rows.lm_pos, V.lm_pos, c)) return rc;
-    if (int rc = upload(c->rows.lm_of, V.lm_of, c)) return rc;
-    if (int rc = upload(c->rows.of_slot, V.of_slot, c)) return rc;
-    if (int rc = upload(c->v2_tile, V.tile, c)) return rc;
-    if (int rc = upload(c->v2_seg, V.seg, c)) return rc;
-    if (int rc = upload(c->v2_wg_tile_off, V.wg_tile_off, c)) return rc;
-    if (int rc = upload(c->v2_wg_cam_off, V.wg_cam_off, c)) return rc;
-    if (int rc = upload(c->v2_wg_cams, V.wg_cams, c)) return rc;
-    if (int rc = upload(c->v2_wg_slot_rec, V.wg_slot_rec, c)) return rc;
-    if (int rc = upload(c->v2_part_range, V.part_range, c)) return rc;
-    if (int rc = upload(c->c3_lm, V.cold_lm, c)) return rc;
-    if (int rc = upload(c->c3_range, V.cold_range, c)) return rc;
-    if (int rc = upload(c->rows.cold_src, V.cold_src, c)) return rc;
-    n_cold_q = (size_t)V.cold_rows * WAVE;
-    c->q_rows = (double)V.cold_lm.size() >= 0.20 * (double)std::max<int64_t>(n_obs, 1);
-    if (const char* e = std::getenv("POVAR_COLD_Q_ROWS")) c->q_rows = e[0] == '1';
-    const int nt = (int)V.tile.size();
-    HIP_TRY(c->v2_lmrec.alloc((size_t)std::max(nt, 1) * LPL_REC_H * WAVE, &c->bytes));  // 9 entries used by step 1
-    HIP_TRY(c->v2_lmx.alloc((size_t)std::max(nt, 1) * WAVE, &c->bytes));
-    HIP_TRY(c->v2_lml.alloc((size_t)std::max(nt, 1) * WAVE, &c->bytes));
-    HIP_TRY(c->v2_lsc.alloc((size_t)std::max(nt, 1) * WAVE, &c->bytes));
-    HIP_TRY(c->v2_part.alloc((size_t)std::max(V.n_part_rec, 1) * 12, &c->bytes));
-    HIP_TRY(c->c3_h.alloc(4 * std::max<size_t>(V.cold_lm.size(), 1), &c->bytes));
-    if (options->robust_norm) HIP_TRY(c->v2_w.alloc((size_t)std::max<int64_t>(c->v2_rows, 1) * WAVE, &c->bytes));
-    n_cold_lpl = V.cold_lm.size();
-    if (want_ck && !V.tile.empty()) {
-      if (int rc = upload(c->ck_zero_range, std::vector<int2>((size_t)n_cams, make_int2(0, 0)), c)) return rc;
-      if (place_mode == 2) {
-        if (!ck_upload(c, c->ck, *ck_nat, false, &c->bytes)) return fail(-1, "camera-chunk layout: upload failed");
-        if (ckh_nat && !ck_upload(c, c->ckh, *ckh_nat, false, &c->bytes, false)) return fail(-1, "camera-chunk layout (step 2): upload failed");
-        lap("camera-chunk layouts (natural rows): uploads");
-      } else {  // (step 2's, and both of the placed rows, come from the host thread with place_mode 2)
-        const auto tk = std::chrono::steady_clock::now();
-        CkLayout K;
-        build_ck(V, n_cams, c->e0c_grid, L.hot_cams, ck_nw, K, ck_place, ck_hmax, ck_ng, ck_shape1, ck_pack);
-        c->ck.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tk).count();
-        if (!ck_upload(c, c->ck, K, false, &c->bytes)) return fail(-1, "camera-chunk layout: upload failed");
-        if (c->fp32_terms && c->ck.ready && !c->ck.packed) {  // fp32 image points where the rows do not pack (8 bytes per entry)
-          std::vector<float2> u32(K.uv.size());
-          for (size_t i = 0; i < u32.size(); ++i) u32[i] = make_float2((float)K.uv[i].x, (float)K.uv[i].y);
-          if (int rc = upload(c->ck32_uv, u32, c)) return rc;
-        }
-        CkLayout KH;  // step 2's instance: 64 bytes of LDS per landmark slot, no image coordinates
-        build_ck(V, n_cams, c->e0c_grid, L.hot_cams, 16, KH, ck_place, ck_hmax, 1, ck_shape2);
-        if (!ck_upload(c, c->ckh, KH, false, &c->bytes, false)) return fail(-1, "camera-chunk layout (step 2): upload failed");
-        lap("camera-chunk layouts");
-      }
-    }
-    if (c->fp32_terms) {
-      // e0_ck_f32 addresses its partial records with 32-bit byte offsets (rec * 96) through a descriptor of their exact size:
-      // the layout must keep them under 2^31 bytes -- checked here, not assumed (e0_ck's descriptor spans 2^31 whatever the size)
-      const char* why = !want_ck || V.tile.empty() || !c->ck.ready ? "the camera-chunk layout could not be built for this problem"
-                        : (uint64_t)c->ck.part.n * sizeof(double) >= (1ull << 31) ? "the partial records exceed 2^31 bytes"
-                        : (uint64_t)c->ck.src.n * sizeof(float2) >= (1ull << 32) ? "the chunk rows exceed 2^32 bytes"
-                        : ck32_lds_bytes(c->ck.slots, c->ck.max_acc) > (size_t)CK_LDS_BYTES ? "the landmark batches exceed the LDS"
-                        : nullptr;
-      if (why) return fail(-1, std::string("POVAR_FLAG_FP32_TERMS: ") + why);
-      HIP_TRY(c->ck32_lmrec.alloc((size_t)std::max(nt, 1) * 9 * WAVE, &c->bytes));
-      HIP_TRY(c->ck32_pimg.alloc((size_t)n_cams * 12, &c->bytes));
-    }
-    c->d.v2 = V2{c->rows.uv.p, c->rows.cw.p, c->rows.cpos.p, c->v2_w.p, c->v2_tile.p, c->v2_seg.p, c->v2_lmrec.p,
-                 c->rows.lm_of.p, c->v2_lmx.p, c->v2_lml.p, c->v2_lsc.p, c->rows.lm_pos.p, c->rows.of_slot.p, c->v2_wg_tile_off.p, c->v2_wg_cam_off.p, c->v2_wg_cams.p,
-                 c->v2_wg_slot_rec.p, nt, V.hubs};
-  }
-  lap("uploads (lane/landmark)");
-  {
-    // resident power series (res_layout.hpp): for contexts whose observations fit the lanes' registers.  POVAR_RES=0|1
-    // forces the choice (default: timed against the per-term kernels at the first series), POVAR_RES_WGS the workgroups,
-    // POVAR_RES_OBS_PER_WG the observations a workgroup gets on small problems before all CUs are used.
-    if (const uint32_t sf = (fl & POVAR_FLAG_SERIES_KERNEL_MASK) >> POVAR_FLAG_SERIES_KERNEL_SHIFT; sf && !c->deterministic) c->res_mode = (int)sf - 1;
-    if (const char* e = std::getenv("POVAR_RES"); e && !c->deterministic) c->res_mode = e[0] == '1' ? 1 : 0;
-    if (const char* e = std::getenv("POVAR_RES_SPIN")) c->res_spin_limit = (unsigned)std::max(1, std::atoi(e));
-    // (measured, profiles/r05_res_term_times.txt: ahead of the per-term kernels up to a shard of 313 k observations, behind them
-    // on one of 625 k, where the partial records -- 21.7 MB written and read per term -- are the term)
-    int64_t max_obs = 400000;
-    if (const char* e = std::getenv("POVAR_RES_MAX_OBS")) max_obs = std::atoll(e);
-    if (c->res_mode != 0 && n_obs <= max_obs) {
-      const auto tr = std::chrono::steady_clock::now();
-      hipDeviceProp_t prop;
-      HIP_TRY(hipGetDeviceProperties(&prop, options->device));
-      const int cus = std::min(std::max(c->cu_limit > 0 ? c->cu_limit : prop.multiProcessorCount, 1), RES_MAX_WG);
-      int per_wg = 256;  // (ladybug-49: 32 workgroups 8.7, 63: 7.5, 125: 7.3 us per term -- the phases of a term are the workgroup's size)
-      if (const char* e = std::getenv("POVAR_RES_OBS_PER_WG")) per_wg = std::max(64, std::atoi(e));
-      int wgs = (int)std::min<int64_t>(cus, std::max<int64_t>(8, (n_obs + per_wg - 1) / per_wg));
-      if (const char* e = std::getenv("POVAR_RES_WGS")) wgs = std::max(1, std::min(std::atoi(e), cus));
-      HIP_TRY(res_set_lds_all());
-      ResLayout R;
-      res_build_for(n_cams, n_lms, lm_offsets, cam_idx, obs, L.cam_hot, L.slot_of_obs, wgs, R);
-      if (R.fits && res_variant_exists(R.NW, R.H, R.R, R.LS)) {
-        if (int rc = res_upload(c, c->res, R)) return rc;
-        c->res.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr).count();
-      }
-      lap("resident-series layout");
-      // step 2 (series_res_h): step 1's instance where its cut fits the step-2 LDS formula and series_res_h has the shape;
-      // else a cut of its own (64 bytes per landmark slot at the instantiation's slot capacity, no image points)
-      const auto th = std::chrono::steady_clock::now();
-      if (c->res.ready && res_shared_fits(R) && res_variant_exists(R.NW, R.H, R.R, R.LS, true)) {
-        c->res_h_shared = true;
-        c->res_h_lds = res_lds_bytes_of(R, res_shape_step2());
-      } else {
-        ResLayout RH;
-        res_build_for(n_cams, n_lms, lm_offsets, cam_idx, obs, L.cam_hot, L.slot_of_obs, wgs, RH, res_shape_step2());
-        if (RH.fits && res_variant_exists(RH.NW, RH.H, RH.R, RH.LS, true)) {
-          if (int rc = res_upload(c, c->res_h, RH)) return rc;
-          c->res_h_lds = RH.lds_bytes;
-        }
-      }
-      c->res_h_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - th).count();
-      lap("resident-series layout (step 2)");
-    }
-  }
+  build_rows(c, plan, J);
+  if (int rc = upload_rows(c, plan, J)) return rc;
+  if (int rc = chunk_layouts(c, plan, J)) return rc;
+  J.lap("uploads (lane/landmark)");
+  if (int rc = resident_layouts(c, plan, J)) return rc;
   part_b.join();
   if (part_b_failed.load()) return fail(-4, "out of host memory while building the lane-per-observation layout");
-  lap("wait for the lane/obs arrays");
-  int rc = 0;
-  if ((rc = upload(c->uv, L.uv, c)) || (rc = upload(c->cam, L.cam, c)) || (rc = upload(c->lm, L.lm, c)) ||
-      (rc = upload(c->meta, L.meta, c)) || (rc = upload(c->hot_cams, L.hot_cams, c)) || (rc = upload(c->cam_hot, L.cam_hot, c)) ||
-      (rc = upload(c->cc_slot, L.cc_slot, c)) || (rc = upload(c->cc_lm, L.cc_lm, c)) ||
-      (rc = upload(c->cc_item_off, L.cc_item_off, c)) || (rc = upload(c->cc_cam_item_off, L.cc_cam_item_off, c)) || (rc = upload(c->long_lm, L.long_lm, c)) ||
-      (rc = upload(c->long_first, L.long_first, c)) || (rc = upload(c->long_cnt, L.long_cnt, c)) ||
-      (rc = upload(c->cm_slot, L.cm_slot, c)) || (rc = upload(c->cm_lm, L.cm_lm, c)) ||
-      (rc = upload(c->cm_uv, L.cm_uv, c)) || (rc = upload(c->item_off, L.item_off, c)) ||
-      (rc = upload(c->item_cam, L.item_cam, c)) || (rc = upload(c->cam_item_off, L.cam_item_off, c)))
-    return rc;
-  lap("uploads (lane/obs)");
-  const size_t nc = n_cams, nl = n_lms, ns = c->n_slots, ni = std::max(c->n_items, 1);
-  const size_t n_part = (size_t)(c->n_reg_blocks + c->n_long) * 4;
-  auto room = [&](auto& buf, size_t count) { return buf.alloc(count, &c->bytes); };  // (state and scratch: allocated, not uploaded)
-  HIP_TRY(room(c->cams4, 3 * nc)); HIP_TRY(room(c->cams_lin4, 3 * nc)); HIP_TRY(room(c->cams_bak4, 3 * nc));
-  HIP_TRY(room(c->lms4, nl)); HIP_TRY(room(c->lms_lin4, nl)); HIP_TRY(room(c->lms_bak4, nl)); HIP_TRY(room(c->jl_scale4, nl));
-  HIP_TRY(room(c->hll_inv, 9 * nl)); HIP_TRY(room(c->lmrec, 16 * nl));
-  HIP_TRY(room(c->sw, ns)); HIP_TRY(room(c->rres, ns)); HIP_TRY(room(c->q4, ns));
-  HIP_TRY(room(c->sigma, 12 * nc)); HIP_TRY(room(c->diag2, 12 * nc)); HIP_TRY(room(c->G, 40 * nc)); HIP_TRY(room(c->binv, 144 * nc));
-  HIP_TRY(room(c->b, 12 * nc)); HIP_TRY(room(c->tmp, 12 * nc)); HIP_TRY(room(c->accum, 12 * nc)); HIP_TRY(room(c->z, 12 * nc)); HIP_TRY(room(c->y, 12 * nc));
-  HIP_TRY(room(c->inc, 12 * nc));
-  HIP_TRY(room(c->item_part, 12 * ni)); HIP_TRY(room(c->item_partG, 40 * ni)); HIP_TRY(room(c->cm_h, 4 * (size_t)n_obs)); HIP_TRY(room(c->ncw, 13 * nc));
-  c->n_cold = (int64_t)L.cc_slot.size();
-  c->n_cold_items = (int)L.cc_item_off.size() - 1;
-  {
-    std::vector<int2> range(n_cams);
-    for (int k = 0; k < n_cams; ++k)
-      range[k] = make_int2(L.cc_item_off[L.cc_cam_item_off[k]], L.cc_item_off[L.cc_cam_item_off[k + 1]]);
-    if (int rc = upload(c->cc_cam_range, range, c)) return rc;
-    if (int rc = upload(c->cold_pos, L.cold_pos, c)) return rc;
-    if (!L.long_lm.empty()) {
-      c->n_cold2 = (int64_t)L.c2_lm.size();
-      if (int rc = upload(c->c2_lm, L.c2_lm, c)) return rc;
-      if (int rc = upload(c->c2_pos, L.c2_pos, c)) return rc;
-      if (int rc = upload(c->c2_range, L.c2_range, c)) return rc;
-      HIP_TRY(c->c2_h.alloc(4 * std::max<size_t>(L.c2_lm.size(), 1), &c->bytes));
-      // knob POVAR_LONG_SEPARATE: keep the lm_long kernel (old lane-per-observation kernels only; e0_lpl has no
-      // long/short distinction and always uses this cold view)
-      c->long_in_kernel = c->use_lpl || std::getenv("POVAR_LONG_SEPARATE") == nullptr;
-    }
-  }
-  {
-    std::vector<int> s0(n_lms, 0), cnt(n_lms, 0);
-    for (int l = 0; l < n_lms; ++l) {
-      cnt[l] = lm_offsets[l + 1] - lm_offsets[l];
-      s0[l] = cnt[l] > 0 ? L.slot_of_obs[lm_offsets[l]] : 0;
-    }
-    if (int rc = upload(c->lm_slot0, s0, c)) return rc;
-    if (int rc = upload(c->lm_cnt_dev, cnt, c)) return rc;
-    c->d.lm_slot0 = c->lm_slot0.p;
-    c->d.lm_cnt = c->lm_cnt_dev.p;
-  }
-  lap("uploads, allocations (lane/obs)");
-  // scatter scalars of the cold observations: one buffer, sized for the largest of the cold views
-  HIP_TRY(c->q4c.alloc(std::max<size_t>(std::max(std::max(std::max(L.cc_slot.size(), L.c2_lm.size()), n_cold_lpl), n_cold_q), 1), &c->bytes));
-  HIP_TRY(room(c->cc_h, 4 * std::max<size_t>(L.cc_slot.size(), 1))); HIP_TRY(room(c->cc_part, 12 * (size_t)std::max(c->n_cold_items, 1)));
-  HIP_TRY(room(c->hot_part, (size_t)c->e0c_grid * c->n_hot_acc * 12));
-  HIP_TRY(room(c->hot_rec, (size_t)std::max(n_cams, HOT_MAX) * HOT_REC_STRIDE));  // every camera, in popularity order
-  HIP_TRY(room(c->zimg, (size_t)n_cams * 12));  // z alone, by rank: what e0_ck gathers Z from (Dp::zimg)
-  HIP_TRY(room(c->norm_part, 2 * (size_t)std::max(c->n_cam_blocks, n_cams))); HIP_TRY(room(c->norms, 4)); HIP_TRY(room(c->flags, 4));
-  HIP_TRY(room(c->part, n_part * 2 + 8 * 1024)); HIP_TRY(room(c->scal, 8));  // + one slot set per workgroup of the lane-per-landmark kernels
-  HIP_TRY(room(c->stage, std::max(3 * nl, 144 * nc)));
-  HIP_TRY(hipMemsetAsync(c->flags.p, 0, sizeof(int) * 4, c->stream));
-  HIP_TRY(hipMemsetAsync(c->lms4.p, 0, sizeof(double4) * nl, c->stream));
-  HIP_TRY(hipMemsetAsync(c->cams4.p, 0, sizeof(double4) * 3 * nc, c->stream));
-  HIP_TRY(hipMemsetAsync(c->y.p, 0, sizeof(double) * 12 * nc, c->stream));
-  HIP_TRY(hipMemsetAsync(c->q4.p, 0, sizeof(double4) * ns, c->stream));
-  HIP_TRY(hipMemsetAsync(c->sw.p, 0, sizeof(double) * ns, c->stream));
-  HIP_TRY(hipMemsetAsync(c->rres.p, 0, sizeof(double4) * ns, c->stream));
-  // every initialisation above (uploads on the null stream, memsets on the context's non-blocking
-  // stream) is complete before the context is handed out
-  HIP_TRY(hipDeviceSynchronize());
-
-  Dp& d = c->d;
-  d.n_cams = n_cams; d.n_lms = n_lms; d.n_bins = c->n_bins; d.n_items = c->n_items;
-  d.n_long = c->n_long; d.n_reg_blocks = c->n_reg_blocks;
-  d.uv = c->uv.p; d.cam = c->cam.p; d.lm = c->lm.p; d.meta = c->meta.p;
-  d.long_lm = c->long_lm.p; d.long_first = c->long_first.p; d.long_cnt = c->long_cnt.p;
-  d.cm_slot = c->cm_slot.p; d.cm_lm = c->cm_lm.p; d.cm_uv = c->cm_uv.p;
-  d.item_off = c->item_off.p; d.item_cam = c->item_cam.p; d.cam_item_off = c->cam_item_off.p;
-  d.cams4 = c->cams4.p; d.cams_lin4 = c->cams_lin4.p; d.lms4 = c->lms4.p; d.lms_lin4 = c->lms_lin4.p;
-  d.jl_scale4 = c->jl_scale4.p; d.hll_inv = c->hll_inv.p; d.lmrec = c->lmrec.p;
-  d.cmv = CmView{c->cm_slot.p, c->cm_h.p, n_obs, c->item_off.p, c->cam_item_off.p, c->item_part.p, c->n_items, nullptr};
-  d.hot_part = nullptr; d.cam_hot = c->cam_hot.p; d.n_hot_acc = c->n_hot_acc; d.n_hot_wg = c->e0c_grid;
-  d.hot_rec = c->hot_rec.p;
-  d.zimg = c->zimg.p;
-  d.hot_cams = c->hot_cams.p; d.n_hot = std::min(n_cams, HOT_MAX);
-  d.part_range = nullptr;
-  d.p2p_peer = nullptr; d.p2p_epoch = nullptr; d.p2p_world = 1; d.p2p_rank = 0;
-  d.sw = c->sw.p; d.rres = c->rres.p; d.q4 = c->q4.p; d.q4c = nullptr; d.cold_pos = nullptr; d.long_in_kernel = 0; d.tiles = nullptr;
-  d.sigma = c->sigma.p; d.diag2 = c->diag2.p; d.G = c->G.p; d.binv = c->binv.p; d.b = c->b.p;
-  d.tmp = c->tmp.p; d.accum = c->accum.p; d.z = c->z.p; d.y = c->y.p; d.inc = c->inc.p;
-  d.item_part = c->item_part.p; d.item_partG = c->item_partG.p; d.cm_h = c->cm_h.p; d.n_obs = n_obs;
-  d.flags = c->flags.p; d.norm_part = c->norm_part.p; d.norms = c->norms.p;
-  d.sa = 0; d.sb = 1; d.eps = options->jacobi_scaling_eps; d.huber = options->huber_parameter;
-  d.lambda_lm = 0; d.robust = options->robust_norm; d.scale_jl = 1;
-  lap("allocations, memsets, sync");
-  c->create_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_create).count();
-  if (timing) std::fprintf(stderr, "[povar_create] total %.1f ms\n", c->create_ms);
+  J.lap("wait for the lane/obs arrays");
+  if (int rc = upload_lane_obs(c, plan, J)) return rc;
+  fill_dp(c);
+  J.lap("allocations, memsets, sync");
+  c->create_ms = std::chrono::duration<double, std::milli>(Laps::Clock::now() - J.lap.t0).count();
+  if (plan.timing) std::fprintf(stderr, "[povar_create] total %.1f ms\n", c->create_ms);
   *out = owner.release();
   return 0;
 }

@@ -42,6 +42,7 @@
 #include "povar_kernels_ck_joint.hpp"
 #include "povar_kernels_ck_f32.hpp"
 #include "res_layout.hpp"
+#include "create_plan.hpp"
 #include "povar_kernels_res.hpp"
 
 using namespace povar;
@@ -79,7 +80,7 @@ inline std::unique_lock<std::mutex> capture_lock(bool locked) {
 //   4. destroy the graph exec, the pinned block, the communicator, the opened IPC mappings, xbuf and both event vectors
 //      (1 to 4: the destructor's body, which runs before any member is destroyed)
 //   5. every DevBuf member frees its memory   6. the stream is destroyed (OwnedStream, below)
-struct povar_ctx {
+struct povar_ctx : CtxSwitches {  // (create_plan.hpp: the switches povar_create resolves)
   povar_ctx() = default;
   povar_ctx(const povar_ctx&) = delete;
   ~povar_ctx();
@@ -95,8 +96,7 @@ struct povar_ctx {
   int64_t n_obs = 0;
   int n_bins = 0, n_slots = 0, n_items = 0, n_long = 0;
   int n_reg_blocks = 0, n_cam_blocks = 0;
-  int n_hot = 0, n_hot_acc = 0, e0c_grid = 0, e0c_bins_per_wg = 0;
-  int cu_limit = 0;              // CUs of the stream's mask (POVAR_CU_MASK), 0: the whole device
+  int n_hot = 0, e0c_grid = 0, e0c_bins_per_wg = 0;
   int64_t n_cold = 0;
   int n_cold_items = 0;
   povar_options opt{};
@@ -153,9 +153,6 @@ struct povar_ctx {
   size_t pl_bytes = 0;        // what the thread allocated (pl_rows, pl_ck, pl_ckh)
   int placement = 0;          // povar_layout_info::placement: 0 natural order, 1 placed in povar_create, 2 pending, 3 swapped in
   double placement_ms = 0;    // host wall time of the background build (valid from state 2 on)
-  bool use_lpl = true;        // POVAR_E0_V1=1: keep e0_lm_cached<true> (lane per observation) for A/B runs
-  bool lpl_forced = false;      // POVAR_E0_V1 set: keep the choice (the peer-to-peer exchange otherwise turns use_lpl on)
-  bool use_lpl_prepare = true;  // POVAR_PREPARE_V1=1: keep lm_regular<OpPrepare> + cm_scatter
   // camera-chunk layout of e0_ck (ck_layout.hpp): derived from the lane-per-landmark rows in use, so it is rebuilt
   // with them (pl_ck: built by the placement thread from the placed rows, swapped in together with them)
   struct CkBufs {                // (the buffers apart from the counts: CkDev::release frees them by assigning an empty CkBufs)
@@ -213,8 +210,6 @@ struct povar_ctx {
   bool res_h_shared = false;
   size_t res_h_lds = 0;          // dynamic LDS of series_res_h on the instance it runs
   double res_h_build_ms = 0;
-  int res_mode = -1;             // -1: the library times the resident series against the per-term kernels once per context
-                                 // (res_autotune); 0: per-term kernels; 1: resident series whenever the context allows
   struct ResTune {               // res_autotune's answer for one step, timed on the system prepared for it
     bool tuned = false, choice = false;
     float us[2] = {0, 0};        // per term: per-term kernels (hipGraph), resident series
@@ -223,28 +218,20 @@ struct povar_ctx {
   bool res_check = false;        // a resident series is in flight whose give-up bit (flags[0] & 4) has not been looked at
   int res_last_m = 0;
   double res_last_tol[2] = {0, 0};
-  unsigned res_spin_limit = 1u << 18;
-  bool deterministic = false;    // POVAR_DETERMINISTIC=1: the E0 mode and the kernel choices are pinned
-  bool det_ck = false;           // ... and step 1's terms run e0_ck_det where the chunk layout fits (else: the gather form)
-  bool det_check = false;        // a series of e0_ck_det is in flight whose failure bit (flags[0] & 8) has not been looked at
-  // POVAR_FLAG_FP32_TERMS: step 1's terms run e0_ck_f32 (povar_kernels_ck_f32.hpp) on the layout of variant 1
-  bool fp32_terms = false;
+  bool det_check = false;        // deterministic: a series of e0_ck_det is in flight whose failure bit (flags[0] & 8) has not been looked at
+  // fp32_terms: step 1's terms run e0_ck_f32 (povar_kernels_ck_f32.hpp) on the layout of variant 1
   int32_t fp32_last = 0;         // 1: the last step-1 power series ran its terms in fp32 (povar_layout_info.fp32_terms)
   DevBuf<float2> ck32_uv;        // [rows][64] fp32 image points of the chunk rows (only where the rows do not pack)
   DevBuf<float> ck32_lmrec;      // [lpl tiles][9][64] fp32 h~ and G of the landmark lanes (ck32_records, after every prepare)
   DevBuf<float> ck32_pimg;       // [n_cams][12] fp32 P3 and translation by rank (ck32_records)
   DevBuf<int2> ck_zero_range;    // [n_cams] empty runs: e0_ck leaves no per-observation cold view to the per-camera kernels
-  int ck_variant = 0;            // 0: e0_lpl; 1..CK_VARIANTS: e0_ck instantiation (POVAR_CK_VARIANTS)
-  int ckh_variant = 0;           // step 2: 0: e0_lpl_h; 1: e0_ck_h
   bool ckh_tuned = false;
   float ckh_tune_us[2] = {0, 0}; // e0_lpl_h, e0_ck_h
-  bool ck_auto = true;           // the library picks e0_lpl or e0_ck by timing both on this problem (ck_autotune); false: forced
   bool ck_tuned = false;
   bool ck_fresh[2] = {false, false};  // a timing of step 1 / step 2 finished on this rank since the ranks last agreed (tune_agree)
   float ck_tune_us[2] = {0, 0};  // what the timing saw: e0_lpl, e0_ck (microseconds per launch)
   DevBuf<double4> q4c;        // scatter scalars of the cold observations, in cold camera-major order
   DevBuf<int> lm_slot0, lm_cnt_dev;
-  bool k1_qr = true;          // POVAR_K1_NORMAL_EQ=1: the round-1 normal-equation kernels (A/B accuracy runs)
   // stage timings (povar_timings): hipEvent pairs around the entry points, summed on demand
   bool timings_on = false;
   std::vector<hipEvent_t> tev;
@@ -332,16 +319,12 @@ struct povar_ctx {
     int kind = 0, mode = 0;
     povar_residual_info ri{};
   } err_memo;
-  bool no_err_memo = false;   // POVAR_NO_ERR_MEMO=1: evaluate every compute_error call (timing the kernel itself)
   bool has_empty_lm = false;  // a landmark without observations has no lane: lms_lin4 is then copied eagerly
   bool flag0_clean = false;  // flags[0] is known to be zero on the device (read back as zero, no writer launched since)
   hipGraphExec_t series_graph = nullptr;
   Dp series_graph_d{};
   int series_graph_key[6] = {0, 0, 0, 0, 0, 0};
   double series_graph_tol[2] = {0, 0};
-  bool use_graph = true;
-  bool graph_with_comm = false;
-  bool fuse_binv = true;   // POVAR_NO_FUSE=1: keep cam_cold_sum and cam_binv_axpy separate
 
   // profiling
   bool profile = false;
@@ -349,22 +332,6 @@ struct povar_ctx {
   std::vector<int> ev_kind;  // 0 e0, 1 binv, 2 comm  (interval between ev[i], ev[i+1])
   size_t ev_used = 0;
 };
-
-// e0_ck instantiations (povar_ctx::ck_variant): wavefronts per workgroup, rows a tile keeps in flight, double-buffered
-// tile records, groups of wavefronts working on different batches (povar_kernels_ck.hpp)
-#define POVAR_CK_VARIANTS(X) \
-  X(1, 16, 2, false, 1) X(2, 16, 4, false, 1) X(3, 12, 2, true, 1) X(4, 16, 2, false, 2) X(5, 16, 4, false, 2) X(6, 8, 2, true, 1)
-constexpr int CK_VARIANTS = 6;
-struct CkVariant { int nw, sd; bool db; int ng; };
-inline CkVariant ck_variant_info(int variant) {
-  switch (variant) {
-#define X(id, nw, sd, db, ng) case id: return CkVariant{nw, sd, db, ng};
-    POVAR_CK_VARIANTS(X)
-#undef X
-    default: return CkVariant{16, 2, false, 1};
-  }
-}
-
 
 // A host vector to a device buffer of its size (one element for an empty one), counted into *bytes (default: the context's).
 // locked: the caller is the row-placement thread -- its HIP calls go in short pieces under g_capture_mu, and a cancelled
@@ -387,6 +354,16 @@ int upload(DevBuf<T>& buf, const std::vector<T>& v, povar_ctx* c, size_t* bytes 
   }
   return 0;
 }
+
+// "upload these vectors, stop at the first failure": up(buf, v)(buf2, v2)...; then look at rc (what upload returned)
+struct Uploader {
+  povar_ctx* c;
+  size_t* bytes = nullptr;
+  bool locked = false;
+  int rc = 0;
+  template <class T>
+  Uploader& operator()(DevBuf<T>& buf, const std::vector<T>& v) { if (!rc) rc = upload(buf, v, c, bytes, locked); return *this; }
+};
 
 inline int grid_for(int64_t n, int block) { return (int)((n + block - 1) / block); }
 
@@ -517,13 +494,8 @@ Dp ldsacc_dp(povar_ctx* c, bool long_in_kernel = false);  // povar_series.hip
 int ck_autotune(povar_ctx* c, int step);  // povar_series.hip
 int tune_agree(povar_ctx* c, int step);  // povar_series.hip
 extern "C" int res_verify(povar_ctx* c);  // povar_series.hip
-int ck_max_cams();  // povar_create.hip
-bool ck_upload(povar_ctx* c, povar_ctx::CkDev& D, const CkLayout& K, bool locked, size_t* bytes, bool need_uv = true);  // povar_create.hip
-int res_upload(povar_ctx* c, povar_ctx::ResDev& D, const ResLayout& R);  // povar_create.hip
-void res_build_for(int n_cams, int n_lms, const int32_t* lm_off, const int32_t* cam_idx, const double* obs, const std::vector<int>& rank1, const std::vector<int>& slot_of_obs, int wgs, ResLayout& R, const ResShape& sh = ResShape());  // povar_create.hip
 int swap_in_placed_rows(povar_ctx* c, bool wait);  // povar_create.hip
 int check_ctx(povar_ctx* c);  // povar_create.hip
-int ensure_pin(povar_ctx* c);  // povar_create.hip
 int read_scal_flags(povar_ctx* c, double* h, int n, int (&f)[4]);  // povar_create.hip
 int read_flags(povar_ctx* c, int (&f)[4]);  // povar_create.hip
 int read_scal(povar_ctx* c, double* h, int n);  // povar_create.hip
