@@ -365,6 +365,44 @@ int povar_observation_covariance_joint(povar_ctx* ctx, double lambda, int32_t ga
                                        const int32_t* lm_ids /* NULL = all landmarks of the context */, int32_t n_ids,
                                        double* obs_cov /* 4 n_rows */, int64_t n_rows);
 
+/* ---- covariance blocks of parameter pairs: the cross-covariances the calls above do not return (ceres::Covariance takes a
+ * list of parameter-block pairs for the same reason): what the uncertainty of a relative pose, a baseline, the distance of two
+ * points or a point in another camera's frame is made of.  In the setting of the landmark calls, with W_i = E_i Hll_l^-1
+ * (E_i the block of Hpl of observation i of landmark l), the block of a pair is
+ *       camera a, camera b        C[a, b]
+ *       camera c, landmark l      -sum_{j in obs(l)} C[c, c_j] W_j                                     (dim x 3)
+ *       landmark l, landmark m    delta_lm Hll_l^-1 + sum_{i in obs(l), j in obs(m)} W_i^T C[c_i, c_j] W_j
+ * and a (landmark, camera) pair gets the transpose of the (camera, landmark) block.
+ *   gauge  POVAR_COV_DAMPED: C = S(lambda)^-1; the blocks are exactly those of H(lambda)^-1.
+ *          POVAR_COV_FREE_GAUGE (lambda = 0): C = S(0)^+; the blocks of the covariance with the gauge fixed on the cameras, the
+ *          one the camera and the landmark calls take their diagonal blocks of (the top-left part of [[H0, Cg], [Cg^T, 0]]^-1,
+ *          Cg = [Q; 0]).  Same lambda rules, pivot rule and errors as the camera calls.
+ *   coords POVAR_COV_SOLVER_COORDS: a camera has 12 (pose) or 11 (joint) coordinates, a landmark 3.  POVAR_COV_CAMERA_COORDS
+ *          (= POVAR_COV_LANDMARK_COORDS, the parameters' own coordinates): a camera 12, a landmark 3 (pose) or 4 (joint); the
+ *          block is M_a T M_b^T with the maps of the calls above (camera: D or D N_c; landmark: diag(s_l) or D4 N_l).
+ *   pairs  4 n_pairs numbers, (kind_a, id_a, kind_b, id_b) per pair, kind POVAR_COV_BLOCK_CAMERA or POVAR_COV_BLOCK_LANDMARK.
+ *          Camera ids are global; landmark ids index the context's own landmarks (on a sharded context: the rank's shard, as
+ *          lm_ids of the landmark calls -- a pair of landmarks of two different shards is therefore not served).  Any pair is
+ *          valid: a == b, a camera with a landmark it does not observe, duplicates.  An unknown kind or an id out of range
+ *          is an argument error.
+ *   blocks, n_out   the blocks one after the other in request order, each rows(a) x cols(b) row-major without padding.  n_out
+ *          must be the number of doubles the request produces, else an argument error.
+ * From the same factor as the landmark calls (C = W W^T off the diagonal too), then one workgroup per pair; no atomics and every
+ * sum in a fixed order: given C a block is reproducible (with the ordered assembly, as above, bit for bit across calls).  Every
+ * pair is evaluated in one canonical order: the block of (b, a) is the bitwise transpose of the block of (a, b), a block with
+ * a == b is symmetric bit for bit, duplicates are the same bits.
+ * Preconditions, the sharded rule (every rank calls) and the memory errors are those of the landmark calls.  Side effects: with
+ * n_pairs > 0 those of a landmark call with n_ids > 0 (POVAR_BUF_COV_INVERSE, _PANEL and _GAUGE hand out W, C and Q;
+ * POVAR_BUF_SC_FACTOR is an argument error afterwards); n_pairs = 0 returns 0 and leaves W alone, as a camera call does.  On
+ * POVAR_NUMERIC_FAILURE every entry of blocks is NaN. ---- */
+enum { POVAR_COV_BLOCK_CAMERA = 0, POVAR_COV_BLOCK_LANDMARK = 1 };
+/* after povar_linearize_pose: the 12 n_cams system of step 1 */
+int povar_covariance_blocks_pose(povar_ctx* ctx, double lambda, int32_t gauge, int32_t coords,
+                                 const int32_t* pairs /* 4 n_pairs */, int32_t n_pairs, double* blocks /* n_out */, int64_t n_out);
+/* after povar_linearize_homogeneous: the 11 n_cams tangent system of step 2 */
+int povar_covariance_blocks_joint(povar_ctx* ctx, double lambda, int32_t gauge, int32_t coords,
+                                  const int32_t* pairs /* 4 n_pairs */, int32_t n_pairs, double* blocks /* n_out */, int64_t n_out);
+
 /* ---- inspection of internal state in the reference's layouts (parity tests) ---- */
 enum {
   POVAR_BUF_DIAG2 = 0,     /* get_Jp_diag2_pOSE, 12 n_cams (linearization_varproj.hpp:183-222) */

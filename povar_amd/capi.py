@@ -28,6 +28,7 @@ SC_PCG, SC_CHOLESKY = 0, 1
 COV_FREE_GAUGE, COV_DAMPED = 0, 1
 COV_CAMERA_COORDS, COV_SOLVER_COORDS = 0, 1
 COV_LANDMARK_COORDS = 0  # povar_landmark_covariance_pose / _joint: the same number as COV_CAMERA_COORDS
+COV_BLOCK_CAMERA, COV_BLOCK_LANDMARK = 0, 1  # povar_covariance_blocks_pose / _joint: the kinds of a pair
 
 
 class Options(C.Structure):
@@ -362,6 +363,30 @@ class Context:
         rc = self._chk(fn(self.h, C.c_double(lam), C.c_int32(gauge), ids_p, C.c_int32(n_ids), _p(out) if n_rows else None,
                           C.c_int64(n_rows)), allow_numeric=True)
         return out, rc
+
+    def covariance_blocks(self, pairs, step=1, lam=0.0, gauge=COV_FREE_GAUGE, coords=COV_CAMERA_COORDS):
+        """Covariance blocks of parameter pairs at the step linearised last: (list of 2-D arrays in request order, rc).  `pairs`
+        is [n, 4]: (kind_a, id_a, kind_b, id_b) with kind COV_BLOCK_CAMERA or COV_BLOCK_LANDMARK; camera ids are global,
+        landmark ids index the context's own landmarks.  A block is rows(a) x cols(b): a camera has 12 coordinates (11 in step
+        2's solver coordinates), a landmark 3 (4 in step 2's own coordinates).  rc = NUMERIC_FAILURE comes with all-NaN blocks
+        (include/povar_hip.h)."""
+        if step not in (1, 2):
+            raise ValueError("covariance_blocks: step is 1 or 2")
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 4)
+        n = pairs.shape[0]
+        solver = coords == COV_SOLVER_COORDS
+        side = np.array([11 if (step == 2 and solver) else 12, 4 if (step == 2 and not solver) else 3], dtype=np.int64)
+        kinds = pairs[:, [0, 2]]
+        if np.any((kinds != COV_BLOCK_CAMERA) & (kinds != COV_BLOCK_LANDMARK)):
+            raise PovarError("covariance_blocks: unknown kind")
+        rows, cols = side[kinds[:, 0]], side[kinds[:, 1]]
+        off = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(rows * cols, out=off[1:])
+        out = np.zeros(int(off[-1]))
+        fn = self.L.povar_covariance_blocks_pose if step == 1 else self.L.povar_covariance_blocks_joint
+        rc = self._chk(fn(self.h, C.c_double(lam), C.c_int32(gauge), C.c_int32(coords), _p(pairs) if n else None, C.c_int32(n),
+                          _p(out) if out.size else None, C.c_int64(out.size)), allow_numeric=True)
+        return [out[off[i]:off[i + 1]].reshape(rows[i], cols[i]).copy() for i in range(n)], rc
 
     def apply_joint(self, inc):
         inc = np.ascontiguousarray(inc, dtype=np.float64)

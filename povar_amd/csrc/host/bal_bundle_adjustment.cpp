@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <limits>
 #include <fstream>
@@ -185,6 +186,51 @@ void write_observation_covariance(Linearizor& linearizor, const BalProblem& bal_
     for (int i = lm_off[l]; i < lm_off[l + 1]; ++i)
       std::fprintf(f, "%d %d %.17g %.17g %.17g %.17g\n", l, cam_idx[i], cov[4 * (size_t)i], cov[4 * (size_t)i + 1], cov[4 * (size_t)i + 2],
                    cov[4 * (size_t)i + 3]);
+  std::fclose(f);
+}
+
+// --covariance-pairs-path IN --covariance-blocks-path OUT: IN holds the number of pairs, then `c|l id c|l id` per pair; OUT gets
+// the number of pairs, then per pair one line: rows cols and the block row-major (povar_covariance_blocks_pose / _joint, free
+// gauge, parameter coordinates: a camera 12, a landmark 3 after step 1 and 4 after step 2); a call of its own
+void write_covariance_blocks(Linearizor& linearizor, const BalProblem& bal_problem, const SolverOptions& so, bool step2) {
+  auto bad = [&](const char* why) {
+    std::fprintf(stderr, "FATAL: %s: %s\n", so.covariance_pairs_path.c_str(), why);
+    std::abort();
+  };
+  std::FILE* in = std::fopen(so.covariance_pairs_path.c_str(), "r");
+  if (!in) bad("cannot read");
+  long count = -1;
+  if (std::fscanf(in, "%ld", &count) != 1 || count < 0 || count > INT32_MAX / 4) bad("the first line is the number of pairs");
+  const int side[2] = {12, step2 ? 4 : 3};
+  std::vector<int32_t> pairs(4 * (size_t)count);
+  std::vector<size_t> first((size_t)count + 1, 0);
+  for (long p = 0; p < count; ++p) {
+    char ka = 0, kb = 0;
+    long a = -1, b = -1;
+    if (std::fscanf(in, " %c %ld %c %ld", &ka, &a, &kb, &b) != 4 || (ka != 'c' && ka != 'l') || (kb != 'c' && kb != 'l'))
+      bad("a pair is `c|l id c|l id`");
+    const long na = ka == 'c' ? bal_problem.num_cameras() : bal_problem.num_landmarks();
+    const long nb = kb == 'c' ? bal_problem.num_cameras() : bal_problem.num_landmarks();
+    if (a < 0 || a >= na || b < 0 || b >= nb) bad("an id is out of range");
+    const int32_t q[4] = {ka == 'c' ? 0 : 1, (int32_t)a, kb == 'c' ? 0 : 1, (int32_t)b};  // POVAR_COV_BLOCK_CAMERA / _LANDMARK
+    std::copy(q, q + 4, pairs.begin() + 4 * p);
+    first[p + 1] = first[p] + (size_t)side[q[0]] * side[q[2]];
+  }
+  std::fclose(in);
+  Linearizor::VecX blocks(first[count], 0.0);
+  const int rc = linearizor.covariance_blocks(step2, so.alpha, pairs, blocks);
+  if (rc < 0) {
+    std::fprintf(stderr, "FATAL: this linearizor does not serve --covariance-pairs-path\n");
+    std::abort();
+  }
+  if (rc != 0) std::printf("\t[WARN] covariance blocks: the reduced system is singular beyond its gauge, the blocks are NaN\n");
+  std::FILE* f = open_for_writing(so.covariance_blocks_path);
+  std::fprintf(f, "%ld\n", count);
+  for (long p = 0; p < count; ++p) {
+    std::fprintf(f, "%d %d", side[pairs[4 * p]], side[pairs[4 * p + 2]]);
+    for (size_t k = first[p]; k < first[p + 1]; ++k) std::fprintf(f, " %.17g", blocks[k]);
+    std::fputc('\n', f);
+  }
   std::fclose(f);
 }
 
@@ -370,6 +416,8 @@ void optimize_lm(BalProblem& bal_problem, const SolverOptions& so, SolverSummary
     write_covariances(*linearizor, bal_problem, so, step2);
   if (!so.observation_covariance_path.empty() && step2 == (so.max_num_iterations_step_2 > 0))
     write_observation_covariance(*linearizor, bal_problem, so, step2);
+  if (!so.covariance_pairs_path.empty() && step2 == (so.max_num_iterations_step_2 > 0))
+    write_covariance_blocks(*linearizor, bal_problem, so, step2);
   std::printf("Final Cost: %s\n", error_summary_oneline(summary.final_cost, so.use_projection_validity_check()).c_str());
   std::printf("%s: %s\n", summary.termination_type == CONVERGENCE ? "CONVERGENCE" : "NO_CONVERGENCE", summary.message.c_str());
   std::fflush(stdout);

@@ -95,6 +95,8 @@ bool parse_bal_app_arguments(int argc, char** argv, BalAppOptions& o) {
   str("camera-covariance-path", &o.solver.camera_covariance_path);
   str("landmark-covariance-path", &o.solver.landmark_covariance_path);
   str("observation-covariance-path", &o.solver.observation_covariance_path);
+  str("covariance-pairs-path", &o.solver.covariance_pairs_path);
+  str("covariance-blocks-path", &o.solver.covariance_blocks_path);
 
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -116,7 +118,12 @@ bool parse_bal_app_arguments(int argc, char** argv, BalAppOptions& o) {
                   "  --observation-covariance-path FILE\n"
                   "      likewise for every observation, independent of the gauge: n_obs, then one line per observation in file order:\n"
                   "      landmark camera h c_uu c_uv c_vv -- the leverage h (redundancy number: 4 - h after step 1, 2 - h after step 2)\n"
-                  "      and the 2 x 2 covariance of the predicted image point\n");
+                  "      and the 2 x 2 covariance of the predicted image point\n"
+                  "  --covariance-pairs-path IN --covariance-blocks-path OUT\n"
+                  "      likewise the covariance block of every pair of parameter blocks listed in IN (the number of pairs, then one\n"
+                  "      line `c|l id c|l id` per pair: c a camera, l a landmark), gauge fixed on the cameras: OUT gets the number of\n"
+                  "      pairs, then one line `rows cols` and the rows x cols numbers per pair (a camera 12 coordinates, a landmark 3\n"
+                  "      after step 1, 4 after step 2); one device only\n");
       return false;
     }
     if (a.rfind("--", 0) != 0) {
@@ -141,6 +148,14 @@ bool parse_bal_app_arguments(int argc, char** argv, BalAppOptions& o) {
   if (o.dataset.input.empty()) { std::fprintf(stderr, "missing --input\n"); return false; }
   if (o.solver.gpus > 1 && !o.solver.camera_covariance_path.empty()) {
     std::fprintf(stderr, "--gpus > 1 does not serve --camera-covariance-path (the dense factor is inverted on one device)\n");
+    return false;
+  }
+  if (o.solver.covariance_pairs_path.empty() != o.solver.covariance_blocks_path.empty()) {
+    std::fprintf(stderr, "--covariance-pairs-path and --covariance-blocks-path go together\n");
+    return false;
+  }
+  if (o.solver.gpus > 1 && !o.solver.covariance_pairs_path.empty()) {
+    std::fprintf(stderr, "--gpus > 1 does not serve --covariance-pairs-path (landmark ids would be those of a shard)\n");
     return false;
   }
   return true;

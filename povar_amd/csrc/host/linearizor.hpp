@@ -2,6 +2,7 @@
 // solver/solver_summary.hpp, bal/residual_info.hpp:59-102).  VecX is a std::vector<double>
 // (the reference's Eigen::VectorXd).
 #pragma once
+#include <cstdint>
 #include <memory>
 #include <string>
 #include <vector>
@@ -131,6 +132,13 @@ class Linearizor {
   // observation in file order (h, c_uu, c_uv, c_vv).  Sharded, the HIP linearizor serves it too.
   virtual int observation_covariance(bool step2, double alpha, VecX& obs_cov) {
     (void)step2; (void)alpha; (void)obs_cov;
+    return -1;
+  }
+  // Likewise for pairs of parameter blocks (povar_covariance_blocks_pose / _joint, free gauge, parameter coordinates): `pairs`
+  // holds (kind_a, id_a, kind_b, id_b) per pair as the library takes them, ids in file order; `blocks` has the size the request
+  // produces and gets the blocks one after the other.  Only the HIP linearizor on a single device serves it.
+  virtual int covariance_blocks(bool step2, double alpha, const std::vector<int32_t>& pairs, VecX& blocks) {
+    (void)step2; (void)alpha; (void)pairs; (void)blocks;
     return -1;
   }
 };

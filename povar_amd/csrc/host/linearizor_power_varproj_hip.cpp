@@ -167,6 +167,17 @@ class LinearizorPowerVarprojHip : public Linearizor, public StateMirror {
                    : povar_observation_covariance_pose(s.ctx, 0.0, POVAR_COV_FREE_GAUGE, nullptr, 0, out, s.on);
     });
   }
+  int covariance_blocks(bool step2, double alpha, const std::vector<int32_t>& pairs, VecX& blocks) override {
+    if (sharded_) return -1;  // (landmark ids are the shard's own)
+    linearize_all(step2, alpha, "povar_linearize (covariance blocks)");
+    return covariance_status("povar_covariance_blocks", [&](Shard& s) {
+      const int32_t n = (int32_t)(pairs.size() / 4);
+      return step2 ? povar_covariance_blocks_joint(s.ctx, 0.0, POVAR_COV_FREE_GAUGE, POVAR_COV_CAMERA_COORDS, pairs.data(), n, blocks.data(),
+                                                   (int64_t)blocks.size())
+                   : povar_covariance_blocks_pose(s.ctx, 0.0, POVAR_COV_FREE_GAUGE, POVAR_COV_CAMERA_COORDS, pairs.data(), n, blocks.data(),
+                                                  (int64_t)blocks.size());
+    });
+  }
   VecX solve(const SolverOptions& so, double lambda, double) override {
     std::vector<Solved> out(shards_.size(), Solved{VecX(12 * (size_t)bal_problem_.num_cameras()), 0, 0});
     if (sc_step1_) {  // LinearizorSC::solve, linearizor_sc.cpp:85-160

@@ -75,6 +75,12 @@ struct SolverOptions {
   // n_obs on the first line, then one line per observation in file order: landmark camera h c_uu c_uv c_vv (%.17g).  A call
   // of its own, independent of the two paths above; served with --gpus N too: every shard writes its own observations.
   std::string observation_covariance_path;
+  // covariance blocks of parameter pairs (povar_covariance_blocks_pose / _joint, free gauge, parameter coordinates).
+  // covariance_pairs_path is read: the number of pairs, then one line `c|l id c|l id` per pair (c: a camera, l: a landmark, ids
+  // in file order).  covariance_blocks_path is written: the number of pairs, then one line per pair: rows cols and the rows x cols
+  // numbers row-major (%.17g); a camera has 12 coordinates, a landmark 3 (after step 1) or 4 (after step 2).  Both or neither;
+  // one device only.
+  std::string covariance_pairs_path, covariance_blocks_path;
 
   // solver_options.cpp:41-51
   bool use_projection_validity_check() const { return optimized_cost != OptimizedCost::ERROR; }

@@ -264,6 +264,9 @@ struct povar_ctx : CtxSwitches {  // (create_plan.hpp: the switches povar_create
   DevBuf<int> sc_cov_ids;
   DevBuf<double> sc_cov_obs;             // povar_observation_covariance_*: the rows (4 per observation) and the first row of
   DevBuf<int> sc_cov_row0;               // every requested landmark, kept likewise (Sigma_l without the gauge part goes to sc_cov_lm)
+  DevBuf<double> sc_cov_pair_out;        // povar_covariance_blocks_*: the blocks in request order, the three index lists (a, b,
+  DevBuf<int> sc_cov_pair_items;         // transposed, -) one after the other and where every block starts, kept likewise
+  DevBuf<long long> sc_cov_pair_off;
   // inspection of the covariance path (povar_set_cov_inspect, POVAR_BUF_COV_*).  sc_cov_kind: what the last call that wrote
   // the dense matrix left there: 0 nothing to hand out (chol_factor, a failure), 1 a camera call's W, 2 a landmark call's W, C
   // and panel; sc_cov_n as sc_factor_n (dim * n_cams of that call); sc_cov_nq: columns of the gauge basis of that call (0:

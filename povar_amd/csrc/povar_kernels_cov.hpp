@@ -17,6 +17,8 @@
 //   lm_cov         Sigma_l = Hll^-1 + sum_ij G_i^T K_ij G_j - T_l^T T_l, then the map to landmark coordinates   workgroup per landmark
 // Observation leverage and predicted-point covariance (povar_observation_covariance_pose / _joint) go on from Sigma_l:
 //   obs_cov        (h_i, c_uu, c_uv, c_vv) of every observation of a landmark from K_ii, R_i = sum_j K_ij G_j and Sigma_l   workgroup per landmark
+// Covariance blocks of parameter pairs (povar_covariance_blocks_pose / _joint) go on from C as well:
+//   pair_cc, pair_cl, pair_ll   the block of a camera-camera, camera-landmark, landmark-landmark pair              workgroup per pair
 #pragma once
 #include "povar_kernels_chol.hpp"
 #include "povar_kernels_sc.hpp"
@@ -574,6 +576,328 @@ __global__ __launch_bounds__(256) void obs_cov(Dp d, const double* ncw, const in
       o[2] = a0[1] * iz + a0[2] * j1;
       o[3] = a1[1] * iz + a1[2] * j1;
     }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// Covariance blocks of parameter pairs (povar_covariance_blocks_pose / _joint): the off-diagonal blocks of the joint covariance
+// the calls above take diagonal blocks of.  With W_i = E_i Hll^-1 (DIM x 3: row r is sum_a u_a[r] G_i[a][:], pair_w) and C as
+// cov_lauum leaves it ((S0 + Q Q^T)^-1 in the free gauge, whose - n n^T part, n = [Q; -F^T Q], is taken off explicitly with
+// T_l = sum_i Q[c_i]^T W_i, as lm_cov does):
+//   pair_cc   camera a, camera b        C[a, b] - Q_a Q_b^T
+//   pair_cl   camera c, landmark l      -sum_{j in obs(l)} C[c, c_j] W_j + Q_c T_l                                   (DIM x 3)
+//   pair_ll   landmark l, landmark m    delta_lm Hll_l^-1 + sum_{i in obs(l), j in obs(m)} W_i^T C[c_i, c_j] W_j - T_l^T T_m
+// then the maps of cov_finish and lm_cov on either side in parameter coordinates (M_cam = D or D N_c, M_lm = diag(s) or D4 N_l).
+// One workgroup per pair.  The host hands every pair over in a canonical order (cameras: a >= b; landmarks: l <= m; the camera
+// of a mixed pair first) with the flag `tr`: the block is then stored transposed, so (b, a) is the bitwise transpose of (a, b).
+// A block with a == b evaluates entry (i, j), i > j, as entry (j, i): symmetric bit for bit.
+// C is read through cov_at alone.  Its lower block triangle is row-major, so the lanes of a 16-lane group lie along the index
+// of the camera with the smaller id: a group reads contiguous runs of a row of C whichever camera of a pair comes first.
+// No floating-point atomics: every thread keeps its partial sums in registers and every sum has a fixed order (one block_sum,
+// and a fixed-order sum over the 16 groups for T_l): a block is reproducible given C.
+// items[p] = (a, b, tr, -), off[p] = where the block of pair p starts in `out`.
+// ------------------------------------------------------------------------------------------
+
+// row r of W_i = E_i Hll^-1
+template <class Step>
+__device__ inline void pair_w(const typename Step::Obs& o, const double* sigma, const double (&h)[4], int r, double (&w)[3]) {
+  double u[3];
+  Step::u(o, sigma, h, r, u);
+#pragma unroll
+  for (int x = 0; x < 3; ++x) w[x] = u[0] * o.G[x] + u[1] * o.G[3 + x] + u[2] * o.G[6 + x];
+}
+
+// tacc += the part of T_l[k = gl][:] of the staged observations grp, grp + 16, ... (lm_cov's gather, a 16-lane group per observation)
+template <class Step>
+__device__ inline void pair_t_add(const typename Step::Obs* os, int n, const double* sigma, const double (&h)[4], const double* Q,
+                                  int nq, int grp, int gl, double (&tacc)[3]) {
+  if (gl >= nq) return;
+  for (int i = grp; i < n; i += 16) {
+    const typename Step::Obs& a = os[i];
+    const double* qrow = Q + (size_t)Step::DIM * a.cam * nq + gl;
+    for (int r = 0; r < Step::DIM; ++r) {
+      double w[3];
+      pair_w<Step>(a, sigma, h, r, w);
+      const double qv = qrow[(size_t)r * nq];
+#pragma unroll
+      for (int b = 0; b < 3; ++b) tacc[b] += qv * w[b];
+    }
+  }
+}
+
+// T_l[k][b] from the 16 groups' partials, in the order of the groups
+__device__ inline double pair_t_sum(const double (&shT)[16][16][3], int k, int b) {
+  double s = 0;
+#pragma unroll
+  for (int g = 0; g < 16; ++g) s += shT[g][k][b];
+  return s;
+}
+
+// N_c[i][p] = delta(i, p + 1) - beta w_i w_{p+1} from ncw = (w[12], beta) (cov_finish's Nm)
+__device__ inline double pair_nc(const double* w, int i, int p) { return (i == p + 1 ? 1.0 : 0.0) - w[12] * w[i] * w[p + 1]; }
+
+template <class Step>
+__global__ __launch_bounds__(192) void pair_cc(const int4* items, const long long* off, const double* M, int64_t ld, const double* panel,
+                                               const double* Q, int nq, const double* sigma, const double* ncw, int coords, double* out) {
+  constexpr int DIM = Step::DIM;
+  __shared__ double T[DIM][DIM + 1];
+  const int4 it = items[blockIdx.x];
+  const int a = it.x, b = it.y, t = threadIdx.x;
+  const bool tr = it.z != 0, same = a == b;
+  double* o = out + off[blockIdx.x];
+  if (t < DIM * DIM) {  // lanes along the columns: a >= b, a row of the block is a run of a row of C
+    int i = t / DIM, j = t - DIM * i;
+    if (same && i > j) { const int s = i; i = j; j = s; }
+    const double* qa = Q + (size_t)(DIM * a + i) * nq;
+    const double* qb = Q + (size_t)(DIM * b + j) * nq;
+    double s = 0;
+    for (int k = 0; k < nq; ++k) s += qa[k] * qb[k];
+    T[t / DIM][t % DIM] = cov_at(M, ld, panel, DIM * a + i, DIM * b + j) - s;
+  }
+  __syncthreads();
+  if (coords == 1) {
+    if (t < DIM * DIM) {
+      const int i = t / DIM, j = t - DIM * i;
+      o[tr ? DIM * j + i : t] = T[i][j];
+    }
+    return;
+  }
+  if (t >= 144) return;
+  const int i0 = t / 12, j0 = t - 12 * i0;
+  int i = i0, j = j0;
+  if (same && i > j) { i = j0; j = i0; }
+  double v = 0;
+  if constexpr (!Step::HOM) {
+    v = T[i][j];
+  } else {
+    const double* wa = ncw + 13 * (size_t)a;
+    const double* wb = ncw + 13 * (size_t)b;
+    for (int p = 0; p < DIM; ++p) {
+      double s = 0;
+      for (int q = 0; q < DIM; ++q) s += T[p][q] * pair_nc(wb, j, q);
+      v += pair_nc(wa, i, p) * s;
+    }
+  }
+  v = sigma[12 * (size_t)a + i] * v * sigma[12 * (size_t)b + j];
+  o[tr ? 12 * j0 + i0 : t] = v;
+}
+
+template <class Step>
+__global__ __launch_bounds__(256) void pair_cl(Dp d, const double* ncw, const int* lm_slot0, const int* lm_cnt, const int4* items,
+                                               const long long* off, const double* M, int64_t ld, const double* panel, const double* Q,
+                                               int nq, int coords, double* out) {
+  typedef typename Step::Obs Obs;
+  constexpr int DIM = Step::DIM, CHUNK = Step::CHUNK, NX = 3 * DIM;
+  __shared__ Obs oj[CHUNK];
+  __shared__ double sh[4 * NX];
+  __shared__ double shT[16][16][3];
+  __shared__ double X[DIM][3];
+  const int4 it = items[blockIdx.x];
+  const int cam = it.x, lm = it.y, t = threadIdx.x;
+  const bool tr = it.z != 0;
+  const int s0 = lm_slot0[lm], k = lm_cnt[lm];
+  const typename Step::Head hd = Step::load(d, lm);
+  const double h[4] = {hd.h[0], hd.h[1], hd.h[2], hd.h[3]};
+  auto stage = [&](int slot, Obs& o) { Step::stage(d, ncw, slot, hd, o); };
+  const int grp = t >> 4, gl = t & 15;
+  double acc[NX];  // lane r of a group: its share of sum_j C[c p, c_j r] W_j[r][b] for every (p, b)  (c >= c_j)
+#pragma unroll
+  for (int e = 0; e < NX; ++e) acc[e] = 0;
+  double accp[3] = {0, 0, 0};  // lane p of a group: sum_j sum_r C[c p, c_j r] W_j[r][b]  (c < c_j)
+  double tacc[3] = {0, 0, 0};
+  for (int jc = 0; jc < k; jc += CHUNK) {
+    const int nj = min(CHUNK, k - jc);
+    __syncthreads();
+    if (t < nj) stage(s0 + jc + t, oj[t]);
+    __syncthreads();
+    if (nq > 0) pair_t_add<Step>(oj, nj, d.sigma, h, Q, nq, grp, gl, tacc);
+    if (gl >= DIM) continue;  // (no shuffle below: the lanes past the block's edge wait at the next barrier)
+    for (int j = grp; j < nj; j += 16) {
+      const Obs& b = oj[j];
+      if (cam >= b.cam) {
+        double w[3];
+        pair_w<Step>(b, d.sigma, h, gl, w);
+#pragma unroll
+        for (int p = 0; p < DIM; ++p) {
+          const double cv = cov_at(M, ld, panel, DIM * cam + p, DIM * b.cam + gl);
+#pragma unroll
+          for (int x = 0; x < 3; ++x) acc[3 * p + x] += cv * w[x];
+        }
+      } else {
+        for (int r = 0; r < DIM; ++r) {
+          double w[3];
+          pair_w<Step>(b, d.sigma, h, r, w);
+          const double cv = cov_at(M, ld, panel, DIM * cam + gl, DIM * b.cam + r);
+#pragma unroll
+          for (int x = 0; x < 3; ++x) accp[x] += cv * w[x];
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int p = 0; p < DIM; ++p)
+#pragma unroll
+    for (int x = 0; x < 3; ++x) acc[3 * p + x] += gl == p ? accp[x] : 0.0;
+  block_sum<NX, 256>(acc, sh);
+#pragma unroll
+  for (int b = 0; b < 3; ++b) shT[grp][gl][b] = tacc[b];
+  __syncthreads();
+  if (t < NX) {
+    const int p = t / 3, b = t - 3 * p;
+    double v = 0;
+#pragma unroll
+    for (int e = 0; e < NX; ++e) v = t == e ? acc[e] : v;
+    v = -v;
+    const double* qc = Q + (size_t)(DIM * cam + p) * nq;
+    for (int q = 0; q < nq; ++q) v += qc[q] * pair_t_sum(shT, q, b);
+    X[p][b] = v;
+  }
+  __syncthreads();
+  double* o = out + off[blockIdx.x];
+  const double* sg = d.sigma + 12 * (size_t)cam;
+  if (coords == 1) {
+    if (t < NX) {
+      const int p = t / 3, b = t - 3 * p;
+      o[tr ? DIM * b + p : t] = X[p][b];
+    }
+    return;
+  }
+  if constexpr (!Step::HOM) {
+    if (t < NX) {
+      const int p = t / 3, b = t - 3 * p;
+      const double sl = b == 0 ? hd.s4[0] : b == 1 ? hd.s4[1] : hd.s4[2];  // (not indexed at run time inside the Head)
+      o[tr ? 12 * b + p : t] = sg[p] * X[p][b] * sl;
+    }
+  } else {
+    if (t < 48) {  // D N_c X N_l^T D4, 12 x 4
+      const int i = t >> 2, y = t & 3;
+      const double* wc = ncw + 13 * (size_t)cam;
+      const double hw[4] = {hd.hw[0], hd.hw[1], hd.hw[2], hd.hw[3]}, s4[4] = {hd.s4[0], hd.s4[1], hd.s4[2], hd.s4[3]};
+      double nl[3];
+#pragma unroll
+      for (int b = 0; b < 3; ++b) nl[b] = (y == b + 1 ? 1.0 : 0.0) - hd.hbeta * hw[y] * hw[b + 1];
+      double v = 0;
+      for (int p = 0; p < DIM; ++p) v += pair_nc(wc, i, p) * (X[p][0] * nl[0] + X[p][1] * nl[1] + X[p][2] * nl[2]);
+      o[tr ? 12 * y + i : t] = sg[i] * v * s4[y];
+    }
+  }
+}
+
+template <class Step>
+__global__ __launch_bounds__(256) void pair_ll(Dp d, const double* ncw, const int* lm_slot0, const int* lm_cnt, const int4* items,
+                                               const long long* off, const double* M, int64_t ld, const double* panel, const double* Q,
+                                               int nq, int coords, double* out) {
+  typedef typename Step::Obs Obs;
+  constexpr int DIM = Step::DIM, CHUNK = Step::CHUNK;
+  __shared__ Obs oi[CHUNK], oj[CHUNK];
+  __shared__ double sh[4 * 9];
+  __shared__ double shTl[16][16][3], shTm[16][16][3];
+  const int4 it = items[blockIdx.x];
+  const int l = it.x, m = it.y, t = threadIdx.x;
+  const bool tr = it.z != 0, same = l == m;
+  const int sl = lm_slot0[l], kl = lm_cnt[l], sm = lm_slot0[m], km = lm_cnt[m];
+  const typename Step::Head hl = Step::load(d, l), hm = Step::load(d, m);
+  const double hhl[4] = {hl.h[0], hl.h[1], hl.h[2], hl.h[3]}, hhm[4] = {hm.h[0], hm.h[1], hm.h[2], hm.h[3]};
+  auto stage_l = [&](int slot, Obs& o) { Step::stage(d, ncw, slot, hl, o); };
+  auto stage_m = [&](int slot, Obs& o) { Step::stage(d, ncw, slot, hm, o); };
+  const int grp = t >> 4, gl = t & 15;
+  double acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  double tl[3] = {0, 0, 0}, tm[3] = {0, 0, 0};
+  // the rectangle obs(l) x obs(m): both chunk loops run in full, each side staged with its own landmark's head
+  for (int ic = 0; ic < kl; ic += CHUNK) {
+    const int ni = min(CHUNK, kl - ic);
+    __syncthreads();
+    if (t < ni) stage_l(sl + ic + t, oi[t]);
+    for (int jc = 0; jc < km; jc += CHUNK) {
+      const int nj = min(CHUNK, km - jc);
+      __syncthreads();
+      if (t < nj) stage_m(sm + jc + t, oj[t]);
+      __syncthreads();
+      if (nq > 0 && jc == 0) pair_t_add<Step>(oi, ni, d.sigma, hhl, Q, nq, grp, gl, tl);
+      if (nq > 0 && ic == 0) pair_t_add<Step>(oj, nj, d.sigma, hhm, Q, nq, grp, gl, tm);
+      for (int pp = grp; pp < ni * nj; pp += 16) {
+        const int i = pp / nj, j = pp - i * nj;
+        const Obs& a = oi[i];
+        const Obs& b = oj[j];
+        const bool by_rows = a.cam >= b.cam;  // the lanes along the index of the camera with the smaller id
+        for (int e = gl; e < DIM * DIM; e += 16) {
+          const int e1 = e / DIM, e2 = e - DIM * e1;
+          const int r = by_rows ? e1 : e2, c = by_rows ? e2 : e1;
+          const double cv = cov_at(M, ld, panel, DIM * a.cam + r, DIM * b.cam + c);
+          double wi[3], wj[3];
+          pair_w<Step>(a, d.sigma, hhl, r, wi);
+          pair_w<Step>(b, d.sigma, hhm, c, wj);
+#pragma unroll
+          for (int x = 0; x < 3; ++x)
+#pragma unroll
+            for (int y = 0; y < 3; ++y) acc[3 * x + y] += wi[x] * cv * wj[y];
+        }
+      }
+    }
+  }
+  block_sum<9, 256>(acc, sh);
+#pragma unroll
+  for (int b = 0; b < 3; ++b) {
+    shTl[grp][gl][b] = tl[b];
+    shTm[grp][gl][b] = tm[b];
+  }
+  __syncthreads();
+  if (t != 0) return;
+  // (l == m: the upper triangle stands for the lower one, here and after the map)
+  double Sg[9];
+#pragma unroll
+  for (int x = 0; x < 3; ++x)
+#pragma unroll
+    for (int y = 0; y < 3; ++y) {
+      double tt = 0;
+      for (int q = 0; q < nq; ++q) tt += pair_t_sum(shTl, q, x) * pair_t_sum(shTm, q, y);
+      Sg[3 * x + y] = (same ? hl.Hi[3 * x + y] : 0.0) + acc[3 * x + y] - tt;
+    }
+#pragma unroll
+  for (int x = 0; x < 3; ++x)
+#pragma unroll
+    for (int y = x + 1; y < 3; ++y) Sg[3 * y + x] = same ? Sg[3 * x + y] : Sg[3 * y + x];
+  double* o = out + off[blockIdx.x];
+  if (coords == 1) {
+#pragma unroll
+    for (int x = 0; x < 3; ++x)
+#pragma unroll
+      for (int y = 0; y < 3; ++y) o[tr ? 3 * y + x : 3 * x + y] = Sg[3 * x + y];
+    return;
+  }
+  if constexpr (!Step::HOM) {
+    double V[9];
+#pragma unroll
+    for (int x = 0; x < 3; ++x)
+#pragma unroll
+      for (int y = 0; y < 3; ++y) V[3 * x + y] = hl.s4[x] * Sg[3 * x + y] * hm.s4[y];
+#pragma unroll
+    for (int x = 0; x < 3; ++x)
+#pragma unroll
+      for (int y = 0; y < 3; ++y) o[tr ? 3 * y + x : 3 * x + y] = same && x > y ? V[3 * y + x] : V[3 * x + y];
+  } else {
+    double Nl[4][3], Nm[4][3];  // N[i][p] = delta(i, p + 1) - beta w_i w_{p+1}
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int p = 0; p < 3; ++p) {
+        Nl[i][p] = (i == p + 1 ? 1.0 : 0.0) - hl.hbeta * hl.hw[i] * hl.hw[p + 1];
+        Nm[i][p] = (i == p + 1 ? 1.0 : 0.0) - hm.hbeta * hm.hw[i] * hm.hw[p + 1];
+      }
+    double V[16];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        double v = 0;
+#pragma unroll
+        for (int p = 0; p < 3; ++p) v += Nl[i][p] * (Sg[3 * p] * Nm[j][0] + Sg[3 * p + 1] * Nm[j][1] + Sg[3 * p + 2] * Nm[j][2]);
+        V[4 * i + j] = hl.s4[i] * v * hm.s4[j];
+      }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o[tr ? 4 * j + i : 4 * i + j] = same && i > j ? V[4 * j + i] : V[4 * i + j];
   }
 }
 

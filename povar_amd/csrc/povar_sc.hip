@@ -597,6 +597,94 @@ static int observation_covariance(povar_ctx* c, int dim, double lambda, int32_t 
   return 0;
 }
 
+// Covariance blocks of parameter pairs: the landmark call's C, then one workgroup per pair in three launches (pair_cc, pair_cl,
+// pair_ll of povar_kernels_cov.hpp).  The request is checked and split into three lists before anything runs; every pair goes to
+// its kernel in the canonical order with a flag for the transposed store, its block to its place in request order.
+static int covariance_blocks(povar_ctx* c, int dim, double lambda, int32_t gauge, int32_t coords, const int32_t* pairs, int32_t n_pairs,
+                             double* blocks, int64_t n_out) {
+  const std::string who = dim == 12 ? "povar_covariance_blocks_pose" : "povar_covariance_blocks_joint";
+  if (int rc = check_ctx(c)) return rc;
+  if (n_pairs < 0) return fail(-1, who + ": negative n_pairs");
+  if (n_pairs > 0 && !pairs) return fail(-1, who + ": null argument");
+  if (coords != POVAR_COV_CAMERA_COORDS && coords != POVAR_COV_SOLVER_COORDS) return fail(-1, who + ": unknown coords");
+  const int side[2] = {coords == POVAR_COV_SOLVER_COORDS ? dim : 12, (coords == POVAR_COV_SOLVER_COORDS || dim == 12) ? 3 : 4};
+  struct List {
+    std::vector<int> items;
+    std::vector<long long> off;
+    void add(int a, int b, bool tr, long long o) {
+      items.insert(items.end(), {a, b, tr ? 1 : 0, 0});
+      off.push_back(o);
+    }
+    int size() const { return (int)off.size(); }
+  } list[3];  // camera-camera, camera-landmark, landmark-landmark
+  long long total = 0;
+  for (int p = 0; p < n_pairs; ++p) {
+    const int ka = pairs[4 * (size_t)p], a = pairs[4 * (size_t)p + 1], kb = pairs[4 * (size_t)p + 2], b = pairs[4 * (size_t)p + 3];
+    for (int s = 0; s < 2; ++s) {
+      const int kind = s ? kb : ka, id = s ? b : a;
+      if (kind != POVAR_COV_BLOCK_CAMERA && kind != POVAR_COV_BLOCK_LANDMARK) return fail(-1, who + ": unknown kind");
+      if (id < 0 || id >= (kind == POVAR_COV_BLOCK_CAMERA ? c->n_cams : c->n_lms))
+        return fail(-1, who + (kind == POVAR_COV_BLOCK_CAMERA ? ": camera id out of range" : ": landmark id out of range"));
+    }
+    if (ka == POVAR_COV_BLOCK_CAMERA && kb == POVAR_COV_BLOCK_CAMERA) list[0].add(std::max(a, b), std::min(a, b), a < b, total);
+    else if (ka == POVAR_COV_BLOCK_LANDMARK && kb == POVAR_COV_BLOCK_LANDMARK) list[2].add(std::min(a, b), std::max(a, b), a > b, total);
+    else if (ka == POVAR_COV_BLOCK_CAMERA) list[1].add(a, b, false, total);
+    else list[1].add(b, a, true, total);
+    total += (long long)side[ka] * side[kb];
+  }
+  if (n_out != total)
+    return fail(-1, who + ": n_out is " + std::to_string(n_out) + ", the request produces " + std::to_string(total));
+  CovInverse f{};
+  std::optional<TimeScope> ts;
+  int rc = cov_inverse(c, dim, who.c_str(), blocks != nullptr || total == 0, lambda, gauge, coords, f, ts);
+  if (rc == POVAR_NUMERIC_FAILURE) std::fill(blocks, blocks + total, std::nan(""));
+  if (rc == 0 && n_pairs == 0) cov_done(c, f, 1);  // nothing requested: W alone is in place (cov_lauum does not run)
+  if (rc != 0 || n_pairs == 0) return rc;
+  if (int rc2 = cov_buffer(c, c->sc_cov_pair_out, (size_t)total, dim)) return rc2;
+  if (int rc2 = cov_buffer(c, c->sc_cov_pair_items, 4 * (size_t)n_pairs, dim)) return rc2;
+  if (int rc2 = cov_buffer(c, c->sc_cov_pair_off, (size_t)n_pairs, dim)) return rc2;
+  size_t first[3], at = 0;
+  for (int k = 0; k < 3; ++k) {
+    first[k] = at;
+    if (list[k].size() == 0) continue;
+    HIP_TRY(hipMemcpyAsync(c->sc_cov_pair_items.p + 4 * at, list[k].items.data(), list[k].items.size() * sizeof(int),
+                           hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->sc_cov_pair_off.p + at, list[k].off.data(), list[k].off.size() * sizeof(long long), hipMemcpyHostToDevice,
+                           c->stream));
+    at += (size_t)list[k].size();
+  }
+  const double* M = c->sc_dense.p;
+  const double* panel = c->sc_cov_panel.p;
+  const int nb = f.N / CH_NB;
+  hipLaunchKernelGGL(cov_lauum, dim3((unsigned)(nb * (nb + 1) / 2)), dim3(256), 0, c->stream, c->sc_dense.p, f.ld, c->sc_cov_panel.p, nb);
+  with_step(dim, [&](auto step) {
+    typedef decltype(step) S;
+    auto items = [&](int k) { return reinterpret_cast<const int4*>(c->sc_cov_pair_items.p) + first[k]; };
+    auto off = [&](int k) { return (const long long*)c->sc_cov_pair_off.p + first[k]; };
+    if (list[0].size())
+      hipLaunchKernelGGL(pair_cc<S>, dim3(list[0].size()), dim3(192), 0, c->stream, items(0), off(0), M, f.ld, panel, f.q, f.nq,
+                         (const double*)c->sigma.p, (const double*)c->ncw.p, coords, c->sc_cov_pair_out.p);
+    if (list[1].size())
+      hipLaunchKernelGGL(pair_cl<S>, dim3(list[1].size()), dim3(256), 0, c->stream, c->d, (const double*)c->ncw.p,
+                         (const int*)c->sc_lm_slot0.p, (const int*)c->sc_lm_cnt.p, items(1), off(1), M, f.ld, panel, f.q, f.nq, coords,
+                         c->sc_cov_pair_out.p);
+    if (list[2].size())
+      hipLaunchKernelGGL(pair_ll<S>, dim3(list[2].size()), dim3(256), 0, c->stream, c->d, (const double*)c->ncw.p,
+                         (const int*)c->sc_lm_slot0.p, (const int*)c->sc_lm_cnt.p, items(2), off(2), M, f.ld, panel, f.q, f.nq, coords,
+                         c->sc_cov_pair_out.p);
+  });
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(blocks, c->sc_cov_pair_out.p, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));  // (also: the lists are host memory that goes out of scope)
+  for (long long i = 0; i < total; ++i)
+    if (!std::isfinite(blocks[i])) {
+      std::fill(blocks, blocks + total, std::nan(""));
+      return POVAR_NUMERIC_FAILURE;
+    }
+  cov_done(c, f, 2);
+  return 0;
+}
+
 // LinearizorSC::solve / solve_joint behind povar_solve_pose_sc and povar_solve_joint_sc_method: PCG / RIPCG or the direct solve
 // of the step's reduced camera system, the increment to the host, POVAR_NUMERIC_FAILURE when it is not finite
 // (bal_bundle_adjustment.cpp:362)
@@ -646,6 +734,16 @@ int povar_observation_covariance_pose(povar_ctx* c, double lambda, int32_t gauge
 int povar_observation_covariance_joint(povar_ctx* c, double lambda, int32_t gauge, const int32_t* lm_ids, int32_t n_ids, double* obs_cov,
                                        int64_t n_rows) {
   return observation_covariance(c, 11, lambda, gauge, lm_ids, n_ids, obs_cov, n_rows);
+}
+
+int povar_covariance_blocks_pose(povar_ctx* c, double lambda, int32_t gauge, int32_t coords, const int32_t* pairs, int32_t n_pairs,
+                                 double* blocks, int64_t n_out) {
+  return covariance_blocks(c, 12, lambda, gauge, coords, pairs, n_pairs, blocks, n_out);
+}
+
+int povar_covariance_blocks_joint(povar_ctx* c, double lambda, int32_t gauge, int32_t coords, const int32_t* pairs, int32_t n_pairs,
+                                  double* blocks, int64_t n_out) {
+  return covariance_blocks(c, 11, lambda, gauge, coords, pairs, n_pairs, blocks, n_out);
 }
 
 int povar_set_cov_inspect(povar_ctx* c, int32_t enable) {

@@ -12,7 +12,10 @@ that is singular beyond its gauge returns after the factorisation, which the lin
 At this size a dense reference is out of reach; the two size-independent checks are printed instead: bitwise symmetry of every
 block, (step 2, camera coordinates) the null-vector residual |block (h0 / sigma_c)| / (|block| |h0 / sigma_c|), and for the
 observation rows of the free gauge sum_i h_i against rank J = dim n_cams + 3 n_lms - nq.
-usage: bench_covariance.py [shape] [lambda] [reps]"""
+--pairs: instead, the covariance blocks of parameter pairs (povar_covariance_blocks_pose / _joint) beside the landmark call of the
+same run: every camera with itself and with its successor, the (camera, landmark) pair of every observation of the first
+100 000 landmarks, 100 000 seeded landmark-landmark pairs.
+usage: bench_covariance.py [--pairs] [shape] [lambda] [reps]"""
 import os
 import sys
 
@@ -23,9 +26,11 @@ from povar_amd import capi, synth  # noqa: E402
 
 
 def main():
-    shape = sys.argv[1] if len(sys.argv) > 1 else "venice-1778"
-    lam = float(sys.argv[2]) if len(sys.argv) > 2 else 1e-2
-    reps = int(sys.argv[3]) if len(sys.argv) > 3 else 3
+    argv = [a for a in sys.argv[1:] if a != "--pairs"]
+    pairs_mode = len(argv) != len(sys.argv) - 1
+    shape = argv[0] if len(argv) > 0 else "venice-1778"
+    lam = float(argv[1]) if len(argv) > 1 else 1e-2
+    reps = int(argv[2]) if len(argv) > 2 else 3
     p = synth.make_bal_problem(shape)
     ctx = capi.Context(p.n_cams, p.lm_off, p.cam_idx, p.obs / 500.0, e0_mode=capi.E0_IMPLICIT_LDSACC)
     ctx.layout_finalize()
@@ -84,6 +89,49 @@ def main():
                 line += f"; sum h = {np.sum(rows[:, 0].astype(np.longdouble)):.6f}, rank J = {rank}"
             print(line + f"; finite c_*: {bool(np.all(np.isfinite(rows[:, 1:])))}; device MiB {mib_lm} -> {ctx.device_bytes() >> 20}", flush=True)
 
+    def pair_requests():
+        """The three requests of --pairs: every camera with itself and with its successor; the (camera, landmark) pair of every
+        observation of the first 100 000 landmarks; 100 000 seeded landmark-landmark pairs."""
+        cam = np.arange(p.n_cams)
+        cc = np.zeros((2 * p.n_cams, 4), dtype=np.int32)
+        cc[:, 1] = np.repeat(cam, 2)
+        cc[0::2, 3], cc[1::2, 3] = cam, (cam + 1) % p.n_cams
+        n_l = min(100000, p.n_lms)
+        n_o = int(p.lm_off[n_l])
+        cl = np.zeros((n_o, 4), dtype=np.int32)
+        cl[:, 1], cl[:, 2], cl[:, 3] = p.cam_idx[:n_o], capi.COV_BLOCK_LANDMARK, np.repeat(np.arange(n_l), np.diff(p.lm_off[:n_l + 1]))
+        ll = np.full((100000, 4), capi.COV_BLOCK_LANDMARK, dtype=np.int32)
+        ll[:, 1::2] = np.random.default_rng(17).integers(0, p.n_lms, size=(100000, 2))
+        return (("camera-camera", cc), ("camera-landmark", cl), ("landmark-landmark", ll))
+
+    def report_pairs(step, dim, solver, solve):
+        """--pairs: the three requests beside the landmark call of the same run (it shares the factorisation, the inversion and
+        cov_lauum with them: the difference is the pair kernels and the copy of the blocks)."""
+        for name, gauge, lm in (("free gauge", capi.COV_FREE_GAUGE, 0.0), ("damped", capi.COV_DAMPED, lam)):
+            (blocks, rc), ms_lm = timed(lambda: ctx.landmark_covariance(step=step, lam=lm, gauge=gauge, coords=capi.COV_LANDMARK_COORDS))
+            line = f"step {step} landmark covariance, all {p.n_lms} landmarks, {name} (lambda {lm:g}): {ms_lm:.1f} ms per call"
+            if rc != 0:
+                print(line + f" -- rc {rc}: singular beyond the gauge, the call ended after the factorisation", flush=True)
+                continue
+            print(line, flush=True)
+            for kind, pairs in pair_requests():
+                fn = ctx.L.povar_covariance_blocks_pose if step == 1 else ctx.L.povar_covariance_blocks_joint
+                side = np.array([12, 3 if step == 1 else 4])
+                n_out = int((side[pairs[:, 0]] * side[pairs[:, 2]]).sum())
+                out = np.zeros(n_out)
+
+                def call():  # (the raw call: capi.Context.covariance_blocks would cut a list of 10^5 arrays on the host)
+                    return out, fn(ctx.h, capi.C.c_double(lm), capi.C.c_int32(gauge), capi.C.c_int32(capi.COV_CAMERA_COORDS),
+                                   capi.C.c_void_p(pairs.ctypes.data), capi.C.c_int32(pairs.shape[0]), capi.C.c_void_p(out.ctypes.data),
+                                   capi.C.c_int64(n_out))
+
+                (_, rc), ms = timed(call)
+                assert rc == 0 and np.all(np.isfinite(out))
+                print(f"step {step} covariance blocks, {pairs.shape[0]} {kind} pairs ({n_out} numbers), {name}: {ms:.1f} ms per call, ratio to "
+                      f"the landmark call {ms / ms_lm:.2f}, difference {ms - ms_lm:+.1f} ms; device MiB {ctx.device_bytes() >> 20}", flush=True)
+
+    if pairs_mode:
+        report = report_pairs
     # step 1 in the units of the normalised observations (the first two rows of every P divided by 500)
     cams1 = p.cams.copy()
     cams1[:, :8] /= 500.0
