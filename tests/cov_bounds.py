@@ -1,9 +1,11 @@
 """Componentwise, condition-free bounds for the covariance path (povar_sc.hip: cov_inverse, cov_camera_blocks,
 landmark_covariance, observation_covariance; povar_kernels_cov.hpp), stage by stage on the device's own intermediates (helper module of
-tests/test_cov_bounds.py and tests/test_gpu_cov_bounds.py; not a test module).  Conventions of sc_bounds.py: LD, g(k) rounded
+tests/test_cov_bounds.py and tests/test_gpu_cov_bounds.py; not a test module).  The last stage of the path, the covariance
+blocks of parameter pairs (covariance_blocks: pair_cc, pair_cl, pair_ll), is held in the same way on the same C and Q by
+tests/pair_bounds.py (tests/test_pair_bounds.py, tests/test_gpu_pair_bounds.py).  Conventions of sc_bounds.py: LD, g(k) rounded
 up, first order, a final factor 1 + 1e-6, `worst` / `flagged` for reporting.  The device's buffers: R = POVAR_BUF_COV_FACTOR
 (upper triangle), W = the upper triangle of POVAR_BUF_COV_INVERSE, C = its strictly lower 64 x 64 blocks and POVAR_BUF_COV_PANEL
-read as cov_at does (povar_kernels_cov.hpp:332-336), Q = POVAR_BUF_COV_GAUGE.  Products of device matrices are formed
+read as cov_at does (povar_kernels_cov.hpp:280-284), Q = POVAR_BUF_COV_GAUGE.  Products of device matrices are formed
 without rounding (sc_bounds.exact_gram for W W^T and R^T R, exact_matmul below for W R and Q^T Q: the same slicing); what the
 slicing leaves out is added to every bound.  An MFMA accumulation counts as "K products in any order": g(K).  Line numbers
 are those of povar_kernels_cov.hpp unless a file is named.
@@ -164,7 +166,7 @@ def c_lower(inv, panel):
 
 
 def cov_at(inv, panel, r, c):
-    """Entry (r, c) of C as the device's cov_at reads it (:332-336); r, c: integer arrays."""
+    """Entry (r, c) of C as the device's cov_at reads it (:280-284); r, c: integer arrays."""
     r, c = np.maximum(r, c), np.minimum(r, c)
     same = (r >> 6) == (c >> 6)
     return np.where(same, np.asarray(panel)[r, c & 63], np.asarray(inv)[r, c])

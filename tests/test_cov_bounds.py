@@ -5,7 +5,9 @@
   irrational stages (Gram-Schmidt, Cholesky, inverse, C, the blocks) run in 60-digit arithmetic, each from the once-rounded
   output of the one before.  All seven checks (assembly with Q Q^T, gauge, span, inverse, camera, lauum, landmark) and both
   coordinate maps admit the once-rounded results: worst err / bound assembly 0.0058, gauge 0.0089, span 1.1e-5, inverse
-  0.90, camera 0.081, lauum 0.015, landmark 3.1e-4 (own coordinates: camera 0.018, landmark 5.2e-4).  Step 1 only: step 2's
+  0.90, camera 0.081, lauum 0.015, landmark 3.1e-4 (own coordinates: camera 0.018, landmark 5.2e-4).  The same chain carries
+  all 36 camera pairs and twenty-odd pairs of each other kind through tests/pair_bounds.py (pair_check, both coordinate
+  systems): pair_cc 0.81, pair_cl 0.0012, pair_ll 1.9e-5 (own coordinates 0.024, 7.0e-4, 1.9e-5).  Step 1 only: step 2's
   reflectors and 1 / z put irrational numbers into the operands themselves; its formulas are held by the emulations below.
 * Both emulated summation orders of the whole chain (assembly, Q Q^T, factor, inverse, camera blocks, C, landmark blocks) lie
   inside every bound on every shape of tests/test_gpu_cov_bounds.py, in both coordinate systems: the bounds are satisfiable
@@ -125,6 +127,7 @@ def test_exact_arithmetic_on_a_tiny_system_stays_inside_every_bound():
     cam0 = np.stack([fl(mp.diag([mpf(t) for t in sig[c]]) * Tc[12 * c:12 * c + 12, 12 * c:12 * c + 12] * mp.diag([mpf(t) for t in sig[c]]))
                      for c in range(p.n_cams)])
     lm, lm0 = np.zeros((p.n_lms, 3, 3)), np.zeros((p.n_lms, 3, 3))
+    mp_ops = []  # per landmark, 60 digits: (cameras, W_i, T_l, Hll^-1) for the pair blocks below
     for l, (cams, Wl, His) in enumerate(lm_ops):
         Wl = [mp.matrix([[mpf(x) for x in row] for row in Wi]) for Wi in Wl]
         Sg = mp.matrix([[mpf(x) for x in row] for row in His])
@@ -134,6 +137,7 @@ def test_exact_arithmetic_on_a_tiny_system_stays_inside_every_bound():
             for j, cj in enumerate(cams):
                 Sg += Wl[i].T * Cr[12 * ci:12 * ci + 12, 12 * cj:12 * cj + 12] * Wl[j]
         Sg -= Tl.T * Tl
+        mp_ops.append((cams, Wl, Tl, mp.matrix([[mpf(x) for x in row] for row in His])))
         D = mp.diag([mpf(t) for t in s[l]])
         lm[l], lm0[l] = fl(Sg), fl(D * Sg * D)
     sym = lambda B: np.triu(B) + np.triu(B, 1).transpose(0, 2, 1)  # (the device mirrors the upper triangle; so does the rounding)
@@ -143,6 +147,49 @@ def test_exact_arithmetic_on_a_tiny_system_stays_inside_every_bound():
     assert set(out) == {"assembly", "inverse", "camera", "lauum", "landmark", "gauge", "span"}
     out0, bad0 = CB.check_all(sy, dict(d, cam=sym(cam0), lm=sym(lm0)), coords=0)
     _report("exact small step 1 free gauge, own coordinates", {k: out0[k] for k in ("camera", "landmark")}, bad0)
+    # The blocks of parameter pairs (tests/pair_bounds.py) from the same once-rounded C and Q: all 36 camera pairs, twenty-odd
+    # pairs of each other kind (both orders, own pairs, camera 5 across the 64-edge), an independent check of the formulas of
+    # pair_reference and of its map to parameter coordinates, as the lines above are of landmark_reference.
+    import pair_bounds as PB
+    CAM, LM = PB.CAMERA, PB.LANDMARK
+    rng = np.random.default_rng(9)
+    cl = [(CAM, int(c), LM, int(l)) for c, l in zip(rng.integers(0, p.n_cams, 14), rng.integers(0, p.n_lms, 14))] + [(CAM, 5, LM, 0), (CAM, 0, LM, 39)]
+    ll = [(LM, int(a), LM, int(b)) for a, b in rng.integers(0, p.n_lms, (14, 2))] + [(LM, l, LM, l) for l in (0, 7, 39)]
+    pairs = ([(CAM, a, CAM, b) for a in range(p.n_cams) for b in range(p.n_cams)] + cl + [(kb, b, ka, a) for ka, a, kb, b in cl[:6]] +
+             ll + [(kb, b, ka, a) for ka, a, kb, b in ll[:4]])
+    crow = lambda c: slice(12 * c, 12 * c + 12)
+    dmat = {CAM: lambda c: mp.diag([mpf(t) for t in sig[c]]), LM: lambda l: mp.diag([mpf(t) for t in s[l]])}
+
+    def canonical(ka, a, kb, b):
+        if ka == CAM and kb == CAM:
+            return Cr[crow(a), crow(b)] - Qm[crow(a), :] * Qm[crow(b), :].T
+        if ka == CAM:
+            cams, Wl, Tl, _ = mp_ops[b]
+            X = Qm[crow(a), :] * Tl
+            for j, cj in enumerate(cams):
+                X -= Cr[crow(a), crow(cj)] * Wl[j]
+            return X
+        (ca, Wa, Ta, Ha), (cb, Wb, Tb, _) = mp_ops[a], mp_ops[b]
+        X = (Ha if a == b else mp.zeros(3, 3)) - Ta.T * Tb
+        for i, ci in enumerate(ca):
+            for j, cj in enumerate(cb):
+                X += Wa[i].T * Cr[crow(ci), crow(cj)] * Wb[j]
+        return X
+
+    blocks = {1: [], 0: []}
+    for ka, a, kb, b in pairs:
+        flip = ka == LM and kb == CAM
+        X = canonical(kb, b, ka, a) if flip else canonical(ka, a, kb, b)
+        X0 = (dmat[kb](b) if flip else dmat[ka](a)) * X * (dmat[ka](a) if flip else dmat[kb](b))
+        for coords, Y in ((1, X), (0, X0)):
+            Y = fl(Y)
+            Y = np.triu(Y) + np.triu(Y, 1).T if (ka == kb and a == b) else Y  # (the device mirrors the upper triangle)
+            blocks[coords].append(Y.T if flip else Y)
+    Cs = CB.c_symmetric(inv, panel)
+    for coords in (1, 0):
+        res = PB.pair_check(sy, Cs, Q, pairs, blocks[coords], coords)
+        _report(f"exact small step 1 free gauge, pairs, coords {coords}", {k: res[k] for k in PB.CHECKS}, res["exact"])
+        assert all(np.any(res[k][1] > 0) for k in PB.CHECKS)
 
 
 @pytest.mark.parametrize("name,step,robust,lam", CB.CASES, ids=[f"{n}-{s}-{r}-{lam:g}" for n, s, r, lam in CB.CASES])

@@ -5,7 +5,8 @@ Tolerance, both modes, per block: |got - want|_F <= m u cond_2(K) |K^-1|_2 f_a f
 (landmark_covariance_reference.Reference.bound: K the full matrix that is actually inverted, m its dimension, u = 2^-53) with
 f = 1 in solver coordinates and f_cam = max sigma, f_lm = max s in parameter coordinates.  tests/test_pair_covariance_reference.py
 holds every case here to bound <= 1e-4 of its smallest diagonal block.  Every case prints its worst error in units of the bound;
-the bound is not tightened to it.
+the bound is not tightened to it.  This is the end-to-end route through the full matrix K; the entrywise, condition-free bound of
+every block on the device's own C and Q is tests/pair_bounds.py (tests/test_pair_bounds.py, tests/test_gpu_pair_bounds.py).
 """
 import ctypes as C
 import os
