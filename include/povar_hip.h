@@ -365,6 +365,37 @@ int povar_observation_covariance_joint(povar_ctx* ctx, double lambda, int32_t ga
                                        const int32_t* lm_ids /* NULL = all landmarks of the context */, int32_t n_ids,
                                        double* obs_cov /* 4 n_rows */, int64_t n_rows);
 
+/* ---- per-observation residuals and hat blocks: what an outlier test (data snooping) of single observations needs.  For every
+ * observation of the requested landmarks the weighted residual r_i (d numbers: the r the step minimises, sqrt(w_i) included)
+ * and the whole d x d block P_ii = J_i H^+ J_i^T of the hat matrix whose trace is the h of the calls above.  One row each:
+ *       pose  (d = 4), stride 14:  r0 r1 r2 r3,  P00 P01 P02 P03 P11 P12 P13 P22 P23 P33
+ *       joint (d = 2), stride  5:  r0 r1,        P00 P01 P11
+ * (the upper triangle by rows; the block is symmetric).  The rows come in the order of the calls above.  Like h, the blocks do
+ * not depend on the gauge, on the Jacobi scaling or on povar_set_jl_col_scaling.
+ * The deletion statistic of observation i is a d x d computation on its row:
+ *       t_i = r_i^T (I_d - P_ii)^+ r_i.
+ * Where J^T r = 0 (a stationary point: a converged state) t_i is exactly the decrease of the linearised cost |r + J delta|^2 when
+ * observation i is removed and all cameras and landmarks are re-estimated; elsewhere it is that decrease only up to the
+ * gradient's part.  The rank of I_d - P_ii is the local redundancy of the observation: every observation of a two-view track has
+ * exactly one null direction (its eigenvalue is rounding noise, the others are of the order 1e-3 and above on ordinary
+ * problems), r_i has no component along it, and the pseudo-inverse leaves it out.  The library returns r and P; the rank
+ * decision is a tolerance on a d x d matrix and is the caller's (capi.deletion_statistics, bal --observation-diagnostics-path).
+ * POVAR_COV_DAMPED: P = J H(lambda)^-1 J^T and the statistic belongs to the damped problem.  Where the damping reaches every
+ * parameter (step 2: cameras and landmarks) I - P_ii is nonsingular; step 1 damps the cameras only (lambda_l = 0), and there
+ * the null direction of a two-view observation, which lives in its undamped landmark, stays null.
+ * From the same walk as the calls above (one body, another row).  Arguments, the gauge / lambda rules, lm_ids and n_rows,
+ * preconditions, side effects, the sharded rule, the memory errors and the NaN rule on POVAR_NUMERIC_FAILURE are exactly those of
+ * povar_observation_covariance_*.  The status judges the factorisation only: y2 == 0 in step 2 leaves the row non-finite by
+ * IEEE rules with status 0. ---- */
+/* after povar_linearize_pose */
+int povar_observation_hat_pose(povar_ctx* ctx, double lambda, int32_t gauge,
+                               const int32_t* lm_ids /* NULL = all landmarks of the context */, int32_t n_ids,
+                               double* rows /* 14 n_rows */, int64_t n_rows);
+/* after povar_linearize_homogeneous */
+int povar_observation_hat_joint(povar_ctx* ctx, double lambda, int32_t gauge,
+                                const int32_t* lm_ids /* NULL = all landmarks of the context */, int32_t n_ids,
+                                double* rows /* 5 n_rows */, int64_t n_rows);
+
 /* ---- covariance blocks of parameter pairs: the cross-covariances the calls above do not return (ceres::Covariance takes a
  * list of parameter-block pairs for the same reason): what the uncertainty of a relative pose, a baseline, the distance of two
  * points or a point in another camera's frame is made of.  In the setting of the landmark calls, with W_i = E_i Hll_l^-1

@@ -130,6 +130,39 @@ def _p(a):
     return C.c_void_p(a.ctypes.data)
 
 
+def unpack_hat_rows(rows, d):
+    """Rows of povar_observation_hat_* ([n, d + d (d + 1) / 2]: r, then the upper triangle of P by rows) as
+    (r [n, d], P [n, d, d] full symmetric)."""
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, d + d * (d + 1) // 2)
+    iu = np.triu_indices(d)
+    P = np.zeros((rows.shape[0], d, d))
+    P[:, iu[0], iu[1]] = rows[:, d:]
+    P[:, iu[1], iu[0]] = rows[:, d:]
+    return rows[:, :d].copy(), P
+
+
+def deletion_statistics(r, P, tol=1e-8):
+    """Per-observation deletion statistic from the weighted residuals r [n, d] and the hat blocks P [n, d, d]
+    (Context.observation_hat): (t [n], rank [n]) with
+
+        t_i = r_i^T (I - P_ii)^+ r_i = sum_k (v_k^T r_i)^2 / mu_k over the eigenpairs (mu_k, v_k) of I - P_ii with mu_k > tol,
+
+    and rank_i the number of eigenvalues kept: the local redundancy of the observation.  Where J^T r = 0 (a converged state)
+    t_i is exactly the decrease of the linearised cost |r + J delta|^2 when observation i is deleted and everything is
+    re-estimated.  An observation of a two-view track has one null direction in I - P_ii, which is why this is a
+    pseudo-inverse.  NumPy only."""
+    r = np.asarray(r, dtype=np.float64)
+    P = np.asarray(P, dtype=np.float64)
+    n, d = r.shape
+    if n == 0:
+        return np.zeros(0), np.zeros(0, dtype=np.int64)
+    mu, V = np.linalg.eigh(np.eye(d)[None] - 0.5 * (P + np.swapaxes(P, 1, 2)))
+    keep = mu > tol
+    proj = np.einsum("nkd,nk->nd", V, r)  # v_k^T r_i: the eigenvectors are the columns of V
+    t = np.where(keep, proj * proj / np.where(keep, mu, 1.0), 0.0).sum(1)
+    return t, keep.sum(1).astype(np.int64)
+
+
 def shard_range(lm_off, world, rank):
     lm_off = np.ascontiguousarray(lm_off, dtype=np.int32)
     b, e = C.c_int32(), C.c_int32()
@@ -363,6 +396,30 @@ class Context:
         rc = self._chk(fn(self.h, C.c_double(lam), C.c_int32(gauge), ids_p, C.c_int32(n_ids), _p(out) if n_rows else None,
                           C.c_int64(n_rows)), allow_numeric=True)
         return out, rc
+
+    def observation_hat(self, step=1, lam=0.0, gauge=COV_FREE_GAUGE, lm_ids=None):
+        """Weighted residual and block of the hat matrix J H^+ J^T of every observation of the context (or of the landmarks
+        `lm_ids`, as observation_covariance takes them) at the step linearised last: (r [n, d], P [n, d, d], rc) with d = 4 in
+        step 1 and d = 2 in step 2, in the caller's CSR order.  P is the full symmetric block, mirrored from the upper triangle
+        the library returns.  Gauge- and scaling-invariant: no coords.  rc = NUMERIC_FAILURE comes with all NaN.
+        deletion_statistics(r, P) turns the two into the per-observation outlier statistic."""
+        if step not in (1, 2):
+            raise ValueError("observation_hat: step is 1 or 2")
+        if lm_ids is None:
+            n_ids, ids_p, n_rows = 0, None, self.n_obs
+        else:
+            lm_ids = np.ascontiguousarray(lm_ids, dtype=np.int32).reshape(-1)
+            if np.any(lm_ids < 0) or np.any(lm_ids >= self.n_lms):
+                raise PovarError("observation_hat: landmark id out of range")
+            n_ids, ids_p = lm_ids.shape[0], _p(lm_ids)
+            n_rows = int(np.diff(self.lm_off)[lm_ids].sum())
+        d = 4 if step == 1 else 2
+        out = np.zeros((n_rows, d + d * (d + 1) // 2))
+        fn = self.L.povar_observation_hat_pose if step == 1 else self.L.povar_observation_hat_joint
+        rc = self._chk(fn(self.h, C.c_double(lam), C.c_int32(gauge), ids_p, C.c_int32(n_ids), _p(out) if n_rows else None,
+                          C.c_int64(n_rows)), allow_numeric=True)
+        r, P = unpack_hat_rows(out, d)
+        return r, P, rc
 
     def covariance_blocks(self, pairs, step=1, lam=0.0, gauge=COV_FREE_GAUGE, coords=COV_CAMERA_COORDS):
         """Covariance blocks of parameter pairs at the step linearised last: (list of 2-D arrays in request order, rc).  `pairs`

@@ -189,6 +189,88 @@ void write_observation_covariance(Linearizor& linearizor, const BalProblem& bal_
   std::fclose(f);
 }
 
+// Eigen-decomposition of the symmetric d x d matrix a (d <= 4) by cyclic Jacobi sweeps: a ends diagonal (the eigenvalues), the
+// columns of v are the eigenvectors.  An off-diagonal entry that no longer changes either of its diagonal entries is set to zero,
+// so the sweeps end with an exactly diagonal matrix (a handful of them: the convergence is quadratic).
+void jacobi_eigen(int d, double (&a)[4][4], double (&v)[4][4]) {
+  for (int i = 0; i < d; ++i)
+    for (int j = 0; j < d; ++j) v[i][j] = i == j ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < 64; ++sweep) {
+    bool diagonal = true;
+    for (int p = 0; p < d; ++p)
+      for (int q = p + 1; q < d; ++q) {
+        const double apq = a[p][q];
+        if (apq == 0.0) continue;
+        if (std::fabs(a[p][p]) + std::fabs(apq) == std::fabs(a[p][p]) && std::fabs(a[q][q]) + std::fabs(apq) == std::fabs(a[q][q])) {
+          a[p][q] = a[q][p] = 0.0;
+          continue;
+        }
+        diagonal = false;
+        const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
+        const double t = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+        const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+        for (int k = 0; k < d; ++k) {  // A <- A G
+          const double akp = a[k][p], akq = a[k][q];
+          a[k][p] = c * akp - s * akq;
+          a[k][q] = s * akp + c * akq;
+        }
+        for (int k = 0; k < d; ++k) {  // A <- G^T A
+          const double apk = a[p][k], aqk = a[q][k];
+          a[p][k] = c * apk - s * aqk;
+          a[q][k] = s * apk + c * aqk;
+        }
+        a[p][q] = a[q][p] = 0.0;
+        for (int k = 0; k < d; ++k) {
+          const double vkp = v[k][p], vkq = v[k][q];
+          v[k][p] = c * vkp - s * vkq;
+          v[k][q] = s * vkp + c * vkq;
+        }
+      }
+    if (diagonal) break;
+  }
+}
+
+// --observation-diagnostics-path: n_obs on the first line, then one line per observation in file order: landmark camera t rank
+// and the raw row of povar_observation_hat_pose / _joint (r, then the upper triangle of P_ii by rows); a call of its own.
+// t = r^T (I - P_ii)^+ r = sum over the eigenpairs (mu, v) of I - P_ii with mu > tol of (v^T r)^2 / mu, rank their number.
+void write_observation_diagnostics(Linearizor& linearizor, const BalProblem& bal_problem, const SolverOptions& so, bool step2) {
+  Linearizor::VecX rows;
+  const int rc = linearizor.observation_hat(step2, so.alpha, rows);
+  if (rc < 0) {
+    std::fprintf(stderr, "FATAL: this linearizor does not serve --observation-diagnostics-path\n");
+    std::abort();
+  }
+  if (rc != 0) std::printf("\t[WARN] observation diagnostics: the reduced system is singular beyond its gauge, the rows are NaN\n");
+  const int d = step2 ? 2 : 4, stride = d + d * (d + 1) / 2;
+  std::FILE* f = open_for_writing(so.observation_diagnostics_path);
+  std::vector<int> lm_off, cam_idx;
+  std::vector<double> obs;
+  bal_problem.flatten(lm_off, cam_idx, obs);
+  std::fprintf(f, "%zu\n", cam_idx.size());
+  for (int l = 0; l < bal_problem.num_landmarks(); ++l)
+    for (int i = lm_off[l]; i < lm_off[l + 1]; ++i) {
+      const double* row = rows.data() + (size_t)stride * i;
+      double m[4][4], v[4][4];
+      for (int p = 0, e = d; p < d; ++p)
+        for (int q = p; q < d; ++q, ++e) m[p][q] = m[q][p] = (p == q ? 1.0 : 0.0) - row[e];
+      jacobi_eigen(d, m, v);
+      double t = 0;
+      int rank = 0;
+      for (int k = 0; k < d; ++k) {
+        if (!(m[k][k] > so.observation_diagnostics_tol)) continue;
+        double vr = 0;
+        for (int p = 0; p < d; ++p) vr += v[p][k] * row[p];
+        t += vr * vr / m[k][k];
+        ++rank;
+      }
+      if (rc != 0) t = row[0];  // (NaN rows: NaN statistic)
+      std::fprintf(f, "%d %d %.17g %d", l, cam_idx[i], t, rank);
+      for (int e = 0; e < stride; ++e) std::fprintf(f, " %.17g", row[e]);
+      std::fprintf(f, "\n");
+    }
+  std::fclose(f);
+}
+
 // --covariance-pairs-path IN --covariance-blocks-path OUT: IN holds the number of pairs, then `c|l id c|l id` per pair; OUT gets
 // the number of pairs, then per pair one line: rows cols and the block row-major (povar_covariance_blocks_pose / _joint, free
 // gauge, parameter coordinates: a camera 12, a landmark 3 after step 1 and 4 after step 2); a call of its own
@@ -416,6 +498,8 @@ void optimize_lm(BalProblem& bal_problem, const SolverOptions& so, SolverSummary
     write_covariances(*linearizor, bal_problem, so, step2);
   if (!so.observation_covariance_path.empty() && step2 == (so.max_num_iterations_step_2 > 0))
     write_observation_covariance(*linearizor, bal_problem, so, step2);
+  if (!so.observation_diagnostics_path.empty() && step2 == (so.max_num_iterations_step_2 > 0))
+    write_observation_diagnostics(*linearizor, bal_problem, so, step2);
   if (!so.covariance_pairs_path.empty() && step2 == (so.max_num_iterations_step_2 > 0))
     write_covariance_blocks(*linearizor, bal_problem, so, step2);
   std::printf("Final Cost: %s\n", error_summary_oneline(summary.final_cost, so.use_projection_validity_check()).c_str());

@@ -95,6 +95,8 @@ bool parse_bal_app_arguments(int argc, char** argv, BalAppOptions& o) {
   str("camera-covariance-path", &o.solver.camera_covariance_path);
   str("landmark-covariance-path", &o.solver.landmark_covariance_path);
   str("observation-covariance-path", &o.solver.observation_covariance_path);
+  str("observation-diagnostics-path", &o.solver.observation_diagnostics_path);
+  dbl("observation-diagnostics-tol", &o.solver.observation_diagnostics_tol);
   str("covariance-pairs-path", &o.solver.covariance_pairs_path);
   str("covariance-blocks-path", &o.solver.covariance_blocks_path);
 
@@ -119,6 +121,12 @@ bool parse_bal_app_arguments(int argc, char** argv, BalAppOptions& o) {
                   "      likewise for every observation, independent of the gauge: n_obs, then one line per observation in file order:\n"
                   "      landmark camera h c_uu c_uv c_vv -- the leverage h (redundancy number: 4 - h after step 1, 2 - h after step 2)\n"
                   "      and the 2 x 2 covariance of the predicted image point\n"
+                  "  --observation-diagnostics-path FILE [--observation-diagnostics-tol 1e-8]\n"
+                  "      likewise the outlier diagnostics of every observation: n_obs, then one line per observation in file order:\n"
+                  "      landmark camera t rank, then the d weighted residuals r and the upper triangle of the d x d hat block P (d = 4\n"
+                  "      after step 1, 2 after step 2).  t = r^T (I - P)^+ r is the decrease of the linearised cost when the observation\n"
+                  "      is deleted and everything re-estimated (exact at a converged state), rank the number of eigenvalues of I - P\n"
+                  "      above the tolerance: the local redundancy (an observation of a two-view track has one null direction)\n"
                   "  --covariance-pairs-path IN --covariance-blocks-path OUT\n"
                   "      likewise the covariance block of every pair of parameter blocks listed in IN (the number of pairs, then one\n"
                   "      line `c|l id c|l id` per pair: c a camera, l a landmark), gauge fixed on the cameras: OUT gets the number of\n"

@@ -134,6 +134,12 @@ class Linearizor {
     (void)step2; (void)alpha; (void)obs_cov;
     return -1;
   }
+  // Likewise the residuals and hat blocks of the observations (povar_observation_hat_pose / _joint, free gauge): rows gets 14
+  // (step 1) or 5 (step 2) numbers per observation in file order: r, then the upper triangle of P_ii.  Sharded as above.
+  virtual int observation_hat(bool step2, double alpha, VecX& rows) {
+    (void)step2; (void)alpha; (void)rows;
+    return -1;
+  }
   // Likewise for pairs of parameter blocks (povar_covariance_blocks_pose / _joint, free gauge, parameter coordinates): `pairs`
   // holds (kind_a, id_a, kind_b, id_b) per pair as the library takes them, ids in file order; `blocks` has the size the request
   // produces and gets the blocks one after the other.  Only the HIP linearizor on a single device serves it.

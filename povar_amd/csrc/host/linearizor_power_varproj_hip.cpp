@@ -167,6 +167,16 @@ class LinearizorPowerVarprojHip : public Linearizor, public StateMirror {
                    : povar_observation_covariance_pose(s.ctx, 0.0, POVAR_COV_FREE_GAUGE, nullptr, 0, out, s.on);
     });
   }
+  int observation_hat(bool step2, double alpha, VecX& rows) override {
+    const size_t stride = step2 ? 5 : 14;
+    rows.assign(stride * (size_t)bal_problem_.num_observations(), 0.0);
+    linearize_all(step2, alpha, "povar_linearize (observation diagnostics)");
+    return covariance_status("povar_observation_hat", [&](Shard& s) {
+      double* out = rows.data() + stride * (size_t)s.ob;
+      return step2 ? povar_observation_hat_joint(s.ctx, 0.0, POVAR_COV_FREE_GAUGE, nullptr, 0, out, s.on)
+                   : povar_observation_hat_pose(s.ctx, 0.0, POVAR_COV_FREE_GAUGE, nullptr, 0, out, s.on);
+    });
+  }
   int covariance_blocks(bool step2, double alpha, const std::vector<int32_t>& pairs, VecX& blocks) override {
     if (sharded_) return -1;  // (landmark ids are the shard's own)
     linearize_all(step2, alpha, "povar_linearize (covariance blocks)");

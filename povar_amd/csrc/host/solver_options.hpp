@@ -75,6 +75,14 @@ struct SolverOptions {
   // n_obs on the first line, then one line per observation in file order: landmark camera h c_uu c_uv c_vv (%.17g).  A call
   // of its own, independent of the two paths above; served with --gpus N too: every shard writes its own observations.
   std::string observation_covariance_path;
+  // residual, hat block and deletion statistic of every observation (povar_observation_hat_pose / _joint, free gauge): n_obs on
+  // the first line, then one line per observation in file order: landmark camera t rank, then the raw row of the call (the d
+  // weighted residuals and the upper triangle of the d x d block P_ii by rows, %.17g; d = 4 after step 1, 2 after step 2).
+  // t = r^T (I - P_ii)^+ r and rank = rank(I - P_ii) come from the host's own eigen-decomposition of I - P_ii, eigenvalues above
+  // observation_diagnostics_tol kept.  A call of its own, independent of the paths above; served with --gpus N as the
+  // observation path is.
+  std::string observation_diagnostics_path;
+  double observation_diagnostics_tol = 1e-8;
   // covariance blocks of parameter pairs (povar_covariance_blocks_pose / _joint, free gauge, parameter coordinates).
   // covariance_pairs_path is read: the number of pairs, then one line `c|l id c|l id` per pair (c: a camera, l: a landmark, ids
   // in file order).  covariance_blocks_path is written: the number of pairs, then one line per pair: rows cols and the rows x cols

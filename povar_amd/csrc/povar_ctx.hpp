@@ -262,8 +262,8 @@ struct povar_ctx : CtxSwitches {  // (create_plan.hpp: the switches povar_create
   DevBuf<double> sc_cov_q, sc_cov_stat, sc_cov_panel, sc_cov_blocks;
   DevBuf<double> sc_cov_lm;              // povar_landmark_covariance_*: the requested landmark blocks and their ids, kept likewise
   DevBuf<int> sc_cov_ids;
-  DevBuf<double> sc_cov_obs;             // povar_observation_covariance_*: the rows (4 per observation) and the first row of
-  DevBuf<int> sc_cov_row0;               // every requested landmark, kept likewise (Sigma_l without the gauge part goes to sc_cov_lm)
+  DevBuf<double> sc_cov_obs;             // povar_observation_covariance_* / _hat_*: the rows (4, or 14 / 5 per observation) and the first
+  DevBuf<int> sc_cov_row0;               // row of every requested landmark, kept likewise (Sigma_l without the gauge part goes to sc_cov_lm)
   DevBuf<double> sc_cov_pair_out;        // povar_covariance_blocks_*: the blocks in request order, the three index lists (a, b,
   DevBuf<int> sc_cov_pair_items;         // transposed, -) one after the other and where every block starts, kept likewise
   DevBuf<long long> sc_cov_pair_off;

@@ -17,6 +17,7 @@
 //   lm_cov         Sigma_l = Hll^-1 + sum_ij G_i^T K_ij G_j - T_l^T T_l, then the map to landmark coordinates   workgroup per landmark
 // Observation leverage and predicted-point covariance (povar_observation_covariance_pose / _joint) go on from Sigma_l:
 //   obs_cov        (h_i, c_uu, c_uv, c_vv) of every observation of a landmark from K_ii, R_i = sum_j K_ij G_j and Sigma_l   workgroup per landmark
+//   obs_hat        the same walk with another row: the weighted residual r_i and the block P_ii of the hat matrix (povar_observation_hat_*)
 // Covariance blocks of parameter pairs (povar_covariance_blocks_pose / _joint) go on from C as well:
 //   pair_cc, pair_cl, pair_ll   the block of a camera-camera, camera-landmark, landmark-landmark pair              workgroup per pair
 #pragma once
@@ -465,10 +466,67 @@ __global__ __launch_bounds__(256) void lm_cov(Dp d, const double* ncw, const int
 // no atomics, a fixed order, the row reproducible given C.  Lane 0 of the group then forms the row at
 // out + 4 (row0[blockIdx.x] + i): the rows of a landmark in the order of its observations.  y2 = 0 leaves c_* non-finite
 // by IEEE rules (step 1: h_i does not depend on J).
+//
+// The same Syy_i gives the whole block of the hat matrix (povar_observation_hat_pose / _joint): with A_i (Step::jac_a) the
+// RES x 3 weighted Jacobian of the residual with respect to y (A_i^T A_i = M_i) and r_i the weighted residual,
+//   P_ii = A_i Syy_i A_i^T   (RES x RES: h_i is its trace),
+// so the walk is one body, obs_rows, and the row is a policy: ObsCovRow (the row above, stride 4) or ObsHatRow
+// (r_i, then the upper triangle of P_ii by rows: stride 14 in step 1, 5 in step 2).  A policy is built from the linearisation
+// point as the staging reads it (the camera, the landmark head, uv, the stored sqrt(w)) and writes the row from y and the mirrored
+// Syy_i.
 template <class Step>
-__global__ __launch_bounds__(256) void obs_cov(Dp d, const double* ncw, const int* lm_slot0, const int* lm_cnt, const int* ids,
-                                               const int* row0, const double* M, int64_t ld, const double* panel,
-                                               const double* sig, double* out) {
+struct ObsCovRow {
+  static constexpr int STRIDE = 4;
+  double Mi[9];
+  __device__ __forceinline__ ObsCovRow(const Dp& d, const Cam& P, const typename Step::Head& hd, double2 uv, double sw) {
+    const double w = sw * sw;
+    Step::gram_m(d, P, hd, uv, w, Mi);
+  }
+  __device__ __forceinline__ void write(const double (&yv)[3], const double (&Syy)[9], double* o) const {
+    double lev = 0;
+#pragma unroll
+    for (int e = 0; e < 9; ++e) lev += Mi[e] * Syy[e];  // (both symmetric)
+    const double iz = 1.0 / yv[2];
+    const double j0 = -yv[0] * iz * iz, j1 = -yv[1] * iz * iz;  // J = [[iz, 0, j0], [0, iz, j1]]
+    const double a0[3] = {iz * Syy[0] + j0 * Syy[6], iz * Syy[1] + j0 * Syy[7], iz * Syy[2] + j0 * Syy[8]};  // J Syy
+    const double a1[3] = {iz * Syy[3] + j1 * Syy[6], iz * Syy[4] + j1 * Syy[7], iz * Syy[5] + j1 * Syy[8]};
+    o[0] = lev;
+    o[1] = a0[0] * iz + a0[2] * j0;
+    o[2] = a0[1] * iz + a0[2] * j1;
+    o[3] = a1[1] * iz + a1[2] * j1;
+  }
+};
+
+// r_i, then P_ii = (A_i Syy_i) A_i^T on the upper triangle only: the caller mirrors it, so the block is symmetric by construction
+template <class Step>
+struct ObsHatRow {
+  static constexpr int RES = Step::RES, STRIDE = RES + RES * (RES + 1) / 2;
+  const Dp& d;
+  const double2 uv;
+  const double sw;
+  __device__ __forceinline__ ObsHatRow(const Dp& d_, const Cam&, const typename Step::Head&, double2 uv_, double sw_)
+      : d(d_), uv(uv_), sw(sw_) {}
+  __device__ __forceinline__ void write(const double (&yv)[3], const double (&Syy)[9], double* o) const {
+    double A[3 * RES], r[RES], T[3 * RES];
+    Step::jac_a(d, uv, sw, yv, A, r);
+#pragma unroll
+    for (int p = 0; p < RES; ++p)
+#pragma unroll
+      for (int x = 0; x < 3; ++x) T[3 * p + x] = A[3 * p] * Syy[x] + A[3 * p + 1] * Syy[3 + x] + A[3 * p + 2] * Syy[6 + x];
+#pragma unroll
+    for (int p = 0; p < RES; ++p) o[p] = r[p];
+    int e = RES;
+#pragma unroll
+    for (int p = 0; p < RES; ++p)
+#pragma unroll
+      for (int q = p; q < RES; ++q) o[e++] = T[3 * p] * A[3 * q] + T[3 * p + 1] * A[3 * q + 1] + T[3 * p + 2] * A[3 * q + 2];
+  }
+};
+
+template <class Step, class Row>
+__device__ __forceinline__ void obs_rows(Dp d, const double* ncw, const int* lm_slot0, const int* lm_cnt, const int* ids,
+                                         const int* row0, const double* M, int64_t ld, const double* panel, const double* sig,
+                                         double* out) {
   typedef typename Step::Obs Obs;
   constexpr int DIM = Step::DIM, CHUNK = Step::CHUNK, STRIDE = Step::LM_STRIDE;
   __shared__ Obs oi[CHUNK], oj[CHUNK];
@@ -531,21 +589,20 @@ __global__ __launch_bounds__(256) void obs_cov(Dp d, const double* ncw, const in
           Kii[e] += shfl_xor_d(Kii[e], m);
         }
       if (!live || gl != 0) continue;
-      // the row of observation ic + i: L_i, M_i and y from the linearisation point, as the staging reads them
+      // the row of observation ic + i: L_i and y from the linearisation point, as the staging reads them
       const int slot = s0 + ic + i;
       const Cam P = load_cam(d.cams_lin4, oi[i].cam);
       const double2 uv = d.uv[slot];
       const double sw = d.robust ? d.sw[slot] : 1.0;
-      const double w = sw * sw;
       const double4 pr[3] = {P.r0, P.r1, P.r2};
-      double L[9], Mi[9], yv[3];
+      double L[9], yv[3];
 #pragma unroll
       for (int x = 0; x < 3; ++x) {
         const double p4[4] = {pr[x].x, pr[x].y, pr[x].z, pr[x].w};
         yv[x] = p4[0] * h[0] + p4[1] * h[1] + p4[2] * h[2] + p4[3] * h[3];
         Step::l_row(hd, p4, L + 3 * x);
       }
-      Step::gram_m(d, P, hd, uv, w, Mi);
+      const Row row(d, P, hd, uv, sw);  // (what the row needs of the linearisation point besides y)
       const double* Sg = sig + (size_t)STRIDE * blockIdx.x;
       double SL[9], Syy[9];  // Sigma_l L_i^T, then the upper triangle of Syy_i, mirrored
 #pragma unroll
@@ -563,20 +620,23 @@ __global__ __launch_bounds__(256) void obs_cov(Dp d, const double* ncw, const in
           Syy[3 * x + y] = v;
           Syy[3 * y + x] = v;
         }
-      double lev = 0;
-#pragma unroll
-      for (int e = 0; e < 9; ++e) lev += Mi[e] * Syy[e];  // (both symmetric)
-      const double iz = 1.0 / yv[2];
-      const double j0 = -yv[0] * iz * iz, j1 = -yv[1] * iz * iz;  // J = [[iz, 0, j0], [0, iz, j1]]
-      const double a0[3] = {iz * Syy[0] + j0 * Syy[6], iz * Syy[1] + j0 * Syy[7], iz * Syy[2] + j0 * Syy[8]};  // J Syy
-      const double a1[3] = {iz * Syy[3] + j1 * Syy[6], iz * Syy[4] + j1 * Syy[7], iz * Syy[5] + j1 * Syy[8]};
-      double* o = out + 4 * ((size_t)row0[blockIdx.x] + ic + i);
-      o[0] = lev;
-      o[1] = a0[0] * iz + a0[2] * j0;
-      o[2] = a0[1] * iz + a0[2] * j1;
-      o[3] = a1[1] * iz + a1[2] * j1;
+      row.write(yv, Syy, out + Row::STRIDE * ((size_t)row0[blockIdx.x] + ic + i));
     }
   }
+}
+
+template <class Step>
+__global__ __launch_bounds__(256) void obs_cov(Dp d, const double* ncw, const int* lm_slot0, const int* lm_cnt, const int* ids,
+                                               const int* row0, const double* M, int64_t ld, const double* panel,
+                                               const double* sig, double* out) {
+  obs_rows<Step, ObsCovRow<Step>>(d, ncw, lm_slot0, lm_cnt, ids, row0, M, ld, panel, sig, out);
+}
+
+template <class Step>
+__global__ __launch_bounds__(256) void obs_hat(Dp d, const double* ncw, const int* lm_slot0, const int* lm_cnt, const int* ids,
+                                               const int* row0, const double* M, int64_t ld, const double* panel,
+                                               const double* sig, double* out) {
+  obs_rows<Step, ObsHatRow<Step>>(d, ncw, lm_slot0, lm_cnt, ids, row0, M, ld, panel, sig, out);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -600,6 +600,19 @@ struct ScdPose {
 #pragma unroll
     for (int e = 0; e < 9; ++e) Mi[e] = w * C9[e];
   }
+  // A_i = sqrt(w) A(alpha, u, v), the RES x 3 weighted Jacobian of the residual with respect to y (A_i^T A_i = M_i), and the
+  // weighted residual r_i = sqrt(w) (A y - (0, 0, sqrt(alpha) u, sqrt(alpha) v)) at y: the row of obs_hat
+  static constexpr int RES = 4;
+  __device__ static __forceinline__ void jac_a(const Dp& d, double2 uv, double sw, const double (&y)[3], double (&A)[12], double (&r)[4]) {
+    const double wb = sw * d.sb, wa = sw * d.sa;
+    const double a12[12] = {wb, 0, -(wb * uv.x), 0, wb, -(wb * uv.y), wa, 0, 0, 0, wa, 0};
+#pragma unroll
+    for (int e = 0; e < 12; ++e) A[e] = a12[e];
+    r[0] = wb * (y[0] - uv.x * y[2]);
+    r[1] = wb * (y[1] - uv.y * y[2]);
+    r[2] = wa * (y[0] - uv.x);
+    r[3] = wa * (y[1] - uv.y);
+  }
 };
 
 POVAR_KERNEL __launch_bounds__(256) void sc_dense_offdiag(Dp d, const int* lm_slot0, const int* lm_cnt, double* S, int64_t ld) {
@@ -769,6 +782,18 @@ struct ScdJoint {
                           hp.D00 * hp.D02, hp.D00 * hp.D12, hp.D02 * hp.D02 + hp.D12 * hp.D12};
 #pragma unroll
     for (int e = 0; e < 9; ++e) Mi[e] = w * m9[e];
+  }
+  // A_i = sqrt(w) d(y0 / y2, y1 / y2) / dy (2 x 3; A_i^T A_i = M_i) and r_i = sqrt(w) ((y0 / y2, y1 / y2) - (u, v)) at y: the row
+  // of obs_hat.  One division, as obs_cov's row; y2 = 0 leaves both non-finite.
+  static constexpr int RES = 2;
+  __device__ static __forceinline__ void jac_a(const Dp&, double2 uv, double sw, const double (&y)[3], double (&A)[6], double (&r)[2]) {
+    const double iz = 1.0 / y[2];
+    const double px = y[0] * iz, py = y[1] * iz, wz = sw * iz;
+    const double a6[6] = {wz, 0, -(wz * px), 0, wz, -(wz * py)};
+#pragma unroll
+    for (int e = 0; e < 6; ++e) A[e] = a6[e];
+    r[0] = sw * (px - uv.x);
+    r[1] = sw * (py - uv.y);
   }
 };
 

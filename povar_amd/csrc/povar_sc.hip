@@ -558,23 +558,28 @@ static int landmark_covariance(povar_ctx* c, int dim, double lambda, int32_t gau
   return 0;
 }
 
-// Per-observation leverage and predicted-point covariance of the requested landmarks' observations: the landmark call's C,
-// Sigma_l without the gauge correction (lm_cov with nq = 0 in solver coordinates, into sc_cov_lm) and the per-landmark
-// contraction obs_cov, which reads no Q: the gauge part of C cancels in J C J^T only if no term carries the correction.
-static int observation_covariance(povar_ctx* c, int dim, double lambda, int32_t gauge, const int32_t* lm_ids, int32_t n_ids,
-                                  double* obs_cov_out, int64_t n_rows) {
+// Per-observation rows of the requested landmarks' observations: the landmark call's C, Sigma_l without the gauge correction
+// (lm_cov with nq = 0 in solver coordinates, into sc_cov_lm) and the per-landmark walk obs_rows, which reads no Q: the gauge part
+// of C cancels in J C J^T only if no term carries the correction.  The two calls differ in the row alone:
+//   hat = false  povar_observation_covariance_*: (h, c_uu, c_uv, c_vv), obs_cov, stride 4
+//   hat = true   povar_observation_hat_*: r_i and the upper triangle of P_ii, obs_hat, stride 14 (step 1) or 5 (step 2)
+static int observation_rows(povar_ctx* c, int dim, bool hat, double lambda, int32_t gauge, const int32_t* lm_ids, int32_t n_ids,
+                            double* rows_out, int64_t n_rows) {
   CovRequest q;
-  q.who = dim == 12 ? "povar_observation_covariance_pose" : "povar_observation_covariance_joint";
+  q.who = hat ? (dim == 12 ? "povar_observation_hat_pose" : "povar_observation_hat_joint")
+              : (dim == 12 ? "povar_observation_covariance_pose" : "povar_observation_covariance_joint");
   if (int rc = q.check(c, lm_ids, n_ids, true)) return rc;
   if (n_rows != q.rows)
     return fail(-1, std::string(q.who) + ": n_rows is " + std::to_string(n_rows) + ", the request produces " + std::to_string(q.rows));
-  q.out = obs_cov_out;
-  q.count = 4 * (size_t)q.rows;
+  const size_t stride = !hat ? 4 : with_step(dim, [](auto step) { return (size_t)ObsHatRow<decltype(step)>::STRIDE; });
+  q.out = rows_out;
+  q.count = stride * (size_t)q.rows;
   CovInverse f{};
   std::optional<TimeScope> ts;
-  int rc = cov_inverse(c, dim, q.who, obs_cov_out != nullptr || q.rows == 0, lambda, gauge, POVAR_COV_SOLVER_COORDS, f, ts);
+  int rc = cov_inverse(c, dim, q.who, rows_out != nullptr || q.rows == 0, lambda, gauge, POVAR_COV_SOLVER_COORDS, f, ts);
   if (q.over(c, f, q.rows == 0, rc)) return rc;
-  if (int rc2 = cov_buffer(c, c->sc_cov_lm, (size_t)lm_stride(dim) * (size_t)q.n_out, dim)) return rc2;
+  const size_t sig_count = (size_t)lm_stride(dim) * (size_t)q.n_out;
+  if (int rc2 = cov_buffer(c, c->sc_cov_lm, sig_count, dim)) return rc2;
   if (int rc2 = cov_buffer(c, c->sc_cov_row0, (size_t)q.n_out, dim)) return rc2;
   if (int rc2 = cov_buffer(c, c->sc_cov_obs, q.count, dim)) return rc2;
   if (int rc2 = q.upload_ids(c, dim)) return rc2;
@@ -582,17 +587,24 @@ static int observation_covariance(povar_ctx* c, int dim, double lambda, int32_t 
   // (rows of a landmark without observations do not exist; every other entry is written)
   cov_lm_launch(c, dim, f, q.ids, q.n_out, nullptr, 0, POVAR_COV_SOLVER_COORDS);
   with_step(dim, [&](auto step) {
-    hipLaunchKernelGGL(obs_cov<decltype(step)>, dim3(q.n_out), dim3(256), 0, c->stream, c->d, (const double*)c->ncw.p,
+    typedef decltype(step) S;
+    const auto rows_kernel = hat ? obs_hat<S> : obs_cov<S>;
+    hipLaunchKernelGGL(rows_kernel, dim3(q.n_out), dim3(256), 0, c->stream, c->d, (const double*)c->ncw.p,
                        (const int*)c->sc_lm_slot0.p, (const int*)c->sc_lm_cnt.p, q.ids, (const int*)c->sc_cov_row0.p,
                        (const double*)c->sc_dense.p, f.ld, (const double*)c->sc_cov_panel.p, (const double*)c->sc_cov_lm.p,
                        c->sc_cov_obs.p);
   });
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(obs_cov_out, c->sc_cov_obs.p, q.count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  std::vector<double> sig(hat ? sig_count : 0);
+  if (hat) HIP_TRY(hipMemcpyAsync(sig.data(), c->sc_cov_lm.p, sig_count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(rows_out, c->sc_cov_obs.p, q.count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));  // (also: row0 is host memory that goes out of scope)
-  // the status judges the factorisation: a leverage that is not finite means C is not; c_* may be non-finite at y2 = 0
-  for (size_t i = 0; i < q.count; i += 4)
-    if (!std::isfinite(obs_cov_out[i])) return q.all_nan();
+  // The status judges the factorisation: a leverage that is not finite means C is not; c_* may be non-finite at y2 = 0.  Every
+  // entry of a step-2 hat row divides by y2, so there Sigma_l answers, which sums every K_ij of the track the rows are made of.
+  for (size_t i = 0; !hat && i < q.count; i += 4)
+    if (!std::isfinite(rows_out[i])) return q.all_nan();
+  for (size_t i = 0; i < sig.size(); ++i)
+    if (!std::isfinite(sig[i])) return q.all_nan();
   cov_done(c, f, 2);
   return 0;
 }
@@ -728,12 +740,22 @@ int povar_landmark_covariance_joint(povar_ctx* c, double lambda, int32_t gauge, 
 
 int povar_observation_covariance_pose(povar_ctx* c, double lambda, int32_t gauge, const int32_t* lm_ids, int32_t n_ids, double* obs_cov,
                                       int64_t n_rows) {
-  return observation_covariance(c, 12, lambda, gauge, lm_ids, n_ids, obs_cov, n_rows);
+  return observation_rows(c, 12, false, lambda, gauge, lm_ids, n_ids, obs_cov, n_rows);
 }
 
 int povar_observation_covariance_joint(povar_ctx* c, double lambda, int32_t gauge, const int32_t* lm_ids, int32_t n_ids, double* obs_cov,
                                        int64_t n_rows) {
-  return observation_covariance(c, 11, lambda, gauge, lm_ids, n_ids, obs_cov, n_rows);
+  return observation_rows(c, 11, false, lambda, gauge, lm_ids, n_ids, obs_cov, n_rows);
+}
+
+int povar_observation_hat_pose(povar_ctx* c, double lambda, int32_t gauge, const int32_t* lm_ids, int32_t n_ids, double* rows,
+                               int64_t n_rows) {
+  return observation_rows(c, 12, true, lambda, gauge, lm_ids, n_ids, rows, n_rows);
+}
+
+int povar_observation_hat_joint(povar_ctx* c, double lambda, int32_t gauge, const int32_t* lm_ids, int32_t n_ids, double* rows,
+                                int64_t n_rows) {
+  return observation_rows(c, 11, true, lambda, gauge, lm_ids, n_ids, rows, n_rows);
 }
 
 int povar_covariance_blocks_pose(povar_ctx* c, double lambda, int32_t gauge, int32_t coords, const int32_t* pairs, int32_t n_pairs,

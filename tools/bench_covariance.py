@@ -7,7 +7,9 @@ context.  Device times (povar_timings.solve_ms: hipEvents on the context's strea
 substitution, or assembly + factorisation + inverse + per-camera Gram, or -- the landmark call -- assembly + factorisation +
 inverse + W W^T + per-landmark contraction + the copy of the blocks to the host; the observation call: the landmark call's stages with
 Sigma_l kept on the device, + the per-observation contraction + the copy of the rows); every call is warmed once, then timed REPS times,
-the median is reported.  The covariance is timed in both modes: free gauge (lambda = 0) and damped (lambda as given); a shape
+the median is reported.  The hat call (povar_observation_hat_pose / _joint: residuals and hat blocks, the same walk with another row) is
+timed beside the observation call of the same run, with |tr P - h| against that call's rows and rank(I - P) of the first 200 000
+observations (capi.deletion_statistics).  The covariance is timed in both modes: free gauge (lambda = 0) and damped (lambda as given); a shape
 that is singular beyond its gauge returns after the factorisation, which the line then says.
 At this size a dense reference is out of reach; the two size-independent checks are printed instead: bitwise symmetry of every
 block, (step 2, camera coordinates) the null-vector residual |block (h0 / sigma_c)| / (|block| |h0 / sigma_c|), and for the
@@ -88,6 +90,18 @@ def main():
                 rank = dim * p.n_cams + 3 * p.n_lms - (12 if step == 1 else 15)
                 line += f"; sum h = {np.sum(rows[:, 0].astype(np.longdouble)):.6f}, rank J = {rank}"
             print(line + f"; finite c_*: {bool(np.all(np.isfinite(rows[:, 1:])))}; device MiB {mib_lm} -> {ctx.device_bytes() >> 20}", flush=True)
+            # the hat call beside the observation call of the same run: the same walk, another row (14 or 5 numbers instead of 4)
+            mib_obs = ctx.device_bytes() >> 20
+            (r, P, rc), ms_hat = timed(lambda: ctx.observation_hat(step=step, lam=lm, gauge=gauge))
+            assert rc == 0
+            d = r.shape[1]
+            tr = np.trace(P, axis1=1, axis2=2)
+            n_stat = min(200000, r.shape[0])
+            t, rk = capi.deletion_statistics(r[:n_stat], P[:n_stat])
+            print(f"step {step} observation hat, all {r.shape[0]} observations, {name} (lambda {lm:g}): {ms_hat:.1f} ms per call, ratio to the "
+                  f"observation call {ms_hat / ms_obs:.2f}, to {solver} {ms_hat / ms_solve:.2f}; worst |tr P - h| {np.abs(tr - rows[:, 0]).max():.2e}; "
+                  f"blocks bitwise symmetric: {np.array_equal(P, P.transpose(0, 2, 1))}; rank(I - P) of the first {n_stat}: "
+                  f"{np.bincount(rk, minlength=d + 1).tolist()}; device MiB {mib_obs} -> {ctx.device_bytes() >> 20}", flush=True)
 
     def pair_requests():
         """The three requests of --pairs: every camera with itself and with its successor; the (camera, landmark) pair of every
