@@ -217,6 +217,25 @@ int povar_normalize_joint(povar_ctx* ctx);
 /* povar_power_series_pose / _begin / _step / povar_get_term / povar_get_increment act on the system
  * prepared last (povar_prepare_pose: 12 n_cams vectors, povar_prepare_joint: 11 n_cams vectors) */
 
+/* ---- constant cameras (Ceres: SetParameterBlockConstant; the reference has no counterpart).  A context carries a set F of
+ * fixed cameras, whole cameras only, empty by default.  With F non-empty every solve -- the power series of both steps in every
+ * kernel family, PCG / RIPCG, CHOLESKY / RICHOLESKY -- returns the increment of the system restricted to the free cameras,
+ * S_ff x_f = -b_f, with the entries of the cameras in F exactly +0.0 or -0.0.  S, b and the landmark elimination are unchanged:
+ * fixed cameras still observe and enter Hpp, E0, the cost, the back substitution and l_diff as constants.  povar_apply_pose /
+ * povar_apply_joint with such an increment leave the 12 numbers of a fixed camera bitwise unchanged (but for the sign of an
+ * entry that is -0.0, which adding +0.0 turns into +0.0); povar_normalize_joint
+ * still rescales every camera to unit norm, fixed ones included (the same projective camera).  With F empty every call is bit
+ * for bit what it is without this call.
+ *   cam_ids: n_ids global camera ids, duplicates allowed; n_ids = 0 or a null pointer clears the set.  An id out of range is an
+ * argument error that leaves the set as it was.  The set takes effect at the next call that prepares a system (povar_prepare_*,
+ * povar_solve_*, a covariance call); a system prepared earlier is what it was.  The linearisation stays.  On a sharded context
+ * every rank passes the same set.
+ *   What the inspection buffers show on F: POVAR_BUF_B_INV[_JOINT] and POVAR_BUF_SC_PRECOND zero blocks; POVAR_BUF_SC_BLOCKDIAG
+ * is unchanged; POVAR_BUF_SC_FACTOR identity rows and columns with y = x = 0. */
+int povar_set_fixed_cameras(povar_ctx* ctx, const int32_t* cam_ids, int32_t n_ids);
+/* the number of fixed cameras (the set as the last povar_set_fixed_cameras left it); flags: n_cams entries 0 / 1, or null */
+int povar_fixed_cameras(povar_ctx* ctx, int32_t* flags /* n_cams or NULL */);
+
 /* ---- explicit-Schur-complement solvers: LinearizorSC (solver/linearizor_sc.cpp), selected by
  * --solver-type-step-1 PCG | CHOLESKY and --solver-type-step-2 RIPCG (solver/linearizor.cpp:51-53,
  * 67-72), and --solver-type-step-2 RICHOLESKY (not in the reference).  The reduced camera system S x = b, S = (Hpp + lambda I) - E0, is solved without landmark
@@ -287,8 +306,19 @@ int povar_right_mul_e0_joint(povar_ctx* ctx, const double* x, double* y);
  * (as povar_solve_pose_sc / povar_solve_joint_sc_method do): the system prepared before, the inspection buffers of the
  * explicit-SC solvers and the increment buffer are overwritten.  Not positive definite, or singular (free gauge): every entry of
  * cov is NaN and the call returns POVAR_NUMERIC_FAILURE.  Not enough device memory: the error of CHOLESKY / RICHOLESKY.
- * On a sharded context every rank calls; the assembly is all-reduced and every rank inverts the same matrix. ---- */
-enum { POVAR_COV_FREE_GAUGE = 0, POVAR_COV_DAMPED = 1 };
+ * On a sharded context every rank calls; the assembly is all-reduced and every rank inverts the same matrix.
+ *   With fixed cameras (povar_set_fixed_cameras, set F) every covariance call -- camera, landmark, observation, hat and pair,
+ * both steps, both coords -- returns C with zero rows and columns on F:
+ *          POVAR_COV_FIXED_GAUGE: lambda must be 0 and F non-empty (both violations are argument errors).  The blocks of
+ *          [S_ff(0)]^-1, the covariance in the gauge the fixed cameras define, zero-padded on F.  No gauge basis is built
+ *          (POVAR_BUF_COV_GAUGE is an argument error afterwards, as after POVAR_COV_DAMPED).  Singularity beyond what F fixes is
+ *          reported by the pivot rule above, applied to the rows of the free cameras: NaN and POVAR_NUMERIC_FAILURE.  ONE fixed
+ *          camera is not enough: it leaves a 4-dimensional null space in step 2 at a generic state, and in step 1 at an affine
+ *          state (third camera row (0, 0, 0, 1), as the pOSE start state has it).  Two or more fix the gauge in both steps.
+ *          POVAR_COV_DAMPED with F non-empty: the blocks of [S_ff(lambda)]^-1, zero-padded.
+ *          POVAR_COV_FREE_GAUGE with F non-empty is an argument error.
+ * A landmark's block contracts its free cameras only; a pair block with a fixed camera on either side is zero. ---- */
+enum { POVAR_COV_FREE_GAUGE = 0, POVAR_COV_DAMPED = 1, POVAR_COV_FIXED_GAUGE = 2 };
 enum { POVAR_COV_CAMERA_COORDS = 0, POVAR_COV_SOLVER_COORDS = 1 };
 /* after povar_linearize_pose: the 12 n_cams system of step 1 */
 int povar_camera_covariance_pose(povar_ctx* ctx, double lambda, int32_t gauge, int32_t coords, double* cov /*144 n_cams*/);

@@ -26,6 +26,7 @@ NUMERIC_FAILURE = 1
 SC_PCG, SC_CHOLESKY = 0, 1
 # povar_camera_covariance_pose / _joint (include/povar_hip.h: POVAR_COV_*)
 COV_FREE_GAUGE, COV_DAMPED = 0, 1
+COV_FIXED_GAUGE = 2  # [S_ff(0)]^-1 in the gauge of the fixed cameras (Context.set_fixed_cameras), zero-padded
 COV_CAMERA_COORDS, COV_SOLVER_COORDS = 0, 1
 COV_LANDMARK_COORDS = 0  # povar_landmark_covariance_pose / _joint: the same number as COV_CAMERA_COORDS
 COV_BLOCK_CAMERA, COV_BLOCK_LANDMARK = 0, 1  # povar_covariance_blocks_pose / _joint: the kinds of a pair
@@ -304,6 +305,22 @@ class Context:
                                                 C.c_double(r_tol), _p(inc), C.byref(it), C.byref(st)),
                        allow_numeric=True)
         return inc, it.value, st.value, rc
+
+    # constant cameras
+    def set_fixed_cameras(self, ids):
+        """Hold the cameras `ids` (global ids, duplicates allowed; empty or None clears the set) constant in every later
+        solve and covariance call: their increment is exactly zero, the rest solves S_ff x_f = -b_f.  Takes effect at the
+        next call that prepares a system (include/povar_hip.h)."""
+        ids = np.ascontiguousarray([] if ids is None else ids, dtype=np.int32).reshape(-1)
+        self._chk(self.L.povar_set_fixed_cameras(self.h, _p(ids) if ids.size else None, C.c_int32(ids.size)))
+
+    def fixed_cameras(self):
+        """The fixed cameras as a sorted array of ids."""
+        flags = np.zeros(self.n_cams, dtype=np.int32)
+        n = self._chk(self.L.povar_fixed_cameras(self.h, _p(flags)), allow_numeric=True)
+        ids = np.flatnonzero(flags).astype(np.int32)
+        assert ids.size == n
+        return ids
 
     # explicit-Schur-complement solvers (LinearizorSC: PCG / CHOLESKY / RIPCG)
     def set_jl_col_scaling(self, enable):

@@ -138,10 +138,14 @@ std::FILE* open_for_writing(const std::string& path) {
   return f;
 }
 
-// count on the first line, then one line of `stride` numbers per item
-void write_blocks(const std::string& path, int count, int stride, const Linearizor::VecX& v) {
+// What follows the count on the first line of every covariance file: nothing in the free gauge; with --fixed-cameras the
+// gauge those cameras fix (POVAR_COV_FIXED_GAUGE: zero on them), named so that no reader takes one for the other
+const char* gauge_note(const SolverOptions& so) { return so.fixed_cameras.empty() ? "" : " fixed-gauge"; }
+
+// count (and the gauge note) on the first line, then one line of `stride` numbers per item
+void write_blocks(const std::string& path, int count, int stride, const Linearizor::VecX& v, const SolverOptions& so) {
   std::FILE* f = open_for_writing(path);
-  std::fprintf(f, "%d\n", count);
+  std::fprintf(f, "%d%s\n", count, gauge_note(so));
   for (int i = 0; i < count; ++i)
     for (int k = 0; k < stride; ++k) std::fprintf(f, "%.17g%c", v[(size_t)stride * i + k], k == stride - 1 ? '\n' : ' ');
   std::fclose(f);
@@ -163,13 +167,13 @@ void write_covariances(Linearizor& linearizor, const BalProblem& bal_problem, co
   Linearizor::VecX lm_cov, cam_cov;
   if (so.landmark_covariance_path.empty()) {
     report_covariance_status(linearizor.camera_covariance(step2, so.alpha, cam_cov), "camera", "blocks");
-    write_blocks(so.camera_covariance_path, bal_problem.num_cameras(), 144, cam_cov);
+    write_blocks(so.camera_covariance_path, bal_problem.num_cameras(), 144, cam_cov, so);
     return;
   }
   const bool with_cameras = !so.camera_covariance_path.empty();
   report_covariance_status(linearizor.landmark_covariance(step2, so.alpha, lm_cov, with_cameras ? &cam_cov : nullptr), "landmark", "blocks");
-  write_blocks(so.landmark_covariance_path, bal_problem.num_landmarks(), step2 ? 16 : 9, lm_cov);
-  if (with_cameras) write_blocks(so.camera_covariance_path, bal_problem.num_cameras(), 144, cam_cov);
+  write_blocks(so.landmark_covariance_path, bal_problem.num_landmarks(), step2 ? 16 : 9, lm_cov, so);
+  if (with_cameras) write_blocks(so.camera_covariance_path, bal_problem.num_cameras(), 144, cam_cov, so);
 }
 
 // --observation-covariance-path: n_obs on the first line, then one line per observation in file order: landmark, camera and
@@ -181,7 +185,7 @@ void write_observation_covariance(Linearizor& linearizor, const BalProblem& bal_
   std::vector<int> lm_off, cam_idx;
   std::vector<double> obs;
   bal_problem.flatten(lm_off, cam_idx, obs);
-  std::fprintf(f, "%zu\n", cam_idx.size());
+  std::fprintf(f, "%zu%s\n", cam_idx.size(), gauge_note(so));
   for (int l = 0; l < bal_problem.num_landmarks(); ++l)
     for (int i = lm_off[l]; i < lm_off[l + 1]; ++i)
       std::fprintf(f, "%d %d %.17g %.17g %.17g %.17g\n", l, cam_idx[i], cov[4 * (size_t)i], cov[4 * (size_t)i + 1], cov[4 * (size_t)i + 2],
@@ -246,7 +250,7 @@ void write_observation_diagnostics(Linearizor& linearizor, const BalProblem& bal
   std::vector<int> lm_off, cam_idx;
   std::vector<double> obs;
   bal_problem.flatten(lm_off, cam_idx, obs);
-  std::fprintf(f, "%zu\n", cam_idx.size());
+  std::fprintf(f, "%zu%s\n", cam_idx.size(), gauge_note(so));
   for (int l = 0; l < bal_problem.num_landmarks(); ++l)
     for (int i = lm_off[l]; i < lm_off[l + 1]; ++i) {
       const double* row = rows.data() + (size_t)stride * i;
@@ -307,7 +311,7 @@ void write_covariance_blocks(Linearizor& linearizor, const BalProblem& bal_probl
   }
   if (rc != 0) std::printf("\t[WARN] covariance blocks: the reduced system is singular beyond its gauge, the blocks are NaN\n");
   std::FILE* f = open_for_writing(so.covariance_blocks_path);
-  std::fprintf(f, "%ld\n", count);
+  std::fprintf(f, "%ld%s\n", count, gauge_note(so));
   for (long p = 0; p < count; ++p) {
     std::fprintf(f, "%d %d", side[pairs[4 * p]], side[pairs[4 * p + 2]]);
     for (size_t k = first[p]; k < first[p + 1]; ++k) std::fprintf(f, " %.17g", blocks[k]);

@@ -2,6 +2,7 @@
 // '_' -> '-' (cli/cli_options.cpp:61, 134), booleans as --x / --no-x (cli_options.cpp:85-91), enums
 // from strings (cli_options.cpp:102-111).  Prefixes: dataset and solver members have none, the
 // nested solver.residual and solver.log structs use "residual-" and "log-".
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -99,6 +100,30 @@ bool parse_bal_app_arguments(int argc, char** argv, BalAppOptions& o) {
   dbl("observation-diagnostics-tol", &o.solver.observation_diagnostics_tol);
   str("covariance-pairs-path", &o.solver.covariance_pairs_path);
   str("covariance-blocks-path", &o.solver.covariance_blocks_path);
+  // LIST: comma-separated tokens, each an id or a range a-b (a <= b); the ids are checked against the camera count once the
+  // problem is loaded (bal.cpp)
+  val["fixed-cameras"] = [&](const std::string& v) {
+    std::vector<int>& ids = o.solver.fixed_cameras;
+    ids.clear();
+    size_t at = 0;
+    while (at <= v.size()) {
+      const size_t comma = std::min(v.find(',', at), v.size());
+      const std::string tok = v.substr(at, comma - at);
+      at = comma + 1;
+      if (tok.empty() || tok[0] < '0' || tok[0] > '9') return false;
+      char* e;
+      const long a = std::strtol(tok.c_str(), &e, 10);
+      long b = a;
+      if (*e == '-') {
+        const char* rest = e + 1;
+        if (*rest < '0' || *rest > '9') return false;
+        b = std::strtol(rest, &e, 10);
+      }
+      if (*e != 0 || b < a || b > 0x7fffffffL || b - a > (1L << 24)) return false;
+      for (long k = a; k <= b; ++k) ids.push_back((int)k);
+    }
+    return true;
+  };
 
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -131,7 +156,11 @@ bool parse_bal_app_arguments(int argc, char** argv, BalAppOptions& o) {
                   "      likewise the covariance block of every pair of parameter blocks listed in IN (the number of pairs, then one\n"
                   "      line `c|l id c|l id` per pair: c a camera, l a landmark), gauge fixed on the cameras: OUT gets the number of\n"
                   "      pairs, then one line `rows cols` and the rows x cols numbers per pair (a camera 12 coordinates, a landmark 3\n"
-                  "      after step 1, 4 after step 2); one device only\n");
+                  "      after step 1, 4 after step 2); one device only\n"
+                  "  --fixed-cameras LIST\n"
+                  "      not an option of the reference: hold these cameras constant in every solve of both steps (comma-separated ids\n"
+                  "      and ranges a-b, in file order); the covariance outputs above are then those of the gauge the fixed cameras\n"
+                  "      define (zero blocks on them) instead of the free gauge.  One fixed camera does not fix the gauge\n");
       return false;
     }
     if (a.rfind("--", 0) != 0) {

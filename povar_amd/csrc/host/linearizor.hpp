@@ -113,6 +113,10 @@ class Linearizor {
   virtual double apply_joint(VecX&& inc) = 0;
   virtual double apply(const SolverOptions& solver_options, double alpha, VecX&& inc) = 0;
   virtual void finish_iteration() = 0;
+  // Not in the reference: SolverOptions::fixed_cameras.  true: this linearizor holds those cameras constant in every solve
+  // (their increment is exactly zero) and reports covariance in the gauge they fix.  The factories refuse to hand out a
+  // linearizor that answers false for a non-empty set: the option is never ignored.
+  virtual bool holds_fixed_cameras() const { return false; }
   // Not in the reference: the free-gauge marginal covariance of every camera at the current state, camera coordinates,
   // 144 n_cams numbers (povar_camera_covariance_pose after linearize_pOSE(alpha), or povar_camera_covariance_joint after
   // linearize_projective_space_homogeneous).  Returns the library's status: 0, or POVAR_NUMERIC_FAILURE (1) with all-NaN blocks

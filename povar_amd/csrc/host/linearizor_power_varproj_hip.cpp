@@ -101,7 +101,10 @@ class LinearizorPowerVarprojHip : public Linearizor, public StateMirror {
       // IterationSummary timings come from the device (hipEvents on the library's stream, povar_timings), not from
       // host clocks around the calls; rank 0's (the ranks run the same calls side by side)
       if (r == 0) check(povar_timings_enable(s.ctx, 1), "povar_timings_enable");
+      // --fixed-cameras: the same set on every shard context (an empty one clears what a context taken over from step 1 holds)
+      check(povar_set_fixed_cameras(s.ctx, options.fixed_cameras.data(), (int32_t)options.fixed_cameras.size()), "povar_set_fixed_cameras");
     });
+    cov_gauge_ = options.fixed_cameras.empty() ? POVAR_COV_FREE_GAUGE : POVAR_COV_FIXED_GAUGE;
     push_state();
     bal_problem_.mirror = this;
   }
@@ -116,6 +119,7 @@ class LinearizorPowerVarprojHip : public Linearizor, public StateMirror {
     }
   }
 
+  bool holds_fixed_cameras() const override { return true; }
   void start_iteration(IterationSummary* it) override { it_summary_ = it; }
   void finish_iteration() override {}
 
@@ -132,6 +136,7 @@ class LinearizorPowerVarprojHip : public Linearizor, public StateMirror {
     linearize_all(true, 0.0, "povar_linearize_homogeneous");
     book_linearize();
   }
+  // Gauge of all of them: the free gauge, or with --fixed-cameras the gauge those cameras fix (POVAR_COV_FIXED_GAUGE).
   // The three covariance calls are the library calls themselves: they run after the LM loop, when the iteration summary
   // start_iteration handed over is gone and the solver summary is finished -- no timing or evaluation count is booked.
   // Sharded, every shard linearises and calls (the assembly is all-reduced, every rank inverts the same matrix) and writes
@@ -141,8 +146,8 @@ class LinearizorPowerVarprojHip : public Linearizor, public StateMirror {
     cov.assign(144 * (size_t)bal_problem_.num_cameras(), 0.0);
     linearize_all(step2, alpha, "povar_linearize (camera covariance)");
     return covariance_status("povar_camera_covariance", [&](Shard& s) {
-      return step2 ? povar_camera_covariance_joint(s.ctx, 0.0, POVAR_COV_FREE_GAUGE, POVAR_COV_CAMERA_COORDS, cov.data())
-                   : povar_camera_covariance_pose(s.ctx, 0.0, POVAR_COV_FREE_GAUGE, POVAR_COV_CAMERA_COORDS, cov.data());
+      return step2 ? povar_camera_covariance_joint(s.ctx, 0.0, cov_gauge_, POVAR_COV_CAMERA_COORDS, cov.data())
+                   : povar_camera_covariance_pose(s.ctx, 0.0, cov_gauge_, POVAR_COV_CAMERA_COORDS, cov.data());
     });
   }
   int landmark_covariance(bool step2, double alpha, VecX& lm_cov, VecX* cam_cov) override {
@@ -154,8 +159,8 @@ class LinearizorPowerVarprojHip : public Linearizor, public StateMirror {
     double* cam = cam_cov ? cam_cov->data() : nullptr;
     return covariance_status("povar_landmark_covariance", [&](Shard& s) {
       double* out = lm_cov.data() + stride * (size_t)s.lb;
-      return step2 ? povar_landmark_covariance_joint(s.ctx, 0.0, POVAR_COV_FREE_GAUGE, POVAR_COV_LANDMARK_COORDS, nullptr, 0, out, cam)
-                   : povar_landmark_covariance_pose(s.ctx, 0.0, POVAR_COV_FREE_GAUGE, POVAR_COV_LANDMARK_COORDS, nullptr, 0, out, cam);
+      return step2 ? povar_landmark_covariance_joint(s.ctx, 0.0, cov_gauge_, POVAR_COV_LANDMARK_COORDS, nullptr, 0, out, cam)
+                   : povar_landmark_covariance_pose(s.ctx, 0.0, cov_gauge_, POVAR_COV_LANDMARK_COORDS, nullptr, 0, out, cam);
     });
   }
   int observation_covariance(bool step2, double alpha, VecX& obs_cov) override {
@@ -163,8 +168,8 @@ class LinearizorPowerVarprojHip : public Linearizor, public StateMirror {
     linearize_all(step2, alpha, "povar_linearize (observation covariance)");
     return covariance_status("povar_observation_covariance", [&](Shard& s) {
       double* out = obs_cov.data() + 4 * (size_t)s.ob;
-      return step2 ? povar_observation_covariance_joint(s.ctx, 0.0, POVAR_COV_FREE_GAUGE, nullptr, 0, out, s.on)
-                   : povar_observation_covariance_pose(s.ctx, 0.0, POVAR_COV_FREE_GAUGE, nullptr, 0, out, s.on);
+      return step2 ? povar_observation_covariance_joint(s.ctx, 0.0, cov_gauge_, nullptr, 0, out, s.on)
+                   : povar_observation_covariance_pose(s.ctx, 0.0, cov_gauge_, nullptr, 0, out, s.on);
     });
   }
   int observation_hat(bool step2, double alpha, VecX& rows) override {
@@ -173,8 +178,8 @@ class LinearizorPowerVarprojHip : public Linearizor, public StateMirror {
     linearize_all(step2, alpha, "povar_linearize (observation diagnostics)");
     return covariance_status("povar_observation_hat", [&](Shard& s) {
       double* out = rows.data() + stride * (size_t)s.ob;
-      return step2 ? povar_observation_hat_joint(s.ctx, 0.0, POVAR_COV_FREE_GAUGE, nullptr, 0, out, s.on)
-                   : povar_observation_hat_pose(s.ctx, 0.0, POVAR_COV_FREE_GAUGE, nullptr, 0, out, s.on);
+      return step2 ? povar_observation_hat_joint(s.ctx, 0.0, cov_gauge_, nullptr, 0, out, s.on)
+                   : povar_observation_hat_pose(s.ctx, 0.0, cov_gauge_, nullptr, 0, out, s.on);
     });
   }
   int covariance_blocks(bool step2, double alpha, const std::vector<int32_t>& pairs, VecX& blocks) override {
@@ -182,9 +187,9 @@ class LinearizorPowerVarprojHip : public Linearizor, public StateMirror {
     linearize_all(step2, alpha, "povar_linearize (covariance blocks)");
     return covariance_status("povar_covariance_blocks", [&](Shard& s) {
       const int32_t n = (int32_t)(pairs.size() / 4);
-      return step2 ? povar_covariance_blocks_joint(s.ctx, 0.0, POVAR_COV_FREE_GAUGE, POVAR_COV_CAMERA_COORDS, pairs.data(), n, blocks.data(),
+      return step2 ? povar_covariance_blocks_joint(s.ctx, 0.0, cov_gauge_, POVAR_COV_CAMERA_COORDS, pairs.data(), n, blocks.data(),
                                                    (int64_t)blocks.size())
-                   : povar_covariance_blocks_pose(s.ctx, 0.0, POVAR_COV_FREE_GAUGE, POVAR_COV_CAMERA_COORDS, pairs.data(), n, blocks.data(),
+                   : povar_covariance_blocks_pose(s.ctx, 0.0, cov_gauge_, POVAR_COV_CAMERA_COORDS, pairs.data(), n, blocks.data(),
                                                   (int64_t)blocks.size());
     });
   }
@@ -444,6 +449,7 @@ class LinearizorPowerVarprojHip : public Linearizor, public StateMirror {
 
   SolverOptions options_;
   bool sc_step1_ = false, sc_step2_ = false;
+  int32_t cov_gauge_ = POVAR_COV_FREE_GAUGE;
   BalProblem& bal_problem_;
   SolverSummary* summary_ = nullptr;
   IterationSummary* it_summary_ = nullptr;
@@ -458,8 +464,17 @@ class LinearizorPowerVarprojHip : public Linearizor, public StateMirror {
 
 LinearizorFactory g_factory = nullptr;
 
+// a linearizor that would ignore --fixed-cameras is not handed out
+std::unique_ptr<Linearizor> fixed_cameras_checked(std::unique_ptr<Linearizor> lin, const SolverOptions& o) {
+  if (!o.fixed_cameras.empty() && !lin->holds_fixed_cameras()) {
+    std::fprintf(stderr, "FATAL: --fixed-cameras: this linearizor does not implement fixed cameras\n");
+    std::abort();
+  }
+  return lin;
+}
+
 std::unique_ptr<Linearizor> make(BalProblem& p, const SolverOptions& o, SolverSummary* s, bool hom) {
-  if (g_factory) return g_factory(p, o, s, hom);
+  if (g_factory) return fixed_cameras_checked(g_factory(p, o, s, hom), o);
   // POVAR_FORCE_MULTI=1: also `--gpus 1` runs sharded (a team of one: an RCCL communicator of one rank created on the
   // worker thread, the all-reduces of the one shard inside its captured term loop with POVAR_GRAPH_COMM=1) -- the branch
   // a one-GPU box can otherwise never execute (tests/test_gpu_bal_cli.py)

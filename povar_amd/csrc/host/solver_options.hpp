@@ -4,6 +4,7 @@
 // scope; a flat parser reproduces the flag names (cli.cpp).
 #pragma once
 #include <string>
+#include <vector>
 
 namespace povar_host {
 
@@ -89,6 +90,11 @@ struct SolverOptions {
   // numbers row-major (%.17g); a camera has 12 coordinates, a landmark 3 (after step 1) or 4 (after step 2).  Both or neither;
   // one device only.
   std::string covariance_pairs_path, covariance_blocks_path;
+  // not in the reference (Ceres: SetParameterBlockConstant): cameras held constant in every solve of both steps, ids in file
+  // order (--fixed-cameras LIST: comma-separated ids and a-b ranges; povar_set_fixed_cameras on every shard context).  With
+  // the set non-empty the covariance outputs above are those of POVAR_COV_FIXED_GAUGE -- [S_ff(0)]^-1, zero on the fixed
+  // cameras -- and their files say so.  One fixed camera does not fix the gauge (include/povar_hip.h).
+  std::vector<int> fixed_cameras;
 
   // solver_options.cpp:41-51
   bool use_projection_validity_check() const { return optimized_cost != OptimizedCost::ERROR; }

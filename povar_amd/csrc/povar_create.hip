@@ -709,6 +709,9 @@ static int upload_lane_obs(povar_ctx* c, const CreatePlan& plan, CreateJob& J) {
   HIP_TRY(room(c->norm_part, 2 * (size_t)std::max(c->n_cam_blocks, n_cams))); HIP_TRY(room(c->norms, 4)); HIP_TRY(room(c->flags, 4));
   HIP_TRY(room(c->part, n_part * 2 + 8 * 1024)); HIP_TRY(room(c->scal, 8));  // + one slot set per workgroup of the lane-per-landmark kernels
   HIP_TRY(room(c->stage, std::max(3 * nl, 144 * nc)));
+  HIP_TRY(room(c->fixed_mask, std::max<size_t>(nc, 1)));  // (povar_set_fixed_cameras: no camera is fixed)
+  c->fixed_next.assign(nc, 0);
+  HIP_TRY(hipMemsetAsync(c->fixed_mask.p, 0, std::max<size_t>(nc, 1), c->stream));
   HIP_TRY(hipMemsetAsync(c->flags.p, 0, sizeof(int) * 4, c->stream));
   HIP_TRY(hipMemsetAsync(c->lms4.p, 0, sizeof(double4) * nl, c->stream));
   HIP_TRY(hipMemsetAsync(c->cams4.p, 0, sizeof(double4) * 3 * nc, c->stream));

@@ -276,6 +276,15 @@ struct povar_ctx : CtxSwitches {  // (create_plan.hpp: the switches povar_create
   bool sc_cov_kept = false;
   DevBuf<double> sc_cov_r;
 
+  // fixed cameras (povar_set_fixed_cameras): fixed_next is the caller's set, fixed_mask its device copy as of the last
+  // preparation (lm_prepare uploads it when fixed_dirty: a system prepared earlier is what it was), n_fixed the cameras
+  // that copy holds.  An explicit argument of cam_build_binv[_h], cam_build_sc, sc_fix_cameras, cov_diag_scan and
+  // cov_fix_cameras: not part of Dp, whose term kernels do not read it.
+  DevBuf<uint8_t> fixed_mask;
+  std::vector<uint8_t> fixed_next;
+  bool fixed_dirty = false;
+  int n_fixed = 0;
+
   Dp d{};
   bool new_linearization_point = false;  // linearizor_power_varproj.cpp:75, 192, 240
   bool linearized = false;

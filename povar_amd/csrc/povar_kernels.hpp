@@ -1837,8 +1837,14 @@ __device__ inline void chol_inverse_16(double* A, int l, double* out) {
 // K8: B_c = Hpp_c + lambda I, B_c^-1 by Cholesky (upper triangle) and solve against I
 // (linearization_power_varproj.hpp:141-154).  Sixteen lanes per camera, four cameras per 64-thread workgroup
 // (one thread per camera was a 1 900-step dependent chain through LDS: 31 us for 1 778 cameras).
+// fixed[c] != 0 (povar_set_fixed_cameras): the camera's block is zero, so every product with it -- the series start, every
+// term, the sum -- is zero on that camera; the other cameras run the arithmetic they always ran.
 constexpr int K8_THREADS = 64, K8_CAMS_PER_WG = 4;
-POVAR_KERNEL __launch_bounds__(K8_THREADS) void cam_build_binv(Dp d, double lambda) {
+// the zero block of a fixed camera: the 16 lanes of the camera write its dim x dim entries
+__device__ inline void binv_zero_block(double* out, int l, int count) {
+  for (int e = l; e < count; e += 16) out[e] = 0.0;
+}
+POVAR_KERNEL __launch_bounds__(K8_THREADS) void cam_build_binv(Dp d, double lambda, const uint8_t* fixed) {
   __shared__ double As[K8_CAMS_PER_WG][144];
   const int q = threadIdx.x >> 4, l = threadIdx.x & 15;
   const int c = blockIdx.x * K8_CAMS_PER_WG + q;
@@ -1865,7 +1871,9 @@ POVAR_KERNEL __launch_bounds__(K8_THREADS) void cam_build_binv(Dp d, double lamb
     for (int e = l; e < 144; e += 16) A[e] = (e / 12 == e % 12) ? 1.0 : 0.0;
   }
   __syncthreads();
-  chol_inverse_16<12>(A, l, in ? d.binv + 144 * (size_t)c : nullptr);
+  const bool fx = in && fixed[c] != 0;
+  chol_inverse_16<12>(A, l, in && !fx ? d.binv + 144 * (size_t)c : nullptr);
+  if (fx) binv_zero_block(d.binv + 144 * (size_t)c, l, 144);
 }
 
 // z_c = sigma * x_c goes to the dense vector and, for a cached camera, into the contiguous record

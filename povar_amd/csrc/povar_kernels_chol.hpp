@@ -12,6 +12,7 @@
 //   chol_syrk        rows of the same 256-block -= R12^T R12     64 x 64 tiles, K = 64
 //   chol_syrk_outer  rows below the block -= P^T P, P = the block's 256 finished rows
 //                                                               128 x 128 tiles, K = 256
+// (before them, with fixed cameras: sc_fix_cameras, identity rows and columns on the assembled matrix -- at the end of this file)
 // Carrying the right-hand side as column N folds the forward substitution into the factorisation;
 // chol_back_* then solve R x = y panel by panel from the bottom.
 // The trailing update is the n^3/3 part (venice-1778: 3.2 TFLOP): the only GEMM-shaped work of
@@ -283,6 +284,27 @@ POVAR_KERNEL __launch_bounds__(256) void chol_back_update(const double* M, int64
 POVAR_KERNEL __launch_bounds__(64) void chol_pad(double* M, int64_t ld, int n, int N) {
   const int r = n + threadIdx.x;
   if (r < N) M[(int64_t)r * ld + r] = 1.0;
+}
+
+// Fixed cameras (povar_set_fixed_cameras), on the assembled and all-reduced matrix, before the factorisation: the dim rows
+// and columns of a fixed camera become the identity's and its right-hand-side entries 0, so the factor keeps e_k^T in those
+// rows (y_k = x_k = 0) and the rest of it is the factor of the free cameras' system S_ff.  One workgroup per camera (the free
+// ones return at once).  Rows: a wavefront per row, contiguous stores through the rhs column N.  Columns: thread i writes the
+// dim adjacent entries of row i (dim N scattered stores per camera).  Plain stores in a fixed pattern, no atomics; where a
+// row of one fixed camera crosses a column of another both write the same value.  Rows < dim n_cams <= N, columns <= N < ld.
+POVAR_KERNEL __launch_bounds__(256) void sc_fix_cameras(double* M, int64_t ld, int N, int dim, const uint8_t* fixed) {
+  const int c = blockIdx.x;
+  if (!fixed[c]) return;
+  const int k0 = dim * c, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (int a = wave; a < dim; a += 4) {
+    const int k = k0 + a;
+    double* row = M + (int64_t)k * ld;
+    for (int j = lane; j <= N; j += 64) row[j] = j == k ? 1.0 : 0.0;
+  }
+  for (int i = threadIdx.x; i < N; i += 256) {
+    double* col = M + (int64_t)i * ld + k0;
+    for (int a = 0; a < dim; ++a) col[a] = i == k0 + a ? 1.0 : 0.0;
+  }
 }
 
 }  // namespace povar

@@ -5,6 +5,7 @@
 //   cov_diag_scan  max_k A_kk before and min_k R_kk^2 after the factorisation (the pivot rule of the free gauge)
 //   cov_diag_inv   W_jj = R_jj^-1 of a 64 x 64 diagonal block          one wavefront, row c of W_jj in lane c
 //   cov_trmm       T = R[0:j, j] W_jj into the scratch panel, then W[0:j, j] = -W[0:j, 0:j] T      64 x 64 tiles, MFMA
+//   cov_fix_cameras  W_kk = 0 on the rows of the fixed cameras (povar_set_fixed_cameras), after the W loop
 //   cov_gram       block c = sum_k W[J, k] W[J, k]^T over the camera's rows J                       workgroup per camera
 //   cov_finish     - Q_J Q_J^T, then the map to camera coordinates (D T D, or D N_c T N_c^T D with the reflector)
 // W overwrites R in place, block column by block column from the left: when column j is formed, W[0:j, 0:j] is final
@@ -46,11 +47,14 @@ POVAR_KERNEL __launch_bounds__(256) void cov_add_qqt(double* M, int64_t ld, int 
 }
 
 // out[which] = max_k M_kk (which = 0: the diagonal of A, before the factorisation) or min_k M_kk^2 (which = 1: the
-// pivots R_kk^2, after it) over k < n.  One workgroup.
-POVAR_KERNEL __launch_bounds__(256) void cov_diag_scan(const double* M, int64_t ld, int n, int which, double* out) {
+// pivots R_kk^2, after it) over the rows k < n of the free cameras (fixed[k / dim] == 0: a decoupled row holds the 1 that
+// sc_fix_cameras put there and says nothing about the system).  One workgroup.
+POVAR_KERNEL __launch_bounds__(256) void cov_diag_scan(const double* M, int64_t ld, int n, int which, double* out, const uint8_t* fixed,
+                                                       int dim) {
   __shared__ double sh[256];
   double v = which == 0 ? -INFINITY : INFINITY;
   for (int k = threadIdx.x; k < n; k += 256) {
+    if (fixed[k / dim]) continue;
     const double a = M[(int64_t)k * ld + k];
     v = which == 0 ? fmax(v, a) : fmin(v, a * a);
   }
@@ -61,6 +65,14 @@ POVAR_KERNEL __launch_bounds__(256) void cov_diag_scan(const double* M, int64_t 
     __syncthreads();
   }
   if (threadIdx.x == 0) out[which] = sh[0];
+}
+
+// Fixed cameras, after the W loop: row k of R is e_k^T on a decoupled row (sc_fix_cameras), so row and column k of W = R^-1 hold
+// W_kk = 1 and nothing else; with W_kk = 0 the row and the column of C = W W^T are zero and every kernel after this one sees
+// the covariance of the free cameras, zero-padded.  One thread per row k < n.
+POVAR_KERNEL __launch_bounds__(256) void cov_fix_cameras(double* M, int64_t ld, int n, int dim, const uint8_t* fixed) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k < n && fixed[k / dim]) M[(int64_t)k * ld + k] = 0.0;
 }
 
 // W_jj = R_jj^-1 of the 64 x 64 upper triangular block at (k0, k0), in place.  One wavefront; lane c forms row c of

@@ -541,8 +541,8 @@ POVAR_KERNEL __launch_bounds__(CFL_THREADS) void cam_finish_linearize_h(Dp d, co
 
 // K8': B_c = N_c^T (Hpp12 + lambda I) N_c = N_c^T Hpp12 N_c + lambda I_11, Cholesky inverse 11x11
 // (linearization_power_varproj.hpp:91-121).  Sixteen lanes per camera as cam_build_binv: lane i owns row i of the two
-// projections, then chol_inverse_16<11>.
-POVAR_KERNEL __launch_bounds__(K8_THREADS) void cam_build_binv_h(Dp d, double lambda, const double* ncw) {
+// projections, then chol_inverse_16<11>.  fixed: as cam_build_binv.
+POVAR_KERNEL __launch_bounds__(K8_THREADS) void cam_build_binv_h(Dp d, double lambda, const double* ncw, const uint8_t* fixed) {
   __shared__ double As[K8_CAMS_PER_WG][144];
   __shared__ double Ts[K8_CAMS_PER_WG][144];
   const int q = threadIdx.x >> 4, l = threadIdx.x & 15;
@@ -582,7 +582,9 @@ POVAR_KERNEL __launch_bounds__(K8_THREADS) void cam_build_binv_h(Dp d, double la
   if (!in)
     for (int e = l; e < 144; e += 16) A[e] = (e / 12 == e % 12) ? 1.0 : 0.0;
   __syncthreads();
-  chol_inverse_16<11>(A, l, in ? d.binv + 144 * (size_t)c : nullptr);  // 11x11 row-major in the first 121 entries
+  const bool fx = in && fixed[c] != 0;
+  chol_inverse_16<11>(A, l, in && !fx ? d.binv + 144 * (size_t)c : nullptr);  // 11x11 row-major in the first 121 entries
+  if (fx) binv_zero_block(d.binv + 144 * (size_t)c, l, 121);
 }
 
 // tangent projection of a per-camera 12-vector: out11 = N_c^T (in12)

@@ -159,10 +159,12 @@ POVAR_KERNEL __launch_bounds__(1024) void cam_sum_parts60(Dp d, const double* pa
 // in step 2 (N_c^T A N_c), + lambda I.  out_mat receives A (dim x dim row-major), out_inv its
 // inverse by Cholesky of the upper triangle (preconditioner.hpp:104-107 / LPV:145-148).
 // One thread per camera, matrices in LDS [element][thread] like cam_build_binv.
+// fixed[c] != 0 (povar_set_fixed_cameras): out_inv's block is zero -- PCG then iterates on the free cameras' system alone;
+// out_mat (B_c) is what it always is.
 constexpr int K8_SC_THREADS = 32;  // one thread per camera (explicit-SC path: not tuned further)
 template <bool HOM>
 __global__ __launch_bounds__(K8_SC_THREADS) void cam_build_sc(Dp d, double lambda, const double* ncw, const double* dm,
-                                                           double* out_inv, double* out_mat) {
+                                                           double* out_inv, double* out_mat, const uint8_t* fixed) {
   __shared__ double A[144 * K8_SC_THREADS];
   __shared__ double X[144 * K8_SC_THREADS];
   const int t = threadIdx.x;
@@ -213,7 +215,10 @@ __global__ __launch_bounds__(K8_SC_THREADS) void cam_build_sc(Dp d, double lambd
     for (int i = 0; i < DIM; ++i)
       for (int j = 0; j < DIM; ++j) o[DIM * i + j] = A_(i, j);
   }
-  if (out_inv) {
+  if (out_inv && fixed[c] != 0) {
+    double* o = out_inv + 144 * (size_t)c;
+    for (int e = 0; e < DIM * DIM; ++e) o[e] = 0.0;
+  } else if (out_inv) {
     for (int j = 0; j < DIM; ++j) {
       double dd = A_(j, j);
       for (int k = 0; k < j; ++k) dd -= A_(j, k) * A_(j, k);

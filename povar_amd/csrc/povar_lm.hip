@@ -352,8 +352,15 @@ static int lm_prepare(povar_ctx* c, int step, double lambda, int32_t solver_type
   }
   if (int rc = allreduce(c, c->d.b, (step == 1 ? 12 : 11) * (size_t)c->n_cams)) return rc;
   const dim3 k8_grid(grid_for(c->n_cams, K8_CAMS_PER_WG));
-  if (step == 1) hipLaunchKernelGGL(cam_build_binv, k8_grid, dim3(K8_THREADS), 0, c->stream, c->d, lambda);
-  else hipLaunchKernelGGL(cam_build_binv_h, k8_grid, dim3(K8_THREADS), 0, c->stream, c->d, lambda, ncw);
+  if (c->fixed_dirty) {  // povar_set_fixed_cameras since the last preparation: this system is the first to see the set
+    HIP_TRY(hipMemcpyAsync(c->fixed_mask.p, c->fixed_next.data(), c->fixed_next.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (fixed_next is pageable and may be rewritten by the caller's next call)
+    c->n_fixed = (int)std::count(c->fixed_next.begin(), c->fixed_next.end(), (uint8_t)1);
+    c->fixed_dirty = false;
+  }
+  const uint8_t* fixed = c->fixed_mask.p;
+  if (step == 1) hipLaunchKernelGGL(cam_build_binv, k8_grid, dim3(K8_THREADS), 0, c->stream, c->d, lambda, fixed);
+  else hipLaunchKernelGGL(cam_build_binv_h, k8_grid, dim3(K8_THREADS), 0, c->stream, c->d, lambda, ncw, fixed);
   if (step == 1)  // (only step 1 has stored tiles)
     if (int rc = ensure_tiles(c)) return rc;
   // the one-off choice between the term kernels is part of the preparation, not of the first solve's time

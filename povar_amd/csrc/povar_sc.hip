@@ -38,9 +38,9 @@ int build_schur_jacobi(povar_ctx* c, double lambda) {
   if (int rc = allreduce(c, c->sc.dm, 60 * (size_t)c->n_cams)) return rc;
   const dim3 g(grid_for(c->n_cams, K8_SC_THREADS)), b(K8_SC_THREADS);
   hipLaunchKernelGGL((cam_build_sc<HOM>), g, b, 0, c->stream, c->d, lambda, c->sc.ncw, (const double*)nullptr,
-                     (double*)nullptr, c->sc.bmat);
+                     (double*)nullptr, c->sc.bmat, (const uint8_t*)c->fixed_mask.p);
   hipLaunchKernelGGL((cam_build_sc<HOM>), g, b, 0, c->stream, c->d, lambda, c->sc.ncw, (const double*)c->sc.dm,
-                     c->sc.minv, (double*)nullptr);
+                     c->sc.minv, (double*)nullptr, (const uint8_t*)c->fixed_mask.p);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -169,7 +169,10 @@ static int chol_factor(povar_ctx* c, int dim, const double* Q, int nq, double* s
   prof_mark(c, -1);
   HIP_TRY(hipGetLastError());
   if (int rc = allreduce(c, M, count)) return rc;
-  if (stat) hipLaunchKernelGGL(cov_diag_scan, dim3(1), dim3(256), 0, c->stream, (const double*)M, ld, n, 0, stat);
+  const uint8_t* fixed = c->fixed_mask.p;
+  // fixed cameras: identity rows and columns, right-hand side 0 -- whichever assembly ran, on every rank alike
+  if (c->n_fixed > 0) hipLaunchKernelGGL(sc_fix_cameras, dim3(c->n_cams), dim3(256), 0, c->stream, M, ld, N, dim, fixed);
+  if (stat) hipLaunchKernelGGL(cov_diag_scan, dim3(1), dim3(256), 0, c->stream, (const double*)M, ld, n, 0, stat, fixed, dim);
   for (int K0 = 0; K0 < N; K0 += CH_OB) {
     const int kdepth = std::min(CH_OB, N - K0), R0 = K0 + kdepth;
     for (int k0 = K0; k0 < R0; k0 += CH_NB) {
@@ -184,7 +187,7 @@ static int chol_factor(povar_ctx* c, int dim, const double* Q, int nq, double* s
       hipLaunchKernelGGL(chol_syrk_outer, dim3((unsigned)((N - R0) / CH_T + 1), (unsigned)((N - R0 + CH_T - 1) / CH_T)),
                          dim3(256), 0, c->stream, M, ld, K0, kdepth);
   }
-  if (stat) hipLaunchKernelGGL(cov_diag_scan, dim3(1), dim3(256), 0, c->stream, (const double*)M, ld, n, 1, stat);
+  if (stat) hipLaunchKernelGGL(cov_diag_scan, dim3(1), dim3(256), 0, c->stream, (const double*)M, ld, n, 1, stat, fixed, dim);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -357,10 +360,18 @@ static int cov_inverse(povar_ctx* c, int dim, const char* who, bool have_out, do
                        CovInverse& f, std::optional<TimeScope>& ts) {
   if (int rc = check_ctx(c)) return rc;
   if (!have_out) return fail(-1, std::string(who) + ": null argument");
-  if (gauge != POVAR_COV_FREE_GAUGE && gauge != POVAR_COV_DAMPED) return fail(-1, std::string(who) + ": unknown gauge");
+  if (gauge != POVAR_COV_FREE_GAUGE && gauge != POVAR_COV_DAMPED && gauge != POVAR_COV_FIXED_GAUGE)
+    return fail(-1, std::string(who) + ": unknown gauge");
   if (coords != POVAR_COV_CAMERA_COORDS && coords != POVAR_COV_SOLVER_COORDS) return fail(-1, std::string(who) + ": unknown coords");
   if (gauge == POVAR_COV_FREE_GAUGE && lambda != 0.0) return fail(-1, std::string(who) + ": POVAR_COV_FREE_GAUGE takes lambda = 0");
   if (gauge == POVAR_COV_DAMPED && !(lambda > 0.0)) return fail(-1, std::string(who) + ": POVAR_COV_DAMPED takes lambda > 0");
+  // (the set as the caller left it: the preparation below is the one that installs it)
+  const bool any_fixed = std::find(c->fixed_next.begin(), c->fixed_next.end(), (uint8_t)1) != c->fixed_next.end();
+  if (gauge == POVAR_COV_FIXED_GAUGE && lambda != 0.0) return fail(-1, std::string(who) + ": POVAR_COV_FIXED_GAUGE takes lambda = 0");
+  if (gauge == POVAR_COV_FIXED_GAUGE && !any_fixed)
+    return fail(-1, std::string(who) + ": POVAR_COV_FIXED_GAUGE needs fixed cameras (povar_set_fixed_cameras)");
+  if (gauge == POVAR_COV_FREE_GAUGE && any_fixed)
+    return fail(-1, std::string(who) + ": POVAR_COV_FREE_GAUGE with fixed cameras: the gauge they fix is POVAR_COV_FIXED_GAUGE");
   if (int rc = prepare_sc(c, dim, lambda)) return rc;
   const size_t nc = c->n_cams;
   static_cast<DenseDims&>(f) = dense_dims(dim, c->n_cams);
@@ -380,16 +391,20 @@ static int cov_inverse(povar_ctx* c, int dim, const char* who, bool have_out, do
     HIP_TRY(hipStreamSynchronize(c->stream));  // (Q is pageable host memory that goes out of scope)
     f.q = c->sc_cov_q.p;
   }
-  // (the pivot scan belongs to the free gauge: the damped mode judges by chol_diag's info alone)
-  if (int rc = chol_factor(c, dim, f.q, f.nq, free_gauge ? c->sc_cov_stat.p : nullptr)) return rc;
+  // (the pivot scan belongs to the undamped gauges: the damped mode judges by chol_diag's info alone)
+  const bool scan = free_gauge || gauge == POVAR_COV_FIXED_GAUGE;
+  if (scan && !free_gauge)
+    if (int rc = cov_buffer(c, c->sc_cov_stat, 2, dim)) return rc;
+  if (int rc = chol_factor(c, dim, f.q, f.nq, scan ? c->sc_cov_stat.p : nullptr)) return rc;
   c->sc_factor_dim = c->sc_factor_n = 0;  // (R becomes R^-1 below: not the factor POVAR_BUF_SC_FACTOR hands out)
   int info = 0;
   double st[2] = {0, 0};
   HIP_TRY(hipMemcpyAsync(&info, c->sc_info.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  if (free_gauge) HIP_TRY(hipMemcpyAsync(st, c->sc_cov_stat.p, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (scan) HIP_TRY(hipMemcpyAsync(st, c->sc_cov_stat.p, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   if (info != 0) return POVAR_NUMERIC_FAILURE;  // not positive definite: CHOLESKY's own rule
-  if (free_gauge) {
+  if (scan) {
+    // (fixed gauge: the same rule on S_ff(0), whose fixed cameras must have taken the whole gauge)
     // a gauge-only system keeps pivots of the order of its smallest eigenvalue; further degeneracy leaves rounding
     // noise of the order u max A_kk: the threshold sqrt(u) max A_kk sits in the gap
     const double thr = std::sqrt(std::ldexp(1.0, -53)) * st[0];
@@ -416,6 +431,9 @@ static int cov_inverse(povar_ctx* c, int dim, const char* who, bool have_out, do
     hipLaunchKernelGGL(cov_trmm, dim3(j), dim3(256), 0, c->stream, (const double*)M, ld, (const double*)panel, (int64_t)CH_NB,
                        M + k0, ld, 1, j, -1.0);
   }
+  // fixed cameras: W_kk = 0 on their rows, so C and everything taken from it is zero there
+  if (c->n_fixed > 0)
+    hipLaunchKernelGGL(cov_fix_cameras, dim3(grid_for(f.n, 256)), dim3(256), 0, c->stream, M, ld, f.n, dim, (const uint8_t*)c->fixed_mask.p);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -772,6 +790,29 @@ int povar_set_cov_inspect(povar_ctx* c, int32_t enable) {
   if (int rc = check_ctx(c)) return rc;
   c->cov_inspect = enable ? 1 : 0;
   return 0;
+}
+
+int povar_set_fixed_cameras(povar_ctx* c, const int32_t* cam_ids, int32_t n_ids) {
+  if (int rc = check_ctx(c)) return rc;
+  if (n_ids < 0) return fail(-1, "povar_set_fixed_cameras: negative n_ids");
+  std::vector<uint8_t> next((size_t)c->n_cams, 0);
+  for (int i = 0; cam_ids && i < n_ids; ++i) {
+    if (cam_ids[i] < 0 || cam_ids[i] >= c->n_cams) return fail(-1, "povar_set_fixed_cameras: camera id out of range");
+    next[(size_t)cam_ids[i]] = 1;
+  }
+  if (next != c->fixed_next) c->fixed_dirty = true;  // (the next preparation uploads it: povar_lm.hip, lm_prepare)
+  c->fixed_next.swap(next);
+  return 0;
+}
+
+int povar_fixed_cameras(povar_ctx* c, int32_t* flags) {
+  if (int rc = check_ctx(c)) return rc;
+  int count = 0;
+  for (int k = 0; k < c->n_cams; ++k) {
+    count += c->fixed_next[(size_t)k];
+    if (flags) flags[k] = c->fixed_next[(size_t)k];
+  }
+  return count;
 }
 
 int povar_set_sc_assembly(povar_ctx* c, int32_t mode) {
