@@ -6,6 +6,8 @@
 //   povar_series.hip   the term loop: E0 / B^-1 launchers, kernel choice by timing, hipGraph, the series entry points
 //   povar_comm.hip     exchange steps: RCCL / host-hook all-reduce, the peer-to-peer term exchange
 //   povar_sc.hip       explicit-Schur-complement solvers (PCG / CHOLESKY / RIPCG / RICHOLESKY)
+//   povar_cov.hip      the covariance calls on CHOLESKY's factor: camera, landmark, observation rows, hat rows, pair blocks
+//   cov_plan.hpp       what a covariance call decides on the host alone: argument rules, requests, gauge basis, pivot rule
 //   dev_buf.hpp        DevBuf<T>, the self-freeing device allocation every buffer of the context is
 // Device code: povar_kernels*.hpp (kernels that are not templates have internal linkage: every unit compiles what it launches).
 #pragma once
@@ -43,6 +45,7 @@
 #include "povar_kernels_ck_f32.hpp"
 #include "res_layout.hpp"
 #include "create_plan.hpp"
+#include "cov_plan.hpp"
 #include "povar_kernels_res.hpp"
 
 using namespace povar;
@@ -257,24 +260,38 @@ struct povar_ctx : CtxSwitches {  // (create_plan.hpp: the switches povar_create
   int sc_assembly = -1, sc_assembly_last = 0;
   int sc_factor_dim = 0;                 // POVAR_BUF_SC_FACTOR: the system whose R, y (sc_dense) and x (sc_xpad) are in place:
   int sc_factor_n = 0;                   // 12 (step 1) or 11 (step 2) and dim * n_cams; 0: none (chol_factor, the covariance calls)
-  // camera covariance (povar_camera_covariance_*), grown on demand and kept: the gauge basis Q, (max A_kk, min R_kk^2), the
-  // N x 64 scratch panel of the triangular inverse, the [n_cams][144] blocks
-  DevBuf<double> sc_cov_q, sc_cov_stat, sc_cov_panel, sc_cov_blocks;
-  DevBuf<double> sc_cov_lm;              // povar_landmark_covariance_*: the requested landmark blocks and their ids, kept likewise
-  DevBuf<int> sc_cov_ids;
-  DevBuf<double> sc_cov_obs;             // povar_observation_covariance_* / _hat_*: the rows (4, or 14 / 5 per observation) and the first
-  DevBuf<int> sc_cov_row0;               // row of every requested landmark, kept likewise (Sigma_l without the gauge part goes to sc_cov_lm)
-  DevBuf<double> sc_cov_pair_out;        // povar_covariance_blocks_*: the blocks in request order, the three index lists (a, b,
-  DevBuf<int> sc_cov_pair_items;         // transposed, -) one after the other and where every block starts, kept likewise
-  DevBuf<long long> sc_cov_pair_off;
-  // inspection of the covariance path (povar_set_cov_inspect, POVAR_BUF_COV_*).  sc_cov_kind: what the last call that wrote
-  // the dense matrix left there: 0 nothing to hand out (chol_factor, a failure), 1 a camera call's W, 2 a landmark call's W, C
-  // and panel; sc_cov_n as sc_factor_n (dim * n_cams of that call); sc_cov_nq: columns of the gauge basis of that call (0:
-  // damped); sc_cov_kept: that call copied its R into sc_cov_r (N x N, row-major, allocated only with the switch on)
-  int cov_inspect = 0;
-  int sc_cov_kind = 0, sc_cov_n = 0, sc_cov_nq = 0;
-  bool sc_cov_kept = false;
-  DevBuf<double> sc_cov_r;
+  // the covariance calls (povar_cov.hip): their buffers, grown on demand and kept, and what POVAR_BUF_COV_* may hand out
+  struct CovState {
+    // camera calls: the gauge basis Q, (max A_kk, min R_kk^2), the N x 64 scratch panel of the triangular inverse, the
+    // [n_cams][144] blocks
+    DevBuf<double> q, stat, panel, blocks;
+    DevBuf<double> lm;                   // povar_landmark_covariance_*: the requested landmark blocks and their ids
+    DevBuf<int> ids;
+    DevBuf<double> obs;                  // povar_observation_covariance_* / _hat_*: the rows (4, or 14 / 5 per observation) and the first
+    DevBuf<int> row0;                    // row of every requested landmark (Sigma_l without the gauge part goes to lm)
+    DevBuf<double> pair_out;             // povar_covariance_blocks_*: the blocks in request order, the three index lists (a, b,
+    DevBuf<int> pair_items;              // transposed, -) one after the other and where every block starts
+    DevBuf<long long> pair_off;
+    // inspection of the covariance path (povar_set_cov_inspect, POVAR_BUF_COV_*).  kind: what the last call that wrote the dense
+    // matrix left there: 0 nothing to hand out (chol_factor, a failure), 1 a camera call's W, 2 a landmark call's W, C and
+    // panel; n as sc_factor_n (dim * n_cams of that call); nq: columns of the gauge basis of that call (0: damped); kept: that
+    // call copied its R into r (N x N, row-major, allocated only with the switch on)
+    int inspect = 0;
+    int kind = 0, n = 0, nq = 0;
+    bool kept = false;
+    DevBuf<double> r;
+    // the dense matrix, Q or the panel are about to be rewritten: nothing to hand out until a call is done
+    void invalidate() {
+      kind = n = nq = 0;
+      kept = false;
+    }
+    // a covariance call has returned 0 (kind 1: W alone is in place, 2: W, C and the panel)
+    void done(int kind_, int n_, int nq_) {
+      kind = kind_;
+      n = n_;
+      nq = nq_;
+    }
+  } cov;
 
   // fixed cameras (povar_set_fixed_cameras): fixed_next is the caller's set, fixed_mask its device copy as of the last
   // preparation (lm_prepare uploads it when fixed_dirty: a system prepared earlier is what it was), n_fixed the cameras
@@ -530,6 +547,37 @@ void p2p_dp(povar_ctx* c, Dp& dt);  // povar_comm.hip
 int ensure_sc(povar_ctx* c);  // povar_sc.hip
 int e0_dense(povar_ctx* c);  // povar_sc.hip
 int run_cholesky(povar_ctx* c, int dim, int32_t* num_iterations, int32_t* termination);  // povar_sc.hip (dim: 12 step 1, 11 step 2)
+int prepare_sc(povar_ctx* c, int dim, double lambda);  // povar_sc.hip
+int chol_factor(povar_ctx* c, int dim, const double* Q, int nq, double* stat);  // povar_sc.hip
+int no_memory(int dim, int n_cams, const char* what, size_t bytes);  // povar_sc.hip
+
+// The run-time block dimension (12: step 1, 11: step 2) to the step type of the dense kernels: fn(ScdPose()) or fn(ScdJoint()),
+// so every launch templated on the step is written once
+template <class F>
+auto with_step(int dim, F fn) {
+  return dim == 12 ? fn(ScdPose()) : fn(ScdJoint());
+}
+
+// A device buffer the context keeps (counted in povar_device_bytes), grown to `count` elements once the stream has drained.
+// `headroom` > 0: the device must have that many bytes free beside the new buffer, else hipErrorOutOfMemory without trying.
+// On an error the buffer is empty.
+template <typename T>
+hipError_t grow_buffer(povar_ctx* c, DevBuf<T>& buf, size_t count, size_t headroom = 0) {
+  if (buf.p && buf.n >= count) return hipSuccess;
+  if (buf.p) {
+    if (hipError_t e = hipStreamSynchronize(c->stream)) return e;
+    c->bytes -= buf.n * sizeof(T);
+    buf.release();
+  }
+  size_t free_b = 0, total_b = 0;
+  if (headroom > 0) {
+    if (hipError_t e = hipMemGetInfo(&free_b, &total_b)) return e;
+    if (count * sizeof(T) + headroom > free_b) return hipErrorOutOfMemory;
+  }
+  const hipError_t e = buf.alloc(count, &c->bytes);
+  if (e != hipSuccess) (void)hipGetLastError();
+  return e;
+}
 
 // Geometry of the augmented dense matrix of CHOLESKY / RICHOLESKY and the covariance calls (povar_kernels_chol.hpp): n = dim *
 // n_cams rows, N = n rounded up to the 64-row panel, row stride ld, and the doubles of the allocation (slack rows / columns for

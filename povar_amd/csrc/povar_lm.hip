@@ -625,25 +625,25 @@ int povar_get_buffer(povar_ctx* c, int32_t which, double* out, int64_t n) {
     case POVAR_BUF_COV_INVERSE:
     case POVAR_BUF_COV_PANEL:
     case POVAR_BUF_COV_GAUGE: {
-      if (c->sc_cov_kind == 0 || !c->sc_dense.p)
+      if (c->cov.kind == 0 || !c->sc_dense.p)
         return fail(-1, "povar_get_buffer: POVAR_BUF_COV_*: no covariance in place (the last call that wrote the dense matrix "
                         "must be a povar_*_covariance_* call that returned 0)");
-      const DenseDims g = dense_dims(c->sc_cov_n / c->n_cams, c->n_cams);  // (sc_cov_n = dim * n_cams, n_cams > 0)
+      const DenseDims g = dense_dims(c->cov.n / c->n_cams, c->n_cams);  // (cov.n = dim * n_cams, n_cams > 0)
       const size_t N = g.N, ld = g.ld;
       if (which == POVAR_BUF_COV_GAUGE) {
-        if (c->sc_cov_nq == 0 || !c->sc_cov_q.p) return fail(-1, "povar_get_buffer: POVAR_BUF_COV_GAUGE: the last covariance call was damped");
-        return copy(c->sc_cov_q.p, (size_t)c->sc_cov_n * (size_t)c->sc_cov_nq);
+        if (c->cov.nq == 0 || !c->cov.q.p) return fail(-1, "povar_get_buffer: POVAR_BUF_COV_GAUGE: the last covariance call was damped");
+        return copy(c->cov.q.p, (size_t)c->cov.n * (size_t)c->cov.nq);
       }
       if (which == POVAR_BUF_COV_PANEL) {
-        if (c->sc_cov_kind != 2 || !c->sc_cov_panel.p)
+        if (c->cov.kind != 2 || !c->cov.panel.p)
           return fail(-1, "povar_get_buffer: POVAR_BUF_COV_PANEL: the last covariance call was not a landmark call with landmarks");
-        return copy(c->sc_cov_panel.p, N * CH_NB);
+        return copy(c->cov.panel.p, N * CH_NB);
       }
-      if (which == POVAR_BUF_COV_FACTOR && (!c->sc_cov_kept || !c->sc_cov_r.p))
+      if (which == POVAR_BUF_COV_FACTOR && (!c->cov.kept || !c->cov.r.p))
         return fail(-1, "povar_get_buffer: POVAR_BUF_COV_FACTOR: povar_set_cov_inspect was off during the last covariance call");
       if ((size_t)n != N * N) return fail(-1, "povar_get_buffer: wrong size");
       if (which == POVAR_BUF_COV_FACTOR)
-        HIP_TRY(hipMemcpyAsync(out, c->sc_cov_r.p, N * N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(out, c->cov.r.p, N * N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
       else
         HIP_TRY(hipMemcpy2DAsync(out, N * sizeof(double), c->sc_dense.p, ld * sizeof(double), N * sizeof(double), N, hipMemcpyDeviceToHost,
                                  c->stream));

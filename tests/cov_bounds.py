@@ -1,4 +1,4 @@
-"""Componentwise, condition-free bounds for the covariance path (povar_sc.hip: cov_inverse, cov_camera_blocks,
+"""Componentwise, condition-free bounds for the covariance path (povar_cov.hip: cov_inverse, cov_camera_blocks,
 landmark_covariance, observation_covariance; povar_kernels_cov.hpp), stage by stage on the device's own intermediates (helper module of
 tests/test_cov_bounds.py and tests/test_gpu_cov_bounds.py; not a test module).  The last stage of the path, the covariance
 blocks of parameter pairs (covariance_blocks: pair_cc, pair_cl, pair_ll), is held in the same way on the same C and Q by
@@ -10,20 +10,20 @@ without rounding (sc_bounds.exact_gram for W W^T and R^T R, exact_matmul below f
 slicing leaves out is added to every bound.  An MFMA accumulation counts as "K products in any order": g(K).  Line numbers
 are those of povar_kernels_cov.hpp unless a file is named.
 
-ASSEMBLY  chol_factor (povar_sc.hip:61-132) with Q: the FACTOR identity of sc_bounds.py on the kept R,
+ASSEMBLY  chol_factor (povar_sc.hip) with Q: the FACTOR identity of sc_bounds.py on the kept R,
               |S_ref(lambda) + Q_dev Q_dev^T - R^T R|_ij <= g(k_f(i)) (|R^T| |R|)_ij + E(S)_ij + E(QQ)_ij       (i <= j < n)
           with S_ref, E(S) from sc_bounds.dense_system at the call's lambda (0 in the free gauge) and, for cov_add_qqt (:29-41),
           the nq-term dot `s += qi[k] * qj[k]` (:38: g(nq)) and `M += s` (:39): one more summand of the entry's atomic sum, i.e.
           g(cnt + shards + 1) on |Q| |Q|^T and one more rounding u on the other summands:
               E(QQ) = (g(nq) + g(cnt + shards + 1)) |Q| |Q|^T + u Sm.
-          Damped calls have no Q term.  cov_add_qqt runs on rank 0 only (povar_sc.hip:96-103): with two shards the term enters
+          Damped calls have no Q term.  cov_add_qqt runs on rank 0 only (povar_sc.hip: chol_factor): with two shards the term enters
           once.  Rows and columns [n, N) of R are the identity's, bit for bit (chol_pad).
-GAUGE     gauge_basis (povar_sc.hip:249-303): twice-applied modified Gram-Schmidt.  Diagonal: the n-term dot of positive terms
+GAUGE     gauge_basis (cov_plan.hpp): twice-applied modified Gram-Schmidt.  Diagonal: the n-term dot of positive terms
           (g(n)), the root (1) squared (2), every division (1) squared (2):  |q_k . q_k - 1| <= g(n + 4).  Off the diagonal, j < k:
           in the second pass t = q_j . v carries g(n) |q_j| . |v|; the update of step j and of every later step of that pass
           rounds v twice per entry (product, difference): 2 (k - j) u |q_j| . |v|; the later steps' own corrections t' q_j'
           move q_j . v by t' (q_j . q_j'), a product of two quantities of the order u kappa(V): second order, dropped as
-          everywhere here (the call itself refuses a column that loses more than 1e-8 of its norm, povar_sc.hip:296); the
+          everywhere here (the call itself refuses a column that loses more than 1e-8 of its norm, cov_plan.hpp: gauge_basis); the
           norm and the division (n + 4 halves, 1):  |q_j . q_k| <= g(n + 2 nq + 4) |q_j| . |q_k|.  Columns on disjoint supports
           (step 1: generators of different gj) are orthogonal exactly: the bound is 0 there.
           Span (gauge_span): every long-double generator v built from the caller's cameras and the reference's sigma and
@@ -31,13 +31,13 @@ GAUGE     gauge_basis (povar_sc.hip:249-303): twice-applied modified Gram-Schmid
           with kappa_2(V_ref) the condition number of the 12- or 15-column generator matrix -- a reference quantity computed
           from the reference, not the system's -- and E_rel(V) the largest relative operand error of a generator entry
           (E(sigma) / sigma; step 2: + the reflector's dNc and the g(40) of the a / N_c^T arithmetic).
-INVERSE   cov_inverse's loop (povar_sc.hip:377-385).  Diagonal block (cov_diag_inv :64-84): lane c forms row c from W R = I
+INVERSE   cov_inverse's loop (povar_cov.hip: cov_inverse).  Diagonal block (cov_diag_inv :64-84): lane c forms row c from W R = I
           left to right, `s += w[p] * R[p][j]` over p < j (:75; the terms p < c are exact zeros) and `-s / d` (:77): a product
           passes its own rounding and at most j - c - 1 additions, the division rounds once:
               |W_jj R_jj - I|_cj <= g(max(j - c, 1)) (|W_jj| |R_jj|)_cj =: D0_cj  (j >= c; below: W = 0 and the residual is 0).
           Block column j, block row i < j (cov_trmm :97-154): T^ = fl(R_0j W_jj) with k_first = 0, k_end = 1 (:123-125,
-          povar_sc.hip:381): 64 products, alpha = 1 exact; W^_ij = -fl(sum_{kb = i .. j-1} W_i,kb T^_kb) with k_first = i, k_end = j
-          (povar_sc.hip:383): 64 (j - i) products, alpha = -1 exact.  Left residual of the block:
+          the loop's first cov_trmm): 64 products, alpha = 1 exact; W^_ij = -fl(sum_{kb = i .. j-1} W_i,kb T^_kb) with k_first = i, k_end = j
+          (its second cov_trmm): 64 (j - i) products, alpha = -1 exact.  Left residual of the block:
               |(W R)_ij| <= A_i D0_j + (g(64) + g(64 (j - i))) (|W_lead| (|R_0j| |W_jj|))_i |R_jj|,  A_i = (|W_lead| |R_0j|)_i
           (|T^| <= (1 + g(64)) |R_0j| |W_jj|: first order).  Everything from the device's own R and W: no condition number.
           Exact: the strictly lower part of every diagonal block of W is zero (cov_diag_inv stores its zeros, :77-83: the
@@ -633,7 +633,7 @@ def _strided_sum(terms, lanes, order):
 
 
 def emulate_gauge(cams, sig, ncw, dim):
-    """gauge_basis (povar_sc.hip:249-303) in fp64: (Q [n, nq], ok)."""
+    """gauge_basis (cov_plan.hpp) in fp64: (Q [n, nq], ok)."""
     nq = 12 if dim == 12 else 15
     P, s = np.asarray(cams, dtype=F).reshape(-1, 12), np.asarray(sig, dtype=F).reshape(-1, 12)
     V = []
@@ -1035,7 +1035,7 @@ def emulate_case(p, joint, order, mutate=None, obs=True):
     inv, panel = emulate_lauum(W, order, mutate)
     lm = emulate_landmarks(p, q, inv, panel, Q, dim, order, mutate=mutate)
     d = dict(R=R, Q=Q, inv=inv, panel=panel, cam=cam, lm=lm, q=q, n=n, N=N, dim=dim)
-    if obs:  # obs_cov reads lm_cov's output with nq = 0 (povar_sc.hip:529), whatever the gauge
+    if obs:  # obs_cov reads lm_cov's output with nq = 0 (povar_cov.hip: observation_rows), whatever the gauge
         d["sig0"] = lm if Q is None else emulate_landmarks(p, q, inv, panel, None, dim, order)
         d["obs"] = emulate_observations(p, q, inv, panel, d["sig0"], dim, order)
     return d

@@ -1,4 +1,4 @@
-"""Componentwise, condition-free bounds for the covariance blocks of parameter pairs (povar_sc.hip: covariance_blocks;
+"""Componentwise, condition-free bounds for the covariance blocks of parameter pairs (povar_cov.hip: covariance_blocks;
 povar_kernels_cov.hpp: pair_cc, pair_cl, pair_ll), entry by entry on the device's own C and Q (helper module of
 tests/test_pair_bounds.py and tests/test_gpu_pair_bounds.py; not a test module).  The last stage of the covariance path of
 tests/cov_bounds.py, with its conventions: LD, g(k) rounded up, first order, a final factor ONE, `worst` / `flagged` /
@@ -95,7 +95,7 @@ def sides(dim, coords):
 
 
 def layout(pairs, dim, coords):
-    """(shape of every block, off [n + 1]: where each starts in the flat request) -- covariance_blocks' `total` (povar_sc.hip)."""
+    """(shape of every block, off [n + 1]: where each starts in the flat request) -- cov_pair_request's `total` (cov_plan.hpp)."""
     sd = sides(dim, coords)
     shapes = [(sd[int(ka)], sd[int(kb)]) for ka, _, kb, _ in pairs]
     return shapes, np.r_[0, np.cumsum([r * c for r, c in shapes])].astype(np.int64)
@@ -491,7 +491,7 @@ def _emu_ll(E, l, m, coords, mut):
 def emulate_pairs(p, q, inv, panel, Q, dim, order, pairs, coords, mutate=None):
     """The blocks of covariance_blocks for `pairs` in `coords`, in request order, from the buffers inv / panel (C through cov_at)
     and Q of an emulated or a real call and the fp64 staged operands q (sc_bounds._emu_pieces_*): the host's canonical order and
-    `tr` (povar_sc.hip: covariance_blocks), then pair_cc / pair_cl / pair_ll.  mutate: the defects of mutations_pairs."""
+    `tr` (cov_plan.hpp: cov_pair_request), then pair_cc / pair_cl / pair_ll.  mutate: the defects of mutations_pairs."""
     mut = mutate or {}
     E = _Emu(p, q, inv, panel, Q, dim, order)
     memo, out = {}, []

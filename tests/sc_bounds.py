@@ -42,7 +42,7 @@ PRECOND   S_cc = B_c - (E0 diagonal) from the sixty cm_gram_sc moments (:50-137)
           (:216-243), Higham 2nd ed. Thm 10.3 / 10.4: |S_cc,ref X_dev - I|_ij <= sum_k (g(3 dim + 1) sqrt(S_ii S_kk) + E(S_cc)_ik)
           |X_dev|_kj, and |X - X^T| <= |X| R + (|X| R)^T.
 
-FACTOR    chol_factor (povar_sc.hip:111-124) is right-looking with panels of 64 inside blocks of 256.  Entry (i, j), i <= j, of
+FACTOR    chol_factor (povar_sc.hip) is right-looking with panels of 64 inside blocks of 256.  Entry (i, j), i <= j, of
           the augmented matrix (j = N: the rhs) receives, in this order: one `*cp -= acc` of chol_syrk_outer per finished
           block (povar_kernels_chol.hpp:196-204; acc: 256 products in any order, MFMA accumulation included), one of chol_syrk
           per earlier panel of its own block (:127-135; 64 products), i mod 64 steps `a -= r r` of chol_diag (:56) or chol_trsm

@@ -293,7 +293,7 @@ def test_buffer_preconditions():
 
 # ======== OBSERVATION: the rows of povar_observation_covariance_* against the C of their own call
 def check_observation_call(ctx, sy, label, ids=None, stages=True):
-    """One observation call and the buffers it leaves (as a landmark call does: povar_sc.hip:544): the assembly, gauge,
+    """One observation call and the buffers it leaves (as a landmark call does: povar_cov.hip: cov_call): the assembly, gauge,
     inverse and lauum checks on them (stages) and every entry of every row against cov_bounds.observation_reference."""
     p = sy.p
     free = p.lam == 0.0

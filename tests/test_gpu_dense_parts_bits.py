@@ -9,7 +9,7 @@ cameras (104 cameras): both chunk loops of both steps' stagings repeat (chunks o
 256-row outer update runs, cov_lauum takes ten or more K steps and camera blocks straddle 64-edges.  Damped gauge: the free
 gauge rightly fails on a block-diagonal system.
 
-This guards refactors of povar_kernels_sc.hpp / _chol.hpp / _cov.hpp and povar_sc.hip: profiles/dense_parts_bits.txt compares
+This guards refactors of povar_kernels_sc.hpp / _chol.hpp / _cov.hpp, povar_sc.hip and povar_cov.hip: profiles/dense_parts_bits.txt compares
 the same buffers between two builds of the library."""
 import numpy as np
 import pytest
