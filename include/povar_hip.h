@@ -236,6 +236,34 @@ int povar_set_fixed_cameras(povar_ctx* ctx, const int32_t* cam_ids, int32_t n_id
 /* the number of fixed cameras (the set as the last povar_set_fixed_cameras left it); flags: n_cams entries 0 / 1, or null */
 int povar_fixed_cameras(povar_ctx* ctx, int32_t* flags /* n_cams or NULL */);
 
+/* ---- compacted dense system (opt-in).  The dense matrix of every dense call -- CHOLESKY / RICHOLESKY and the camera, landmark,
+ * observation, hat and pair covariance calls of both steps -- spans
+ *   mode 0 (default): all cameras, the fixed ones as identity rows: n = dim n_cams rows, camera c at row dim c (today's layout);
+ *   mode 1:           the free cameras only, in ascending camera id: A = S_ff (or S_ff(lambda)), n = dim (n_cams - |F|) rows.
+ * The mode takes effect, like the fixed set, at the next call that prepares a system.  An unknown mode is an argument error.  On
+ * a sharded context every rank passes the same mode.  PCG / RIPCG and the power series do not read it.
+ *   Solves in mode 1: the increment keeps the fixed-camera contract -- the entries on F are exactly +0.0, the free entries solve
+ * S_ff x_f = -b_f from the compact factor; num_iterations, termination and the not-positive-definite rule are unchanged.
+ *   Covariance in mode 1: the outputs are those of the fixed-set rules, [S_ff(0)]^-1 or [S_ff(lambda)]^-1 zero-padded on F,
+ * computed from the compact W and C (a block with a camera of F is exactly zero); the rules of gauge, coords and lambda are
+ * unchanged; the pivot rule is applied to all rows of the compact matrix.
+ *   Inspection buffers in mode 1: POVAR_BUF_SC_FACTOR, POVAR_BUF_COV_FACTOR, _INVERSE and _PANEL have N = the n of
+ * povar_dense_layout rounded up to 64, with the padding rows as documented there; no identity rows stand for fixed cameras: a
+ * camera is found through cam_row.  POVAR_BUF_COV_GAUGE (free gauge: F is empty), POVAR_BUF_SC_BLOCKDIAG and _PRECOND are as in
+ * mode 0.
+ *   F empty in mode 1: every call is bit for bit what it is in mode 0, and the map is dim c.
+ *   Every camera fixed in mode 1 (n = 0): no matrix is allocated and no factorisation is launched.  A solve returns all +0.0
+ * with status 0 and POVAR_LINEAR_SOLVER_SUCCESS; a covariance call returns the status mode 0 returns for the same request, camera
+ * blocks exactly zero and the landmark, observation, hat and pair outputs of mode 0 (the same kernels on the same nonzero
+ * operands); POVAR_BUF_SC_FACTOR and POVAR_BUF_COV_* are argument errors afterwards.
+ *   Memory: the dense matrix, the padded solution, the covariance panel, the kept factor of povar_set_cov_inspect and the
+ * all-reduce of a sharded context are sized by n; the out-of-memory message names the rows asked for. */
+int povar_set_dense_compaction(povar_ctx* ctx, int32_t mode);
+int povar_dense_compaction(povar_ctx* ctx);            /* the mode as last set; < 0 on error */
+/* Layout of the dense matrix the last dense call built: returns its row count n (0: none yet, or no camera in it; < 0 on error).
+ * cam_row: NULL, or n_cams entries: first row of camera c in that matrix, -1 for a camera that is not in it. */
+int povar_dense_layout(povar_ctx* ctx, int32_t* cam_row /* n_cams or NULL */);
+
 /* ---- explicit-Schur-complement solvers: LinearizorSC (solver/linearizor_sc.cpp), selected by
  * --solver-type-step-1 PCG | CHOLESKY and --solver-type-step-2 RIPCG (solver/linearizor.cpp:51-53,
  * 67-72), and --solver-type-step-2 RICHOLESKY (not in the reference).  The reduced camera system S x = b, S = (Hpp + lambda I) - E0, is solved without landmark
@@ -486,6 +514,9 @@ enum {
                               j >= i, S = R^T R; the columns j < i are unspecified), then y_i (R^T y = -b: column N of the
                               augmented matrix after the factorisation) and x_i (R x = y; the increment is x[0:dim n_cams]).
                               Rows and columns past dim n_cams are the padding: identity in R, 0 in y and x.
+                              With povar_set_dense_compaction(1) read n = the row count of povar_dense_layout for dim n_cams,
+                              here and in the three POVAR_BUF_COV_* below that are sized by N: x[0:n] is the increment of the
+                              free cameras in the order of cam_row.
                               Precondition: the last call that wrote the dense matrix was a CHOLESKY / RICHOLESKY solve
                               that found it positive definite; any other state (no direct solve yet, a failed
                               factorisation, a povar_*_covariance_* call since, which inverts R in place) is an argument

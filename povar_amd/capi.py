@@ -322,6 +322,23 @@ class Context:
         assert ids.size == n
         return ids
 
+    def set_dense_compaction(self, mode):
+        """0 (default): the dense matrix of CHOLESKY / RICHOLESKY and the covariance calls spans all cameras, the fixed ones as
+        identity rows; 1: it spans the free cameras only.  Takes effect, like the fixed set, at the next call that prepares a
+        system (include/povar_hip.h)."""
+        self._chk(self.L.povar_set_dense_compaction(self.h, C.c_int32(int(mode))))
+
+    def dense_compaction(self):
+        """The mode as last set."""
+        return self._chk(self.L.povar_dense_compaction(self.h), allow_numeric=True)
+
+    def dense_layout(self):
+        """(n, cam_row) of the dense matrix the last dense call built: its row count (0: none yet, or no camera in it) and the
+        first row of every camera in it, -1 for a camera that is not."""
+        rows = np.full(self.n_cams, -1, dtype=np.int32)
+        n = self._chk(self.L.povar_dense_layout(self.h, _p(rows)), allow_numeric=True)
+        return n, rows
+
     # explicit-Schur-complement solvers (LinearizorSC: PCG / CHOLESKY / RIPCG)
     def set_jl_col_scaling(self, enable):
         self._chk(self.L.povar_set_jl_col_scaling(self.h, C.c_int32(1 if enable else 0)))
@@ -515,14 +532,16 @@ class Context:
             out = np.zeros(n)
             self._chk(self.L.povar_get_buffer(self.h, C.c_int32(which), _p(out), C.c_int64(n)))
             return out
-        if which == BUF_SC_FACTOR:  # [N, N + 2]: R (upper), y, x; N = dim n_cams rounded up to 64
-            N = ((11 if joint else 12) * self.n_cams + 63) // 64 * 64
+        # the four dense buffers: n = the rows of the matrix the last dense call built (dense_layout: dim n_cams, or the free
+        # cameras' alone); with none in place the call below is the library's argument error
+        rows = self.dense_layout()[0] or (11 if joint else 12) * self.n_cams
+        if which == BUF_SC_FACTOR:  # [N, N + 2]: R (upper), y, x; N = n rounded up to 64
+            N = (rows + 63) // 64 * 64
             out = np.zeros(N * (N + 2))
             self._chk(self.L.povar_get_buffer(self.h, C.c_int32(which), _p(out), C.c_int64(out.size)))
             return out.reshape(N, N + 2)
         if which in (BUF_COV_FACTOR, BUF_COV_INVERSE, BUF_COV_PANEL, BUF_COV_GAUGE):
-            dim = 11 if joint else 12  # [N, N], [N, N], [N, 64], [n, nq]; N = n = dim n_cams rounded up to 64
-            n = dim * self.n_cams
+            n = rows  # [N, N], [N, N], [N, 64], [n, nq]; N = n rounded up to 64
             N = (n + 63) // 64 * 64
             shape = {BUF_COV_FACTOR: (N, N), BUF_COV_INVERSE: (N, N), BUF_COV_PANEL: (N, 64), BUF_COV_GAUGE: (n, 15 if joint else 12)}[which]
             out = np.zeros(shape)

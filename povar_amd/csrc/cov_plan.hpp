@@ -1,6 +1,7 @@
 // cov_plan.hpp -- what a covariance call (povar_cov.hip) decides before it touches the device: the argument rules of gauge, lambda,
 // coords and the fixed set, the landmark request (ids to rows), the pair request (pairs to three canonical lists), the gauge basis
-// of the free gauge and the pivot rule.  Host-only plain C++17 (no HIP, no context): tests/cpp/cov_plan_check.cpp holds every rule
+// of the free gauge and the pivot rule -- and the layout of the dense matrix they share with CHOLESKY / RICHOLESKY (cam_row_map;
+// tests/cpp/cam_row_map_check.cpp).  Host-only plain C++17 (no HIP, no context): tests/cpp/cov_plan_check.cpp holds every rule
 // to a table on the CPU.  The request functions return false with the message in *err, without the caller's name in front.
 #pragma once
 #include "../../include/povar_hip.h"
@@ -29,6 +30,21 @@ inline bool cov_check_mode(const char* who, int32_t gauge, int32_t coords, doubl
   if (gauge == POVAR_COV_FREE_GAUGE && any_fixed)
     return no(": POVAR_COV_FREE_GAUGE with fixed cameras: the gauge they fix is POVAR_COV_FIXED_GAUGE");
   return true;
+}
+
+// Layout of the dense matrix of CHOLESKY / RICHOLESKY and the covariance calls (povar_set_dense_compaction): rows[c] is the first
+// of the dim rows of camera c, -1 for a camera that is not in the matrix; the return value is the row count n.
+//   mode 0: every camera at dim c, fixed ones included (they become identity rows), n = dim n_cams;
+//   mode 1: the free cameras (fixed[c] == 0) alone, in ascending camera id, n = dim (n_cams - |F|).  No fixed camera: mode 0's map.
+inline int cam_row_map(const uint8_t* fixed, int n_cams, int dim, int mode, std::vector<int32_t>& rows) {
+  rows.assign((size_t)std::max(n_cams, 0), -1);
+  int n = 0;
+  for (int c = 0; c < n_cams; ++c) {
+    if (mode == 1 && fixed[c]) continue;
+    rows[(size_t)c] = n;
+    n += dim;
+  }
+  return n;
 }
 
 // A request of the landmark and observation calls: which landmarks (lm_ids null: all of them)

@@ -24,6 +24,8 @@ int main(int argc, char** argv) {
       seen[(size_t)id] = 1;
     }
     std::printf("fixed cameras: %d of %d\n", k, bal_problem.num_cameras());
+    if (options.solver.dense_compaction)  // --compact-fixed-cameras (no effect, and no line, without the set)
+      std::printf("dense system: compacted to the %d free cameras\n", bal_problem.num_cameras() - k);
     std::fflush(stdout);
   }
   bundle_adjust_manual(bal_problem, options.solver, &summary.solver, &summary.timing);

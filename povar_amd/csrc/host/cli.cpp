@@ -91,6 +91,7 @@ bool parse_bal_app_arguments(int argc, char** argv, BalAppOptions& o) {
   str("e0-mode", &o.solver.e0_mode);
   flag["deterministic"] = &o.solver.deterministic;
   flag["fp32-terms"] = &o.solver.fp32_terms;
+  flag["compact-fixed-cameras"] = &o.solver.dense_compaction;
   integer("device", &o.solver.device);
   integer("gpus", &o.solver.gpus);
   str("camera-covariance-path", &o.solver.camera_covariance_path);
@@ -160,7 +161,10 @@ bool parse_bal_app_arguments(int argc, char** argv, BalAppOptions& o) {
                   "  --fixed-cameras LIST\n"
                   "      not an option of the reference: hold these cameras constant in every solve of both steps (comma-separated ids\n"
                   "      and ranges a-b, in file order); the covariance outputs above are then those of the gauge the fixed cameras\n"
-                  "      define (zero blocks on them) instead of the free gauge.  One fixed camera does not fix the gauge\n");
+                  "      define (zero blocks on them) instead of the free gauge.  One fixed camera does not fix the gauge\n"
+                  "  --compact-fixed-cameras\n"
+                  "      with --fixed-cameras: CHOLESKY / RICHOLESKY and the covariance outputs build their dense matrix over the free\n"
+                  "      cameras only (same results; memory and factorisation scale with the free cameras).  No effect without it\n");
       return false;
     }
     if (a.rfind("--", 0) != 0) {

@@ -103,6 +103,8 @@ class LinearizorPowerVarprojHip : public Linearizor, public StateMirror {
       if (r == 0) check(povar_timings_enable(s.ctx, 1), "povar_timings_enable");
       // --fixed-cameras: the same set on every shard context (an empty one clears what a context taken over from step 1 holds)
       check(povar_set_fixed_cameras(s.ctx, options.fixed_cameras.data(), (int32_t)options.fixed_cameras.size()), "povar_set_fixed_cameras");
+      // --compact-fixed-cameras: likewise the layout of the dense matrix (0 again on a context taken over from step 1)
+      check(povar_set_dense_compaction(s.ctx, options.dense_compaction ? 1 : 0), "povar_set_dense_compaction");
     });
     cov_gauge_ = options.fixed_cameras.empty() ? POVAR_COV_FREE_GAUGE : POVAR_COV_FIXED_GAUGE;
     push_state();

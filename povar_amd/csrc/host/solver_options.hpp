@@ -95,6 +95,10 @@ struct SolverOptions {
   // the set non-empty the covariance outputs above are those of POVAR_COV_FIXED_GAUGE -- [S_ff(0)]^-1, zero on the fixed
   // cameras -- and their files say so.  One fixed camera does not fix the gauge (include/povar_hip.h).
   std::vector<int> fixed_cameras;
+  // --compact-fixed-cameras: the dense matrix of CHOLESKY / RICHOLESKY and the covariance outputs spans the free cameras only
+  // (povar_set_dense_compaction(1) on every shard context): memory and factorisation follow the window, the outputs are the
+  // same.  No effect without --fixed-cameras.
+  bool dense_compaction = false;
 
   // solver_options.cpp:41-51
   bool use_projection_validity_check() const { return optimized_cost != OptimizedCost::ERROR; }

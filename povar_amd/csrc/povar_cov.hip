@@ -12,7 +12,7 @@ namespace {
 template <typename T>
 int cov_buffer(povar_ctx* c, DevBuf<T>& buf, size_t count, int dim) {
   const hipError_t e = grow_buffer(c, buf, count);
-  if (e == hipErrorOutOfMemory) return no_memory(dim, c->n_cams, "covariance scratch", count * sizeof(T));
+  if (e == hipErrorOutOfMemory) return no_memory(dim, c->cam_row_n, "covariance scratch", count * sizeof(T));
   HIP_TRY(e);
   return 0;
 }
@@ -40,7 +40,7 @@ struct CovInverse : DenseDims {
 static int cov_inverse(povar_ctx* c, int dim, double lambda, int32_t gauge, CovInverse& f, std::optional<TimeScope>& ts) {
   if (int rc = prepare_sc(c, dim, lambda)) return rc;
   const size_t nc = c->n_cams;
-  static_cast<DenseDims&>(f) = dense_dims(dim, c->n_cams);
+  static_cast<DenseDims&>(f) = dense_dims(dim, c->cam_row_n / dim);  // (the cameras of the step's map: povar_set_dense_compaction)
   ts.emplace(c, 2);
   c->cov.invalidate();  // (from here on Q, the dense matrix and the panel are rewritten: POVAR_BUF_COV_* wait for CovState::done)
   const bool free_gauge = gauge == POVAR_COV_FREE_GAUGE;
@@ -63,6 +63,9 @@ static int cov_inverse(povar_ctx* c, int dim, double lambda, int32_t gauge, CovI
     if (int rc = cov_buffer(c, c->cov.stat, 2, dim)) return rc;
   if (int rc = chol_factor(c, dim, f.q, f.nq, scan ? c->cov.stat.p : nullptr)) return rc;
   c->sc_factor_dim = c->sc_factor_n = 0;  // (R becomes R^-1 below: not the factor POVAR_BUF_SC_FACTOR hands out)
+  // every camera fixed in the compacted layout: no matrix, and the answer of the full layout -- whose scan skips every row and
+  // whose pivot rule then passes -- is C = 0: the readers of C take exact zeros from the map alone
+  if (f.n == 0) return 0;
   int info = 0;
   double st[2] = {0, 0};
   HIP_TRY(hipMemcpyAsync(&info, c->sc_info.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -90,8 +93,9 @@ static int cov_inverse(povar_ctx* c, int dim, double lambda, int32_t gauge, CovI
     hipLaunchKernelGGL(cov_trmm, dim3(j), dim3(256), 0, c->stream, (const double*)M, ld, (const double*)panel, (int64_t)CH_NB,
                        M + k0, ld, 1, j, -1.0);
   }
-  // fixed cameras: W_kk = 0 on their rows, so C and everything taken from it is zero there
-  if (c->n_fixed > 0)
+  // fixed cameras: W_kk = 0 on their rows, so C and everything taken from it is zero there (the compacted matrix has no such
+  // row: the readers of C take the zeros from the map)
+  if (c->n_fixed > 0 && !c->compaction)
     hipLaunchKernelGGL(cov_fix_cameras, dim3(grid_for(f.n, 256)), dim3(256), 0, c->stream, M, ld, f.n, dim, (const uint8_t*)c->fixed_mask.p);
   HIP_TRY(hipGetLastError());
   return 0;
@@ -107,7 +111,7 @@ static int cov_camera_blocks(povar_ctx* c, int dim, const CovInverse& f, int32_t
   HIP_TRY(hipMemsetAsync(blocks, 0, out_count * sizeof(double), c->stream));
   with_step(dim, [&](auto step) {
     constexpr int DIM = decltype(step)::DIM;
-    hipLaunchKernelGGL(cov_gram<DIM>, dim3(c->n_cams), dim3(256), 0, c->stream, M, f.ld, f.n, blocks);
+    hipLaunchKernelGGL(cov_gram<DIM>, dim3(c->n_cams), dim3(256), 0, c->stream, M, f.ld, f.n, (const int*)c->cam_row.p, blocks);
     hipLaunchKernelGGL(cov_finish<DIM>, dim3(c->n_cams), dim3(256), 0, c->stream, blocks, f.q, f.nq,
                        (const double*)c->sigma.p, (const double*)c->ncw.p, coords);
   });
@@ -146,12 +150,13 @@ static int cov_call(povar_ctx* c, int dim, const CovCall& q, double lambda, int3
   if (rc != 0) return rc == POVAR_NUMERIC_FAILURE ? all_nan() : rc;
   if (!q.empty) {
     const int nb = f.N / CH_NB;
-    hipLaunchKernelGGL(cov_lauum, dim3((unsigned)(nb * (nb + 1) / 2)), dim3(256), 0, c->stream, c->sc_dense.p, f.ld, c->cov.panel.p, nb);
+    if (nb > 0)
+      hipLaunchKernelGGL(cov_lauum, dim3((unsigned)(nb * (nb + 1) / 2)), dim3(256), 0, c->stream, c->sc_dense.p, f.ld, c->cov.panel.p, nb);
     if (int rc2 = stage(f)) return rc2;
     HIP_TRY(hipStreamSynchronize(c->stream));  // (also: the request's lists are host memory that goes out of scope)
     if (!judge()) return all_nan();
   }
-  c->cov.done(q.empty ? 1 : 2, f.n, f.nq);
+  if (f.n > 0) c->cov.done(q.empty ? 1 : 2, f.n, f.nq);  // (no matrix: nothing for POVAR_BUF_COV_* to hand out)
   return 0;
 }
 
@@ -168,7 +173,7 @@ static void cov_lm_launch(povar_ctx* c, int dim, const CovInverse& f, const int*
   with_step(dim, [&](auto step) {
     hipLaunchKernelGGL(lm_cov<decltype(step)>, dim3(n_out), dim3(256), 0, c->stream, c->d, (const double*)c->ncw.p,
                        (const int*)c->sc_lm_slot0.p, (const int*)c->sc_lm_cnt.p, ids, (const double*)c->sc_dense.p, f.ld,
-                       (const double*)c->cov.panel.p, q, nq, coords, c->cov.lm.p);
+                       (const double*)c->cov.panel.p, (const int*)c->cam_row.p, q, nq, coords, c->cov.lm.p);
   });
 }
 
@@ -238,7 +243,8 @@ static int observation_rows(povar_ctx* c, int dim, bool hat, double lambda, int3
       const auto rows_kernel = hat ? obs_hat<S> : obs_cov<S>;
       hipLaunchKernelGGL(rows_kernel, dim3(r.n_out), dim3(256), 0, c->stream, c->d, (const double*)c->ncw.p,
                          (const int*)c->sc_lm_slot0.p, (const int*)c->sc_lm_cnt.p, ids, (const int*)c->cov.row0.p,
-                         (const double*)c->sc_dense.p, f.ld, (const double*)c->cov.panel.p, (const double*)c->cov.lm.p, c->cov.obs.p);
+                         (const double*)c->sc_dense.p, f.ld, (const double*)c->cov.panel.p, (const int*)c->cam_row.p,
+                         (const double*)c->cov.lm.p, c->cov.obs.p);
     });
     HIP_TRY(hipGetLastError());
     if (hat) HIP_TRY(hipMemcpyAsync(sig.data(), c->cov.lm.p, sig_count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -278,20 +284,21 @@ static int covariance_blocks(povar_ctx* c, int dim, double lambda, int32_t gauge
     }
     const double* M = c->sc_dense.p;
     const double* panel = c->cov.panel.p;
+    const int* rows = c->cam_row.p;
     with_step(dim, [&](auto step) {
       typedef decltype(step) S;
       auto items = [&](int k) { return reinterpret_cast<const int4*>(c->cov.pair_items.p) + first[k]; };
       auto off = [&](int k) { return (const long long*)c->cov.pair_off.p + first[k]; };
       if (r.list[0].size())
-        hipLaunchKernelGGL(pair_cc<S>, dim3(r.list[0].size()), dim3(192), 0, c->stream, items(0), off(0), M, f.ld, panel, f.q, f.nq,
+        hipLaunchKernelGGL(pair_cc<S>, dim3(r.list[0].size()), dim3(192), 0, c->stream, items(0), off(0), M, f.ld, panel, rows, f.q, f.nq,
                            (const double*)c->sigma.p, (const double*)c->ncw.p, coords, c->cov.pair_out.p);
       if (r.list[1].size())
         hipLaunchKernelGGL(pair_cl<S>, dim3(r.list[1].size()), dim3(256), 0, c->stream, c->d, (const double*)c->ncw.p,
-                           (const int*)c->sc_lm_slot0.p, (const int*)c->sc_lm_cnt.p, items(1), off(1), M, f.ld, panel, f.q, f.nq, coords,
+                           (const int*)c->sc_lm_slot0.p, (const int*)c->sc_lm_cnt.p, items(1), off(1), M, f.ld, panel, rows, f.q, f.nq, coords,
                            c->cov.pair_out.p);
       if (r.list[2].size())
         hipLaunchKernelGGL(pair_ll<S>, dim3(r.list[2].size()), dim3(256), 0, c->stream, c->d, (const double*)c->ncw.p,
-                           (const int*)c->sc_lm_slot0.p, (const int*)c->sc_lm_cnt.p, items(2), off(2), M, f.ld, panel, f.q, f.nq, coords,
+                           (const int*)c->sc_lm_slot0.p, (const int*)c->sc_lm_cnt.p, items(2), off(2), M, f.ld, panel, rows, f.q, f.nq, coords,
                            c->cov.pair_out.p);
     });
     HIP_TRY(hipGetLastError());

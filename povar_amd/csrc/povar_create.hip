@@ -712,6 +712,7 @@ static int upload_lane_obs(povar_ctx* c, const CreatePlan& plan, CreateJob& J) {
   HIP_TRY(room(c->fixed_mask, std::max<size_t>(nc, 1)));  // (povar_set_fixed_cameras: no camera is fixed)
   c->fixed_next.assign(nc, 0);
   HIP_TRY(hipMemsetAsync(c->fixed_mask.p, 0, std::max<size_t>(nc, 1), c->stream));
+  HIP_TRY(room(c->cam_row, std::max<size_t>(nc, 1)));  // (povar_set_dense_compaction: the first preparation fills it)
   HIP_TRY(hipMemsetAsync(c->flags.p, 0, sizeof(int) * 4, c->stream));
   HIP_TRY(hipMemsetAsync(c->lms4.p, 0, sizeof(double4) * nl, c->stream));
   HIP_TRY(hipMemsetAsync(c->cams4.p, 0, sizeof(double4) * 3 * nc, c->stream));

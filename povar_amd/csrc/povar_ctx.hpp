@@ -302,6 +302,16 @@ struct povar_ctx : CtxSwitches {  // (create_plan.hpp: the switches povar_create
   bool fixed_dirty = false;
   int n_fixed = 0;
 
+  // layout of the dense matrix (povar_set_dense_compaction; cov_plan.hpp: cam_row_map): compaction_next is the caller's mode,
+  // compaction / cam_row_dim / cam_row_n what the device map cam_row holds -- lm_prepare rebuilds and uploads it after the fixed
+  // set, when the set, the mode or the step's dim changed: every dense call of a step reads the step's own map.  An explicit
+  // argument of the assembly kernels, the scatter of the solution and the readers of C.  layout_*: the map of the matrix the
+  // last dense call built (povar_dense_layout; layout_n = 0 and no rows: none yet).
+  DevBuf<int> cam_row;
+  std::vector<int32_t> cam_row_host, layout_rows;
+  int compaction_next = 0, compaction = 0, cam_row_dim = 0, cam_row_n = 0, layout_n = 0;
+  bool cam_row_dirty = true;
+
   Dp d{};
   bool new_linearization_point = false;  // linearizor_power_varproj.cpp:75, 192, 240
   bool linearized = false;
@@ -549,7 +559,7 @@ int e0_dense(povar_ctx* c);  // povar_sc.hip
 int run_cholesky(povar_ctx* c, int dim, int32_t* num_iterations, int32_t* termination);  // povar_sc.hip (dim: 12 step 1, 11 step 2)
 int prepare_sc(povar_ctx* c, int dim, double lambda);  // povar_sc.hip
 int chol_factor(povar_ctx* c, int dim, const double* Q, int nq, double* stat);  // povar_sc.hip
-int no_memory(int dim, int n_cams, const char* what, size_t bytes);  // povar_sc.hip
+int no_memory(int dim, int rows, const char* what, size_t bytes);  // povar_sc.hip
 
 // The run-time block dimension (12: step 1, 11: step 2) to the step type of the dense kernels: fn(ScdPose()) or fn(ScdJoint()),
 // so every launch templated on the step is written once
@@ -580,8 +590,8 @@ hipError_t grow_buffer(povar_ctx* c, DevBuf<T>& buf, size_t count, size_t headro
 }
 
 // Geometry of the augmented dense matrix of CHOLESKY / RICHOLESKY and the covariance calls (povar_kernels_chol.hpp): n = dim *
-// n_cams rows, N = n rounded up to the 64-row panel, row stride ld, and the doubles of the allocation (slack rows / columns for
-// the 128 x 128 update tiles)
+// n_cams rows (n_cams: the cameras in the matrix -- all of them, or the free ones: povar_ctx::cam_row_n / dim), N = n rounded up
+// to the 64-row panel, row stride ld, and the doubles of the allocation (slack rows / columns for the 128 x 128 update tiles)
 struct DenseDims {
   int n, N;
   int64_t ld;

@@ -286,6 +286,16 @@ POVAR_KERNEL __launch_bounds__(64) void chol_pad(double* M, int64_t ld, int n, i
   if (r < N) M[(int64_t)r * ld + r] = 1.0;
 }
 
+// The solution x (the matrix's rows) into the increment (dim entries per camera, by camera id): camera c takes the dim entries
+// from cam_row[c] on, a camera that is not in the matrix (povar_set_dense_compaction) +0.0.  One thread per entry.
+POVAR_KERNEL __launch_bounds__(256) void chol_scatter_x(const double* x, const int* cam_row, int dim, int n_cams, double* inc) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)dim * n_cams) return;
+  const int c = (int)(i / dim), e = (int)(i - (int64_t)dim * c);
+  const int r0 = cam_row[c];
+  inc[i] = r0 < 0 ? 0.0 : x[r0 + e];
+}
+
 // Fixed cameras (povar_set_fixed_cameras), on the assembled and all-reduced matrix, before the factorisation: the dim rows
 // and columns of a fixed camera become the identity's and its right-hand-side entries 0, so the factor keeps e_k^T in those
 // rows (y_k = x_k = 0) and the rest of it is the factor of the free cameras' system S_ff.  One workgroup per camera (the free

@@ -14,7 +14,8 @@
 //
 // Landmark covariance (povar_landmark_covariance_pose / _joint) goes on from W:
 //   cov_lauum      C = W W^T: the strictly lower 64 x 64 blocks into M, the diagonal blocks into the scratch panel     MFMA
-//   cov_at         entry (r, c) of C in that layout
+//   cov_at         entry (r, c) of C in that layout; by camera pair through the map cam_row (povar_set_dense_compaction: a camera
+//                  that is not in the matrix reads as exact zeros)
 //   lm_cov         Sigma_l = Hll^-1 + sum_ij G_i^T K_ij G_j - T_l^T T_l, then the map to landmark coordinates   workgroup per landmark
 // Observation leverage and predicted-point covariance (povar_observation_covariance_pose / _joint) go on from Sigma_l:
 //   obs_cov        (h_i, c_uu, c_uv, c_vv) of every observation of a landmark from K_ii, R_i = sum_j K_ij G_j and Sigma_l   workgroup per landmark
@@ -48,13 +49,14 @@ POVAR_KERNEL __launch_bounds__(256) void cov_add_qqt(double* M, int64_t ld, int 
 
 // out[which] = max_k M_kk (which = 0: the diagonal of A, before the factorisation) or min_k M_kk^2 (which = 1: the
 // pivots R_kk^2, after it) over the rows k < n of the free cameras (fixed[k / dim] == 0: a decoupled row holds the 1 that
-// sc_fix_cameras put there and says nothing about the system).  One workgroup.
+// sc_fix_cameras put there and says nothing about the system; fixed null: the compacted matrix, which holds no such row, and no
+// row is skipped).  One workgroup.
 POVAR_KERNEL __launch_bounds__(256) void cov_diag_scan(const double* M, int64_t ld, int n, int which, double* out, const uint8_t* fixed,
                                                        int dim) {
   __shared__ double sh[256];
   double v = which == 0 ? -INFINITY : INFINITY;
   for (int k = threadIdx.x; k < n; k += 256) {
-    if (fixed[k / dim]) continue;
+    if (fixed && fixed[k / dim]) continue;
     const double a = M[(int64_t)k * ld + k];
     v = which == 0 ? fmax(v, a) : fmin(v, a * a);
   }
@@ -141,7 +143,8 @@ POVAR_KERNEL __launch_bounds__(256) void cov_trmm(const double* A, int64_t lda, 
   t.store([&](int r, int c, double v) { crow[(int64_t)r * ldc + c] = alpha * v; });
 }
 
-// Solver-coordinate block of camera c: T[a][b] = sum_k W[J_a][k] W[J_b][k], J_a = DIM c + a, over the columns
+// Solver-coordinate block of camera c: T[a][b] = sum_k W[J_a][k] W[J_b][k], J_a = cam_row[c] + a (a camera that is not in the
+// matrix keeps the zeros `out` holds), over the columns
 // k < n (the padding columns of these rows are zero: they contribute nothing).  W is upper triangular.  Inside a 64 x 64
 // diagonal block cov_diag_inv has stored its zeros below the diagonal, but the strictly lower 64 x 64 blocks of M still
 // hold what the assembly left there (or C, after cov_lauum), and a camera block that straddles a 64-edge reaches into
@@ -149,11 +152,12 @@ POVAR_KERNEL __launch_bounds__(256) void cov_trmm(const double* A, int64_t lda, 
 // reads), keeps the DIM (DIM + 1) / 2 products of the upper triangle, one deterministic workgroup sum, mirrored on
 // the way out so the block is symmetric bit for bit.  out: DIM x DIM row-major at stride 144.
 template <int DIM>
-__global__ __launch_bounds__(256) void cov_gram(const double* M, int64_t ld, int n, double* out) {
+__global__ __launch_bounds__(256) void cov_gram(const double* M, int64_t ld, int n, const int* cam_row, double* out) {
   constexpr int NP = DIM * (DIM + 1) / 2;
   __shared__ double sh[4 * NP];
   const int c = blockIdx.x;
-  const int r0 = DIM * c;
+  const int r0 = cam_row[c];
+  if (r0 < 0) return;
   double acc[NP];
 #pragma unroll
   for (int p = 0; p < NP; ++p) acc[p] = 0;
@@ -295,6 +299,12 @@ __device__ inline double cov_at(const double* M, int64_t ld, const double* panel
   if ((r >> 6) == (c >> 6)) return panel[(int64_t)r * CH_NB + (c & 63)];
   return M[(int64_t)r * ld + c];
 }
+// Entry (r, c) of the block of a camera pair whose cameras start at rows ra and rb of the matrix (cam_row of each: the map of
+// povar_set_dense_compaction); a camera that is not in the matrix (< 0) is a fixed one, whose rows and columns of C are exactly 0.
+__device__ inline double cov_at(const double* M, int64_t ld, const double* panel, int ra, int r, int rb, int c) {
+  if ((ra | rb) < 0) return 0.0;
+  return cov_at(M, ld, panel, ra + r, rb + c);
+}
 
 // Per-landmark contraction.  With C the camera covariance (S(lambda)^-1, or S0^+ = (S0 + Q Q^T)^-1 - Q Q^T), E_i the
 // DIM x 3 block of Hpl of observation i and G_i = F_i Hll^-1 (scd_stage / scdh_stage):
@@ -317,8 +327,8 @@ __device__ inline double cov_at(const double* M, int64_t ld, const double* panel
 // form's loop over the DIM^2 entries, K G_j, and the two arms of the map to landmark coordinates below.
 template <class Step>
 __global__ __launch_bounds__(256) void lm_cov(Dp d, const double* ncw, const int* lm_slot0, const int* lm_cnt, const int* ids,
-                                              const double* M, int64_t ld, const double* panel, const double* Q, int nq,
-                                              int coords, double* out) {
+                                              const double* M, int64_t ld, const double* panel, const int* cam_row, const double* Q,
+                                              int nq, int coords, double* out) {
   typedef typename Step::Obs Obs;
   constexpr int DIM = Step::DIM, CHUNK = Step::CHUNK, STRIDE = Step::LM_STRIDE;
   __shared__ Obs oi[CHUNK], oj[CHUNK];
@@ -368,9 +378,10 @@ __global__ __launch_bounds__(256) void lm_cov(Dp d, const double* ncw, const int
         if (live) {
           const Obs& a = oi[i];
           const Obs& b = oj[j];
+          const int ra = cam_row[a.cam], rb = cam_row[b.cam];
           for (int e = gl; e < DIM * DIM; e += 16) {
             const int r = e / DIM, c = e - DIM * r;
-            const double cv = cov_at(M, ld, panel, DIM * a.cam + r, DIM * b.cam + c);
+            const double cv = cov_at(M, ld, panel, ra, r, rb, c);
             double u[3], v[3];
             Step::u(a, d.sigma, h, r, u);
             Step::u(b, d.sigma, h, c, v);
@@ -537,8 +548,8 @@ struct ObsHatRow {
 
 template <class Step, class Row>
 __device__ __forceinline__ void obs_rows(Dp d, const double* ncw, const int* lm_slot0, const int* lm_cnt, const int* ids,
-                                         const int* row0, const double* M, int64_t ld, const double* panel, const double* sig,
-                                         double* out) {
+                                         const int* row0, const double* M, int64_t ld, const double* panel, const int* cam_row,
+                                         const double* sig, double* out) {
   typedef typename Step::Obs Obs;
   constexpr int DIM = Step::DIM, CHUNK = Step::CHUNK, STRIDE = Step::LM_STRIDE;
   __shared__ Obs oi[CHUNK], oj[CHUNK];
@@ -569,12 +580,14 @@ __device__ __forceinline__ void obs_rows(Dp d, const double* ncw, const int* lm_
         }
         if (!live) continue;
         const Obs& a = oi[i];
+        const int ra = cam_row[a.cam];
         for (int j = 0; j < nj; ++j) {
           const Obs& b = oj[j];
+          const int rb = cam_row[b.cam];
           double K[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
           for (int e = gl; e < DIM * DIM; e += 16) {
             const int r = e / DIM, c = e - DIM * r;
-            const double cv = cov_at(M, ld, panel, DIM * a.cam + r, DIM * b.cam + c);
+            const double cv = cov_at(M, ld, panel, ra, r, rb, c);
             double u[3], v[3];
             Step::u(a, d.sigma, h, r, u);
             Step::u(b, d.sigma, h, c, v);
@@ -640,15 +653,15 @@ __device__ __forceinline__ void obs_rows(Dp d, const double* ncw, const int* lm_
 template <class Step>
 __global__ __launch_bounds__(256) void obs_cov(Dp d, const double* ncw, const int* lm_slot0, const int* lm_cnt, const int* ids,
                                                const int* row0, const double* M, int64_t ld, const double* panel,
-                                               const double* sig, double* out) {
-  obs_rows<Step, ObsCovRow<Step>>(d, ncw, lm_slot0, lm_cnt, ids, row0, M, ld, panel, sig, out);
+                                               const int* cam_row, const double* sig, double* out) {
+  obs_rows<Step, ObsCovRow<Step>>(d, ncw, lm_slot0, lm_cnt, ids, row0, M, ld, panel, cam_row, sig, out);
 }
 
 template <class Step>
 __global__ __launch_bounds__(256) void obs_hat(Dp d, const double* ncw, const int* lm_slot0, const int* lm_cnt, const int* ids,
                                                const int* row0, const double* M, int64_t ld, const double* panel,
-                                               const double* sig, double* out) {
-  obs_rows<Step, ObsHatRow<Step>>(d, ncw, lm_slot0, lm_cnt, ids, row0, M, ld, panel, sig, out);
+                                               const int* cam_row, const double* sig, double* out) {
+  obs_rows<Step, ObsHatRow<Step>>(d, ncw, lm_slot0, lm_cnt, ids, row0, M, ld, panel, cam_row, sig, out);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -710,7 +723,8 @@ __device__ inline double pair_nc(const double* w, int i, int p) { return (i == p
 
 template <class Step>
 __global__ __launch_bounds__(192) void pair_cc(const int4* items, const long long* off, const double* M, int64_t ld, const double* panel,
-                                               const double* Q, int nq, const double* sigma, const double* ncw, int coords, double* out) {
+                                               const int* cam_row, const double* Q, int nq, const double* sigma, const double* ncw,
+                                               int coords, double* out) {
   constexpr int DIM = Step::DIM;
   __shared__ double T[DIM][DIM + 1];
   const int4 it = items[blockIdx.x];
@@ -724,7 +738,7 @@ __global__ __launch_bounds__(192) void pair_cc(const int4* items, const long lon
     const double* qb = Q + (size_t)(DIM * b + j) * nq;
     double s = 0;
     for (int k = 0; k < nq; ++k) s += qa[k] * qb[k];
-    T[t / DIM][t % DIM] = cov_at(M, ld, panel, DIM * a + i, DIM * b + j) - s;
+    T[t / DIM][t % DIM] = cov_at(M, ld, panel, cam_row[a], i, cam_row[b], j) - s;
   }
   __syncthreads();
   if (coords == 1) {
@@ -756,8 +770,8 @@ __global__ __launch_bounds__(192) void pair_cc(const int4* items, const long lon
 
 template <class Step>
 __global__ __launch_bounds__(256) void pair_cl(Dp d, const double* ncw, const int* lm_slot0, const int* lm_cnt, const int4* items,
-                                               const long long* off, const double* M, int64_t ld, const double* panel, const double* Q,
-                                               int nq, int coords, double* out) {
+                                               const long long* off, const double* M, int64_t ld, const double* panel, const int* cam_row,
+                                               const double* Q, int nq, int coords, double* out) {
   typedef typename Step::Obs Obs;
   constexpr int DIM = Step::DIM, CHUNK = Step::CHUNK, NX = 3 * DIM;
   __shared__ Obs oj[CHUNK];
@@ -768,6 +782,7 @@ __global__ __launch_bounds__(256) void pair_cl(Dp d, const double* ncw, const in
   const int cam = it.x, lm = it.y, t = threadIdx.x;
   const bool tr = it.z != 0;
   const int s0 = lm_slot0[lm], k = lm_cnt[lm];
+  const int rc = cam_row[cam];
   const typename Step::Head hd = Step::load(d, lm);
   const double h[4] = {hd.h[0], hd.h[1], hd.h[2], hd.h[3]};
   auto stage = [&](int slot, Obs& o) { Step::stage(d, ncw, slot, hd, o); };
@@ -786,12 +801,13 @@ __global__ __launch_bounds__(256) void pair_cl(Dp d, const double* ncw, const in
     if (gl >= DIM) continue;  // (no shuffle below: the lanes past the block's edge wait at the next barrier)
     for (int j = grp; j < nj; j += 16) {
       const Obs& b = oj[j];
+      const int rb = cam_row[b.cam];
       if (cam >= b.cam) {
         double w[3];
         pair_w<Step>(b, d.sigma, h, gl, w);
 #pragma unroll
         for (int p = 0; p < DIM; ++p) {
-          const double cv = cov_at(M, ld, panel, DIM * cam + p, DIM * b.cam + gl);
+          const double cv = cov_at(M, ld, panel, rc, p, rb, gl);
 #pragma unroll
           for (int x = 0; x < 3; ++x) acc[3 * p + x] += cv * w[x];
         }
@@ -799,7 +815,7 @@ __global__ __launch_bounds__(256) void pair_cl(Dp d, const double* ncw, const in
         for (int r = 0; r < DIM; ++r) {
           double w[3];
           pair_w<Step>(b, d.sigma, h, r, w);
-          const double cv = cov_at(M, ld, panel, DIM * cam + gl, DIM * b.cam + r);
+          const double cv = cov_at(M, ld, panel, rc, gl, rb, r);
 #pragma unroll
           for (int x = 0; x < 3; ++x) accp[x] += cv * w[x];
         }
@@ -857,8 +873,8 @@ __global__ __launch_bounds__(256) void pair_cl(Dp d, const double* ncw, const in
 
 template <class Step>
 __global__ __launch_bounds__(256) void pair_ll(Dp d, const double* ncw, const int* lm_slot0, const int* lm_cnt, const int4* items,
-                                               const long long* off, const double* M, int64_t ld, const double* panel, const double* Q,
-                                               int nq, int coords, double* out) {
+                                               const long long* off, const double* M, int64_t ld, const double* panel, const int* cam_row,
+                                               const double* Q, int nq, int coords, double* out) {
   typedef typename Step::Obs Obs;
   constexpr int DIM = Step::DIM, CHUNK = Step::CHUNK;
   __shared__ Obs oi[CHUNK], oj[CHUNK];
@@ -892,10 +908,11 @@ __global__ __launch_bounds__(256) void pair_ll(Dp d, const double* ncw, const in
         const Obs& a = oi[i];
         const Obs& b = oj[j];
         const bool by_rows = a.cam >= b.cam;  // the lanes along the index of the camera with the smaller id
+        const int ra = cam_row[a.cam], rb = cam_row[b.cam];
         for (int e = gl; e < DIM * DIM; e += 16) {
           const int e1 = e / DIM, e2 = e - DIM * e1;
           const int r = by_rows ? e1 : e2, c = by_rows ? e2 : e1;
-          const double cv = cov_at(M, ld, panel, DIM * a.cam + r, DIM * b.cam + c);
+          const double cv = cov_at(M, ld, panel, ra, r, rb, c);
           double wi[3], wj[3];
           pair_w<Step>(a, d.sigma, hhl, r, wi);
           pair_w<Step>(b, d.sigma, hhm, c, wj);

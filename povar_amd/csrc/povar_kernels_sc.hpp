@@ -525,10 +525,24 @@ POVAR_KERNEL __launch_bounds__(256) void pcg_finish(const double* x, double* acc
 // One workgroup per landmark, observations staged 64 at a time in LDS, 16-lane groups take one
 // camera pair each and add its 144 entries with fp64 atomics (hub cameras' blocks are shared by many
 // landmarks).  S is the augmented row-major matrix of povar_kernels_chol.hpp (row stride ld).
+// Every dense assembly kernel addresses the block of cameras (a, b) at (cam_row[a], cam_row[b]), the map of the step's matrix
+// (povar_ctx::cam_row: dim c, or with povar_set_dense_compaction the rows of the free cameras and -1 for a fixed one), and skips
+// a block with a member that is not in the matrix.
 // The atomics land in arrival order, so this assembly is reproducible to rounding only; sc_dense_ordered below adds the same
 // terms (ScdPose::term) in an order the layout fixes and is what a POVAR_FLAG_DETERMINISTIC context runs (povar_set_sc_assembly).
 // ------------------------------------------------------------------------------------------
 constexpr int SCD_CHUNK = 64;
+
+// Whether any of the k observations from slot s0 on (one landmark's) has its camera in the dense matrix (cam_row[cam] >= 0,
+// povar_set_dense_compaction): a landmark without one adds no block, and its workgroup returns before it stages anything.
+// Uniform over the workgroup (every thread calls it).  The kernels ask only where the host says that some camera is out of the
+// matrix (some_out): with every camera in it the walk could not end a workgroup and is not made.
+__device__ inline bool scd_any_row(const Dp& d, const int* cam_row, int s0, int k) {
+  int any = 0;
+  for (int i = threadIdx.x; i < k; i += blockDim.x) any |= cam_row[d.cam[s0 + i]] >= 0;
+  return __syncthreads_or(any) != 0;
+}
+
 struct ScdObs {
   double F[9], G[9];  // F_i and F_i Hll^-1
   int cam;
@@ -620,10 +634,12 @@ struct ScdPose {
   }
 };
 
-POVAR_KERNEL __launch_bounds__(256) void sc_dense_offdiag(Dp d, const int* lm_slot0, const int* lm_cnt, double* S, int64_t ld) {
+POVAR_KERNEL __launch_bounds__(256) void sc_dense_offdiag(Dp d, const int* lm_slot0, const int* lm_cnt, const int* cam_row, int some_out,
+                                                          double* S, int64_t ld) {
   __shared__ ScdObs oi[SCD_CHUNK], oj[SCD_CHUNK];
   const int lm = blockIdx.x;
   const int s0 = lm_slot0[lm], k = lm_cnt[lm];
+  if (some_out && !scd_any_row(d, cam_row, s0, k)) return;
   const ScdPose::Head hd = ScdPose::load(d, lm);
   const double h[4] = {hd.h[0], hd.h[1], hd.h[2], hd.h[3]};  // (indexed at run time: not left inside the Head)
   const int grp = threadIdx.x >> 4, gl = threadIdx.x & 15;
@@ -639,11 +655,12 @@ POVAR_KERNEL __launch_bounds__(256) void sc_dense_offdiag(Dp d, const int* lm_sl
       for (int pp = grp; pp < ni * nj; pp += 16) {
         const int i = pp / nj, j = pp - i * nj;
         if (ic == jc && i > j) continue;  // cameras ascend inside a landmark: keep camera_i <= camera_j
-        const int ci = oi[i].cam, cj = oj[j].cam;
+        const int ri = cam_row[oi[i].cam], rj = cam_row[oj[j].cam];
+        if ((ri | rj) < 0) continue;  // a camera that is not in the matrix: no block
         const ScdPose::Pair pr = ScdPose::pair(d, oi[i], oj[j]);
         for (int e = gl; e < 144; e += 16) {
           const int r = e / 12, c = e - 12 * r;
-          atomicAdd(S + (12 * (int64_t)ci + r) * ld + 12 * (int64_t)cj + c, ScdPose::term(pr, oi[i], oj[j], h, r, c));
+          atomicAdd(S + ((int64_t)ri + r) * ld + (int64_t)rj + c, ScdPose::term(pr, oi[i], oj[j], h, r, c));
         }
       }
     }
@@ -655,13 +672,15 @@ POVAR_KERNEL __launch_bounds__(256) void sc_dense_offdiag(Dp d, const int* lm_sl
 // (povar_kernels_chol.hpp).  DIM = 12 (step 1) or 11 (step 2): B_c is DIM x DIM row-major at stride 144.
 // WITH_B = false: the right-hand side alone (the ordered assembly adds B_c itself, without an atomic).
 template <int DIM, bool WITH_B = true>
-__global__ __launch_bounds__(256) void sc_dense_diag(Dp d, const double* bmat, double* S, int64_t ld, int N) {
+__global__ __launch_bounds__(256) void sc_dense_diag(Dp d, const double* bmat, const int* cam_row, double* S, int64_t ld, int N) {
   const int c = blockIdx.x, e = threadIdx.x;
+  const int64_t r0 = cam_row[c];  // the camera's rows in the matrix (< 0: it is not in it)
+  if (r0 < 0) return;
   if (WITH_B && e < DIM * DIM) {
     const int r = e / DIM, cc = e - DIM * r;
-    atomicAdd(S + (DIM * (int64_t)c + r) * ld + DIM * (int64_t)c + cc, bmat[144 * (size_t)c + e]);
+    atomicAdd(S + (r0 + r) * ld + r0 + cc, bmat[144 * (size_t)c + e]);
   }
-  if (e < DIM) S[(DIM * (int64_t)c + e) * ld + N] = -d.b[DIM * (size_t)c + e];
+  if (e < DIM) S[(r0 + e) * ld + N] = -d.b[DIM * (size_t)c + e];
 }
 
 // ------------------------------------------------------------------------------------------
@@ -803,10 +822,11 @@ struct ScdJoint {
 };
 
 POVAR_KERNEL __launch_bounds__(256) void sc_dense_offdiag_h(Dp d, const double* ncw, const int* lm_slot0, const int* lm_cnt,
-                                                            double* S, int64_t ld) {
+                                                            const int* cam_row, int some_out, double* S, int64_t ld) {
   __shared__ ScdObsH oi[SCDH_CHUNK], oj[SCDH_CHUNK];
   const int lm = blockIdx.x;
   const int s0 = lm_slot0[lm], k = lm_cnt[lm];
+  if (some_out && !scd_any_row(d, cam_row, s0, k)) return;
   const ScdJoint::Head hd = ScdJoint::load(d, lm);
   const int grp = threadIdx.x >> 4, gl = threadIdx.x & 15;
   for (int ic = 0; ic < k; ic += SCDH_CHUNK) {
@@ -823,8 +843,10 @@ POVAR_KERNEL __launch_bounds__(256) void sc_dense_offdiag_h(Dp d, const double* 
         if (ic == jc && i > j) continue;  // cameras ascend inside a landmark: keep camera_i <= camera_j
         const ScdObsH& a = oi[i];
         const ScdObsH& b = oj[j];
+        const int ri = cam_row[a.cam], rj = cam_row[b.cam];
+        if ((ri | rj) < 0) continue;  // a camera that is not in the matrix: no block
         const ScdJoint::Pair pr = ScdJoint::pair(d, a, b);  // F_i Hll^-1 F_j^T
-        double* blk = S + 11 * (int64_t)a.cam * ld + 11 * (int64_t)b.cam;
+        double* blk = S + (int64_t)ri * ld + (int64_t)rj;
         for (int e = gl; e < 121; e += 16) {
           const int r = e / 11, c = e - 11 * r;
           atomicAdd(blk + r * ld + c, ScdJoint::term(pr, a, b, hd.h, r, c));
@@ -853,7 +875,8 @@ POVAR_KERNEL __launch_bounds__(256) void sc_dense_offdiag_h(Dp d, const double* 
 //   write-out  B_c once per entry of the diagonal block (bmat: rank 0 only), then S += accumulator with plain loads and stores
 //              (S holds zeros, or Q Q^T of the free gauge); columns no term touched are left alone.
 // grid = n_cams * ceil(n_cams / SCO_T); the row cameras in popularity order (Dp::hot_cams: the long walks first); a workgroup
-// whose tile lies left of the diagonal returns at once.  On a sharded context the camera-major arrays hold the shard's
+// whose tile lies left of the diagonal, or whose row camera is not in the matrix (cam_row), returns at once; a column camera that
+// is not in it loses its accumulator at the write-out, so every other entry keeps its additions and their order.  On a sharded context the camera-major arrays hold the shard's
 // observations: every rank adds its part in its order and the all-reduce sums the parts.
 // ------------------------------------------------------------------------------------------
 constexpr int SCO_T = 32, SCO_WALK = 256, SCO_WAVES = SCO_WALK / 64, SCO_PAIRS = 32;
@@ -869,7 +892,8 @@ __device__ inline int sco_lower(const int* cam, int lo, int hi, int v) {
 }
 
 template <class Step>
-__global__ __launch_bounds__(SCO_WALK) void sc_dense_ordered(Dp d, const double* ncw, const double* bmat, double* S, int64_t ld) {
+__global__ __launch_bounds__(SCO_WALK) void sc_dense_ordered(Dp d, const double* ncw, const double* bmat, const int* cam_row, double* S,
+                                                            int64_t ld) {
   constexpr int DIM = Step::DIM, DD = DIM * DIM;
   typedef typename Step::Obs Obs;
   __shared__ double acc[SCO_T * DD];
@@ -883,6 +907,8 @@ __global__ __launch_bounds__(SCO_WALK) void sc_dense_ordered(Dp d, const double*
   const int ci = d.hot_cams[blockIdx.x / n_tiles];
   const int t0 = SCO_T * (int)(blockIdx.x % n_tiles);
   if (t0 + SCO_T <= ci) return;
+  const int64_t row_i = cam_row[ci];  // a row camera that is not in the matrix owns no block
+  if (row_i < 0) return;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   for (int col = wave; col < SCO_T; col += SCO_WAVES)
     for (int e = lane; e < DD; e += 64) acc[col * DD + e] = 0.0;
@@ -953,7 +979,9 @@ __global__ __launch_bounds__(SCO_WALK) void sc_dense_ordered(Dp d, const double*
   }
   for (int col = wave; col < SCO_T; col += SCO_WAVES) {
     if (!((touched >> col) & 1u)) continue;
-    double* blk = S + DIM * (int64_t)ci * ld + DIM * (int64_t)(t0 + col);
+    const int row_j = cam_row[t0 + col];  // (touched: t0 + col < n_cams)
+    if (row_j < 0) continue;  // a column camera that is not in the matrix: its terms are dropped here, the others' order is kept
+    double* blk = S + row_i * ld + row_j;
     for (int e = lane; e < DD; e += 64) {
       const int r = e / DIM, c = e - DIM * r;
       blk[r * ld + c] += acc[col * DD + e];

@@ -357,6 +357,19 @@ static int lm_prepare(povar_ctx* c, int step, double lambda, int32_t solver_type
     HIP_TRY(hipStreamSynchronize(c->stream));  // (fixed_next is pageable and may be rewritten by the caller's next call)
     c->n_fixed = (int)std::count(c->fixed_next.begin(), c->fixed_next.end(), (uint8_t)1);
     c->fixed_dirty = false;
+    c->cam_row_dirty = true;
+  }
+  // the map of the dense matrix follows the set, the mode (povar_set_dense_compaction) and the step's dim
+  const int map_dim = step == 1 ? 12 : 11;
+  if (c->cam_row_dirty || c->compaction != c->compaction_next || c->cam_row_dim != map_dim) {
+    c->cam_row_n = cam_row_map(c->fixed_next.data(), c->n_cams, map_dim, c->compaction_next, c->cam_row_host);
+    if (c->n_cams > 0) {
+      HIP_TRY(hipMemcpyAsync(c->cam_row.p, c->cam_row_host.data(), c->cam_row_host.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));  // (pageable, as fixed_next)
+    }
+    c->compaction = c->compaction_next;
+    c->cam_row_dim = map_dim;
+    c->cam_row_dirty = false;
   }
   const uint8_t* fixed = c->fixed_mask.p;
   if (step == 1) hipLaunchKernelGGL(cam_build_binv, k8_grid, dim3(K8_THREADS), 0, c->stream, c->d, lambda, fixed);
@@ -610,7 +623,7 @@ int povar_get_buffer(povar_ctx* c, int32_t which, double* out, int64_t n) {
       if (c->sc_factor_dim == 0 || !c->sc_dense.p || !c->sc_xpad.p)
         return fail(-1, "povar_get_buffer: POVAR_BUF_SC_FACTOR: no factor in place (the last call that wrote the dense matrix "
                         "must be a CHOLESKY / RICHOLESKY solve that found it positive definite)");
-      const DenseDims g = dense_dims(c->sc_factor_dim, c->n_cams);
+      const DenseDims g = dense_dims(c->sc_factor_dim, c->sc_factor_n / c->sc_factor_dim);  // (the cameras in that matrix)
       const size_t N = g.N, ld = g.ld;
       if ((size_t)n != N * (N + 2)) return fail(-1, "povar_get_buffer: wrong size");
       std::vector<double> xh(N);
@@ -628,7 +641,7 @@ int povar_get_buffer(povar_ctx* c, int32_t which, double* out, int64_t n) {
       if (c->cov.kind == 0 || !c->sc_dense.p)
         return fail(-1, "povar_get_buffer: POVAR_BUF_COV_*: no covariance in place (the last call that wrote the dense matrix "
                         "must be a povar_*_covariance_* call that returned 0)");
-      const DenseDims g = dense_dims(c->cov.n / c->n_cams, c->n_cams);  // (cov.n = dim * n_cams, n_cams > 0)
+      const DenseDims g = dense_dims(1, c->cov.n);  // (cov.n: the rows of that call's matrix; the geometry depends on them alone)
       const size_t N = g.N, ld = g.ld;
       if (which == POVAR_BUF_COV_GAUGE) {
         if (c->cov.nq == 0 || !c->cov.q.p) return fail(-1, "povar_get_buffer: POVAR_BUF_COV_GAUGE: the last covariance call was damped");

@@ -60,9 +60,9 @@ bool sc_assembly_ordered(const povar_ctx* c) { return c->sc_assembly == 2 || (c-
 
 }  // namespace
 
-int no_memory(int dim, int n_cams, const char* what, size_t bytes) {
+int no_memory(int dim, int rows, const char* what, size_t bytes) {
   return fail(-1, std::string(dim == 11 ? "RICHOLESKY" : "CHOLESKY") + ": not enough device memory for the " + what + " of " +
-                      std::to_string(dim * n_cams) + " rows (" + std::to_string(bytes >> 20) + " MiB)");
+                      std::to_string(rows) + " rows (" + std::to_string(bytes >> 20) + " MiB)");
 }
 
 // The system as the direct and PCG solvers prepare it (an argument error without the step's linearisation): B_c and the
@@ -82,17 +82,23 @@ int prepare_sc(povar_ctx* c, int dim, double lambda) {
 // First half, shared with the covariance calls (povar_cov.hip): assembly of the augmented matrix and its factorisation, R left in
 // sc_dense.  Q (device, n x nq row-major; null for the solvers) is the free-gauge term: A = S + Q Q^T, added on rank 0 before
 // the all-reduce; `stat` (device, 2 doubles; null for the solvers) then receives max_k A_kk and min_k R_kk^2.
+// The matrix spans the cameras of the step's map (povar_ctx::cam_row, povar_set_dense_compaction): all of them, the fixed ones
+// turned into identity rows after the all-reduce, or the free ones alone.  No camera in it (n = 0): nothing is allocated or
+// launched.
 int chol_factor(povar_ctx* c, int dim, const double* Q, int nq, double* stat) {
   c->sc_factor_dim = c->sc_factor_n = 0;  // (run_cholesky sets it again once the factorisation has succeeded)
   c->cov.invalidate();  // (a covariance call sets it again once it has returned its blocks)
-  const DenseDims g = dense_dims(dim, c->n_cams);
+  const DenseDims g = dense_dims(dim, c->cam_row_n / dim);
   const int n = g.n, N = g.N;
   const int64_t ld = g.ld;
   const size_t count = g.count;
-  if (const hipError_t e = grow_buffer(c, c->sc_dense, count, (size_t)1 << 30)) {
-    if (e == hipErrorOutOfMemory) return no_memory(dim, c->n_cams, "dense reduced camera matrix", count * sizeof(double));
-    HIP_TRY(e);
-  }
+  c->layout_n = n;  // (povar_dense_layout: this call's matrix)
+  c->layout_rows = c->cam_row_host;
+  if (n > 0)
+    if (const hipError_t e = grow_buffer(c, c->sc_dense, count, (size_t)1 << 30)) {
+      if (e == hipErrorOutOfMemory) return no_memory(dim, n, "dense reduced camera matrix", count * sizeof(double));
+      HIP_TRY(e);
+    }
   if (!c->sc_info.p) {
     HIP_TRY(c->sc_info.alloc(1, &c->bytes));
     std::vector<int> s0(c->n_lms), cnt(c->n_lms);
@@ -103,6 +109,9 @@ int chol_factor(povar_ctx* c, int dim, const double* Q, int nq, double* stat) {
     if (int rc = upload(c->sc_lm_slot0, s0, c)) return rc;
     if (int rc = upload(c->sc_lm_cnt, cnt, c)) return rc;
   }
+  if (n == 0) return 0;
+  const int* rows = c->cam_row.p;
+  const int some_out = n < dim * c->n_cams ? 1 : 0;  // a camera is not in the matrix: sc_dense_offdiag[_h] may skip whole landmarks
   double* M = c->sc_dense.p;
   HIP_TRY(hipMemsetAsync(M, 0, count * sizeof(double), c->stream));
   HIP_TRY(hipMemsetAsync(c->sc_info.p, 0, sizeof(int), c->stream));
@@ -114,9 +123,9 @@ int chol_factor(povar_ctx* c, int dim, const double* Q, int nq, double* stat) {
     with_step(dim, [&](auto step) {
       constexpr int DIM = decltype(step)::DIM;
       if (ordered)  // (B_c is sc_dense_ordered's last addition: the right-hand side alone)
-        hipLaunchKernelGGL((sc_dense_diag<DIM, false>), dim3(c->n_cams), dim3(256), 0, c->stream, c->d, (const double*)c->sc.bmat, M, ld, N);
+        hipLaunchKernelGGL((sc_dense_diag<DIM, false>), dim3(c->n_cams), dim3(256), 0, c->stream, c->d, (const double*)c->sc.bmat, rows, M, ld, N);
       else
-        hipLaunchKernelGGL(sc_dense_diag<DIM>, dim3(c->n_cams), dim3(256), 0, c->stream, c->d, (const double*)c->sc.bmat, M, ld, N);
+        hipLaunchKernelGGL(sc_dense_diag<DIM>, dim3(c->n_cams), dim3(256), 0, c->stream, c->d, (const double*)c->sc.bmat, rows, M, ld, N);
     });
     if (N > n) hipLaunchKernelGGL(chol_pad, dim3(1), dim3(64), 0, c->stream, M, ld, n, N);
     if (Q) hipLaunchKernelGGL(cov_add_qqt, dim3(N / CH_NB, N / CH_NB), dim3(256), 0, c->stream, M, ld, n, Q, nq);
@@ -127,22 +136,23 @@ int chol_factor(povar_ctx* c, int dim, const double* Q, int nq, double* stat) {
     const unsigned n_tiles = (unsigned)((c->n_cams + SCO_T - 1) / SCO_T);
     with_step(dim, [&](auto step) {
       hipLaunchKernelGGL(sc_dense_ordered<decltype(step)>, dim3((unsigned)c->n_cams * n_tiles), dim3(SCO_WALK), 0, c->stream, c->d,
-                         (const double*)c->sc.ncw, c->rank == 0 ? (const double*)c->sc.bmat : (const double*)nullptr, M, ld);
+                         (const double*)c->sc.ncw, c->rank == 0 ? (const double*)c->sc.bmat : (const double*)nullptr, rows, M, ld);
     });
   } else if (c->n_lms > 0) {
     if (dim == 11)
       hipLaunchKernelGGL(sc_dense_offdiag_h, dim3(c->n_lms), dim3(256), 0, c->stream, c->d, c->sc.ncw, (const int*)c->sc_lm_slot0.p,
-                         (const int*)c->sc_lm_cnt.p, M, ld);
+                         (const int*)c->sc_lm_cnt.p, rows, some_out, M, ld);
     else
       hipLaunchKernelGGL(sc_dense_offdiag, dim3(c->n_lms), dim3(256), 0, c->stream, c->d, (const int*)c->sc_lm_slot0.p,
-                         (const int*)c->sc_lm_cnt.p, M, ld);
+                         (const int*)c->sc_lm_cnt.p, rows, some_out, M, ld);
   }
   prof_mark(c, -1);
   HIP_TRY(hipGetLastError());
   if (int rc = allreduce(c, M, count)) return rc;
-  const uint8_t* fixed = c->fixed_mask.p;
-  // fixed cameras: identity rows and columns, right-hand side 0 -- whichever assembly ran, on every rank alike
-  if (c->n_fixed > 0) hipLaunchKernelGGL(sc_fix_cameras, dim3(c->n_cams), dim3(256), 0, c->stream, M, ld, N, dim, fixed);
+  // fixed cameras: identity rows and columns, right-hand side 0 -- whichever assembly ran, on every rank alike.  The compacted
+  // matrix holds no such row: nothing to fix, and the pivot scan skips nothing
+  const uint8_t* fixed = c->compaction ? nullptr : c->fixed_mask.p;
+  if (fixed && c->n_fixed > 0) hipLaunchKernelGGL(sc_fix_cameras, dim3(c->n_cams), dim3(256), 0, c->stream, M, ld, N, dim, fixed);
   if (stat) hipLaunchKernelGGL(cov_diag_scan, dim3(1), dim3(256), 0, c->stream, (const double*)M, ld, n, 0, stat, fixed, dim);
   for (int K0 = 0; K0 < N; K0 += CH_OB) {
     const int kdepth = std::min(CH_OB, N - K0), R0 = K0 + kdepth;
@@ -168,9 +178,16 @@ int chol_factor(povar_ctx* c, int dim, const double* Q, int nq, double* stat) {
 // step 2 (RICHOLESKY; not in the reference).  A context that solves both keeps one dense buffer, sized for the larger.
 int run_cholesky(povar_ctx* c, int dim, int32_t* num_iterations, int32_t* termination) {
   if (int rc = chol_factor(c, dim, nullptr, 0, nullptr)) return rc;
-  const DenseDims g = dense_dims(dim, c->n_cams);
+  const DenseDims g = dense_dims(dim, c->cam_row_n / dim);
   const int n = g.n, N = g.N;
   const int64_t ld = g.ld;
+  const size_t n_inc = (size_t)dim * (size_t)c->n_cams;
+  if (num_iterations) *num_iterations = 0;  // LinearizationSC::Summary default (linearization_sc.hpp:71-81)
+  if (termination) *termination = POVAR_LINEAR_SOLVER_SUCCESS;
+  if (n == 0) {  // every camera fixed: the increment is +0.0, no factor is in place
+    HIP_TRY(hipMemsetAsync(c->accum.p, 0, n_inc * sizeof(double), c->stream));
+    return 0;
+  }
   double* M = c->sc_dense.p;
   HIP_TRY(grow_buffer(c, c->sc_xpad, (size_t)N));
   double* x = c->sc_xpad.p;  // N entries, the first n are the solution
@@ -186,16 +203,17 @@ int run_cholesky(povar_ctx* c, int dim, int32_t* num_iterations, int32_t* termin
   HIP_TRY(hipStreamSynchronize(c->stream));
   if (info != 0) {
     // S not positive definite: Eigen's SimplicialLLT would hand back garbage; report a non-finite step
-    std::vector<double> nanv((size_t)n, std::nan(""));
-    HIP_TRY(hipMemcpyAsync(c->accum.p, nanv.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    std::vector<double> nanv(n_inc, std::nan(""));
+    HIP_TRY(hipMemcpyAsync(c->accum.p, nanv.data(), n_inc * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
   } else {
-    HIP_TRY(hipMemcpyAsync(c->accum.p, x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    // x by rows of the matrix -> the increment by camera id; +0.0 for a camera that is not in the matrix
+    hipLaunchKernelGGL(chol_scatter_x, dim3(grid_for((int64_t)n_inc, 256)), dim3(256), 0, c->stream, (const double*)x, (const int*)c->cam_row.p,
+                       dim, c->n_cams, c->accum.p);
+    HIP_TRY(hipGetLastError());
     c->sc_factor_dim = dim;
     c->sc_factor_n = n;
   }
-  if (num_iterations) *num_iterations = 0;  // LinearizationSC::Summary default (linearization_sc.hpp:71-81)
-  if (termination) *termination = POVAR_LINEAR_SOLVER_SUCCESS;
   return 0;
 }
 
@@ -283,6 +301,24 @@ int povar_fixed_cameras(povar_ctx* c, int32_t* flags) {
     if (flags) flags[k] = c->fixed_next[(size_t)k];
   }
   return count;
+}
+
+int povar_set_dense_compaction(povar_ctx* c, int32_t mode) {
+  if (int rc = check_ctx(c)) return rc;
+  if (mode != 0 && mode != 1) return fail(-1, "povar_set_dense_compaction: unknown mode");
+  c->compaction_next = mode;  // (the next preparation rebuilds the map: povar_lm.hip, lm_prepare)
+  return 0;
+}
+
+int povar_dense_compaction(povar_ctx* c) {
+  if (int rc = check_ctx(c)) return rc;
+  return c->compaction_next;
+}
+
+int povar_dense_layout(povar_ctx* c, int32_t* cam_row) {
+  if (int rc = check_ctx(c)) return rc;
+  for (int k = 0; cam_row && k < c->n_cams; ++k) cam_row[k] = c->layout_rows.empty() ? -1 : c->layout_rows[(size_t)k];
+  return c->layout_n;
 }
 
 int povar_set_sc_assembly(povar_ctx* c, int32_t mode) {

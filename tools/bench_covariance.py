@@ -17,7 +17,10 @@ observation rows of the free gauge sum_i h_i against rank J = dim n_cams + 3 n_l
 --pairs: instead, the covariance blocks of parameter pairs (povar_covariance_blocks_pose / _joint) beside the landmark call of the
 same run: every camera with itself and with its successor, the (camera, landmark) pair of every observation of the first
 100 000 landmarks, 100 000 seeded landmark-landmark pairs.
-usage: bench_covariance.py [--pairs] [shape] [lambda] [reps]"""
+--free-first K fixes all but the first K cameras (a window; the undamped mode is then POVAR_COV_FIXED_GAUGE), --compaction 0|1|both
+selects the layout of the dense matrix (set_dense_compaction; both: the two layouts alternate on the one context, three runs
+each, device bytes printed after each), --short stops every report after the landmark call.
+usage: bench_covariance.py [--pairs] [--free-first K] [--compaction 0|1|both] [--short] [shape] [lambda] [reps]"""
 import os
 import sys
 
@@ -28,8 +31,20 @@ from povar_amd import capi, synth  # noqa: E402
 
 
 def main():
-    argv = [a for a in sys.argv[1:] if a != "--pairs"]
-    pairs_mode = len(argv) != len(sys.argv) - 1
+    argv, opts = [], {"--free-first": None, "--compaction": "0"}
+    flags = set()
+    it = iter(sys.argv[1:])
+    for a in it:
+        if a in opts:
+            opts[a] = next(it)
+        elif a in ("--pairs", "--short"):
+            flags.add(a)
+        else:
+            argv.append(a)
+    pairs_mode, short = "--pairs" in flags, "--short" in flags
+    free_first = None if opts["--free-first"] is None else int(opts["--free-first"])
+    assert opts["--compaction"] in ("0", "1", "both"), "--compaction 0|1|both"
+    layouts = [0, 1] * 3 if opts["--compaction"] == "both" else [int(opts["--compaction"])]
     shape = argv[0] if len(argv) > 0 else "venice-1778"
     lam = float(argv[1]) if len(argv) > 1 else 1e-2
     reps = int(argv[2]) if len(argv) > 2 else 3
@@ -37,6 +52,11 @@ def main():
     ctx = capi.Context(p.n_cams, p.lm_off, p.cam_idx, p.obs / 500.0, e0_mode=capi.E0_IMPLICIT_LDSACC)
     ctx.layout_finalize()
     ctx.timings_enable(True)
+    undamped = ("free gauge", capi.COV_FREE_GAUGE, 0.0)
+    if free_first is not None and free_first < p.n_cams:
+        ctx.set_fixed_cameras(np.arange(free_first, p.n_cams))
+        undamped = ("fixed gauge", capi.COV_FIXED_GAUGE, 0.0)
+        print(f"fixed cameras: all but the first {free_first} of {p.n_cams}", flush=True)
 
     def timed(call):
         out = call()  # warm-up: code objects, the dense buffer
@@ -52,8 +72,9 @@ def main():
     def report(step, dim, solver, solve):
         (x, it, st, rc), ms_solve = timed(solve)
         assert rc == 0 and it == 0
-        print(f"step {step} {solver} n = {dim * p.n_cams}: {ms_solve:.1f} ms per factorisation + solve (device, median of {reps})", flush=True)
-        for name, gauge, lm in (("free gauge", capi.COV_FREE_GAUGE, 0.0), ("damped", capi.COV_DAMPED, lam)):
+        rows_now = ctx.dense_layout()[0] if hasattr(ctx.L, "povar_dense_layout") else dim * p.n_cams
+        print(f"step {step} {solver} n = {rows_now} (dense rows; {p.n_cams} cameras): {ms_solve:.1f} ms per factorisation + solve (device, median of {reps})", flush=True)
+        for name, gauge, lm in (undamped, ("damped", capi.COV_DAMPED, lam)):
             (cov, rc), ms = timed(lambda: ctx.camera_covariance(step=step, lam=lm, gauge=gauge, coords=capi.COV_CAMERA_COORDS))
             line = f"step {step} covariance, {name} (lambda {lm:g}): {ms:.1f} ms per call, ratio to {solver} {ms / ms_solve:.2f}"
             if rc != 0:
@@ -61,9 +82,9 @@ def main():
                 assert np.all(np.isnan(cov))
                 continue
             sym = np.array_equal(cov, cov.transpose(0, 2, 1))
-            ev = np.linalg.eigvalsh(cov)
+            ev = np.linalg.eigvalsh(cov[:free_first])  # (the blocks of fixed cameras are zero)
             line += f"; blocks bitwise symmetric: {sym}; smallest eigenvalue / largest, worst camera: {(ev[:, 0] / ev[:, -1]).min():.2e}"
-            if step == 2:
+            if step == 2 and free_first is None:
                 sigma = ctx.get_buffer(capi.BUF_POSE_SCALING).reshape(-1, 12)
                 ncw = ctx.get_buffer(capi.BUF_NC_HOUSEHOLDER).reshape(-1, 13)
                 h0 = -ncw[:, 12:13] * ncw[:, :12] * ncw[:, 0:1]
@@ -80,6 +101,8 @@ def main():
                   f"camera call {ms_lm / ms:.2f}, to {solver} {ms_lm / ms_solve:.2f}; blocks bitwise symmetric: "
                   f"{np.array_equal(blocks, blocks.transpose(0, 2, 1))}; eigenvalue {1 if step == 1 else 2} / largest, worst landmark: "
                   f"{(ev[:, 0 if step == 1 else 1] / ev[:, -1]).min():.2e}; device MiB {mib_cam} -> {ctx.device_bytes() >> 20}", flush=True)
+            if short:
+                continue
             mib_lm = ctx.device_bytes() >> 20
             (rows, rc), ms_obs = timed(lambda: ctx.observation_covariance(step=step, lam=lm, gauge=gauge))
             assert rc == 0
@@ -87,7 +110,7 @@ def main():
                     f"ratio to the landmark call {ms_obs / ms_lm:.2f}, to {solver} {ms_obs / ms_solve:.2f}; leverage in "
                     f"[{rows[:, 0].min():.3g}, {rows[:, 0].max():.3g}] (d = {4 if step == 1 else 2})")
             if gauge == capi.COV_FREE_GAUGE:
-                rank = dim * p.n_cams + 3 * p.n_lms - (12 if step == 1 else 15)
+                rank = dim * p.n_cams + 3 * p.n_lms - (12 if step == 1 else 15)  # (fixed gauge: the line is not printed)
                 line += f"; sum h = {np.sum(rows[:, 0].astype(np.longdouble)):.6f}, rank J = {rank}"
             print(line + f"; finite c_*: {bool(np.all(np.isfinite(rows[:, 1:])))}; device MiB {mib_lm} -> {ctx.device_bytes() >> 20}", flush=True)
             # the hat call beside the observation call of the same run: the same walk, another row (14 or 5 numbers instead of 4)
@@ -121,7 +144,7 @@ def main():
     def report_pairs(step, dim, solver, solve):
         """--pairs: the three requests beside the landmark call of the same run (it shares the factorisation, the inversion and
         cov_lauum with them: the difference is the pair kernels and the copy of the blocks)."""
-        for name, gauge, lm in (("free gauge", capi.COV_FREE_GAUGE, 0.0), ("damped", capi.COV_DAMPED, lam)):
+        for name, gauge, lm in (undamped, ("damped", capi.COV_DAMPED, lam)):
             (blocks, rc), ms_lm = timed(lambda: ctx.landmark_covariance(step=step, lam=lm, gauge=gauge, coords=capi.COV_LANDMARK_COORDS))
             line = f"step {step} landmark covariance, all {p.n_lms} landmarks, {name} (lambda {lm:g}): {ms_lm:.1f} ms per call"
             if rc != 0:
@@ -146,6 +169,17 @@ def main():
 
     if pairs_mode:
         report = report_pairs
+    report_one = report
+
+    def report(step, dim, solver, solve):  # every layout of --compaction in turn, on the one context
+        new = hasattr(ctx.L, "povar_set_dense_compaction")  # (POVAR_LIB may name a library from before the switch)
+        for layout in layouts:
+            if new:
+                ctx.set_dense_compaction(layout)
+            print(f"step {step} compaction {layout}:", flush=True)
+            report_one(step, dim, solver, solve)
+            print(f"step {step} compaction {layout}: dense rows {ctx.dense_layout()[0] if new else dim * p.n_cams}, "
+                  f"device bytes {ctx.device_bytes()}", flush=True)
     # step 1 in the units of the normalised observations (the first two rows of every P divided by 500)
     cams1 = p.cams.copy()
     cams1[:, :8] /= 500.0

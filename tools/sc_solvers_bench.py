@@ -8,7 +8,12 @@ RICHOLESKY on step 2's, the states of tools/joint_cholesky_bench.py) per assembl
 set_sc_assembly on ONE context: the assembly's own launches (HIP events around them: povar_profile_info.e0_ms of a dense call)
 and the whole solve stage (povar_timings.solve_ms: assembly + factorisation + substitution), one warm-up solve and --reps timed
 ones each.  `auto` leaves the library's choice and calls no setter, so it also runs a library from before the switch (POVAR_LIB),
-whose assembly interval reads 0.   usage: sc_solvers_bench.py [shape] [lambda] --assembly both [--reps 3]"""
+whose assembly interval reads 0.   usage: sc_solvers_bench.py [shape] [lambda] --assembly both [--reps 3]
+
+--free-first K fixes all but the first K cameras (set_fixed_cameras: a window), --compaction 0|1|both selects the layout of the
+dense matrix (set_dense_compaction; 1: the free cameras only).  With `both` the two layouts alternate on the one context, --runs
+times each (one warm-up solve and --reps timed ones per run), and the device bytes after each are printed.  "rest of the solve
+stage" is whole solve - assembly: the all-reduce, the fixing of the cameras, factorisation, substitution and the scatter."""
 import argparse
 import sys
 import time
@@ -22,12 +27,16 @@ from povar_amd import capi, synth  # noqa: E402
 ASSEMBLY = {"atomics": 1, "ordered": 2}
 
 
-def assembly_report(shape, lam, which, reps):
+def assembly_report(shape, lam, which, reps, free_first=None, compaction="0", runs=1):
     p = synth.make_bal_problem(shape)
     ctx = capi.Context(p.n_cams, p.lm_off, p.cam_idx, p.obs / 500.0, e0_mode=capi.E0_IMPLICIT_LDSACC)
     ctx.layout_finalize()
     ctx.timings_enable(True)
     modes = ["atomics", "ordered"] if which == "both" else [which]
+    layouts = [0, 1] if compaction == "both" else [int(compaction)]
+    if free_first is not None:
+        ctx.set_fixed_cameras(np.arange(min(free_first, p.n_cams), p.n_cams))
+        print(f"fixed cameras: all but the first {min(free_first, p.n_cams)} of {p.n_cams}", flush=True)
 
     def timed(solve):
         solve()  # warm-up: code objects, the dense buffer
@@ -47,11 +56,17 @@ def assembly_report(shape, lam, which, reps):
         for m in modes:
             if m != "auto":
                 ctx.set_sc_assembly(ASSEMBLY[m])
-            x, asm_ms, solve_ms = timed(solve)
-            ran = ctx.sc_assembly() if hasattr(ctx.L, "povar_sc_assembly") else "?"
-            out[m] = (x, asm_ms, solve_ms)
-            print(f"{name} n = {dim * p.n_cams}, assembly {m} (ran {ran}): assembly {asm_ms:.2f} ms, whole solve {solve_ms:.1f} ms "
-                  f"(device, mean of {reps})", flush=True)
+            for run in range(runs):
+                for layout in layouts:
+                    if hasattr(ctx.L, "povar_set_dense_compaction"):
+                        ctx.set_dense_compaction(layout)
+                    x, asm_ms, solve_ms = timed(solve)
+                    ran = ctx.sc_assembly() if hasattr(ctx.L, "povar_sc_assembly") else "?"
+                    rows = ctx.dense_layout()[0] if hasattr(ctx.L, "povar_dense_layout") else dim * p.n_cams
+                    out[m] = (x, asm_ms, solve_ms)
+                    print(f"{name} n = {rows}, compaction {layout}, run {run}, assembly {m} (ran {ran}): assembly {asm_ms:.2f} ms, "
+                          f"rest of the solve stage {solve_ms - asm_ms:.1f} ms, whole solve {solve_ms:.1f} ms (device, mean of {reps}); "
+                          f"device bytes {ctx.device_bytes()}", flush=True)
         if len(out) == 2:
             (xa, aa, sa), (xo, ao, so) = out["atomics"], out["ordered"]
             print(f"{name} ordered / atomics: assembly {ao / aa:.2f} x, whole solve {so / sa:.2f} x, "
@@ -86,9 +101,13 @@ def main():
     ap.add_argument("lam", nargs="?", type=float, default=None)
     ap.add_argument("--assembly", choices=["atomics", "ordered", "both", "auto"])
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--free-first", type=int, default=None, metavar="K", help="fix all but the first K cameras")
+    ap.add_argument("--compaction", choices=["0", "1", "both"], default="0", help="layout of the dense matrix (set_dense_compaction)")
+    ap.add_argument("--runs", type=int, default=3, help="with --compaction both: alternations of the two layouts")
     a = ap.parse_args()
-    if a.assembly:
-        return assembly_report(a.shape, 1e-2 if a.lam is None else a.lam, a.assembly, a.reps)
+    if a.assembly or a.free_first is not None or a.compaction != "0":
+        return assembly_report(a.shape, 1e-2 if a.lam is None else a.lam, a.assembly or "auto", a.reps, a.free_first, a.compaction,
+                               a.runs if a.compaction == "both" else 1)
     shape, lam = a.shape, 1e-4 if a.lam is None else a.lam
     p = synth.make_bal_problem(shape)
     ctx = capi.Context(p.n_cams, p.lm_off, p.cam_idx, p.obs, e0_mode=capi.E0_IMPLICIT_LDSACC)
